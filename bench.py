@@ -704,6 +704,31 @@ def train_measure(args, A, rank, world, dev, steps, warmup):
             "loss_first": float(losses[0]), "loss_last": float(losses[-1]), "finite": bool(torch.isfinite(torch.stack(losses)).all())}
 
 
+DUMP_BYTES = 64 << 20   # --dump-outputs: budget of all files together
+DUMP_SEED = 0           # the fixed element sample taken of an array when the arrays together exceed the budget
+
+
+def dump_outputs(out_dir, arrays):
+    """Writes every tensor of ``arrays`` (name -> tensor) as ``out_dir/<name>.npy`` in float32.  When together they exceed DUMP_BYTES,
+    each is replaced by the same seeded sample of its flattened elements (index order kept), sized in proportion to it; returns
+    {name: {"shape": full shape, "sampled": number of elements written, or None when the whole array was written}}"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(t.numel() for t in arrays.values())
+    fits = (DUMP_BYTES - 4096 * len(arrays)) // 4          # elements (4096 bytes of header room per file)
+    info = {}
+    for name, t in arrays.items():
+        a = t.detach().float().reshape(-1).cpu()
+        k = None
+        if total > fits:
+            k = max(1, a.numel() * fits // total)
+            idx = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(DUMP_SEED))[:k].sort().values
+            a = a[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a.numpy().reshape(tuple(t.shape) if k is None else (k,)))
+        info[name] = {"shape": list(t.shape), "sampled": k}
+    return info
+
+
 def train_main(args, A, rank, world, dev):
     """--train: the training step as the bench's step (same launch contract); prints ONE JSON line on rank 0"""
     import torch.distributed as dist
@@ -754,7 +779,12 @@ def main():
     ap.add_argument("--no-train-leg", action="store_true", help="skip the `train` sub-object (cfg 5: 5 optimizer steps at batch 4) of the default line")
     ap.add_argument("--no-in-step", action="store_true", help="skip the live in-step kernel timing (roofline falls back to the isolated timing)")
     ap.add_argument("--stub-step-ms", type=float, default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0) as DIR/<name>.npy, float32, at most 64 MB "
+                         "in all: latents [B,8,250,16] after the step and the UNet's eps [2B,8,250,16] on the CFG batch")
     args = ap.parse_args()
+    if args.dump_outputs and (args.train or args.stub_step_ms is not None):
+        ap.error("--dump-outputs writes the outputs of the denoise step; it does not apply to --train or the stub")
 
     from ap_adapter_amd import distributed as D
     if args.gpus > 1 and not D.launched_by_torchrun():
@@ -812,11 +842,14 @@ def main():
         unet.low_res_streams = tuple(torch.cuda.Stream() for _ in range(int(os.environ.get("APAD_LOW_RES_NSTREAMS", "1"))))
         unet.low_res_levels = args.low_res_streams
 
+    last = {}  # the UNet output of the latest step() call: after the capture, the graph's own buffer, rewritten by every replay
+
     def step():
         # (round 2 also ran the two CFG halves as two concurrent batch-32 forwards on forked streams: +1.5 % step time, removed)
         eps2 = unet.forward_nhwc(unet_in, H, W, None, ge, pe, None, am, batch_repeat=2)
         ops.cfg_ddim_step(eps2, lat, unet_in, coef, step_ptr, args.guidance)
         ops.step_advance(step_ptr)
+        last["eps2"] = eps2
 
     with torch.no_grad():
         s = torch.cuda.Stream()
@@ -847,6 +880,10 @@ def main():
     reset()
     dt, every = D.timed_steps(run, args.steps, world, torch.cuda.synchronize, dev)  # barrier + sync | K steps | sync + barrier; MAX over ranks
     finite = bool(torch.isfinite(lat).all().item())
+    if args.dump_outputs and rank == 0:
+        nchw = lambda t: t.reshape(t.shape[0], H, W, Cc).permute(0, 3, 1, 2)
+        dumped = dump_outputs(args.dump_outputs, {"latents": nchw(lat), "unet_eps": nchw(last["eps2"])})
+        print(f"bench: wrote {args.dump_outputs}/<name>.npy: {dumped}", file=sys.stderr)
 
     if rank == 0:
         ms_per_step = dt / args.steps * 1e3

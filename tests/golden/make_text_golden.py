@@ -130,10 +130,31 @@ def build_real_widths():
     return {"clap.out": rc.contiguous(), "t5.out": r5.contiguous(), "gpt2.out": rg.contiguous()}
 
 
-if __name__ == "__main__":
+# CPU kernel paths that give the same fp32 bits on every x86-64 host: one thread, MKL's conditional-numerical-reproducibility path and
+# ATen's baseline kernels.  On the per-ISA paths t5.out at the real widths moves by ~2e-5 of its maximum from one host (or thread count)
+# to another -- even in fp64, since T5LayerNorm takes its variance in fp32 -- which is more than the re-derivation test allows.
+PINNED_ENV = {"MKL_CBWR": "COMPATIBLE,STRICT", "ATEN_CPU_CAPABILITY": "default", "OMP_NUM_THREADS": "1", "MKL_NUM_THREADS": "1"}
+
+
+def build_real_widths_pinned():
+    """build_real_widths() in a child process on the kernel paths of PINNED_ENV: what the fixture holds, re-derivable on any host"""
+    import subprocess
+    import tempfile
+    from safetensors.torch import load_file
+    with tempfile.TemporaryDirectory() as d:
+        out = os.path.join(d, "real_widths.safetensors")
+        subprocess.run([sys.executable, *(["-s"] if sys.flags.no_user_site else []), os.path.abspath(__file__), "--real-widths-only", out],
+                       env={**os.environ, **PINNED_ENV}, check=True, timeout=900)
+        return load_file(out)
+
+
+if __name__ == "__main__" and sys.argv[1:2] == ["--real-widths-only"]:  # (the child of build_real_widths_pinned)
+    from safetensors.torch import save_file
+    save_file({k: v.contiguous() for k, v in build_real_widths().items()}, sys.argv[2])
+elif __name__ == "__main__":
     from safetensors.torch import save_file
     from text_models import GOLD, GOLD_REAL
-    real = build_real_widths()
+    real = build_real_widths_pinned()
     save_file(real, GOLD_REAL)
     print(f"wrote {GOLD_REAL}: {len(real)} tensors, {sum(v.numel() * v.element_size() for v in real.values()) / 1e6:.2f} MB")
     o = {k: v.detach().clone().contiguous() for k, v in build().items()}  # (some entries alias one another: masks handed through)

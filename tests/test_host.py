@@ -114,17 +114,23 @@ def test_copy_frozen_kv_equals_what_copy_weight_extracts():
             assert isinstance(p.to_k_ip.weight, torch.nn.Parameter)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/copied_cross_attention"), reason="the reference tree is only in the build container")
-def test_do_copy_loads_real_reference_files():
-    """build container only: two of the 64 real files (fp16 [C, 768]) through the same loader"""
+def test_do_copy_loads_real_reference_files(tmp_path):
+    """two of the 64 files at the real geometry and in the real files' exact format (fp16 [C, 768] Parameters whose storages are tagged
+    ``cuda:0``: copy_weight.py saved them from the GPU) through the same loader, which must map them to the host"""
+    from make_copied_fixture import write_copied_cross_attention
     u = A.AudioLDM2UNet2DConditionModel()
-    d = "/root/reference/copied_cross_attention"
-    for n in (A.ip_layer_names(u)[0], A.ip_layer_names(u)[-1]):
+    d = str(tmp_path)
+    sites = [A.ip_layer_names(u)[0], A.ip_layer_names(u)[-1]]
+    files = write_copied_cross_attention(u, d, names=sites, std=0.03, location="cuda:0")  # std inside the real range (SURVEY 8c)
+    for n in sites:
         C_ = u.get_submodule(n[: -len(".processor")]).to_q.in_features
         p = A.IPAttnProcessor2_0(hidden_size=C_, name=n, cross_attention_dim=768, num_tokens=8, do_copy=True, copy_dir=d)
         assert list(p.to_k_ip.weight.shape) == INDEX[n + "_k.bin"] == [C_, 768]
         assert p.to_k_ip.weight.dtype == torch.float32 and p.to_k_ip.weight.requires_grad
+        assert p.to_k_ip.weight.device.type == "cpu"
         assert 0.003 < float(p.to_k_ip.weight.detach().std()) < 0.1  # real weights (SURVEY 8c: std 0.007-0.066)
+        assert torch.equal(p.to_k_ip.weight.detach(), files[n + "_k.bin"].float())
+        assert torch.equal(p.to_v_ip.weight.detach(), files[n + "_v.bin"].float())
 
 
 def test_install_and_checkpoint_roundtrip(tmp_path):

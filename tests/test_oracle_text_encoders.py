@@ -86,14 +86,15 @@ def test_committed_fixture_equals_the_installed_transformers_outputs():
 
 def test_real_width_fixture_equals_the_installed_transformers_outputs():
     """tests/golden/text_encoders_real_widths.safetensors re-derived from the live transformers modules carrying the seeded weights (the
-    GPU test builds the same weights from the same seed and never imports transformers)"""
+    GPU test builds the same weights from the same seed and never imports transformers), on the CPU kernel paths the fixture was written
+    with (make_text_golden.PINNED_ENV: the same bits on every host)"""
     import os
     import sys
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
     import make_text_golden as G
     from safetensors.torch import load_file
     from text_models import GOLD_REAL
-    fresh, gold = G.build_real_widths(), load_file(GOLD_REAL)
+    fresh, gold = G.build_real_widths_pinned(), load_file(GOLD_REAL)
     assert set(fresh) == set(gold)
     for k, v in fresh.items():
         assert float((v - gold[k]).abs().max()) <= 1e-5 * max(float(gold[k].abs().max()), 1.0), k
