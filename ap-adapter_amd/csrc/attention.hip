@@ -46,10 +46,6 @@ struct AttnP {
 constexpr float LOG2E = 1.4426950408889634f;
 constexpr float NEG_BIG = -1.0e30f;
 constexpr int KT = 64;  // keys per LDS tile
-#ifndef APAD_ABL
-#define APAD_ABL 0  // ablation probes of the key loop (tools/ab_build.sh builds only): 1 no exp, 2 no score MFMAs, 4 no P.V MFMAs, 8 no staging
-                    // (two-tile kernel also: 16 no barrier (staging kept), 32 no LDS fragment reads, 64 no sums / range check)
-#endif
 
 
 template <int D> struct Lay {
@@ -162,17 +158,11 @@ __device__ __forceinline__ void tile_compute(const uint8_t* buf, int key0, int L
     for (int u = 0; u < 2; ++u) {
         if (u == 1 && one_sub) break;
         const uint8_t* kp = buf + (u * 32 + l31) * Y::KROW + half * 16;
-        if (APAD_ABL & 2) {
-            const uint4 kq = *reinterpret_cast<const uint4*>(kp);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) s[u][r] = __uint_as_float(kq.x + r) * 1e-30f;
-        } else {
         s[u] = E::mfma32(as_v8<DT>(*reinterpret_cast<const uint4*>(kp)), qf[0], zero16);
 #pragma unroll
         for (int cc = 1; cc < KC; ++cc) {
             typename E::v8 kf = as_v8<DT>(*reinterpret_cast<const uint4*>(kp + cc * 32));
             s[u] = E::mfma32(kf, qf[cc], s[u]);
-        }
         }
     }
     float tmax = NEG_BIG;
@@ -228,8 +218,8 @@ __device__ __forceinline__ void tile_compute(const uint8_t* buf, int key0, int L
             for (int r = 0; r < 16; r += 2) {
                 f32x2 v = {s[u][r], s[u][r + 1]};
                 v = __builtin_elementwise_fma(v, c2, nm2);
-                s[u][r] = (APAD_ABL & 1) ? v[0] * 0.5f : __builtin_amdgcn_exp2f(v[0]);
-                s[u][r + 1] = (APAD_ABL & 1) ? v[1] * 0.5f : __builtin_amdgcn_exp2f(v[1]);
+                s[u][r] = __builtin_amdgcn_exp2f(v[0]);
+                s[u][r + 1] = __builtin_amdgcn_exp2f(v[1]);
                 part[(r >> 1) & 3] += (f32x2){s[u][r], s[u][r + 1]};
             }
         osum += (part[0] + part[1]) + (part[2] + part[3]);
@@ -245,8 +235,7 @@ __device__ __forceinline__ void tile_compute(const uint8_t* buf, int key0, int L
 #pragma unroll
         for (int dt = 0; dt < Y::DT_TILES; ++dt) {
             typename E::v8 vf = as_v8<DT>(*reinterpret_cast<const uint4*>(vtile + (dt * 32 + l31) * Y::VROW + (st * 16 + 8 * half) * 2));
-            if (APAD_ABL & 4) o[dt][st] += (float)vf[0] * (float)pf[0];
-            else o[dt] = E::mfma32(vf, pf, o[dt]);
+            o[dt] = E::mfma32(vf, pf, o[dt]);
         }
     }
 }
@@ -286,11 +275,9 @@ __device__ __forceinline__ void segment(uint8_t* smem, const uint8_t* kbase, int
         if (t + 1 < nfull)  // the next tile is a full one too
             tile_load_full<D>(rk, rv, kbase + (int64_t)(t + 1) * KT * k_sl * 2, vbase + (int64_t)(t + 1) * KT * 2, koff, voff, tid);
         else if (t + 1 < ntiles) tile_load<D>(rk, rv, kbase, k_sl, vbase, L, Lpad, (t + 1) * KT, tid);
-        tile_compute<DT, D, false>((APAD_ABL & 8) ? smem : buf, t * KT, L, bias, c, qf, o, osum, m, l31, half);
-        if (!(APAD_ABL & 8)) {
+        tile_compute<DT, D, false>(buf, t * KT, L, bias, c, qf, o, osum, m, l31, half);
         if (t + 1 < ntiles) tile_store<D>(rk, rv, smem + ((t + 1) & 1) * Y::BUF, tid);
         __syncthreads();
-        }
     }
     for (; t < ntiles; ++t) {
         const uint8_t* buf = smem + (t & 1) * Y::BUF;
@@ -451,27 +438,17 @@ __device__ __forceinline__ void tile_compute2(const uint8_t* buf, int key0, int 
 #pragma unroll
     for (int u = 0; u < 2; ++u)
 #pragma unroll
-        for (int cc = 0; cc < KC; ++cc) {
-            if (APAD_ABL & 32) kf[u][cc] = qf[0][cc];
-            else
+        for (int cc = 0; cc < KC; ++cc)
             kf[u][cc] = as_v8<DT>(*reinterpret_cast<const uint4*>(buf + (u * 32 + l31) * Y::KROW + half * 16 + cc * 32));
-        }
 #pragma unroll
     for (int st = 0; st < 4; ++st)
 #pragma unroll
-        for (int dt = 0; dt < Y::DT_TILES; ++dt) {
-            if (APAD_ABL & 32) { vf[st][dt] = qf[1][0]; continue; }
+        for (int dt = 0; dt < Y::DT_TILES; ++dt)
             vf[st][dt] = as_v8<DT>(*reinterpret_cast<const uint4*>(buf + Y::K_BYTES + (dt * 32 + l31) * Y::VROW + (st * 16 + 8 * half) * 2));
-        }
 #pragma unroll
     for (int qt = 0; qt < 2; ++qt)
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
-            if (APAD_ABL & 2) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) s[qt][u][r] = mi[qt][r] * 1e-30f + (float)kf[u][0][r & 7] * (float)qf[qt][0][r & 7];
-                continue;
-            }
             s[qt][u] = E::mfma32(kf[u][0], qf[qt][0], (DIRECT && !MASK) ? mi[qt] : zero16);
 #pragma unroll
             for (int cc = 1; cc < KC; ++cc) s[qt][u] = E::mfma32(kf[u][cc], qf[qt][cc], s[qt][u]);
@@ -490,12 +467,12 @@ __device__ __forceinline__ void tile_compute2(const uint8_t* buf, int key0, int 
             for (int u = 0; u < 2; ++u)
 #pragma unroll
                 for (int r = 0; r < 16; r += 2) {
-                    s[qt][u][r] = (APAD_ABL & 1) ? s[qt][u][r] * 0.5f : __builtin_amdgcn_exp2f(s[qt][u][r]);
-                    s[qt][u][r + 1] = (APAD_ABL & 1) ? s[qt][u][r + 1] * 0.5f : __builtin_amdgcn_exp2f(s[qt][u][r + 1]);
-                    if (!(APAD_ABL & 64)) part[(r >> 1) & 3] += (f32x2){s[qt][u][r], s[qt][u][r + 1]};
+                    s[qt][u][r] = __builtin_amdgcn_exp2f(s[qt][u][r]);
+                    s[qt][u][r + 1] = __builtin_amdgcn_exp2f(s[qt][u][r + 1]);
+                    part[(r >> 1) & 3] += (f32x2){s[qt][u][r], s[qt][u][r + 1]};
                 }
             f32x2 ts = (part[0] + part[1]) + (part[2] + part[3]);
-            if (!(APAD_ABL & 64) && __any(!(ts[0] + ts[1] < BIG))) {  // wave-uniform, rare: first tile / the maximum jumped by more than log2(BIG)
+            if (__any(!(ts[0] + ts[1] < BIG))) {  // wave-uniform, rare: first tile / the maximum jumped by more than log2(BIG)
                 float tmax = NEG_BIG;
 #pragma unroll
                 for (int u = 0; u < 2; ++u) {
@@ -590,11 +567,7 @@ __device__ __forceinline__ void tile_compute2(const uint8_t* buf, int key0, int 
 #pragma unroll
             for (int j = 0; j < 8; ++j) pf[j] = (typename E::elem)s[qt][st >> 1][(st & 1) * 8 + j];
 #pragma unroll
-            for (int dt = 0; dt < Y::DT_TILES; ++dt) {
-                if (APAD_ABL & 4) o[qt][dt][st] += (float)vf[st][dt][0] * (float)pf[0] + (float)pf[7];
-                else
-                o[qt][dt] = E::mfma32(vf[st][dt], pf, o[qt][dt]);
-            }
+            for (int dt = 0; dt < Y::DT_TILES; ++dt) o[qt][dt] = E::mfma32(vf[st][dt], pf, o[qt][dt]);
         }
     }
 }
@@ -720,15 +693,11 @@ __device__ __forceinline__ void attn2q_body(const AttnP& p, uint8_t* smem) {
         int t = 0;
         for (; t < nfull; ++t) {
             const uint8_t* buf = smem + (t & 1) * Y::BUF;
-            if (!(APAD_ABL & 8)) {
             if (t + 1 < nfull) load_tile(t + 1, true);
             else if (t + 1 < ntiles) load_tile(t + 1, false);
-            }
             tile_compute2<DT, D, false, DIRECT>(buf, t * KT, L, c, qf, o, osum, m, mi, l31, half);
-            if (!(APAD_ABL & 8)) {
             if (t + 1 < ntiles) store_tile(smem + ((t + 1) & 1) * Y::BUF);
-            if (!(APAD_ABL & 16)) __syncthreads();
-            }
+            __syncthreads();
         }
         for (; t < ntiles; ++t) {
             const uint8_t* buf = smem + (t & 1) * Y::BUF;
@@ -809,53 +778,19 @@ __device__ __forceinline__ sf_gptr sf_sgpr_ptr(const uint8_t* p) {
     const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a), hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
     return (sf_gptr)(((uint64_t)hi << 32) | lo);
 }
-#ifndef SF_NSET
-#define SF_NSET 0  // (0: per-geometry default)
-#endif
-#ifndef SF_NSET48
-#define SF_NSET48 1  // weight / token fragment register sets of the projection loop at d = 48 (1: one rolling set, re-requested behind the k-step's MFMAs -- what fits
-                     // beside 160 accumulator registers when two workgroups share a CU; 2 spills 124 registers there)
-#endif
-#ifndef SF_STG_NSW
-#define SF_STG_NSW 1  // weight-fragment register sets of the staged projection loop (1: one rolling set; 137 us at d = 32 against 145 with 2 -- registers)
-#endif
-#ifndef SF_STAGE
-#define SF_STAGE(D_) true  // token fragments of the projection staged through LDS (sf_project_stg) per head size (false: the gathered loads, for A/B builds)
-#endif
+constexpr int SF_NSET32 = 4;  // weight / token fragment register sets of the projection loop at d = 32
+constexpr int SF_NSET48 = 1;  // ... at d = 48 (1: one rolling set, re-requested behind the k-step's MFMAs -- what fits beside 160 accumulator registers when
+                              // two workgroups share a CU; 2 spills 124 registers there)
+constexpr int SF_STG_NSW = 1;  // weight-fragment register sets of the staged projection loop (1: one rolling set; 137 us at d = 32 against 145 with 2 -- registers)
 #ifndef SF_STAT
 #define SF_STAT 1  // row statistics of the projection loop: 0 = shifted sums on the vector ALU (8 x (convert, subtract, add, fma) per fragment), 1 = un-shifted sums on
                    // the dot-product instruction (8 instructions per fragment)
 #endif
-#ifndef SF_DIRECT
-#define SF_DIRECT(D_) ((D_) == 32)  // the key loop's direct form (running max through the score MFMA's C operand: 32 more registers) per head size: at d = 48 /
-                                    // 252 tokens (four key tiles) the classic two-tile form keeps the kernel inside 256 registers
-#endif
-#ifndef SF_OCC
-#define SF_OCC 2  // waves per SIMD the fused self-attention kernel is compiled for (1: the compiler's own choice, for A/B builds)
-#endif
-#ifndef SF_NPP48
-#define SF_NPP48 2  // panels projected at once at d = 48 (2: 160 accumulator registers; 47.7 -> 42.4 us at 64 x 252 tokens: every weight fragment feeds two panels)
-#endif
-#ifndef SF_VPM
-#define SF_VPM 9  // vector instructions scheduled behind each MFMA of the projection loop
-#endif
-#ifndef SF_ABL
-#define SF_ABL 0  // timing ablations (tools/ab_build.sh; results are wrong): 1 = no key loop, 2 = no projection, 4 = projection without the statistics, 8 = x fragments loaded once, 16 = weight fragments loaded once, 64 = x loaded as whole rows (same bytes, 8 instead of 32 rows per instruction)
-#endif
-
-// probe build (tools/ab_build.sh <tag> attention.hip -DSF_TRACE=<wave>; tools/sf_trace.py): s_memtime at the phase boundaries of one wave of every
-// workgroup.  Never part of the product library.
-#ifdef SF_TRACE
-__device__ unsigned long long sf_trace_buf[1024][16];
-#define SF_STAMP(i_)                                                                                      \
-    if (lane == 0 && wave == (SF_TRACE) && blockIdx.x < 1024) {                                           \
-        sf_trace_buf[blockIdx.x][i_] = __builtin_amdgcn_s_memtime();                                      \
-        if ((i_) == 0) sf_trace_buf[blockIdx.x][14] = wall_clock64();                                     \
-        if ((i_) == 9) sf_trace_buf[blockIdx.x][15] = wall_clock64();                                     \
-    }
-#else
-#define SF_STAMP(i_)
-#endif
+// the key loop's direct form (running max through the score MFMA's C operand: 32 more registers) per head size: at d = 48 / 252 tokens (four key tiles)
+// the classic two-tile form keeps the kernel inside 256 registers
+constexpr bool sf_direct(int d) { return d == 32; }
+constexpr int SF_NPP48 = 2;  // panels projected at once at d = 48 (2: 160 accumulator registers; 47.7 -> 42.4 us at 64 x 252 tokens: every weight fragment feeds two panels)
+constexpr int SF_VPM = 9;    // vector instructions scheduled behind each MFMA of the projection loop
 
 // sum / sum of squares of a pair of 16-bit values on the dot-product instruction (v_dot2c_f32_bf16 / _f16): no conversion, two values per instruction
 typedef __bf16 sf_bf2 __attribute__((ext_vector_type(2)));
@@ -875,17 +810,17 @@ __device__ __forceinline__ void sf_project(sf_gptr wb, uint32_t loff, const uint
     static_assert(KC % NSET == 0, "the register sets rotate over the k-steps");
     typename E::v8 wf[NSET][NT3], xf[NSET][NPP];
 #define SF_LD(i_, kk_)                                                                                                                \
-    _Pragma("unroll") for (int j = 0; j < NT3; ++j) wf[i_][j] = __builtin_bit_cast(typename E::v8, *(sf_gptr16)(wb + (j * KC + ((SF_ABL & 16) ? 0 : (kk_))) * 1024 + loff)); \
-    _Pragma("unroll") for (int n = 0; n < NPP; ++n) xf[i_][n] = as_v8<DT>(*reinterpret_cast<const uint4*>(xrow[n] + ((SF_ABL & 8) ? 0 : (kk_)) * ((SF_ABL & 64) ? 1024 : 32)));
+    _Pragma("unroll") for (int j = 0; j < NT3; ++j) wf[i_][j] = __builtin_bit_cast(typename E::v8, *(sf_gptr16)(wb + (j * KC + (kk_)) * 1024 + loff)); \
+    _Pragma("unroll") for (int n = 0; n < NPP; ++n) xf[i_][n] = as_v8<DT>(*reinterpret_cast<const uint4*>(xrow[n] + (kk_) * 32));
 #define SF_MM(i_)                                                                                   \
     _Pragma("unroll") for (int n = 0; n < NPP; ++n) {                                               \
         _Pragma("unroll") for (int j = 0; j < NT3; ++j) acc[n][j] = E::mfma32(wf[i_][j], xf[i_][n], acc[n][j]); \
-        if (!(SF_ABL & 4) && SF_STAT == 1) _Pragma("unroll") for (int w_ = 0; w_ < 4; ++w_) {       \
+        if (SF_STAT == 1) _Pragma("unroll") for (int w_ = 0; w_ < 4; ++w_) {                        \
             const uint32_t pr_ = __builtin_bit_cast(u32x4, xf[i_][n])[w_];                          \
             ssum[n] = sf_dot2<DT>(pr_, sf_ones2<DT>(), ssum[n]);                                    \
             sq[n] = sf_dot2<DT>(pr_, pr_, sq[n]);                                                   \
         }                                                                                           \
-        if (!(SF_ABL & 4) && SF_STAT == 0) _Pragma("unroll") for (int e = 0; e < 8; ++e) {          \
+        if (SF_STAT == 0) _Pragma("unroll") for (int e = 0; e < 8; ++e) {                           \
             const float d_ = (float)xf[i_][n][e] - shift[n];                                        \
             ssum[n] += d_;                                                                          \
             sq[n] = __builtin_fmaf(d_, d_, sq[n]);                                                  \
@@ -913,7 +848,7 @@ __device__ __forceinline__ void sf_project(sf_gptr wb, uint32_t loff, const uint
 #pragma unroll
             for (int m_ = 0; m_ < NT3 * NPP; ++m_) {
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                if (!(SF_ABL & 4)) __builtin_amdgcn_sched_group_barrier(0x002, SF_VPM, 0);
+                __builtin_amdgcn_sched_group_barrier(0x002, SF_VPM, 0);
             }
             __builtin_amdgcn_sched_group_barrier(0x020, NT3 + NPP, 0);
         }
@@ -926,7 +861,7 @@ __device__ __forceinline__ void sf_project(sf_gptr wb, uint32_t loff, const uint
 
 // The same contraction with the token fragments STAGED THROUGH LDS (round 6).  A B-operand fragment straight from global memory is 32 rows x 32 bytes: 32 cache
 // lines per load instruction, and the vector memory pipe takes about a cycle per line -- with the statistics on the dot-product instruction (SF_STAT) that gather is
-// what bounds the projection phase (probe build with whole-row loads, SF_ABL = 64: 144 -> 131 us at d = 32).  Here the wave fetches its 64 rows of a four-k-step
+// what bounds the projection phase (probe build with whole-row loads: 144 -> 131 us at d = 32).  Here the wave fetches its 64 rows of a four-k-step
 // chunk as whole 128-byte pieces (8 rows per instruction = 8 lines), parks them in a private 8 KB LDS window (128-byte row records, 16-byte slot s of row r at
 // s ^ ((r >> 1) & 7): conflict-free for the b128 writes and the fragment reads) and reads the fragments back one k-step ahead; the chunk after next is in flight in
 // registers meanwhile.  Same MFMA order, same operands: bit-equal to sf_project.  The window aliases key tiles (sf_go picks the instantiation only where no finished
@@ -1020,9 +955,9 @@ __device__ __forceinline__ void sf_project_stg(sf_gptr wb, uint32_t loff, const 
 }
 
 // (two waves per SIMD by contract: at d = 48 the four-wave workgroups need TWO per CU -- round 6 found the kernel at 256 + 44 registers, i.e. one workgroup per
-//  CU and its 512 workgroups in two rounds of 22 us; SF_OCC = 1 re-creates that build)
+//  CU and its 512 workgroups in two rounds of 22 us)
 template <int DT, int D, int KC, int NW, int NPP, int NSET, bool STAGED>
-__global__ __launch_bounds__(NW * 64, SF_OCC) void sattn_fused_kernel(SfP p) {
+__global__ __launch_bounds__(NW * 64, 2) void sattn_fused_kernel(SfP p) {
     using E = ET<DT>;
     using Y = Lay<D>;
     // the head's q | k | v rows are packed DENSELY: 3 d virtual rows in ceil(3 d / 32) row tiles (d = 48: 4.5 -> 5 tiles, not 3 x 2); an 8-row
@@ -1034,7 +969,6 @@ __global__ __launch_bounds__(NW * 64, SF_OCC) void sattn_fused_kernel(SfP p) {
     const int xcd = blockIdx.x & 7, seq = blockIdx.x >> 3;
     const int b = (seq / p.H) * 8 + xcd, h = seq % p.H;  // (all heads of a sample on one XCD: they share its rows)
     if (b >= p.B) return;
-    SF_STAMP(0);
     const int N = p.N;
     const int npan = (N + 31) >> 5, ntiles = (N + KT - 1) / KT, nfull = N / KT;
     const int rounds = (npan + NPW * NW - 1) / (NPW * NW);
@@ -1061,7 +995,6 @@ __global__ __launch_bounds__(NW * 64, SF_OCC) void sattn_fused_kernel(SfP p) {
         }
         __syncthreads();
     }
-    SF_STAMP(1);
     const sf_gptr wb = sf_sgpr_ptr(p.w + (int64_t)h * NT3 * KC * 1024);
     const uint32_t loff = (uint32_t)lane * 16u;
     const uint8_t* const xb = p.x + (int64_t)b * N * C * 2;
@@ -1083,7 +1016,6 @@ __global__ __launch_bounds__(NW * 64, SF_OCC) void sattn_fused_kernel(SfP p) {
                 int tok = pan[n] * 32 + l31;
                 tok = tok < N ? tok : N - 1;
                 xrow[n] = xb + ((int64_t)tok * C + half * 8) * 2;
-                if (SF_ABL & 64) xrow[n] = xb + ((int64_t)min(pan[n] * 32 + half, N - 32) * C + l31 * 8) * 2;  // (timing only: two whole rows per load instruction)
                 act = act || pan[n] < npan;
             }
             // STAGED (sf_project_stg): every wave's 8 KB window at the END of the key-tile region.  sf_go launches this instantiation only where no EARLIER round
@@ -1101,14 +1033,10 @@ __global__ __launch_bounds__(NW * 64, SF_OCC) void sattn_fused_kernel(SfP p) {
 #pragma unroll
                     for (int q_ = 0; q_ < 16; ++q_) acc[n][j][q_] = 0.f;
             float ssum[NPP], sq[NPP], shift[NPP];
-            if (SF_ABL & 2) {
-#pragma unroll
-                for (int n = 0; n < NPP; ++n) ssum[n] = sq[n] = shift[n] = 1.f;
-            } else if (act) {  // (wave-uniform)
+            if (act) {  // (wave-uniform)
                 if constexpr (STAGED) sf_project_stg<DT, NT3, NPP, KC, STG_KCH>(wb, loff, xb, pan, N, smem + stg_off + wave * STG, lane, acc, ssum, sq, shift);
                 else sf_project<DT, NT3, NPP, KC, NSET>(wb, loff, xrow, acc, ssum, sq, shift);
             }
-            SF_STAMP(2 + 2 * r);
             if (STAGED && r == 0) {
 #pragma unroll
                 for (int k = 0; k < NCSB; ++k)
@@ -1134,7 +1062,7 @@ __global__ __launch_bounds__(NW * 64, SF_OCC) void sattn_fused_kernel(SfP p) {
                 const float s1 = half_sum(ssum[n]), s2 = half_sum(sq[n]);
                 const float md = s1 * (1.0f / C), mean = shift[n] + md;
                 const float var = fmaxf(s2 * (1.0f / C) - md * md, 0.f);
-                const float rstd = (SF_ABL & 4) ? (ok ? 1.f : 0.f) : (ok ? rsqrtf(var + p.eps) : 0.f), nmr = (SF_ABL & 4) ? 0.f : -mean * rstd, okf = ok ? 1.f : 0.f;
+                const float rstd = ok ? rsqrtf(var + p.eps) : 0.f, nmr = -mean * rstd, okf = ok ? 1.f : 0.f;
                 uint8_t* const kt = smem + (key >> 6) * Y::BUF;
                 const int krow = key & 63;
                 const int kpos = (krow & ~12) | ((krow & 4) << 1) | ((krow & 8) >> 1);  // position of the key inside the tile's V^T rows (Lay::VROW: bits 2, 3 swapped)
@@ -1173,17 +1101,15 @@ __global__ __launch_bounds__(NW * 64, SF_OCC) void sattn_fused_kernel(SfP p) {
                 }
             }
             }
-            SF_STAMP(3 + 2 * r);
         }
     }
     __syncthreads();
-    SF_STAMP(6);
     // ---- 2. attention over the resident tiles: two query panels per wave and round ----
 #pragma unroll
     for (int r = 0; r < MAXR; ++r) {
         if (r >= rounds) break;
         const int pa = (r * NPW) * NW + wave, pb = pa + NW;
-        if (pa >= npan || (SF_ABL & 1)) continue;  // (wave-uniform; pb >= npan: its lanes carry the clamped last row and are not stored)
+        if (pa >= npan) continue;  // (wave-uniform; pb >= npan: its lanes carry the clamped last row and are not stored)
         f32x16 o[2][Y::DT_TILES];
         f32x2 osum[2];
         float m[2];
@@ -1201,8 +1127,8 @@ __global__ __launch_bounds__(NW * 64, SF_OCC) void sattn_fused_kernel(SfP p) {
         }
         int t = 0;
 #pragma unroll 1
-        for (; t < nfull; ++t) tile_compute2<DT, D, false, SF_DIRECT(D)>(smem + t * Y::BUF, t * KT, N, 1.0f, qkeep[r], o, osum, m, mi, l31, half);
-        if (t < ntiles) tile_compute2<DT, D, true, SF_DIRECT(D)>(smem + t * Y::BUF, t * KT, N, 1.0f, qkeep[r], o, osum, m, mi, l31, half);
+        for (; t < nfull; ++t) tile_compute2<DT, D, false, sf_direct(D)>(smem + t * Y::BUF, t * KT, N, 1.0f, qkeep[r], o, osum, m, mi, l31, half);
+        if (t < ntiles) tile_compute2<DT, D, true, sf_direct(D)>(smem + t * Y::BUF, t * KT, N, 1.0f, qkeep[r], o, osum, m, mi, l31, half);
 #pragma unroll
         for (int qt = 0; qt < 2; ++qt) {
             const int q = (qt == 0 ? pa : pb) * 32 + l31;
@@ -1223,21 +1149,14 @@ __global__ __launch_bounds__(NW * 64, SF_OCC) void sattn_fused_kernel(SfP p) {
                     }
             }
         }
-        SF_STAMP(7 + r);
     }
-    SF_STAMP(9);
 }
-#ifdef SF_TRACE
-extern "C" int apad_sf_trace_read(void* dst, int bytes) {
-    return hipMemcpyFromSymbol(dst, HIP_SYMBOL(sf_trace_buf), (size_t)bytes, 0, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
-}
-#endif
 
 template <int DT, int D, int KC, int NW, int NPP, int NSET, bool STAGED = false> int sf_go(const SfP& p, hipStream_t s) {
     using Y = Lay<D>;
     constexpr int NT3 = (3 * D + 31) / 32;
     const int ntiles = (p.N + KT - 1) / KT;
-    if constexpr (!STAGED && SF_STAGE(D) && NPP == 2) {
+    if constexpr (!STAGED && NPP == 2) {
         // the LDS-staged projection (sf_project_stg) where every wave's 8 KB window fits behind the tiles the earlier rounds fill
         const int npan = (p.N + 31) / 32, rounds = (npan + 2 * NW - 1) / (2 * NW), stg_off = ntiles * Y::BUF - NW * NPP * 32 * (D == 32 ? 128 : 64);
         if (stg_off >= (rounds - 1) * (2 * NW * 32 / KT) * Y::BUF) return sf_go<DT, D, KC, NW, NPP, NSET, true>(p, s);
@@ -1427,7 +1346,7 @@ template <int DT, int D> int launch_d(const AttnP& p, bool dual, dim3 grid, hipS
     if constexpr (D == 32 || D == 48 || D == 64) {
         // long single-segment launches without a key bias (the UNet's self-attention): two query tiles per wave
         constexpr int two_q = 1;
-        // (A/B knob; round 3: 512 -> 200, i.e. the 252-token level's d = 48 self-attention too: step 44.87 -> 44.74 ms; in round 2,
+        // (round 3: 512 -> 200, i.e. the 252-token level's d = 48 self-attention too: step 44.87 -> 44.74 ms; in round 2,
         //  before the batched fragment reads, it measured slower there; the gain is 0.1 ms)
         constexpr int two_q_min = 200;
         if (two_q && !dual && p.key_bias == nullptr && p.N >= two_q_min && p.L >= (two_q_min < 256 ? two_q_min : 256) && (D == 32 || D == 48 || two_q > 1)) {
@@ -1492,9 +1411,6 @@ template <int DT> int launch_dt(const AttnP& p, int D, bool dual, dim3 grid, hip
 //      heads' outputs into the X tile (the normalised tokens are dead)
 //   4. out^T = Wo . O^T (+ bias) -> Q tile (rounded like the chain's to_out), then one coalesced pass adds the residual x and stores.
 // HBM traffic per launch: x once in, out once out (the chain: six activation passes).
-#ifndef XR_ABL
-#define XR_ABL 0  // timing ablations (tools/ab_build.sh; results are wrong): 1 = weight fragments loaded once, 2 = no attention phase, 4 = no projections, 8 = no LayerNorm arithmetic
-#endif
 struct XrP {
     const uint8_t* x;
     const uint8_t* gamma;
@@ -1561,7 +1477,7 @@ __device__ __forceinline__ void xr_project(const uint8_t* wpk, const uint8_t* sr
 #pragma unroll
         for (int i = 0; i < NSET; ++i) {
             xr_step<DT, NT, ROWB, PW>(acc, wf[i], sl, kk + i);
-            if (!(XR_ABL & 1) && kk + i + NSET < KS) xr_ldw<DT, NT>(wf[i], wl, KS, kk + i + NSET);
+            if (kk + i + NSET < KS) xr_ldw<DT, NT>(wf[i], wl, KS, kk + i + NSET);
         }
     }
 #pragma unroll
@@ -1627,7 +1543,7 @@ __global__ __launch_bounds__(NW * 64) void xattn_rows_kernel(XrP p) {
                 if (ok) u = *reinterpret_cast<const uint4*>(xb + ((int64_t)row * C + (sub + 8 * i) * 8) * 2);
                 unpack8<DT>(u, v[i]);
             }
-            if (p.gamma != nullptr && !(XR_ABL & 8)) {
+            if (p.gamma != nullptr) {
                 float s1 = 0.f;
 #pragma unroll
                 for (int i = 0; i < CH; ++i)
@@ -1665,7 +1581,7 @@ __global__ __launch_bounds__(NW * 64) void xattn_rows_kernel(XrP p) {
     __syncthreads();
 
     // ---- 2. q = to_q(X) -> Q ----
-    if (!(XR_ABL & 4)) xr_project<DT, C, PW, NSET>(p.wq, X, Q, nullptr, wave, lane);
+    xr_project<DT, C, PW, NSET>(p.wq, X, Q, nullptr, wave, lane);
 
     // ---- 3. attention, heads 2 w and 2 w + 1: Q -> X.  All K / V^T fragments of a head (both segments) are requested before any of its
     //         arithmetic, and the first head's before the barrier: one exposed L2 round trip per wave ----
@@ -1687,14 +1603,14 @@ __global__ __launch_bounds__(NW * 64) void xattn_rows_kernel(XrP p) {
 #define XR_FETCH1(h_) do { if (pk1) short_load<DT, D, NS1>(f1, XR_PK1(h_), l31, half); else short_load<DT, D, NS1>(f1, XR_RAW1(h_), l31, half); } while (0)
 #define XR_FETCH2(h_) do { if (pk2) short_load<DT, D, NSB>(f2, XR_PK2(h_), l31, half); else short_load<DT, D, NSB>(f2, XR_RAW2(h_), l31, half); } while (0)
     // (macros, not lambdas: a fragment struct captured by a lambda is kept in scratch by this compiler)
-    if (!(XR_ABL & 2) && !SPLITF) {
+    if (!SPLITF) {
         XR_FETCH1((wave & 3) * 2);
         if (DUAL && !BIG2) XR_FETCH2((wave & 3) * 2);
     }
     __syncthreads();
     const float* const bias1 = p.bias1 ? p.bias1 + (int64_t)b * p.L1 : nullptr;
 #pragma unroll
-    for (int hh = 0; hh < ((XR_ABL & 2) ? 0 : 2); ++hh) {
+    for (int hh = 0; hh < 2; ++hh) {
         const int h = (wave & 3) * 2 + hh;
         if (hh == 1 && !SPLITF) {
             XR_FETCH1(h);
@@ -1771,7 +1687,7 @@ __global__ __launch_bounds__(NW * 64) void xattn_rows_kernel(XrP p) {
     __syncthreads();
 
     // ---- 4. to_out(O) + bias -> Q, then + residual -> out ----
-    if (!(XR_ABL & 4)) xr_project<DT, C, PW, NSET>(p.wo, X, Q, p.bo, wave, lane);
+    xr_project<DT, C, PW, NSET>(p.wo, X, Q, p.bo, wave, lane);
     __syncthreads();
     uint8_t* const ob = p.out + ((int64_t)b * p.N + row0) * C * 2;
     constexpr int CPR = C / 8;
@@ -1904,9 +1820,8 @@ extern "C" int apad_self_attention_fused(const void* x, const void* w_packed, co
     SfP p;
     p.x = (const uint8_t*)x; p.w = (const uint8_t*)w_packed; p.csbb = colsum_bias; p.out = (uint8_t*)out; p.B = B; p.N = N; p.H = heads; p.eps = ln_eps;
     hipStream_t s = (hipStream_t)stream;
-    constexpr int NS32 = SF_NSET ? SF_NSET : 4, NS48 = SF_NSET ? SF_NSET : SF_NSET48;
-    if (g256) return dtype == APAD_BF16 ? sf_go<APAD_BF16, 32, 16, 8, 2, NS32>(p, s) : sf_go<APAD_F16, 32, 16, 8, 2, NS32>(p, s);
-    return dtype == APAD_BF16 ? sf_go<APAD_BF16, 48, 24, 4, SF_NPP48, NS48>(p, s) : sf_go<APAD_F16, 48, 24, 4, SF_NPP48, NS48>(p, s);
+    if (g256) return dtype == APAD_BF16 ? sf_go<APAD_BF16, 32, 16, 8, 2, SF_NSET32>(p, s) : sf_go<APAD_F16, 32, 16, 8, 2, SF_NSET32>(p, s);
+    return dtype == APAD_BF16 ? sf_go<APAD_BF16, 48, 24, 4, SF_NPP48, SF_NSET48>(p, s) : sf_go<APAD_F16, 48, 24, 4, SF_NPP48, SF_NSET48>(p, s);
 }
 
 extern "C" int apad_cross_attention_rows(const apad_xrows_desc* d, void* stream) {

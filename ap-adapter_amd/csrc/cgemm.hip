@@ -5,7 +5,7 @@
 // What differs from the 128x128 tiled kernel (gemm.hip), whose k-loop spends as many issue cycles on the gather's address
 // arithmetic, its exec-masked loads and the register -> LDS copy as on its MFMAs:
 //   * 512 threads = 8 waves on a 256 x 128 x 64 tile (4 x 2 waves of 64 x 64, three 48 KB LDS stages) or, when N % 256 == 0, a
-//     256 x 256 x 64 tile (2 x 4 waves of 128 x 64, two 64 KB stages): measured with ablation builds (CG_ABL), the 256 x 128 form is
+//     256 x 256 x 64 tile (2 x 4 waves of 128 x 64, two 64 KB stages): measured with ablation builds, the 256 x 128 form is
 //     bound by the CU's LDS fill + fragment-read traffic (48 KB in, 128 KB out per k-tile against 1024 MFMA cycles), not by the MFMAs
 //     -- the square tile moves a third fewer bytes per FLOP through L2 -> LDS and a quarter fewer through LDS -> registers
 //   * operands go HBM / L2 -> LDS directly (`buffer_load_dwordx4 ... lds`): no staging registers, no ds_write pass.  The DMA writes
@@ -17,15 +17,11 @@
 //   * the two waves of a SIMD (waves w and w + 4) run half a phase apart: a phase is [fragment reads | barrier | 8 MFMAs + DMA issue |
 //     barrier]; while one wave of the SIMD is in its MFMA segment the other is in its read segment
 //     (MI355X_MICROARCH.md, "Two waves per SIMD")
-#include <stdlib.h>
 #include <type_traits>
 #include "common.h"
 
 namespace {
 
-#ifndef CG_ABL
-#define CG_ABL 0  // ablation bits for timing-only probe builds (tools/ab_build.sh): 1 no DMA in the loop, 2 no fragment reads, 4 no MFMAs
-#endif
 constexpr int CBM = 256, CBK = 64;
 constexpr int CA_BYTES = CBM * CBK * 2;       // 32 768
 constexpr uint32_t C_OOB = 0x80000000u;       // an offset no operand reaches (sizes are checked < 2 GB on the host)
@@ -259,7 +255,6 @@ __global__ __launch_bounds__(512) void cgemm_kernel(CgP p) {
     u32x4 fa[KSP][MI] = {}, fb[KSP][2] = {};  // [k-step of the phase][MFMA tile]
     const uint32_t lds0 = (uint32_t)(size_t)(lds_ptr)smem;
     auto read_frags = [&](int stage, int ph) {
-        if (CG_ABL & 2) return;
         const uint32_t st = lds0 + (uint32_t)(stage * STAGE);
 #pragma unroll
         for (int u = 0; u < KSP; ++u) {
@@ -287,8 +282,7 @@ __global__ __launch_bounds__(512) void cgemm_kernel(CgP p) {
             for (int i = 0; i < MI; ++i)
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
-                    if (!(CG_ABL & 4))
-                        acc[i][j] = E::mfma32(__builtin_bit_cast(typename E::v8, fa[u][i]), __builtin_bit_cast(typename E::v8, fb[u][j]), acc[i][j]);
+                    acc[i][j] = E::mfma32(__builtin_bit_cast(typename E::v8, fa[u][i]), __builtin_bit_cast(typename E::v8, fb[u][j]), acc[i][j]);
                     if (n < 3) {
                         __builtin_amdgcn_sched_barrier(0);
                         dma(n);
@@ -315,7 +309,7 @@ __global__ __launch_bounds__(512) void cgemm_kernel(CgP p) {
     // One k-tile.  Stage indices are compile-time (the loop is unrolled by the stage count).
     auto ktile = [&](int t, auto stage_tag) {
         constexpr int S = decltype(stage_tag)::value, SR = (S + D) % NST;  // SR: the stage tile t + D goes to (it held tile t - 1)
-        const bool req = (CG_ABL & 1) ? false : t + D < nk;  // wave-uniform
+        const bool req = t + D < nk;  // wave-uniform
 #pragma unroll
         for (int ph = 0; ph < NPH; ++ph) {
             read_frags(S, ph);
@@ -595,25 +589,20 @@ template <int DT, int MODE, int BN> int cg_launch(const CgP& p, hipStream_t s) {
 // Called by apad_gemm before its own dispatch.  Returns 1 when the problem is outside this kernel's envelope (the caller goes on),
 // 0 after a launch, < 0 on a launch error.
 int apad_cgemm_try(const apad_gemm_desc* d, hipStream_t s) {
-    static const int mode = [] { const char* e = getenv("APAD_CGEMM"); return e ? atoi(e) : 1; }();  // A/B knob: 0 = off
     constexpr long min_rows = 16000L;  // (step-level A/B: 32768 -> 16000 = -1.0 ms, 4000 / 2000: no further gain)
-    if (!mode) return 1;
     if (d->dtype != APAD_BF16 && d->dtype != APAD_F16) return 1;
     if (d->epilogue != APAD_EPI_NONE || d->out_mode != APAD_OUT_ROWMAJOR || d->rowstat_out || d->rowstat_in) return 1;
-    constexpr int bn_mode = 0;  // A/B knob: 128 = never the square tile
-    constexpr int small_mode = 1;  // A/B knob: 0 = off
     // below the row threshold: the small-tile form for 3x3 convolutions with long reductions (the 64-token level)
-    const bool small = d->M < min_rows && small_mode && d->a_mode == APAD_A_CONV3X3 && d->K >= 2304 && d->N % SBN == 0;
+    const bool small = d->M < min_rows && d->a_mode == APAD_A_CONV3X3 && d->K >= 2304 && d->N % SBN == 0;
     if ((d->N % 128 != 0 && !small) || d->K % CBK != 0 || (d->M < min_rows && !small) || d->M >= (1LL << 30)) return 1;
-    const bool sq = d->N % 256 == 0 && bn_mode != 128;
+    const bool sq = d->N % 256 == 0;
     if (d->rowgroup_bias && d->rows_per_group < d->M) return 1;  // only the table form (every row reads row *step_ptr)
     const bool conv = d->a_mode == APAD_A_CONV3X3;
     bool general = false;
     int64_t a_bytes;
     if (conv) {
-        constexpr int gen_mode = 1;  // A/B knob: 0 = stride-1 only
         general = d->stride != 1 || d->Hup != 0;
-        if ((d->stride != 1 && d->stride != 2) || d->src_batch_mod != 0 || d->conv_asym_pad || d->Cin % CBK != 0 || (general && !gen_mode)) return 1;
+        if ((d->stride != 1 && d->stride != 2) || d->src_batch_mod != 0 || d->conv_asym_pad || d->Cin % CBK != 0) return 1;
         if (!general && (d->Hout != d->Hin || d->Wout != d->Win)) return 1;
         a_bytes = (d->M / ((int64_t)d->Hout * d->Wout)) * d->Hin * d->Win * (int64_t)d->Cin * 2;
     } else if (d->a_mode == APAD_A_PLAIN) {

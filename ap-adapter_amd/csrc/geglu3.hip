@@ -16,10 +16,6 @@
 #include <stdlib.h>
 #include "mlp3_shared.h"
 
-#ifndef G3_ABL
-#define G3_ABL 0  // timing ablations (results are wrong): 1 no GELU arithmetic, 2 no MFMAs, 8 no DMA in the loop, 16 no barrier, 32 no output stores, 64 no fragment reads, 128 two iterations only
-#endif
-
 namespace {
 
 constexpr int G3_C = 384, G3_KS = G3_C / 16, G3_HID = 4 * G3_C, G3_PARTS = 4, G3_NCH = G3_HID / 16 / G3_PARTS;  // 24 k-steps; 24 chunks per part
@@ -64,25 +60,9 @@ template <> struct G3Asm<APAD_F16> {
     }
 };
 
-// probe build (tools/ab_build.sh <tag> geglu3.hip -DG3_TRACE=<wave>; tools/g3_trace.py): s_memtime at the phase boundaries of one wave of every workgroup
-#ifdef G3_TRACE
-__device__ unsigned long long g3_trace_buf[1024][40];
-#define G3_STAMP(i_)                                                                                                 \
-    if (lane == 0 && wave == (G3_TRACE) && blockIdx.x < 1024) {                                                      \
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                           \
-        g3_trace_buf[blockIdx.x][i_] = __builtin_amdgcn_s_memtime();                                                 \
-        if ((i_) == 0) g3_trace_buf[blockIdx.x][38] = wall_clock64();                                                \
-        if ((i_) == 37) g3_trace_buf[blockIdx.x][39] = wall_clock64();                                               \
-    }
-#else
-#define G3_STAMP(i_)
-#endif
-
 template <int OFF> __device__ __forceinline__ void g3_write(uint32_t a, const u32x4& d) {
     asm volatile("ds_write_b128 %0, %1 offset:%2" ::"v"(a), "v"(d), "n"(OFF) : "memory");
 }
-
-#define G3_RD2(k_, f_) do { if (!(G3_ABL & 64)) m3_read2<k_>(f_, fa); } while (0)
 
 template <int DT, bool LN>
 __global__ __launch_bounds__(512, 1) void geglu3_kernel(G3P p) {
@@ -98,13 +78,11 @@ __global__ __launch_bounds__(512, 1) void geglu3_kernel(G3P p) {
     const int mtile = (seq >> 2) * 8 + xcd, part = seq & 3;
     if (mtile >= p.ntile) return;
     const int64_t mw0 = ((int64_t)mtile * G3_NW + wave) * 32;
-    G3_STAMP(0);
 
     const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(p.wpk), 0, G3_PARTS * G3_NCH * G3_STAGE, 0x00020000);
     const uint32_t dvoff = (uint32_t)(lane * 16);
     const int part_off = part * G3_NCH * G3_STAGE;
     auto dma = [&](int stage, int slot, int q) __attribute__((always_inline)) {
-        if (G3_ABL & 8) return;
         // (the immediate offset moves the memory address AND the LDS address: the wave's three 1 KB pieces of a stage share one M0 / scalar offset)
         const m3_lds_ptr lp = (m3_lds_ptr)(smem + slot * G3_STAGE + wave * 3072);
         const int so = part_off + stage * G3_STAGE + wave * 3072;
@@ -139,7 +117,6 @@ __global__ __launch_bounds__(512, 1) void geglu3_kernel(G3P p) {
 #pragma unroll
             for (int i = 0; i < 12; ++i) stg[h][i] = *(g3_gptr16)(xb + go[i] + h * 384);
     }
-    G3_STAMP(1);
     // this part's bias table (3 KB) -> LDS by the DMA as well (waves 0..2, one 1 KB piece each)
     if (wave < 3) {
         const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.b1p), 0, G3_PARTS * G3_B1_BYTES, 0x00020000);
@@ -149,7 +126,6 @@ __global__ __launch_bounds__(512, 1) void geglu3_kernel(G3P p) {
     for (int s = 0; s < 2; ++s)
 #pragma unroll
         for (int q = 0; q < 3; ++q) dma(s, s, q);  // (stages 0, 1 -> slots 0, 1; slots 2.. hold the transposition until the barrier below)
-    G3_STAMP(2);
     V8 xf[G3_KS];
     {
         const uint32_t tw = (uint32_t)(size_t)(m3_lds_ptr)smem + (uint32_t)(2 * G3_STAGE + wave * G3_TROWS);
@@ -175,7 +151,6 @@ __global__ __launch_bounds__(512, 1) void geglu3_kernel(G3P p) {
         }
     }
     if (LN) layernorm_panel<DT, G3_KS, true>(xf, p.gamma, p.beta, p.eps, l31, half);
-    G3_STAMP(3);
     // the panel moves to AGPRs HERE, once (left to the allocator, part of it stays in the VGPRs the LayerNorm wrote and is copied in front of every MFMA)
 #pragma unroll
     for (int k = 0; k < G3_KS; ++k) asm volatile("" : "+a"(xf[k]));
@@ -191,20 +166,18 @@ __global__ __launch_bounds__(512, 1) void geglu3_kernel(G3P p) {
     const int64_t m0 = mw0 + l31;
     uint8_t* const orow = p.out + ((m0 < p.M ? m0 : 0) * G3_HID + part * (G3_NCH * 16) + 8 * half) * 2;
     const bool ok = m0 < p.M;
-    G3_STAMP(4);
     __syncthreads();  // the bias table is in LDS, every wave is done with the transposition region
 #pragma unroll
     for (int s = 2; s < G3_NS - 1; ++s)
 #pragma unroll
         for (int q = 0; q < 3; ++q) dma(s, s, q);
-    G3_STAMP(5);
 
     // the activated chunk c (C layout: units 4 half + {0..3}, 8 + 4 half + {0..3}) -> 8 consecutive units per lane -> one 16-byte store
     auto store_h = [&](const V8& hn, int c) __attribute__((always_inline)) {
         const uint4 u = as_u4<DT>(hn);
         const auto s0 = __builtin_amdgcn_permlane32_swap(u.x, u.z, false, false);
         const auto s1 = __builtin_amdgcn_permlane32_swap(u.y, u.w, false, false);
-        if (ok && !(G3_ABL & 32)) *reinterpret_cast<uint4*>(orow + c * 32) = make_uint4(s0[0], s1[0], s0[1], s1[1]);
+        if (ok) *reinterpret_cast<uint4*>(orow + c * 32) = make_uint4(s0[0], s1[0], s0[1], s1[1]);
     };
 
     // iteration i: the 24 MFMAs of chunk i into `anxt` with the GEGLU of chunk i - 1 (`acur`) one phase behind each of the first 16, then the wave's
@@ -213,7 +186,7 @@ __global__ __launch_bounds__(512, 1) void geglu3_kernel(G3P p) {
         asm volatile("s_waitcnt vmcnt(12)" ::: "memory");  // stage i has landed for this wave's pieces (stores only make the count stricter)
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
-        if (!(G3_ABL & 16)) __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
         const uint32_t fa = fbase + (uint32_t)(slot * G3_STAGE);
         const uint32_t ta = tbase + (uint32_t)(i * 128);
@@ -221,15 +194,14 @@ __global__ __launch_bounds__(512, 1) void geglu3_kernel(G3P p) {
         const int nslot = slot == 0 ? G3_NS - 1 : slot - 1;
 
         u32x4 bq[4], f0[2], f1[2], f2[2];  // fragments two steps ahead (eight waves share the LDS pipe: one step ahead left every step waiting on it)
-        if (G3_ABL & 64) f0[0] = f0[1] = f1[0] = f1[1] = f2[0] = f2[1] = u32x4{0u, 0u, 0u, 0u};
         V8 hn;
         M3Geglu<DT> gg;
         m3_read<0>(bq[0], ta);
         m3_read<16>(bq[1], ta);
         m3_read<32>(bq[2], ta);
         m3_read<48>(bq[3], ta);
-        G3_RD2(0, f0);
-        G3_RD2(2, f1);
+        m3_read2<0>(f0, fa);
+        m3_read2<2>(f1, fa);
         __builtin_amdgcn_sched_barrier(0);
 
         // MFMA slot m (k-step m) and what follows it: the 16 GEGLU phases of chunk i - 1 behind two of every three MFMAs, the wave's three DMA pieces and
@@ -239,18 +211,16 @@ __global__ __launch_bounds__(512, 1) void geglu3_kernel(G3P p) {
             const int g = m / 3, o = m % 3;           // group of three MFMAs: phases 2 g, 2 g + 1 behind the first two
             if (o < 2) {
                 const int ph = 2 * g + o, r = 2 * (ph / 4);
-                if (!(G3_ABL & 1)) {
-                    if ((ph & 3) == 0) gg.ph1(acur[8 + r], acur[9 + r]);
-                    else if ((ph & 3) == 1) gg.ph2();
-                    else if ((ph & 3) == 2) gg.ph3();
-                    else gg.template ph4<V8, EL>(acur[r], acur[r + 1], hn, r);
-                }
+                if ((ph & 3) == 0) gg.ph1(acur[8 + r], acur[9 + r]);
+                else if ((ph & 3) == 1) gg.ph2();
+                else if ((ph & 3) == 2) gg.ph3();
+                else gg.template ph4<V8, EL>(acur[r], acur[r + 1], hn, r);
             } else if (g >= 1 && g <= 3) {
                 dma(nstage, nslot, g - 1);
             }
         };
         auto mf = [&](int m, const V8& w) __attribute__((always_inline)) {
-            if (!(G3_ABL & 2)) G3Asm<DT>::acc(anxt, w, xf[m]);
+            G3Asm<DT>::acc(anxt, w, xf[m]);
             M3_PIN();
             after(m);
             M3_PIN();
@@ -261,7 +231,7 @@ __global__ __launch_bounds__(512, 1) void geglu3_kernel(G3P p) {
         };
 
         // ---- step 0: b1 (C-layout register order) is the C operand of the first MFMA ----
-        G3_RD2(4, f2);
+        m3_read2<4>(f2, fa);
         m3_wait_lgkm<4>();
         {
             f32x16 bias;
@@ -269,42 +239,38 @@ __global__ __launch_bounds__(512, 1) void geglu3_kernel(G3P p) {
             for (int qd = 0; qd < 4; ++qd)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) bias[qd * 4 + e] = __uint_as_float(bq[qd][e]);
-            if (!(G3_ABL & 2)) {
-                G3Asm<DT>::first(anxt, __builtin_bit_cast(V8, f0[0]), xf[0], bias);
-                asm volatile("s_nop 7\n\ts_nop 6" ::: "memory");  // (the b1 registers may be recycled right here: 13 wait states behind an MFMA that reads them as C)
-            } else {
-                anxt = bias;
-            }
+            G3Asm<DT>::first(anxt, __builtin_bit_cast(V8, f0[0]), xf[0], bias);
+            asm volatile("s_nop 7\n\ts_nop 6" ::: "memory");  // (the b1 registers may be recycled right here: 13 wait states behind an MFMA that reads them as C)
             M3_PIN();
             after(0);
             M3_PIN();
             mf(1, __builtin_bit_cast(V8, f0[1]));
         }
-        G3_RD2(6, f0);
+        m3_read2<6>(f0, fa);
         m3_wait_lgkm<4>();
         step(f1, 2);
-        G3_RD2(8, f1);
+        m3_read2<8>(f1, fa);
         m3_wait_lgkm<4>();
         step(f2, 4);
-        G3_RD2(10, f2);
+        m3_read2<10>(f2, fa);
         m3_wait_lgkm<4>();
         step(f0, 6);
-        G3_RD2(12, f0);
+        m3_read2<12>(f0, fa);
         m3_wait_lgkm<4>();
         step(f1, 8);
-        G3_RD2(14, f1);
+        m3_read2<14>(f1, fa);
         m3_wait_lgkm<4>();
         step(f2, 10);
-        G3_RD2(16, f2);
+        m3_read2<16>(f2, fa);
         m3_wait_lgkm<4>();
         step(f0, 12);
-        G3_RD2(18, f0);
+        m3_read2<18>(f0, fa);
         m3_wait_lgkm<4>();
         step(f1, 14);
-        G3_RD2(20, f1);
+        m3_read2<20>(f1, fa);
         m3_wait_lgkm<4>();
         step(f2, 16);
-        G3_RD2(22, f2);
+        m3_read2<22>(f2, fa);
         m3_wait_lgkm<4>();
         step(f0, 18);
         m3_wait_lgkm<2>();
@@ -316,16 +282,13 @@ __global__ __launch_bounds__(512, 1) void geglu3_kernel(G3P p) {
 
     int slot = 0;
 #pragma unroll 1
-    for (int i = 0; i < ((G3_ABL & 128) ? 2 : G3_NCH); i += 2) {
-        G3_STAMP(6 + i);
+    for (int i = 0; i < G3_NCH; i += 2) {
         iteration(i, slot, a0, b0);
         slot = slot == G3_NS - 1 ? 0 : slot + 1;
-        G3_STAMP(7 + i);
         iteration(i + 1, slot, b0, a0);
         slot = slot == G3_NS - 1 ? 0 : slot + 1;
     }
     static_assert(G3_NCH % 2 == 0, "the loop body is two iterations");
-    G3_STAMP(36);
     // ---- the last chunk's GEGLU (a0 after an even number of iterations) ----
     {
         V8 hn;
@@ -341,7 +304,6 @@ __global__ __launch_bounds__(512, 1) void geglu3_kernel(G3P p) {
         store_h(hn, G3_NCH - 1);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the tail's dummy re-loads must land before the workgroup's LDS is released)
-    G3_STAMP(37);
 }
 
 // ---- apad_geglu_pack: W1 [8C][C], b1 [8C] -> [4 parts][24 chunks][24 k-steps][64 lanes][8] + the fp32 bias table [4][24][2][16] ----
@@ -373,12 +335,6 @@ template <int DT, bool LN> int geglu3_launch(const G3P& p, hipStream_t s) {
 }
 
 }  // namespace
-
-#ifdef G3_TRACE
-extern "C" int apad_g3_trace_read(void* dst, int bytes) {
-    return hipMemcpyFromSymbol(dst, HIP_SYMBOL(g3_trace_buf), (size_t)bytes, 0, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
-}
-#endif
 
 extern "C" int64_t apad_geglu_packed_bytes(int32_t C) { return C == G3_C ? (int64_t)G3_PARTS * G3_NCH * G3_STAGE : -1; }
 extern "C" int64_t apad_geglu_packed_bias_floats(int32_t C) { return C == G3_C ? (int64_t)G3_PARTS * G3_NCH * 32 : -1; }

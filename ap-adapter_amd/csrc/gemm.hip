@@ -10,7 +10,6 @@
 // Staging: global -> registers (16 B/lane, coalesced along K) -> XOR-swizzled LDS (conflict-free
 // ds_read_b128 fragment reads); next K-tile's global loads are issued before the MFMAs of the current one.
 // Epilogue: accumulators -> LDS tile -> full-row 16 B stores (residual read with the same coalescing).
-#include <stdlib.h>
 #include <type_traits>
 #include "common.h"
 #include "f32_ops.h"
@@ -262,10 +261,7 @@ __global__ __launch_bounds__(256 * KG) void gemm_kernel(GemmP p) {
     // Global -> register staging, PF k-tiles ahead of the LDS copy.  Depths 2 and 3 were measured on the 64x64 variant
     // (the 640- and 384-wide levels): no gain (10.5 / 11.2 us vs 10.7 us at M=4096, K=640; 41.8 / 44.1 vs 39.9 us at
     // M=16128, K=1536) -- those launches are bound by the two barriers per k-tile, not by load latency -- so PF stays 1.
-#ifndef APAD_GEMM_PF64
-#define APAD_GEMM_PF64 1
-#endif
-    constexpr int PF = (TM == 64) ? APAD_GEMM_PF64 : 1;
+    constexpr int PF = 1;
     u32x4 ga[PF][NLD], gb[PF][NLD];  // (native vectors: HIP's uint4 class type kept such arrays in scratch)
     int ftap = 0, fc0 = 0;  // CONV3X3_FAST: filter tap and first channel of the NEXT k-tile to load (tiles load in order)
     auto gload = [&](int kt, u32x4* gA, u32x4* gB) {
@@ -845,7 +841,7 @@ int launch_ring(const GemmP& p, bool kgroups, hipStream_t s) {
     return go(gemm_ring_kernel<DT, EPI, OUTMODE, 1>);
 }
 
-// process-wide switch of the ring form (apad_set_gemm_ring): -1 = the APAD_GEMM_RING environment variable (default 0)
+// process-wide switch of the ring form (apad_set_gemm_ring): -1 = the default form (0)
 int g_ring_mode = -1;
 
 template <int DT, int AMODE, int EPI, int OUTMODE, int TM, int NS = 1, int KG = 1>
@@ -866,49 +862,32 @@ int launch(const GemmP& p, hipStream_t s) {
     const int64_t blocks128 = ((p.N + BN_OUT - 1) / BN_OUT) * ((p.M + 127) / 128);
     // long reductions amortise the under-fill: with K >= 1024 the 128-tile wins from ~1.25 workgroups per CU (measured:
     // conv 63x4 384->384 76.5 -> 71.5 us, FF2 M=16128 K=1536 38.5 -> 37.1 us), short-K launches prefer the 64-tile
-    constexpr int t128_min = 512;  // (A/B knob)
-    const bool t128 = blocks128 >= t128_min || (blocks128 >= 320 && t128_min <= 512 && p.K >= 1024);
-    if constexpr (AMODE == APAD_A_CONV3X3_FAST && EPI == APAD_EPI_NONE && OUTMODE == APAD_OUT_ROWMAJOR) {
-        // under-filled 3x3 convolutions (the 640- / 384-wide resnets: 90..180 k-tiles on a few hundred 64x64 tiles): K groups
-        constexpr int conv_kg = 0;  // (A/B knob)
-        if (!t128 && conv_kg >= 4) return launch_tm<DT, AMODE, EPI, OUTMODE, 64, 1, 4>(p, s);
-        if (!t128 && conv_kg >= 2) return launch_tm<DT, AMODE, EPI, OUTMODE, 64, 1, 2>(p, s);
-    }
+    const bool t128 = blocks128 >= 512 || (blocks128 >= 320 && p.K >= 1024);
     if constexpr (AMODE == APAD_A_CONV3X3_FAST || AMODE == APAD_A_CONV3X3 || AMODE == APAD_A_CONV1D) {
-        constexpr bool one_stage = false;
         // long reductions on launches of <= ~4 workgroups per CU: two LDS stages, one barrier per k-tile (larger grids
         // lose more from the halved residency than they gain: 250x16 128->128 118.9 -> 132.6 us)
-        if (p.K >= 2048 && blocks128 <= 1024 && !one_stage)
+        if (p.K >= 2048 && blocks128 <= 1024)
             return t128 ? launch_tm<DT, AMODE, EPI, OUTMODE, 128, 2>(p, s) : launch_tm<DT, AMODE, EPI, OUTMODE, 64, 2>(p, s);
     }
     if constexpr (AMODE == APAD_A_PLAIN && (EPI == APAD_EPI_NONE || EPI == APAD_EPI_GEGLU) && (OUTMODE == APAD_OUT_ROWMAJOR || OUTMODE == APAD_OUT_QKV) &&
                   !(EPI == APAD_EPI_GEGLU && OUTMODE == APAD_OUT_QKV)) {
-        // latency-bound launches: the LDS-DMA ring form (apad_set_gemm_ring / APAD_GEMM_RING: 0 off, 1 = grids the 128-tile rule calls
-        // under-filled, 2 = every launch; below APAD_GEMM_RING_MAX_M = 16000 rows).  Bit-equal to the tiled kernels (same k-summation order, K groups included).
-        static const int ring_env = [] { const char* e = getenv("APAD_GEMM_RING"); return e ? atoi(e) : 0; }();
-        constexpr int kg_mode_r = 2;
+        // latency-bound launches: the LDS-DMA ring form (apad_set_gemm_ring: 0 off, 1 = grids the 128-tile rule calls under-filled,
+        // 2 = every launch; below ring_max_m = 16000 rows).  Bit-equal to the tiled kernels (same k-summation order, K groups included).
         constexpr int ring_max_m = 16000;
-        const int ring_mode = g_ring_mode >= 0 ? g_ring_mode : ring_env;
-        constexpr int ring_max_wg = (1 << 30);
-        constexpr int ring_min_wg = 0;
-        const int64_t ring_wgs = ((p.M + 63) / 64) * (p.N / (EPI == APAD_EPI_GEGLU ? 32 : 64));
-        if (ring_mode && p.K >= 128 && p.M < ring_max_m && (!t128 || ring_mode >= 2) && ring_wgs <= ring_max_wg && ring_wgs >= ring_min_wg) {
-            constexpr int ring_kg = 1;
-            const bool kgroups = EPI == APAD_EPI_NONE && kg_mode_r >= 2 && p.K >= 384 && p.N >= 640;
-            if (!kgroups || ring_kg) {
-                const int rc = launch_ring<DT, EPI, OUTMODE>(p, kgroups, s);
-                if (rc <= 0) return rc;
-            }
+        const int ring_mode = g_ring_mode > 0 ? g_ring_mode : 0;
+        if (ring_mode && p.K >= 128 && p.M < ring_max_m && (!t128 || ring_mode >= 2)) {
+            const bool kgroups = EPI == APAD_EPI_NONE && p.K >= 384 && p.N >= 640;
+            const int rc = launch_ring<DT, EPI, OUTMODE>(p, kgroups, s);
+            if (rc <= 0) return rc;
         }
     }
     if constexpr (AMODE == APAD_A_PLAIN && EPI == APAD_EPI_NONE) {
         // K groups inside the workgroup for the skinny launches of the 640- / 384-wide levels.  The choice depends on (N, K) ONLY,
         // never on M, and both tile sizes implement it: a row's k-summation order must not change with the batch size -- a clip's
         // result is bit-identical whatever batch it rides in (tests/test_gpu_unet.py::test_full_size_clips_are_independent_of_their_batch)
-        constexpr int kg_mode = 2;  // (A/B knob: 1 = off)
         // (N >= 640: the 640-wide level's to_q / to_out / FF2 / q|k|v.  At N = 384 the FF2 of the 384-wide level, M = 16128 on 128-tiles,
         //  measured 39 -> 58 us with K groups: the rule stops short of it)
-        if (kg_mode >= 2 && p.K >= 384 && p.N >= 640)
+        if (p.K >= 384 && p.N >= 640)
             return t128 ? launch_tm<DT, AMODE, EPI, OUTMODE, 128, 1, 2>(p, s) : launch_tm<DT, AMODE, EPI, OUTMODE, 64, 1, 2>(p, s);
     }
     if (t128) return launch_tm<DT, AMODE, EPI, OUTMODE, 128>(p, s);

@@ -22,16 +22,12 @@
 //   * MFMA roles swapped against cgemm.hip (weights are the A operand): a lane's accumulators are 16 output channels of ONE pixel, so
 //     the epilogue packs, exchanges half-wave pairs (v_permlane32_swap) and stores 16 bytes per lane straight from registers -- no LDS
 //     round trip, no barrier
-#include <stdlib.h>
 #include <type_traits>
 #include <utility>
 #include "common.h"
 
 namespace {
 
-#ifndef HC_ABL
-#define HC_ABL 0  // ablation bits for timing-only probe builds (tools/ab_build.sh): 1 no DMA in the loop, 2 no fragment reads, 4 no MFMAs, 8 no stage barrier
-#endif
 constexpr uint32_t H_OOB = 0x80000000u;
 
 struct HcP {
@@ -51,15 +47,7 @@ struct HcP {
     int32_t ksplit;   // K slices per output tile (whole 64-channel chunks each); > 1: fp32 partial slabs, summed in slice order by hconv_reduce_kernel
     float* partial;   // [ksplit][M][N]
     uint32_t a_bytes, w_bytes;
-    unsigned long long* trace;  // (probe builds, HC_TRACE: 32 s_memtime stamps per workgroup; tools/hconv_trace.py)
 };
-#ifndef HC_TRACE
-#define HC_TRACE 0
-#endif
-#define HC_STAMP(k)                                                                   \
-    do {                                                                              \
-        if (HC_TRACE && p.trace && tid == 0 && (k) < 32) p.trace[blockIdx.x * 32 + (k)] = __builtin_amdgcn_s_memtime(); \
-    } while (0)
 
 typedef __attribute__((address_space(3))) void* lds_ptr;
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
@@ -91,18 +79,6 @@ template <int N_> __device__ __forceinline__ void h_wait_vm() {
 
 template <int... S, class F> __device__ __forceinline__ void h_for_each(std::integer_sequence<int, S...>, F&& f) {
     (f(std::integral_constant<int, S>{}), ...);
-}
-
-#ifndef HC_AGPR
-#define HC_AGPR 0  // 1: accumulators in the AGPR half of the register file (inline-asm MFMAs); 0: the compiler's VGPR-form MFMAs
-#endif
-// acc += a . b with the accumulator block in AGPRs: the 16-register C read / D write-back of every MFMA then goes through the accumulator file's
-// ports and leaves the VGPR ports to the fragment reads coming back from LDS.  (a, b: fragment registers written by ds_read_b128, waited for with
-// lgkmcnt by the caller -- no VALU-write -> MFMA-read hazard; back-to-back MFMAs on the same accumulator need no wait states)
-template <int DT> __device__ __forceinline__ void h_mfma_acc(f32x16& acc, const unsigned int __attribute__((ext_vector_type(4)))& a,
-                                                              const unsigned int __attribute__((ext_vector_type(4)))& b) {
-    if constexpr (DT == APAD_BF16) asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b));
-    else asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b));
 }
 
 template <int OFF> __device__ __forceinline__ void h_read(u32x4& dst, uint32_t addr) {
@@ -239,11 +215,9 @@ __global__ __launch_bounds__(T::NT) void hconv_kernel(HcP p) {
     };
     // ONE fragment read of MFMA step KSI (0..3 of the chunk; k-chunk 2 KSI + half) into register set SET: IDX < MI the pixel tile IDX (from
     // a0, or a0n when NEXT), else the weight tile IDX - MI at bb (= bfo[KSI & 1] + ring slot)
-    bool abl_reads_off = false;  // (HC_ABL & 2: the prologue still fills both register sets with real data, so the MFMAs draw their real power)
     auto read_one = [&](auto set_tag, auto ks_tag, auto idx_tag, auto next_tag, uint32_t bb) {
         constexpr int SET = decltype(set_tag)::value, KSI = decltype(ks_tag)::value, IDX = decltype(idx_tag)::value;
         constexpr bool NEXT = decltype(next_tag)::value != 0;
-        if ((HC_ABL & 2) && abl_reads_off) return;
         if constexpr (IDX < MI) {
             h_read<0>(fa[SET][IDX], (NEXT ? a0n[IDX] : a0[IDX]) ^ (uint32_t)(KSI << 5));
         } else if constexpr (IDX < MI + NJ) {
@@ -271,11 +245,8 @@ __global__ __launch_bounds__(T::NT) void hconv_kernel(HcP p) {
     };
     if (tid < 16) *reinterpret_cast<uint4*>(smem + T::OFF_Z + tid * 16) = make_uint4(0, 0, 0, 0);  // the zero region
     const int ntiles = p.m_tiles * p.n_tiles * p.ksplit;
-    HC_STAMP(0);
     setup_tile(blockIdx.x);
     issue_prologue();
-    HC_STAMP(1);
-    int tstamp = 2;
 #pragma unroll 1
     for (int tl = blockIdx.x; tl < ntiles; tl += gridDim.x) {
     const int cm0 = m0, cn0 = n0, cks = kslice, cb = c_begin, ce = c_end;  // (the next tile's setup overwrites them before this tile's epilogue)
@@ -291,12 +262,6 @@ __global__ __launch_bounds__(T::NT) void hconv_kernel(HcP p) {
 #pragma unroll
     for (int i = 0; i < MI; ++i) a0[i] = a0n[i] = tap_address(i, 0, 0);
     h_for_each(std::make_integer_sequence<int, NRD>{}, [&](auto idx_tag) { read_one(I0{}, I0{}, idx_tag, I0{}, bfo[0]); });
-    HC_STAMP(tstamp);  // prologue waited for, first reads requested
-    if (HC_ABL & 2) {
-        h_for_each(std::make_integer_sequence<int, NRD>{}, [&](auto idx_tag) { read_one(std::integral_constant<int, 1>{}, std::integral_constant<int, 1>{}, idx_tag, I0{}, bfo[1]); });
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        abl_reads_off = true;
-    }
 
     // ---- main loop: chunks (run time) x SPC stages (unrolled) ----
     int slot = 0;  // ring slot of the current stage
@@ -309,13 +274,12 @@ __global__ __launch_bounds__(T::NT) void hconv_kernel(HcP p) {
             constexpr int TAP = S / SPT, KS0 = (S % SPT) * KS;  // first MFMA step (of the chunk's four) of this stage
             // (1) stage t + 1 has landed: at most what the previous iteration issued may be outstanding (the halo piece goes first in an
             //     iteration, so a halo piece is covered two iterations after its issue)
-            if (HC_TRACE && tl == (int)blockIdx.x && c == cb + 1 && S < 12) HC_STAMP(19 + S);  // (probe: the stages of the tile's SECOND chunk)
             constexpr bool prevA = S >= 1 && S - 1 < NLD;  // the previous iteration issued a halo piece (not in the last chunk)
             if (!last) h_wait_vm<PBW + (prevA ? 1 : 0)>();
             else if (S == 0 || S - 1 + 3 < SPC) h_wait_vm<PBW>();
             else h_wait_vm<0>();
-            if (!(HC_ABL & 128)) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            if (!(HC_ABL & 8)) H_BARRIER();
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            H_BARRIER();
             // (2) the MFMA steps.  Behind single MFMAs: the fragment reads of step k + 1 (of the next stage behind the last step: the barrier
             //     above certified it), the next tap's addresses, and this iteration's requests -- halo piece S of the next chunk, weight stage
             //     t + 3 (into the slot read in iteration t - 1)
@@ -331,14 +295,11 @@ __global__ __launch_bounds__(T::NT) void hconv_kernel(HcP p) {
                 constexpr int NTAP = (TAP + 1) % 9;
                 const bool pf = SAME || S + 1 < SPC || !last;
                 const uint32_t bb = bfo[PKSI & 1] + (uint32_t)((SAME ? slot : nslot) * T::STAGE_B);
-                const bool dma_here = !(HC_ABL & 1) && grp == (KK == 0 ? 0 : (KK == KS / 2 ? 1 : 2));
+                const bool dma_here = grp == (KK == 0 ? 0 : (KK == KS / 2 ? 1 : 2));
                 h_for_each(std::make_integer_sequence<int, NMF>{}, [&](auto idx_tag) {
                     constexpr int IDX = decltype(idx_tag)::value;
-                    if (!(HC_ABL & 4)) {
-                        if constexpr (HC_AGPR) h_mfma_acc<DT>(acc[IDX / MI][IDX % MI], fb[SET][IDX / MI], fa[SET][IDX % MI]);
-                        else acc[IDX / MI][IDX % MI] = E::mfma32(__builtin_bit_cast(typename E::v8, fb[SET][IDX / MI]),
-                                                                 __builtin_bit_cast(typename E::v8, fa[SET][IDX % MI]), acc[IDX / MI][IDX % MI]);
-                    }
+                    acc[IDX / MI][IDX % MI] = E::mfma32(__builtin_bit_cast(typename E::v8, fb[SET][IDX / MI]),
+                                                        __builtin_bit_cast(typename E::v8, fa[SET][IDX % MI]), acc[IDX / MI][IDX % MI]);
                     __builtin_amdgcn_sched_barrier(0);
                     if constexpr (IDX < RSLOTS) if (pf) {
                         read_one(std::integral_constant<int, SET ^ 1>{}, std::integral_constant<int, PKSI>{}, std::integral_constant<int, 2 * IDX>{},
@@ -356,7 +317,7 @@ __global__ __launch_bounds__(T::NT) void hconv_kernel(HcP p) {
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 });
-                if constexpr (SAME && !(HC_ABL & 64)) {
+                if constexpr (SAME) {
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                     __builtin_amdgcn_sched_barrier(0);
                 }
@@ -395,11 +356,7 @@ __global__ __launch_bounds__(T::NT) void hconv_kernel(HcP p) {
             if (p.bias && p.ksplit == 1) braw[j][g] = *reinterpret_cast<const uint2*>(p.bias + (int64_t)n * 2);
             if (rg_table && p.ksplit == 1) traw[j][g] = *reinterpret_cast<const uint2*>(p.rg + (step * p.ld_rg + n) * 2);
         }
-    abl_reads_off = false;
-    HC_STAMP(tstamp + 1);  // main loop done
     H_BARRIER();
-    HC_STAMP(tstamp + 2);
-    if constexpr (HC_AGPR) asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");  // the last MFMAs' results before the compiler's v_accvgpr_read
     // the next tile's setup + requests go out first: their DMA latency runs under this tile's epilogue.  (The 256 x 256 form keeps 164 bytes per lane of
     // loop-invariant addressing state in scratch -- written in the prologue, reloaded here: profiles/r06_pmc_hconv256_v6.txt shows it as 22 MB of WRITE_SIZE
     // beside the 32.8 MB output; moving this setup behind the epilogue or packing the results first did not remove it -- the main loop's 128 accumulators +
@@ -408,7 +365,6 @@ __global__ __launch_bounds__(T::NT) void hconv_kernel(HcP p) {
         setup_tile(tl + (int)gridDim.x);
         issue_prologue();
     }
-    HC_STAMP(tstamp + 3);  // next tile's setup + requests
     // ---- epilogue: (acc + bias) + time-embedding row -> storage type -> transposed through a wave-private LDS tile (ring slot 3 + halo buffer 1: idle until
     //      the next tile's first stage barrier) -> (+ residual) -> full-line stores.  Lane (pixel l31, half) holds channels 8 g + 4 half + (0..3) of a
     //      32-channel block in accumulators 4 g .. 4 g + 3: one ds_write_b64 per group; a row of the wave's NJ x 32 channels is then read back by NJ x 4
@@ -444,7 +400,6 @@ __global__ __launch_bounds__(T::NT) void hconv_kernel(HcP p) {
                 rres[k] = *reinterpret_cast<const uint4*>(p.residual + ((int64_t)m * p.ldr + cn_w + (lane % LPR) * 8) * 2);
             }
         }
-        if (HC_TRACE && ntiles <= (int)gridDim.x) HC_STAMP(8 + 2 * i);
         const int mp = mrow0 + l31 < p.M ? mrow0 + l31 : p.M - 1;
         const int64_t grp = rg_rows ? mp / p.rows_per_group + step : 0;
 #pragma unroll
@@ -479,14 +434,11 @@ __global__ __launch_bounds__(T::NT) void hconv_kernel(HcP p) {
                 for (int e = 0; e < 8; ++e) f[e] += rr[e];
                 o = pack8<DT>(f);
             }
-            if (m < p.M && !((HC_ABL & 32) && p.Btot > 0))  // (ablation 32: the stores stay in the code, no lane executes them)
+            if (m < p.M)
                 *reinterpret_cast<uint4*>(p.out + ((int64_t)m * p.ldo + cn_w + (lane % LPR) * 8) * 2) = o;
         }
-        if (HC_TRACE && ntiles <= (int)gridDim.x) HC_STAMP(8 + 2 * i + 1);
     }
     }
-    HC_STAMP(tstamp + 4);  // epilogue issued
-    tstamp += 5;
     }  // tiles
 }
 
@@ -507,8 +459,7 @@ __global__ void hconv_pack_kernel(const TE* __restrict__ w, TE* __restrict__ out
     *reinterpret_cast<uint4*>(out + idx * 8) = v;
 }
 
-int64_t g_hconv_launches = 0;
-unsigned long long* g_hconv_trace = nullptr;  // (tests assert the route with it; not synchronised: a diagnostic)
+int64_t g_hconv_launches = 0;  // (tests assert the route with it; not synchronised: a diagnostic)
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // Narrow form: N <= 16 output channels (the UNet's conv_out, 128 -> 8 at 4000 pixels; modeling_audioldm2.py:867).  The im2col kernels pad N to a
@@ -751,8 +702,7 @@ template <int DT, class T> int hc_launch(const HcP& p, hipStream_t s) {
         if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
         cus[dev] = n;
     }
-    static const int grid_cap = [] { const char* e = getenv("APAD_HCONV_GRID"); return e ? atoi(e) : 0; }();  // A/B knob: workgroups (0 = one per CU)
-    const int tiles = p.m_tiles * p.n_tiles * p.ksplit, cap = grid_cap > 0 ? grid_cap : cus[dev];
+    const int tiles = p.m_tiles * p.n_tiles * p.ksplit, cap = cus[dev];
     hipLaunchKernelGGL(kern, dim3((unsigned)(tiles < cap ? tiles : cap)), dim3(T::NT), T::SMEM, s, p);
     int rc = apad_check_launch("apad_gemm(halo convolution)");
     if (rc || p.ksplit == 1) return rc;
@@ -777,8 +727,6 @@ extern "C" int64_t apad_conv_halo_workspace_bytes(int64_t M, int64_t N, int64_t 
 }
 
 extern "C" int64_t apad_hconv_launch_count(void) { return g_hconv_launches; }
-// probe builds (-DHC_TRACE=1) only: device buffer of 32 x workgroups uint64 time stamps; not part of the ABI header
-extern "C" void apad_hconv_set_trace(void* buf) { g_hconv_trace = (unsigned long long*)buf; }
 
 // bytes of the packed form: the wide form re-lays the N * 9 * Cin elements; the narrow form (N <= 16) is 18 fragments of 1 KB per 64-channel chunk
 extern "C" int64_t apad_conv_halo_packed_bytes(int64_t N, int64_t Cin) { return N <= 16 ? (Cin / 64) * 18 * 1024 : N * 9 * Cin * 2; }
@@ -801,8 +749,7 @@ extern "C" int apad_conv_halo_pack(const void* w, void* out, int64_t N, int64_t 
 // Called by apad_gemm before its other dispatches.  1 = outside this kernel's envelope (the caller goes on), 0 = launched, < 0 = error.
 // The envelope depends on the layer (geometry, channels, the packed weight form), never on the row count.
 int apad_hconv_try(const apad_gemm_desc* d, hipStream_t s) {
-    static const int mode = [] { const char* e = getenv("APAD_HCONV"); return e ? atoi(e) : 1; }();  // A/B knob: 0 = off
-    if (!mode || !d->w_halo || d->a_mode != APAD_A_CONV3X3) return 1;
+    if (!d->w_halo || d->a_mode != APAD_A_CONV3X3) return 1;
     if (d->dtype != APAD_BF16 && d->dtype != APAD_F16) return 1;
     if (d->epilogue != APAD_EPI_NONE || d->out_mode != APAD_OUT_ROWMAJOR || d->rowstat_out || d->rowstat_in) return 1;
     if (d->stride != 1 || d->src_batch_mod != 0 || d->conv_asym_pad || d->residual_row_mod != 0 || d->Cin % 64 != 0 || d->K != 9 * (int64_t)d->Cin) return 1;
@@ -849,7 +796,7 @@ int apad_hconv_try(const apad_gemm_desc* d, hipStream_t s) {
     p.H = H; p.W = W; p.Wlog = __builtin_ctz((unsigned)W); p.Hs = d->Hin; p.Ws = d->Win; p.Btot = (int32_t)Btot;
     p.m_tiles = (int32_t)((d->M + BM - 1) / BM); p.n_tiles = (int32_t)(d->N / BNc); p.nchunks = d->Cin / 64;
     p.ksplit = ksplit; p.partial = (float*)d->workspace;
-    p.a_bytes = (uint32_t)a_bytes; p.w_bytes = (uint32_t)w_bytes; p.trace = g_hconv_trace;
+    p.a_bytes = (uint32_t)a_bytes; p.w_bytes = (uint32_t)w_bytes;
     if (d->dtype == APAD_BF16) return cfg == 0 ? hc_launch<APAD_BF16, HcA>(p, s) : hc_launch<APAD_BF16, HcB>(p, s);
     return cfg == 0 ? hc_launch<APAD_F16, HcA>(p, s) : hc_launch<APAD_F16, HcB>(p, s);
 }

@@ -36,30 +36,9 @@ constexpr float NEG_BIG = -1.0e30f;
 
 #include "short_seg.h"
 
-#ifndef HS_NSET
-#define HS_NSET 8  // register sets of weight fragments = k-steps a fragment is requested ahead of its use (per wave: NSET x NT KB in flight)
-#endif
-#ifndef HS_PRE
-#define HS_PRE 2  // of those, the sets requested BEFORE the sample's rows are normalised (the rest right after: a wave that is still pushing 16 KB
-                  // of weight requests into the memory pipe cannot start on rows that have long arrived)
-#endif
-#ifndef HS_ABL
-#define HS_ABL 0  // timing ablations (tools/ab_build.sh; results are wrong): 1 = weight fragments loaded once, 2 = no attention phase, 4 = no projection MFMAs
-#endif
-
-// probe build (tools/ab_build.sh <tag> hsattn.hip -DHS_TRACE=<wave>; tools/hs_trace.py): s_memtime at the phase boundaries of one wave of every
-// workgroup + the 100 MHz wall clock at its start / end.  Never part of the product library.
-#ifdef HS_TRACE
-__device__ unsigned long long hs_trace_buf[2][1024][16];
-#define HS_STAMP(k_, i_)                                                                                   \
-    if (lane == 0 && wave == (HS_TRACE) && blockIdx.x < 1024) {                                            \
-        hs_trace_buf[k_][blockIdx.x][i_] = __builtin_amdgcn_s_memtime();                                   \
-        if ((i_) == 0) hs_trace_buf[k_][blockIdx.x][14] = wall_clock64();                                  \
-        if ((i_) == 9) hs_trace_buf[k_][blockIdx.x][15] = wall_clock64();                                  \
-    }
-#else
-#define HS_STAMP(k_, i_)
-#endif
+constexpr int HS_NSET = 8;  // register sets of weight fragments = k-steps a fragment is requested ahead of its use (per wave: NSET x NT KB in flight)
+constexpr int HS_PRE = 2;   // of those, the sets requested BEFORE the sample's rows are normalised (the rest right after: a wave that is still pushing 16 KB
+                            // of weight requests into the memory pipe cannot start on rows that have long arrived)
 
 // wave-uniform global pointer pinned to SGPRs (xattn.hip): loads take the scalar base + 32-bit lane offset form
 typedef const __attribute__((address_space(1))) uint8_t* hs_gptr;
@@ -169,14 +148,12 @@ __device__ __forceinline__ void hs_project(const hs_gptr (&wb)[NT], uint32_t lof
     t[s_][1] = as_v8<DT>(*reinterpret_cast<const uint4*>(xs + 32 * XROWB + (kk_) * 32));
 #define HS_MM(i_, s_)                                                                               \
     _Pragma("unroll") for (int j = 0; j < NT; ++j) {                                                \
-        if (!(HS_ABL & 4)) {                                                                        \
-            if (SWAP1 && j == 1) {                                                                  \
-                acc[j][0] = E::mfma32(t[s_][0], wf[i_][j], acc[j][0]);                              \
-                acc[j][1] = E::mfma32(t[s_][1], wf[i_][j], acc[j][1]);                              \
-            } else {                                                                                \
-                acc[j][0] = E::mfma32(wf[i_][j], t[s_][0], acc[j][0]);                              \
-                acc[j][1] = E::mfma32(wf[i_][j], t[s_][1], acc[j][1]);                              \
-            }                                                                                       \
+        if (SWAP1 && j == 1) {                                                                      \
+            acc[j][0] = E::mfma32(t[s_][0], wf[i_][j], acc[j][0]);                                  \
+            acc[j][1] = E::mfma32(t[s_][1], wf[i_][j], acc[j][1]);                                  \
+        } else {                                                                                    \
+            acc[j][0] = E::mfma32(wf[i_][j], t[s_][0], acc[j][0]);                                  \
+            acc[j][1] = E::mfma32(wf[i_][j], t[s_][1], acc[j][1]);                                  \
         }                                                                                           \
     }
     HS_LDT(0, 0);
@@ -186,10 +163,8 @@ __device__ __forceinline__ void hs_project(const hs_gptr (&wb)[NT], uint32_t lof
         for (int i = 0; i < NSET; ++i) {
             HS_LDT(kk + i + 1, (i + 1) & 1);
             HS_MM(i, i & 1);
-            if (!(HS_ABL & 1)) {
 #pragma unroll
-                for (int j = 0; j < NT; ++j) wf[i][j] = __builtin_bit_cast(typename E::v8, hs_ld16(wb[j] + (kk + i + NSET) * 1024, loff));
-            }
+            for (int j = 0; j < NT; ++j) wf[i][j] = __builtin_bit_cast(typename E::v8, hs_ld16(wb[j] + (kk + i + NSET) * 1024, loff));
         }
 #pragma unroll
         for (int i = 0; i < NSET; ++i) {
@@ -223,7 +198,7 @@ __device__ __forceinline__ void hs_project(const hs_gptr (&wb)[NT], uint32_t lof
 // through its XCD's memory-side port (~1 TB/s per XCD: what the prologue of these kernels waits for), so the map decides how many bytes that
 // is: with m sample classes on the XCD axis an XCD sees 1 / m of the samples' rows and m / 2 of the four weight quarters.  m = 2 (id = 4 b + q):
 // one quarter, half of the rows; m = 8: all four quarters, an eighth of the rows.  Rows are 80 KB per sample, a quarter is 600 KB (q|k|v) or
-// 200 KB (q / to_out): m = 4 for self-attention, 8 for the others.
+// 200 KB (q / to_out): m = 2 for the GEGLU kernel, 8 for the others.
 __device__ __forceinline__ void hs_decode(int id, int m, int& b, int& q) {
     const int x = id & 7, r = id >> 3;
     const int pl = 8 / m, ph = 4 / pl;  // quarter classes on the XCD axis / on the remaining axis
@@ -260,7 +235,6 @@ __global__ __launch_bounds__(512) void hs_attn_kernel(HsP p) {
     if (b >= p.B) return;  // (the grid is padded to whole XCD rounds)
     const int N = p.N;
 
-    HS_STAMP(0, 0);
     // ---- 0. the sample's rows are requested first, the weight stream right behind them: wave w owns row tiles w (and w + 8) of the pair's block ----
     uint4 xr[HS_CH];
     hs_rows_load(xr, p.x + (int64_t)b * N * HS_C * 2, N, tid);
@@ -285,7 +259,6 @@ __global__ __launch_bounds__(512) void hs_attn_kernel(HsP p) {
     }
     if (tid < NTILE * 8 && p.wbias != nullptr)  // the pair's fp32 bias -> LDS (read by the projection epilogue)
         *reinterpret_cast<float4*>(BIAS + tid * 16) = *reinterpret_cast<const float4*>(p.wbias + pr * NTILE * 32 + tid * 4);
-    HS_STAMP(0, 1);
 
     // ---- 1. LayerNorm -> X ----
     hs_rows_store<DT, NORM>(xr, p.eps, N, X, tid);
@@ -295,9 +268,7 @@ __global__ __launch_bounds__(512) void hs_attn_kernel(HsP p) {
 #pragma unroll
             for (int j = 0; j < NT; ++j) wf[i][j] = __builtin_bit_cast(typename E::v8, hs_ld16(wb[j] + i * 1024, loff));
     }
-    HS_STAMP(0, 2);
     __syncthreads();
-    HS_STAMP(0, 3);
 
     // ---- 2. projections -> Q (K, V^T) ----
     if (proj) {
@@ -312,7 +283,6 @@ __global__ __launch_bounds__(512) void hs_attn_kernel(HsP p) {
             hs_project<DT, NT, NSET, SELF>(wb, loff, X + l31 * XROWB + half * 16, wf, acc);
         else
             hs_project<DT, NT, NSET, false>(wb, loff, X + l31 * XROWB + half * 16, wf, acc);
-        HS_STAMP(0, 4);
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
             const int t = tile[j];
@@ -357,7 +327,7 @@ __global__ __launch_bounds__(512) void hs_attn_kernel(HsP p) {
     constexpr bool LONG2 = NS2 > 4;  // ... in 64-key chunks with a running maximum / sum (long_segment: 129 .. 512 audio keys)
     constexpr bool SPLITF = DUAL && !BIG2 && NS1 + NS2 > 3;  // both resident sets would not fit: the second segment loads as it goes too
     constexpr int NSB = (DUAL && !BIG2 && !SPLITF) ? NS2 : 1;
-    const bool att = wave < 4 && !(HS_ABL & 2);
+    const bool att = wave < 4;
     ShortFr<DT, D, NS1> f1;
     ShortFr<DT, D, NSB> f2;
     // the fragment sources of the head's two segments: fragment-packed sets (vtN == nullptr: apad_rows_pack_kv, round 6) or apad_attention's tensors
@@ -375,9 +345,7 @@ __global__ __launch_bounds__(512) void hs_attn_kernel(HsP p) {
             else short_load<DT, D, NSB>(f2, HS_RAW2, l31, half);
         }
     }
-    HS_STAMP(0, 5);
     __syncthreads();
-    HS_STAMP(0, 6);
     if (att) {
         if (SELF) short_load<DT, D, NS1>(f1, KvRaw<DT, D>{K + h * D * 2, QROWB / 2, VT + h * D * VROWB, N, VROWB / 2}, l31, half);
         typename E::v8 qf[KC];
@@ -427,7 +395,6 @@ __global__ __launch_bounds__(512) void hs_attn_kernel(HsP p) {
                     o[dt][r] = t + (float)(typename E::elem)(p.scale2 * a);
                 }
         }
-        HS_STAMP(0, 7);
         // O(head, panel) over this wave's own q values in the Q tile (nobody else reads them)
 #pragma unroll
         for (int dt = 0; dt < DTT; ++dt)
@@ -449,7 +416,6 @@ __global__ __launch_bounds__(512) void hs_attn_kernel(HsP p) {
     __syncthreads();
     // ---- 4. O(pair) [64][160] -> HBM, whole 16-byte chunks ----
     hs_tile_to_rows(Q, p.out + (int64_t)b * N * HS_C * 2, pr * HS_PW, N, tid);
-    HS_STAMP(0, 9);
 }
 
 // ---- the feed-forward's first half at the same level: H = value * gelu(gate), [value | gate] = Linear(LayerNorm(x)) (diffusers GEGLU: proj 640 -> 5120) ----
@@ -578,7 +544,6 @@ __global__ __launch_bounds__(512) void hs_out_kernel(HoP p) {
     hs_decode(blockIdx.x, p.xm, b, cq);
     if (b >= p.B) return;
     const int N = p.N;
-    HS_STAMP(1, 0);
     // the O rows first, then this wave's weight stream, then what the epilogue needs (bias in the C layout, the residual chunks of the
     // final coalesced pass): everything is in flight before the first wait
     uint4 xr[HS_CH];
@@ -594,7 +559,6 @@ __global__ __launch_bounds__(512) void hs_out_kernel(HoP p) {
 #pragma unroll
         for (int i = 0; i < PRE; ++i) wf[i][0] = __builtin_bit_cast(typename E::v8, hs_ld16(wb[0] + i * 1024, loff));
     }
-    HS_STAMP(1, 1);
     hs_rows_store<DT, false>(xr, 0.f, N, X, tid);
     if (proj) {
 #pragma unroll
@@ -610,9 +574,7 @@ __global__ __launch_bounds__(512) void hs_out_kernel(HoP p) {
         rres[it] = make_uint4(0u, 0u, 0u, 0u);
         if (p.res != nullptr && row < N) rres[it] = *reinterpret_cast<const uint4*>(p.res + (((int64_t)b * N + row) * HS_C + cq * HS_PW + ch * 8) * 2);
     }
-    HS_STAMP(1, 2);
     __syncthreads();
-    HS_STAMP(1, 3);
     if (proj) {
         f32x16 acc[1][2];
 #pragma unroll
@@ -620,7 +582,6 @@ __global__ __launch_bounds__(512) void hs_out_kernel(HoP p) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[0][mt][r] = 0.f;
         hs_project<DT, 1, NSET, false>(wb, loff, X + l31 * XROWB + half * 16, wf, acc);
-        HS_STAMP(1, 4);
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             const typename E::v4 bv = __builtin_bit_cast(typename E::v4, bq[g]);
@@ -668,7 +629,6 @@ __global__ __launch_bounds__(512) void hs_out_kernel(HoP p) {
             if (p.rs_out != nullptr && (lane & 3) == 0) *reinterpret_cast<float2*>(p.rs_out + (((int64_t)b * N + row) * 20 + cq * NTILE + (ch >> 2)) * 2) = make_float2(s1, s2);
         }
     }
-    HS_STAMP(1, 9);
 }
 
 // ---- the feed-forward's second half: out = x + (H . W2^T + b2), H [64][2560] per sample, workgroup = (sample, output-column quarter) ----
@@ -916,12 +876,6 @@ inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) =
 
 }  // namespace
 
-#ifdef HS_TRACE
-extern "C" int apad_hs_trace_read(void* dst, int bytes) {
-    return hipMemcpyFromSymbol(dst, HIP_SYMBOL(hs_trace_buf), (size_t)bytes, 0, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
-}
-#endif
-
 extern "C" int apad_sizeof_hs_attn_desc(void) { return (int)sizeof(apad_hs_attn_desc); }
 extern "C" int apad_sizeof_hs_out_desc(void) { return (int)sizeof(apad_hs_out_desc); }
 
@@ -955,8 +909,7 @@ extern "C" int apad_hs_attention(const apad_hs_attn_desc* d, void* stream) {
     p.out = (uint8_t*)d->out;
     p.B = d->B; p.N = d->N; p.L1 = d->L1; p.Lpad1 = d->Lpad1; p.L2 = d->L2; p.Lpad2 = d->Lpad2;
     p.eps = d->ln_eps; p.scale_log2 = d->q_prescaled ? 1.0f : d->softmax_scale * LOG2E; p.scale2 = d->scale2;
-    static const int xm_self = 8, xm_cross = 8;  // (A/B knobs, read once)
-    p.xm = self ? xm_self : xm_cross;
+    p.xm = 8;
     hipStream_t s = (hipStream_t)stream;
     return d->dtype == APAD_BF16 ? hs_attn_launch<APAD_BF16>(p, self, s) : hs_attn_launch<APAD_F16>(p, self, s);
 }
@@ -973,8 +926,7 @@ extern "C" int apad_hs_geglu(const void* x, const void* w_packed, const float* w
     HgP p;
     p.x = (const uint8_t*)x; p.w = (const uint8_t*)w_packed; p.wbias = w_bias; p.out = (uint8_t*)out;
     p.B = B; p.N = N; p.normalize = normalize ? 1 : 0; p.eps = ln_eps;
-    static const int xm = 2;
-    p.xm = xm;
+    p.xm = 2;
     hipStream_t s = (hipStream_t)stream;
     if (dtype == APAD_BF16) return p.normalize ? hs_geglu_go<APAD_BF16, true>(p, s) : hs_geglu_go<APAD_BF16, false>(p, s);
     return p.normalize ? hs_geglu_go<APAD_F16, true>(p, s) : hs_geglu_go<APAD_F16, false>(p, s);
@@ -993,8 +945,7 @@ extern "C" int apad_hs_ff2(const apad_hs_out_desc* d, void* stream) {
     HfP p;
     p.h = (const uint8_t*)d->o; p.w = (const uint8_t*)d->w_packed; p.bo = (const uint8_t*)d->bias; p.res = (const uint8_t*)d->residual;
     p.out = (uint8_t*)d->out; p.rs_out = d->rowstat_out; p.B = d->B; p.N = d->N;
-    static const int xm = 8;
-    p.xm = xm;
+    p.xm = 8;
     hipStream_t s = (hipStream_t)stream;
     return d->dtype == APAD_BF16 ? hs_ff2_launch<APAD_BF16>(p, s) : hs_ff2_launch<APAD_F16>(p, s);
 }
@@ -1013,8 +964,7 @@ extern "C" int apad_hs_out(const apad_hs_out_desc* d, void* stream) {
     HoP p;
     p.o = (const uint8_t*)d->o; p.w = (const uint8_t*)d->w_packed; p.bo = (const uint8_t*)d->bias; p.res = (const uint8_t*)d->residual;
     p.out = (uint8_t*)d->out; p.rs_out = d->rowstat_out; p.B = d->B; p.N = d->N;
-    static const int xm_out = 8;
-    p.xm = xm_out;
+    p.xm = 8;
     hipStream_t s = (hipStream_t)stream;
     return d->dtype == APAD_BF16 ? hs_out_launch<APAD_BF16>(p, s) : hs_out_launch<APAD_F16>(p, s);
 }

@@ -160,14 +160,9 @@ __global__ __launch_bounds__(512, 1) void mlp2_kernel(MlpP p) {
         }
     };
 
-#ifndef MLP2_ABL
-#define MLP2_ABL 0  // timing ablations (results are wrong): 1 = no global weight loads, 2 = no LDS weight stores, 4 = no per-chunk barrier, 8 = no GELU
-#endif
     for (int jc = 0; jc < G::NCHUNK; ++jc) {
-        if (!(MLP2_ABL & 1)) {
-            load_w1(jc + 2 < G::NCHUNK ? jc + 2 : G::NCHUNK - 1);
-            load_w2(jc + 1 < G::NCHUNK ? jc + 1 : G::NCHUNK - 1);
-        }
+        load_w1(jc + 2 < G::NCHUNK ? jc + 2 : G::NCHUNK - 1);
+        load_w2(jc + 1 < G::NCHUNK ? jc + 1 : G::NCHUNK - 1);
         // operands of the second GEMM of chunk jc-1 (weights in slot (jc+2)%3, activations of both halves handed over at the last
         // barrier) and the first fragment group of the first GEMM of chunk jc+1: one batch of LDS reads
         typename E::v8 w2f[G::CT][2], hp[2];
@@ -192,7 +187,7 @@ __global__ __launch_bounds__(512, 1) void mlp2_kernel(MlpP p) {
             const float v0 = acur[r];
             const float v1 = acur[r + 1];
             const apad_f32x2 gt = {acur[8 + r], acur[9 + r]};
-            const apad_f32x2 ge = (MLP2_ABL & 8) ? gt : gelu_erf_2(gt);
+            const apad_f32x2 ge = gelu_erf_2(gt);
             float pr0 = v0 * ge[0], pr1 = v1 * ge[1];  // (fp32 product, then one rounding: see mlp_kernel)
             asm volatile("" : "+v"(pr0), "+v"(pr1));
             hb[r] = (typename E::elem)pr0;
@@ -216,22 +211,10 @@ __global__ __launch_bounds__(512, 1) void mlp2_kernel(MlpP p) {
             for (int cc = 0; cc < 4; ++cc) anxt = E::mfma32(wfb[cc][0], xf[(g + 1) * 4 + cc], anxt);
             geglu_step(2 * g + 2);
         }
-#ifndef MLP2_VALU
-#define MLP2_VALU 0
-#endif
-#if MLP2_VALU > 0
-#pragma unroll
-        for (int i = 0; i < 24; ++i) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x002, MLP2_VALU, 0);
-        }
-#endif
         *reinterpret_cast<uint4*>(hxs + (jc & 1) * G::HX_BYTES + hxoff + hh * 1024) = as_u4<DT>(hb);
-        if (!(MLP2_ABL & 2)) {
-            store_w1(w1s + (jc & 1) * G::W1_BYTES);
-            store_w2(w2s + ((jc + 1) % 3) * G::W2_BYTES);
-        }
-        if (!(MLP2_ABL & 4)) __syncthreads();
+        store_w1(w1s + (jc & 1) * G::W1_BYTES);
+        store_w2(w2s + ((jc + 1) % 3) * G::W2_BYTES);
+        __syncthreads();
         acur = anxt;
     }
     gemm2((G::NCHUNK - 1) % 3, (G::NCHUNK - 1) & 1);

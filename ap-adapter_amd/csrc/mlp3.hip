@@ -18,15 +18,6 @@
 #include <stdlib.h>
 #include "mlp3_shared.h"
 
-#ifndef M3_DMA_IMM
-#define M3_DMA_IMM 1  // 1: a wave's pieces of a stage share one LDS base / scalar offset, the piece picked by the instruction's immediate offset
-#endif
-#ifndef M3_DMA_BARE
-#define M3_DMA_BARE 1  // 1: the DMA instructions sit between the MFMAs of the gemm1 steps that carry no GEGLU arithmetic
-#endif
-#ifndef M3_ABL
-#define M3_ABL 0  // timing ablations (results are wrong): 1 no GELU arithmetic, 2 no gemm1 MFMAs, 4 no gemm2 MFMAs, 8 no DMA in the loop, 16 no barrier
-#endif
 
 namespace {
 
@@ -71,8 +62,6 @@ __global__ __launch_bounds__(256, 1) void mlp3_kernel(Mlp3P p) {
     const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(p.wpk), 0, M3_NIT * M3_STAGE, 0x00020000);
     const uint32_t dvoff = (uint32_t)(lane * 16);
     auto dma = [&](int stage, int slot, int q) __attribute__((always_inline)) {
-        if (M3_ABL & 8) return;
-#if M3_DMA_IMM
         // the instruction's immediate offset moves the memory address AND the LDS address: pieces 0..3 of the wave share one M0 / scalar offset,
         // pieces 4, 5 the next (the packed stream and the ring slot have the same piece order)
         const int grp = q >> 2;
@@ -84,10 +73,6 @@ __global__ __launch_bounds__(256, 1) void mlp3_kernel(Mlp3P p) {
             case 2: __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, lp, 16, dvoff, so, 2048, 0); break;
             default: __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, lp, 16, dvoff, so, 3072, 0); break;
         }
-#else
-        const int piece = wave * 6 + q;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (m3_lds_ptr)(smem + slot * M3_STAGE + piece * 1024), 16, dvoff, stage * M3_STAGE + piece * 1024, 0, 0);
-#endif
     };
 
     // ---- x panels -> registers (requested first: HBM latency), biases -> LDS (fp32; ahead of the first DMA: an LDS store the compiler can see is
@@ -133,7 +118,7 @@ __global__ __launch_bounds__(256, 1) void mlp3_kernel(Mlp3P p) {
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CF::VM) : "memory");
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
-        if (!(M3_ABL & 16)) __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
         const uint32_t fa = fbase + (uint32_t)(slot * M3_STAGE);
         const uint32_t ta = tbase + (uint32_t)(i * 128);
@@ -147,60 +132,58 @@ __global__ __launch_bounds__(256, 1) void mlp3_kernel(Mlp3P p) {
         using EL = typename E::elem;
         M3Geglu<DT> gg;
         // one step of gemm2 (chunk i - 2): output-column tiles ct, ct + 1 x two panels, the GEGLU of hidden units r, r + 1 of panel 0 between the MFMAs
-        auto step2 = [&](const u32x4 (&f)[2], int ct, int r, int q) __attribute__((always_inline)) {
+        auto step2 = [&](const u32x4 (&f)[2], int ct, int r) __attribute__((always_inline)) {
             const V8 w0 = __builtin_bit_cast(V8, f[0]), w1 = __builtin_bit_cast(V8, f[1]);
-            if (CF::DMA && !M3_DMA_BARE) dma(nstage, nslot, q);
-            if (!(M3_ABL & 4)) y0[ct] = E::mfma32(w0, hp0, y0[ct]);
+            y0[ct] = E::mfma32(w0, hp0, y0[ct]);
             M3_PIN();
-            if (CF::GG && !(M3_ABL & 1)) gg.ph1(acur0[8 + r], acur0[9 + r]);
+            if (CF::GG) gg.ph1(acur0[8 + r], acur0[9 + r]);
             M3_PIN();
-            if (!(M3_ABL & 4)) y1[ct] = E::mfma32(w0, hp1, y1[ct]);
+            y1[ct] = E::mfma32(w0, hp1, y1[ct]);
             M3_PIN();
-            if (CF::GG && !(M3_ABL & 1)) gg.ph2();
+            if (CF::GG) gg.ph2();
             M3_PIN();
-            if (!(M3_ABL & 4)) y0[ct + 1] = E::mfma32(w1, hp0, y0[ct + 1]);
+            y0[ct + 1] = E::mfma32(w1, hp0, y0[ct + 1]);
             M3_PIN();
-            if (CF::GG && !(M3_ABL & 1)) gg.ph3();
+            if (CF::GG) gg.ph3();
             M3_PIN();
-            if (!(M3_ABL & 4)) y1[ct + 1] = E::mfma32(w1, hp1, y1[ct + 1]);
+            y1[ct + 1] = E::mfma32(w1, hp1, y1[ct + 1]);
             M3_PIN();
-            if (CF::GG && !(M3_ABL & 1)) gg.template ph4<V8, EL>(acur0[r], acur0[r + 1], hn0, r);
+            if (CF::GG) gg.template ph4<V8, EL>(acur0[r], acur0[r + 1], hn0, r);
             M3_PIN();
         };
         // one step of gemm1 (chunk i): k-steps ks, ks + 1 x two panels; r >= 0: the GEGLU of hidden units r, r + 1 of panel 1 between the MFMAs
         auto step1 = [&](const u32x4 (&f)[2], int ks, int r, int q, int q2) __attribute__((always_inline)) {
             const V8 w0 = __builtin_bit_cast(V8, f[0]), w1 = __builtin_bit_cast(V8, f[1]);
-            if (CF::DMA && !M3_DMA_BARE && q >= 0) dma(nstage, nslot, q);
-            if (CF::G1 && !(M3_ABL & 2)) M3Asm<DT>::acc(anxt0, w0, xf0[ks]);
+            if (CF::G1) M3Asm<DT>::acc(anxt0, w0, xf0[ks]);
             M3_PIN();
-            if (CF::DMA && M3_DMA_BARE && q >= 0) dma(nstage, nslot, q);
-            if (CF::GG && r >= 0 && !(M3_ABL & 1)) gg.ph1(acur1[8 + r], acur1[9 + r]);
+            if (CF::DMA && q >= 0) dma(nstage, nslot, q);
+            if (CF::GG && r >= 0) gg.ph1(acur1[8 + r], acur1[9 + r]);
             M3_PIN();
-            if (CF::G1 && !(M3_ABL & 2)) M3Asm<DT>::acc(anxt1, w0, xf1[ks]);
+            if (CF::G1) M3Asm<DT>::acc(anxt1, w0, xf1[ks]);
             M3_PIN();
-            if (CF::GG && r >= 0 && !(M3_ABL & 1)) gg.ph2();
+            if (CF::GG && r >= 0) gg.ph2();
             M3_PIN();
-            if (CF::G1 && !(M3_ABL & 2)) M3Asm<DT>::acc(anxt0, w1, xf0[ks + 1]);
+            if (CF::G1) M3Asm<DT>::acc(anxt0, w1, xf0[ks + 1]);
             M3_PIN();
-            if (CF::DMA && M3_DMA_BARE && q2 >= 0) dma(nstage, nslot, q2);
-            if (CF::GG && r >= 0 && !(M3_ABL & 1)) gg.ph3();
+            if (CF::DMA && q2 >= 0) dma(nstage, nslot, q2);
+            if (CF::GG && r >= 0) gg.ph3();
             M3_PIN();
-            if (CF::G1 && !(M3_ABL & 2)) M3Asm<DT>::acc(anxt1, w1, xf1[ks + 1]);
+            if (CF::G1) M3Asm<DT>::acc(anxt1, w1, xf1[ks + 1]);
             M3_PIN();
-            if (CF::GG && r >= 0 && !(M3_ABL & 1)) gg.template ph4<V8, EL>(acur1[r], acur1[r + 1], hn1, r);
+            if (CF::GG && r >= 0) gg.template ph4<V8, EL>(acur1[r], acur1[r + 1], hn1, r);
             M3_PIN();
         };
 
         // ---- gemm2 of chunk i - 2 (4 steps) with the activation of panel 0 under it ----
         m3_read2<18>(fB, fa);
         m3_wait_lgkm<2>();
-        step2(fA, 0, 0, 0);
+        step2(fA, 0, 0);
         m3_read2<20>(fA, fa);
         m3_wait_lgkm<2>();
-        step2(fB, 2, 2, 1);
+        step2(fB, 2, 2);
         m3_read2<22>(fB, fa);
         m3_wait_lgkm<2>();
-        step2(fA, 4, 4, 2);
+        step2(fA, 4, 4);
         if (CF::G1) {
             m3_read2<0>(fA, fa);  // W1 k-steps 0, 1; then b1 of chunk i (C-layout register order): short-lived, read just ahead of its use
             m3_read<0>(bq[0], ta);
@@ -212,7 +195,7 @@ __global__ __launch_bounds__(256, 1) void mlp3_kernel(Mlp3P p) {
             m3_wait_lgkm<0>();
             bq[0] = bq[1] = bq[2] = bq[3] = fA[0] = fA[1] = u32x4{0u, 0u, 0u, 0u};
         }
-        step2(fB, 6, 6, 3);
+        step2(fB, 6, 6);
         // ---- gemm1 of chunk i (8 steps; b1 is the C operand of the first MFMA of each panel) with the activation of panel 1 under it ----
         if (CF::G1) m3_read2<2>(fB, fa);
         m3_wait_lgkm<2>();
@@ -223,45 +206,41 @@ __global__ __launch_bounds__(256, 1) void mlp3_kernel(Mlp3P p) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) bias[qd * 4 + e] = __uint_as_float(bq[qd][e]);
             const V8 w0 = __builtin_bit_cast(V8, fA[0]), w1 = __builtin_bit_cast(V8, fA[1]);
-            if (CF::DMA && !M3_DMA_BARE) dma(nstage, nslot, 4);
-            if (CF::G1 && !(M3_ABL & 2)) {
+            if (CF::G1) {
                 M3Asm<DT>::first(anxt0, w0, xf0[0], bias);
                 M3Asm<DT>::first(anxt1, w0, xf1[0], bias);
                 // (a vector write to a register an in-flight MFMA still reads as its C operand is a software hazard -- 13 wait states for a 32x32
                 //  MFMA --, and the compiler, which does not see an MFMA in the asm, is free to recycle the b1 registers right here)
                 asm volatile("s_nop 7\n\ts_nop 6" ::: "memory");
-            } else if (CF::G1) {
-                anxt0 = bias;
-                anxt1 = bias;
             }
             M3_PIN();
-            if (CF::GG && !(M3_ABL & 1)) gg.ph1(acur1[8], acur1[9]);
-            if (CF::GG && !(M3_ABL & 1)) gg.ph2();
+            if (CF::GG) gg.ph1(acur1[8], acur1[9]);
+            if (CF::GG) gg.ph2();
             M3_PIN();
-            if (CF::G1 && !(M3_ABL & 2)) M3Asm<DT>::acc(anxt0, w1, xf0[1]);
+            if (CF::G1) M3Asm<DT>::acc(anxt0, w1, xf0[1]);
             M3_PIN();
-            if (CF::GG && !(M3_ABL & 1)) gg.ph3();
+            if (CF::GG) gg.ph3();
             M3_PIN();
-            if (CF::G1 && !(M3_ABL & 2)) M3Asm<DT>::acc(anxt1, w1, xf1[1]);
+            if (CF::G1) M3Asm<DT>::acc(anxt1, w1, xf1[1]);
             M3_PIN();
-            if (CF::GG && !(M3_ABL & 1)) gg.template ph4<V8, EL>(acur1[0], acur1[1], hn1, 0);
+            if (CF::GG) gg.template ph4<V8, EL>(acur1[0], acur1[1], hn1, 0);
             M3_PIN();
         }
         if (CF::G1) m3_read2<4>(fA, fa);
         m3_wait_lgkm<2>();
-        step1(fB, 2, -1, M3_DMA_BARE ? 0 : 5, M3_DMA_BARE ? 1 : -1);
+        step1(fB, 2, -1, 0, 1);
         if (CF::G1) m3_read2<6>(fB, fa);
         m3_wait_lgkm<2>();
         step1(fA, 4, 2, -1, -1);
         if (CF::G1) m3_read2<8>(fA, fa);
         m3_wait_lgkm<2>();
-        step1(fB, 6, -1, M3_DMA_BARE ? 2 : -1, M3_DMA_BARE ? 3 : -1);
+        step1(fB, 6, -1, 2, 3);
         if (CF::G1) m3_read2<10>(fB, fa);
         m3_wait_lgkm<2>();
         step1(fA, 8, 4, -1, -1);
         if (CF::G1) m3_read2<12>(fA, fa);
         m3_wait_lgkm<2>();
-        step1(fB, 10, -1, M3_DMA_BARE ? 4 : -1, M3_DMA_BARE ? 5 : -1);
+        step1(fB, 10, -1, 4, 5);
         if (CF::G1) m3_read2<14>(fB, fa);
         m3_wait_lgkm<2>();
         step1(fA, 12, 6, -1, -1);

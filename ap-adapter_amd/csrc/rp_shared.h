@@ -4,10 +4,6 @@
 #pragma once
 #include "common.h"
 
-#ifndef RP_EXPERIMENT
-#define RP_EXPERIMENT 0  // A/B builds only: 1 = skip global stores, 2 = skip GELU, 3 = both, 4 = skip MFMAs
-#endif
-
 namespace {
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
@@ -33,10 +29,7 @@ struct RpP {
 };
 
 template <int KC> struct Cfg {
-#ifndef RP_BNT
-#define RP_BNT 32
-#endif
-    static constexpr int BNT = RP_BNT;                 // weight rows per LDS tile (32 = one MFMA tile)
+    static constexpr int BNT = 32;                     // weight rows per LDS tile (32 = one MFMA tile)
     static constexpr int NT = BNT / 32;               // MFMA tiles per LDS tile
     static constexpr int CPR = KC * 2;                // 16-byte chunks per weight row
     static constexpr int ROWB = KC * 32 + 16;         // padded LDS row stride (bytes)
@@ -69,7 +62,7 @@ __device__ __forceinline__ void scratch_flush(const uint8_t* scr, int width, uin
             for (int e = 0; e < 8; ++e) f[e] += r[e];
             v = pack8<DT>(f);
         }
-        if (!(RP_EXPERIMENT & 1) || v.x == 0x12345678u) *reinterpret_cast<uint4*>(out + (m * ldo + col0 + ch * 8) * 2) = v;
+        *reinterpret_cast<uint4*>(out + (m * ldo + col0 + ch * 8) * 2) = v;
     }
 }
 
@@ -170,10 +163,8 @@ __device__ __forceinline__ void rp_mainloop(f32x16 (&acc)[Cfg<KC>::NT], const ui
 #pragma unroll
         for (int cc = 0; cc < 4; ++cc)
 #pragma unroll
-            for (int s = 0; s < C::NT; ++s) {
-                if (RP_EXPERIMENT & 4) acc[s][0] += (float)wfa[cc][s][0] * (float)xf[g * 4 + cc][0];
-                else acc[s] = SWAP ? E::mfma32(xf[g * 4 + cc], wfa[cc][s], acc[s]) : E::mfma32(wfa[cc][s], xf[g * 4 + cc], acc[s]);
-            }
+            for (int s = 0; s < C::NT; ++s)
+                acc[s] = SWAP ? E::mfma32(xf[g * 4 + cc], wfa[cc][s], acc[s]) : E::mfma32(wfa[cc][s], xf[g * 4 + cc], acc[s]);
         if (g + 1 < NG) {
             if (g + 2 < NG) rp_load_group<DT, KC>(wfa, wt, (g + 2) * 4);
             rp_pin<DT, KC>(wfb);

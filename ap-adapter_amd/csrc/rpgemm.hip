@@ -221,7 +221,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void rpgemm_kernel(RpP p)
 #pragma unroll
                     for (int j = 0; j < 4; j += 2) {
                         const apad_f32x2 gt = {acc[s][8 + 4 * g + j], acc[s][8 + 4 * g + j + 1]};
-                        const apad_f32x2 ge = (RP_EXPERIMENT & 2) ? gt : gelu_erf_2(gt);
+                        const apad_f32x2 ge = gelu_erf_2(gt);
                         float pr0 = acc[s][4 * g + j] * ge[0], pr1 = acc[s][4 * g + j + 1] * ge[1];  // fp32 product, then ONE rounding (never a v_fma_mix)
                         asm volatile("" : "+v"(pr0), "+v"(pr1));
                         y[j] = (typename E::elem)pr0;
@@ -392,13 +392,12 @@ extern "C" int apad_rowpanel_gemm(const apad_rp_desc* d, void* stream) {
         APAD_CHECK(d->n_segments == 1 && d->seg[0].mode == APAD_OUT_ROWMAJOR && d->ldr % 8 == 0 && al16(d->residual),
                    "apad_rowpanel_gemm: residual needs a single row-major segment and 8-byte aligned rows");
     hipStream_t s = (hipStream_t)stream;
-    // weight-stationary schedule first; APAD_RP_IMPL=stream forces the x-stationary kernel (A/B tests)
-    constexpr bool force_stream = false, force_ws = false;
+    // weight-stationary schedule first
     // measured on MI355X (tools/microbench.py): the weight-stationary schedule wins when all weight rows fit one or a
     // few resident slices (q / to_out / proj_in / proj_out, N = C); fused q|k|v and the 8C-wide GEGLU re-read x once
     // per slice and are faster on the streamed-tile kernel.
     const bool narrow = !geglu && p.n_total <= 512;
-    if (!force_stream && (narrow || force_ws)) {
+    if (narrow) {
         const int rc = apad_ws_dispatch(&p, d->K, d->dtype, ln, geglu, stream);
         if (rc != -3) return rc;
     }

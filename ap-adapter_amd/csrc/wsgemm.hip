@@ -13,19 +13,6 @@
 
 namespace {
 
-// probe build (tools/ab_build.sh wstr wsgemm.hip -DWS_TRACE=<wave>; tools/ws_trace.py): wall-clock stamps (100 MHz) of one wave of every workgroup.  Never
-// part of the product library.
-#ifdef WS_TRACE
-__device__ unsigned long long ws_trace_buf[1024][16];
-#define WS_STAMP(i_) if (lane == 0 && wave == (WS_TRACE) && blockIdx.x < 1024) ws_trace_buf[blockIdx.x][i_] = wall_clock64();
-#else
-#define WS_STAMP(i_)
-#endif
-
-#ifndef APAD_WS_XCD
-#define APAD_WS_XCD 1  // (0: the plain block order, for A/B builds)
-#endif
-
 template <int KC> struct WsCfg {
     static constexpr int NS = (KC <= 16) ? 256 : 128;  // weight rows resident in LDS per workgroup
     static constexpr int NTILES = NS / 32;             // MFMA tiles per slice
@@ -56,21 +43,17 @@ __global__ __launch_bounds__(512) void wsgemm_kernel(RpP p) {
     int slice, rgrp;
     {
         const int b = blockIdx.x, full = (ngrp / 8) * 8 * nslices;
-        if (APAD_WS_XCD && b < full) {
+        if (b < full) {
             const int g = b / (8 * nslices), rem = b - g * 8 * nslices;
             slice = rem >> 3;
             rgrp = g * 8 + (rem & 7);
-        } else if (APAD_WS_XCD) {
+        } else {
             const int rem = b - full, tail = ngrp - (ngrp / 8) * 8;
             slice = rem / tail;
             rgrp = (ngrp / 8) * 8 + rem - slice * tail;
-        } else {
-            slice = b % nslices;
-            rgrp = b / nslices;
         }
     }
     const int t0 = slice * W::NTILES;  // first MFMA tile (global tile index) of this slice
-    WS_STAMP(0);
     constexpr bool PREFETCH = W::PREFETCH && !RES;
     const int64_t npanels = (p.M + 31) >> 5;
     const int64_t pstride = (int64_t)ngrp * W::WAVES;
@@ -131,7 +114,6 @@ __global__ __launch_bounds__(512) void wsgemm_kernel(RpP p) {
         load_panel<DT, KC>(xf, p.x, p.lda, p.M, pi * 32, l31, half);
         __builtin_amdgcn_sched_barrier(0);
     }
-    WS_STAMP(1);
     uint8_t* const scr = smem + W::W_BYTES + wave * SCR_BYTES;
     float* const lbias = reinterpret_cast<float*>(smem + W::W_BYTES + W::WAVES * SCR_BYTES);
     const int bias_cols = W::NTILES * COLS_PER_TILE;
@@ -154,7 +136,6 @@ __global__ __launch_bounds__(512) void wsgemm_kernel(RpP p) {
         }
     }
     __syncthreads();  // the only workgroup barrier
-    WS_STAMP(2);
     if (has_res && pi < npanels) {  // (behind the barrier: in front of it the 32 requests per lane slowed the weight staging of the whole chip down, 1.4 -> 4.9 us)
         res_load(pi * 32);
         __builtin_amdgcn_sched_barrier(0);
@@ -178,7 +159,7 @@ __global__ __launch_bounds__(512) void wsgemm_kernel(RpP p) {
 
         if constexpr (RES) {
             // the lean tile loop of the residual launches: one row-major segment, no activation -- none of the general loop's per-tile segment selection,
-            // 64-bit row arithmetic and activation branches (the general loop issues ~400 instructions per tile and wave: 1.4-2.0 us per tile, tools/ws_trace.py)
+            // 64-bit row arithmetic and activation branches (the general loop issues ~400 instructions per tile and wave: 1.4-2.0 us per tile, measured with wall-clock stamps)
             uint8_t* op[2];
             bool ok[2];
 #pragma unroll
@@ -192,7 +173,6 @@ __global__ __launch_bounds__(512) void wsgemm_kernel(RpP p) {
             static_assert(W::NTILES % 2 == 0, "tiles run in pairs");
 #pragma unroll
             for (int tp = 0; tp < W::NTILES; tp += 2) {
-                if (tp < 9) { WS_STAMP(3 + tp); }
                 // two tiles at a time: 2 independent accumulator chains (a single tile's 16-24 MFMAs are one dependent chain: ~1000 cycles of latency per
                 // tile with nothing else to issue); the fragments of a group of 4 k-steps are read together, the next group's reads run under these MFMAs
                 f32x16 acc[2];
@@ -246,7 +226,6 @@ __global__ __launch_bounds__(512) void wsgemm_kernel(RpP p) {
             }
         } else
         for (int ti = 0; ti < W::NTILES; ++ti) {
-            if (ti < 9) { WS_STAMP(3 + ti); }
             const int n0 = (t0 + ti) * COLS_PER_TILE;
             const bool s1 = p.nseg > 1 && n0 >= p.seg[1].n_begin, s2 = p.nseg > 2 && n0 >= p.seg[2].n_begin;
             uint8_t* sg_out = s2 ? p.seg[2].out : (s1 ? p.seg[1].out : p.seg[0].out);
@@ -322,7 +301,6 @@ __global__ __launch_bounds__(512) void wsgemm_kernel(RpP p) {
             }
         }
         if (GEGLU && cursor > 0) scratch_flush<DT>(scr, cursor, p.seg[0].out, p.seg[0].ldo, win_col0, nullptr, 0, mw0, p.M, lane);
-        WS_STAMP(12);
 
         if constexpr (PREFETCH) {
 #pragma unroll
@@ -367,12 +345,6 @@ template <int DT, int KC> int ws_dispatch2(RpP& p, bool ln, bool geglu, hipStrea
 }
 
 }  // namespace
-
-#ifdef WS_TRACE
-extern "C" int apad_ws_trace_read(void* dst, int bytes) {
-    return hipMemcpyFromSymbol(dst, HIP_SYMBOL(ws_trace_buf), (size_t)bytes, 0, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
-}
-#endif
 
 // returns -3 when the shape does not fit the weight-stationary schedule (caller falls back to the streamed kernel)
 int apad_ws_dispatch(void* rp_params, int K, int dtype, bool ln, bool geglu, void* stream) {

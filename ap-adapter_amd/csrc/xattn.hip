@@ -37,10 +37,6 @@ constexpr int TILE_BYTES = XTM * TROWB;   // 67 584
 constexpr int XA_LDS = 2 * TILE_BYTES + XC * 4 + XTM * 2 * 4 + 2 * XC * 4;  // + bo, per-row (rstd, -mean rstd), the q-projection's fold vectors
 constexpr int XMAXSUB = 4;                // <= 128 keys per segment with resident fragments (segment 1: <= 64)
 constexpr int XMAXSUB2 = 16;              // <= 512 keys in segment 2 on the chunked form (64-key chunks, running max / sum)
-#ifndef XA_SPLIT_Q
-#define XA_SPLIT_Q 0
-#endif
-constexpr bool XA_SPLIT = XA_SPLIT_Q != 0;  // A/B: q-projection of all four panels first (q parked in LDS) vs panel pair by panel pair
 
 struct XaP {
     const uint8_t* x;
@@ -318,14 +314,6 @@ template <int DT, bool RES = false> __device__ __forceinline__ void xa_store_sli
     *reinterpret_cast<uint4*>(q + 16) = pc[1];
 }
 
-#ifdef XATTN_TRACE  // probe build (tools/xattn_trace.py): s_memtime stamps of wave 0 / wave 7 at the phase boundaries
-__device__ unsigned long long g_xa_trace[1024 * 32];
-#define XA_STAMP(i) \
-    do { if (lane == 0 && (wave == 0 || wave == 7)) g_xa_trace[(tile * 2 + (wave == 7)) * 16 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define XA_STAMP(i)
-#endif
-
 // NS1 / NS2 = 32-key sub-tiles per segment (NS2 = 0: single segment).  G1 > 0 selects the exact form: L1 = 8 G1 and L2 = 8 G2
 // keys precisely, BIAS1 = segment 1 carries a key bias; G1 = 0: lengths and bias are run-time (any L <= 32 NS).
 // CHUNK: segment 2 is LONG (L2 = 64 * n <= 512 keys): its fragments are fetched 64 keys at a time (NS2 = 2 is the chunk's shape) and folded in with a
@@ -338,7 +326,7 @@ __global__ __launch_bounds__(512) void xattn_kernel(XaP p) {
     // fragments + four score tiles do not fit beside the stationary Wq rows, so the q-projection of all four panels runs first (q parked
     // in LDS, Wq registers dead afterwards), the fragments are fetched behind it, and panels are attended one at a time
     constexpr bool BIG2 = NS2 > 2;
-    constexpr bool SPLIT = XA_SPLIT || BIG2 || CHUNK;
+    constexpr bool SPLIT = BIG2 || CHUNK;
     using E = ET<DT>;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     uint8_t* const xt = smem;                 // x^ tile, later the output tile
@@ -406,10 +394,6 @@ __global__ __launch_bounds__(512) void xattn_kernel(XaP p) {
     rows_of(tile_of(vnext >= 0 ? vnext : v), xoff_next);
     if (vnext < 0) xoff_next[0] = xoff_next[1] = NOROW;  // the last tile: the loads stay unconditional but all hit row 0 (round 4 re-requested the
                                                         // tile's own rows here: half of all tiles fetched twice, 12 MB of the launch's extra reads)
-    XA_STAMP(0);
-#ifdef XATTN_TRACE
-    if (lane == 0 && wave == 0) g_xa_trace[tile * 32 + 12] = wall_clock64();
-#endif
     // ---- phase 1: the tile's RAW rows -> x tile (they stay there: B operand of the q-projection, then the residual, added in place in phase
     //      3); with a LayerNorm: the rows' statistics -> lst (the normalisation itself is algebra on the q accumulators) ----
     {
@@ -448,9 +432,7 @@ __global__ __launch_bounds__(512) void xattn_kernel(XaP p) {
 #pragma unroll
         for (int kk = 0; kk < XKC; ++kk) wf[kk] = __builtin_bit_cast(typename ET<DT>::v8, xa_ld16(wp + kk * 1024, (uint32_t)(lane * 16)));
     }
-    XA_STAMP(1);
     __syncthreads();
-    XA_STAMP(2);
 
     // ---- phase 2: wave = head h.  (a) q-projection of all four panels at once: q_h^T [32 dims x 32 tokens] = Wq_h . x^^T, A =
     //      stationary registers, B = token fragments from the x^ tile; four independent accumulator chains keep the matrix
@@ -519,7 +501,6 @@ __global__ __launch_bounds__(512) void xattn_kernel(XaP p) {
             }
         }
         if constexpr ((!EXACT || BIG2) && !CHUNK) fetch_kv(bfirst < p.B ? bfirst : p.B - 1);
-        XA_STAMP(3);
         // attention of `n` panels (pp, pp + 1) of ONE sample, interleaved: the panels share the K / V fragments
         auto attend = [&](int pp, auto n_tag, int b) {
             constexpr int NP = decltype(n_tag)::value;
@@ -656,8 +637,6 @@ __global__ __launch_bounds__(512) void xattn_kernel(XaP p) {
                     chunk_group(pp, One{}, bp < p.B ? bp : p.B - 1);
                 }
             }
-            XA_STAMP(4);
-            XA_STAMP(5);
         } else {
         int bnext = bfirst, rem = tile * 4 - bfirst * p.ppn;  // sample / panel-in-sample walk over the tile's panels
         int bcur = bfirst < p.B ? bfirst : p.B - 1;           // sample whose fragments are loaded
@@ -684,7 +663,6 @@ __global__ __launch_bounds__(512) void xattn_kernel(XaP p) {
                     attend(pp + u, One{}, bcur);
                 }
             }
-            XA_STAMP(4 + (pp >> 1));
         }
         }
     }
@@ -694,9 +672,7 @@ __global__ __launch_bounds__(512) void xattn_kernel(XaP p) {
 #pragma unroll
         for (int kk = 0; kk < XKC; ++kk) wf[kk] = __builtin_bit_cast(typename ET<DT>::v8, xa_ld16(wp + kk * 1024, (uint32_t)(lane * 16)));
     }
-    XA_STAMP(7);
     __syncthreads();  // O tile complete; the x^ tile is free
-    XA_STAMP(8);
 
     // the NEXT tile's rows are requested now: their HBM latency hides under the output projection instead of standing at the head of the
     // next tile (the residual of THIS tile is in the x tile: nothing is read twice)
@@ -744,9 +720,7 @@ __global__ __launch_bounds__(512) void xattn_kernel(XaP p) {
             xa_store_slice<DT, true>(d0 + 32 * TROWB, yb, bo, half);
         }
     }
-    XA_STAMP(9);
     __syncthreads();
-    XA_STAMP(10);
 
     // ---- phase 4: the finished rows stream out, whole cache lines per store instruction ----
 #pragma unroll
@@ -756,15 +730,6 @@ __global__ __launch_bounds__(512) void xattn_kernel(XaP p) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) *reinterpret_cast<uint4*>(p.out + (xoff[j] + i * 128)) = *reinterpret_cast<const uint4*>(src + i * 128);
     }
-    XA_STAMP(11);
-#ifdef XATTN_TRACE
-    if (lane == 0 && wave == 0) {
-        g_xa_trace[tile * 32 + 13] = wall_clock64();
-        unsigned xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        g_xa_trace[tile * 32 + 14] = xcc & 0xf;
-    }
-#endif
     if (vnext < 0) break;
     v = vnext;
     xoff[0] = xoff_next[0];
@@ -836,12 +801,6 @@ template <int DT, int NS1, int NS2, int G1 = 0, int G2 = 0, bool BIAS1 = false, 
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
-
-#ifdef XATTN_TRACE
-extern "C" int apad_xattn_trace_read(unsigned long long* host, int n) {
-    return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_xa_trace), (size_t)n * sizeof(unsigned long long));
-}
-#endif
 
 extern "C" int64_t apad_xattn_packed_kv_bytes(int32_t B, int32_t L) { return (int64_t)B * XH * xa_kv_block(L); }
 

@@ -40,7 +40,7 @@ def round_up(x, m):
 
 def set_gemm_ring(mode):
     """process-wide kernel form of apad_gemm's latency-bound plain launches (apad_set_gemm_ring): 0 tiled, 1 / 2 LDS-DMA ring for
-    under-filled grids / every launch below 16000 rows, -1 the APAD_GEMM_RING environment variable.  Returns the previous setting."""
+    under-filled grids / every launch below 16000 rows, -1 the default (0).  Returns the previous setting."""
     return int(L.lib().apad_set_gemm_ring(int(mode)))
 
 
@@ -77,7 +77,6 @@ def gemm(a, w, *, M, N, K, lda, out, ldo, bias=None, residual=None, ldr=0, act=N
     return out
 
 
-import os as _os
 import weakref as _weakref
 
 # LayerNorm folded into the Linear behind it where no fused row-panel kernel covers the width (the 640-wide level): the producing
@@ -398,7 +397,7 @@ def cross_attention_rows(x, wq_packed, wo_packed, bo, k1, vt1, heads, ln=None, k
 
 
 # ---- LayerNorm + q|k|v + self-attention in one launch for the two large levels (csrc/attention.hip, sattn_fused_kernel) ----
-SATTN_FUSED = _os.environ.get("APAD_SATTN_FUSED", "1") == "1"  # A/B switch (read once): 0 = row-panel LN + q|k|v launch, then apad_attention
+SATTN_FUSED = True  # False: row-panel LN + q|k|v launch, then apad_attention
 SATTN_ENVELOPE = {256: (513, 1024), 384: (129, 256)}  # C -> token counts routed to it (shorter sequences keep the two-launch route)
 
 
@@ -448,7 +447,7 @@ def self_attention_fused(x, w_packed, csbb, heads, ln_eps, out=None):
 
 # ---- the 64-token level's attention sub-layers (csrc/hsattn.hip): head-sliced LayerNorm + projections + attention, then to_out + residual ----
 HS_C, HS_HEADS, HS_MAXN = 640, 8, 64
-HS_ATTN = _os.environ.get("APAD_HS_ATTN", "1") == "1"  # A/B switch (read once): 0 = the LN-folded q|k|v GEMM -> attention -> to_out chain
+HS_ATTN = True  # False: the LN-folded q|k|v GEMM -> attention -> to_out chain
 
 
 def hs_ok(x, heads, n_q_rows):
@@ -628,7 +627,7 @@ def hs_out(o, wo_packed, bias, residual, rowstat=False, out=None):
 MLP_C = (256,)  # envelope of apad_geglu_mlp
 # the 64-token register-block form from packed weights (csrc/mlp3.hip): routed from MLP_PACKED_MIN_M rows -- 256-token workgroups, one per CU, so a
 # launch needs most of a chip's worth of them (the CFG-shared prefix's 32 000-row launches keep the 128-token kernel)
-MLP_PACKED = _os.environ.get("APAD_MLP_PACKED", "1") == "1"  # A/B switch (read once)
+MLP_PACKED = True
 MLP_PACKED_MIN_M = 48000
 
 

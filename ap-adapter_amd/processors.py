@@ -22,10 +22,9 @@ from . import ops
 _vt_pool = {}
 
 # Route the C = 256 / 8-head cross-attention sub-layers (<= 64 keys per segment) through the single-launch
-# apad_fused_cross_attention kernel (LN + to_q + decoupled attention + to_out + residual).  APAD_FUSED_XATTN=0 selects the
-# three-kernel chain it replaces (A/B measurements, tests).
-import os as _os
-USE_FUSED_XATTN = _os.environ.get("APAD_FUSED_XATTN", "1") == "1"
+# apad_fused_cross_attention kernel (LN + to_q + decoupled attention + to_out + residual).  False selects the
+# three-kernel chain it replaces (tests).
+USE_FUSED_XATTN = True
 # Self-attention behind the row-panel projection: scale the to_q rows by log2(e) / sqrt(d) once (cached with the stacked weight) so
 # that apad_attention takes q as the base-2 exponent operand (q_prescaled)
 PRESCALE_Q = True

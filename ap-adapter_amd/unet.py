@@ -7,7 +7,6 @@ modules are used as PARAMETER CONTAINERS only; every forward below calls the C A
 token-major NHWC activations ``[B, H*W, C]`` (so Transformer2DModel's permute/reshape is free and the 3x3
 convolutions run as implicit GEMMs).  There is no PyTorch compute fallback.
 """
-import os
 from dataclasses import dataclass, field
 from typing import Dict, Optional, Tuple
 
@@ -213,9 +212,9 @@ def cfg_expand(x, cond):
     return x.repeat(cond.shape[0] // x.shape[0], *([1] * (x.dim() - 1)))
 
 
-CFG_SHARED_PREFIX = os.environ.get("APAD_CFG_SHARED_PREFIX", "1") == "1"  # A/B switch (read once)
+CFG_SHARED_PREFIX = True
 _CFG_EXPAND = [False]  # set by forward_nhwc for the duration of a shared-prefix forward: only then does cfg_expand replicate rows
-NO_CAT = os.environ.get("APAD_NO_CAT", "1") == "1"  # up blocks: two-source GroupNorm / shortcut instead of torch.cat (A/B switch)
+NO_CAT = True  # up blocks: two-source GroupNorm / shortcut instead of torch.cat
 
 
 class BasicTransformerBlock(nn.Module):
@@ -550,7 +549,7 @@ class AudioLDM2UNet2DConditionModel(nn.Module):
         Bs = x.shape[0]
         B = Bs * batch_repeat
         # CFG duplication deferred to the first conditioned attention (cfg_expand): inference only, and only when a condition of
-        # the full batch exists to trigger it (APAD_CFG_SHARED_PREFIX=0: duplicate in conv_in's gather, the A/B reference)
+        # the full batch exists to trigger it (CFG_SHARED_PREFIX = False: duplicate in conv_in's gather, the reference)
         # (table mode only: with explicit per-sample timesteps the two halves of the batch may sit at different steps, and the prefix
         #  would read the time projection of the first half for both)
         share = (batch_repeat > 1 and CFG_SHARED_PREFIX and not AG.on(x) and ehs is not None and ehs.dim() == 3 and ehs.shape[0] == B

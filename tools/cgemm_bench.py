@@ -1,15 +1,10 @@
-"""Big-tile LDS-DMA kernel (csrc/cgemm.hip) vs the 128x128 tiled kernel on the compute-bound launches of the step: correctness against
-fp32 torch and hipGraph-timed launches.  Runs itself twice (APAD_CGEMM=0 / 1, the knob is read once per process).
+"""The compute-bound GEMM / convolution launches of the step (csrc/cgemm.hip's big-tile LDS-DMA kernel where they fit): correctness against
+fp32 torch and hipGraph-timed launches.
 usage: python tools/cgemm_bench.py"""
 import os
-import subprocess
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-if os.environ.get("CGEMM_CHILD") is None:
-    for mode in ("0", "1"):
-        subprocess.run([sys.executable, __file__], env=dict(os.environ, CGEMM_CHILD="1", APAD_CGEMM=mode), check=False)
-    sys.exit(0)
 
 import torch  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
@@ -19,7 +14,6 @@ from bench import time_kernel_graphed  # noqa: E402
 
 dev = torch.device("cuda:0")
 dt = torch.bfloat16
-print("== APAD_CGEMM =", os.environ.get("APAD_CGEMM"))
 torch.manual_seed(0)
 CHECK = os.environ.get("CGEMM_NOCHECK") is None
 # correctness on small-but-eligible shapes (M >= 32768) incl. ragged M and borders

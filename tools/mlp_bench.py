@@ -1,6 +1,6 @@
 """The fused feed-forward at the 1000-token level (M = 64 000 rows, C = 256): the 128-token kernel (apad_geglu_mlp) against the 64-token register-block
-kernel from packed weights (apad_geglu_mlp_packed), hipGraph-timed; with APAD_LIB_PATH=exp/lib_<tag>.so an ablation build of csrc/mlp3.hip
-(tools/ab_build.sh <tag> mlp3.hip -DM3_ABL=<bits>).   usage: python tools/mlp_bench.py [M ...]"""
+kernel from packed weights (apad_geglu_mlp_packed), hipGraph-timed; with APAD_LIB_PATH=exp/lib_<tag>.so another build of csrc/mlp3.hip
+(tools/ab_build.sh <tag> mlp3.hip [flags]).   usage: python tools/mlp_bench.py [M ...]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

@@ -1,5 +1,5 @@
-"""apad_self_attention_fused at the two routed levels (B' = 64), hipGraph-timed; with APAD_LIB_PATH an ablation build of attention.hip
-(tools/ab_build.sh <tag> attention.hip -DSF_ABL=<bits>).   usage: python tools/sattn_bench.py"""
+"""apad_self_attention_fused at the two routed levels (B' = 64), hipGraph-timed; with APAD_LIB_PATH another build of attention.hip
+(tools/ab_build.sh <tag> attention.hip [flags]).   usage: python tools/sattn_bench.py"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
