@@ -19,12 +19,11 @@
 // V must be supplied transposed per head, [Bk][H][D][Lpad] with zero padding (apad_gemm / apad_rowpanel_gemm
 // APAD_OUT_VT).
 #include <stdlib.h>
-#include "common.h"
+#include "gfx950_prims.h"
 #include "f32_ops.h"
 
 namespace {
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
@@ -771,13 +770,6 @@ struct SfP {
     int32_t B, N, H;
     float eps;
 };
-typedef const __attribute__((address_space(1))) uint8_t* sf_gptr;
-typedef const __attribute__((address_space(1))) u32x4* sf_gptr16;
-__device__ __forceinline__ sf_gptr sf_sgpr_ptr(const uint8_t* p) {
-    const uint64_t a = reinterpret_cast<uint64_t>(p);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a), hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
-    return (sf_gptr)(((uint64_t)hi << 32) | lo);
-}
 constexpr int SF_NSET32 = 4;  // weight / token fragment register sets of the projection loop at d = 32
 constexpr int SF_NSET48 = 1;  // ... at d = 48 (1: one rolling set, re-requested behind the k-step's MFMAs -- what fits beside 160 accumulator registers when
                               // two workgroups share a CU; 2 spills 124 registers there)
@@ -804,13 +796,13 @@ template <int DT> __device__ __forceinline__ uint32_t sf_ones2() { return DT == 
 // acc[n][j] += W_tile_j . x_panel_n^T over the KC k-steps (raw x), with the row statistics of the panels summed on the way (shifted by the row's
 // first element: both halves of a row use the same shift)
 template <int DT, int NT3, int NPP, int KC, int NSET>
-__device__ __forceinline__ void sf_project(sf_gptr wb, uint32_t loff, const uint8_t* const (&xrow)[NPP], f32x16 (&acc)[NPP][NT3], float (&ssum)[NPP],
+__device__ __forceinline__ void sf_project(gptr wb, uint32_t loff, const uint8_t* const (&xrow)[NPP], f32x16 (&acc)[NPP][NT3], float (&ssum)[NPP],
                                            float (&sq)[NPP], float (&shift)[NPP]) {
     using E = ET<DT>;
     static_assert(KC % NSET == 0, "the register sets rotate over the k-steps");
     typename E::v8 wf[NSET][NT3], xf[NSET][NPP];
 #define SF_LD(i_, kk_)                                                                                                                \
-    _Pragma("unroll") for (int j = 0; j < NT3; ++j) wf[i_][j] = __builtin_bit_cast(typename E::v8, *(sf_gptr16)(wb + (j * KC + (kk_)) * 1024 + loff)); \
+    _Pragma("unroll") for (int j = 0; j < NT3; ++j) wf[i_][j] = __builtin_bit_cast(typename E::v8, *(gptr16)(wb + (j * KC + (kk_)) * 1024 + loff)); \
     _Pragma("unroll") for (int n = 0; n < NPP; ++n) xf[i_][n] = as_v8<DT>(*reinterpret_cast<const uint4*>(xrow[n] + (kk_) * 32));
 #define SF_MM(i_)                                                                                   \
     _Pragma("unroll") for (int n = 0; n < NPP; ++n) {                                               \
@@ -867,7 +859,7 @@ __device__ __forceinline__ void sf_project(sf_gptr wb, uint32_t loff, const uint
 // registers meanwhile.  Same MFMA order, same operands: bit-equal to sf_project.  The window aliases key tiles (sf_go picks the instantiation only where no finished
 // round has written them; the kernel fences it from the round's own epilogue).
 template <int DT, int NT3, int NPP, int KC, int KCH>
-__device__ __forceinline__ void sf_project_stg(sf_gptr wb, uint32_t loff, const uint8_t* xb, const int (&pan)[NPP], int N, uint8_t* stg, int lane,
+__device__ __forceinline__ void sf_project_stg(gptr wb, uint32_t loff, const uint8_t* xb, const int (&pan)[NPP], int N, uint8_t* stg, int lane,
                                                f32x16 (&acc)[NPP][NT3], float (&ssum)[NPP], float (&sq)[NPP], float (&shift)[NPP]) {
     using E = ET<DT>;
     // KCH k-steps per chunk: 4 = 128-byte row records (8 rows = 8 lines per load instruction, 32 staging registers, slot swizzle (row >> 1) & 7);
@@ -901,7 +893,7 @@ __device__ __forceinline__ void sf_project_stg(sf_gptr wb, uint32_t loff, const 
 #define SFS_READ(s_, kl_)                                                                                                 \
     _Pragma("unroll") for (int n = 0; n < NPP; ++n)                                                                       \
         xf[s_][n] = as_v8<DT>(*reinterpret_cast<const uint4*>(stg + raddr[n] + ((((uint32_t)((kl_) * 2 + half)) ^ rsw[n]) << 4)));
-#define SFS_LDW(i_, kk_) _Pragma("unroll") for (int j = 0; j < NT3; ++j) wf[i_][j] = __builtin_bit_cast(typename E::v8, *(sf_gptr16)(wb + (j * KC + (kk_)) * 1024 + loff));
+#define SFS_LDW(i_, kk_) _Pragma("unroll") for (int j = 0; j < NT3; ++j) wf[i_][j] = __builtin_bit_cast(typename E::v8, *(gptr16)(wb + (j * KC + (kk_)) * 1024 + loff));
     SFS_GLOAD(0);
 #pragma unroll
     for (int i = 0; i < NSW; ++i) { SFS_LDW(i, i); }
@@ -995,7 +987,7 @@ __global__ __launch_bounds__(NW * 64, 2) void sattn_fused_kernel(SfP p) {
         }
         __syncthreads();
     }
-    const sf_gptr wb = sf_sgpr_ptr(p.w + (int64_t)h * NT3 * KC * 1024);
+    const gptr wb = sgpr_ptr(p.w + (int64_t)h * NT3 * KC * 1024);
     const uint32_t loff = (uint32_t)lane * 16u;
     const uint8_t* const xb = p.x + (int64_t)b * N * C * 2;
     // rounds of (NPW x NW) panels a workgroup needs: 1024 tokens / 8 waves = 2; the 384-wide level's <= 256 tokens / 4 waves = 1 (apad_self_attention_fused's envelope)

@@ -12,13 +12,13 @@
 //     lane-linear, so the bank-conflict-free XOR layout of the tile is produced on the SOURCE side (lane -> (row, 16-byte chunk)).
 //     The convolution's zero padding is the buffer range check: a lane whose filter tap falls outside the image gets an
 //     out-of-range offset and the hardware writes zeros (tools/probes/buflds.hip) -- no branches, no selects on data
-//   * a tile is requested NST - 1 k-tiles ahead and waited for with a COUNTED s_waitcnt vmcnt, raw s_barrier (a __syncthreads()
+//   * a tile is requested NST - 1 k-tiles ahead and waited for with a COUNTED vmcnt wait, raw s_barrier (a __syncthreads()
 //     would drain the queue), so loads stay in flight across barriers; the DMA instructions are issued between the MFMAs
 //   * the two waves of a SIMD (waves w and w + 4) run half a phase apart: a phase is [fragment reads | barrier | 8 MFMAs + DMA issue |
 //     barrier]; while one wave of the SIMD is in its MFMA segment the other is in its read segment
 //     (MI355X_MICROARCH.md, "Two waves per SIMD")
 #include <type_traits>
-#include "common.h"
+#include "gfx950_prims.h"
 
 namespace {
 
@@ -64,13 +64,6 @@ struct CgP {
     uint32_t a2_bytes;
 };
 
-typedef __attribute__((address_space(3))) void* lds_ptr;
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t c_rsrc(const void* p, uint32_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
-}
-
 // General 3x3-convolution source mapping (stride 2: Downsample2D; nearest-upsampled source: Upsample2D with the interpolation folded
 // into the gather, modeling_audioldm2.py:1156 / :1509): the source pixel of tap (ky, kx) is not "centre + a uniform delta" any more,
 // so a row keeps three row offsets yo (byte offset of (b * Hin + sy(ky)) * Win * Cin * 2), three column offsets xo (sx(kx) * Cin * 2 +
@@ -95,24 +88,6 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t c_rsrc(const void* p, uint32_t
         }                                                                                                             \
     } while (0)
 __device__ __forceinline__ uint32_t cg_pick3(const uint32_t (&v)[3], int k) { return k == 0 ? v[0] : (k == 1 ? v[1] : v[2]); }
-
-#define C_FENCE() asm volatile("" ::: "memory")
-#define C_BARRIER()                          \
-    do {                                     \
-        __builtin_amdgcn_sched_barrier(0);   \
-        C_FENCE();                           \
-        __builtin_amdgcn_s_barrier();        \
-        C_FENCE();                           \
-        __builtin_amdgcn_sched_barrier(0);   \
-    } while (0)
-
-template <int N_> __device__ __forceinline__ void c_wait_vm() {
-    if constexpr (N_ == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if constexpr (N_ == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-    else if constexpr (N_ == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    else if constexpr (N_ == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else static_assert(N_ == 0, "add the count");
-}
 
 template <int DT, int MODE, int BN>  // MODE: 0 plain A, 1 3x3 convolution (stride 1), 2 general 3x3 convolution (stride 2 / up-sampled source)
 __global__ __launch_bounds__(512) void cgemm_kernel(CgP p) {
@@ -147,7 +122,7 @@ __global__ __launch_bounds__(512) void cgemm_kernel(CgP p) {
 
     // ---- DMA sources.  One instruction of a wave fills one 1 KB block = 8 tile rows x 128 bytes; lane -> (row r = lane / 8,
     //      LDS slot lane % 8), and the slot holds source chunk slot ^ ((row >> 1) & 7): the swizzle the fragment reads undo. ----
-    const __amdgpu_buffer_rsrc_t ra = c_rsrc(p.a, p.a_bytes), rw = c_rsrc(p.w, p.w_bytes);
+    const __amdgpu_buffer_rsrc_t ra = buf_rsrc(p.a, p.a_bytes), rw = buf_rsrc(p.w, p.w_bytes);
     uint32_t aoff2[4];  // plain, two sources: the row's offset in the second one
     uint32_t aoff[4];   // plain: byte offset of (row, chunk) at k = 0, or C_OOB; conv: of the CENTRE tap, channel 0
     uint32_t amask[4];  // conv: bit (3 ky + kx) = that tap lies inside the image (0 for rows past M)
@@ -225,7 +200,7 @@ __global__ __launch_bounds__(512) void cgemm_kernel(CgP p) {
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (lds_ptr)(smem + stage * STAGE + (wave * 4 + q) * 1024), 16, av[q], a_soff, 0, 0);
             } else {
                 // (the descriptor is rebuilt from scalar selects: two descriptors selected per call were kept in scratch)
-                const __amdgpu_buffer_rsrc_t rs = c_rsrc(a_second ? p.a2 : p.a, a_second ? p.a2_bytes : p.a_bytes);
+                const __amdgpu_buffer_rsrc_t rs = buf_rsrc(a_second ? p.a2 : p.a, a_second ? p.a2_bytes : p.a_bytes);
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr)(smem + stage * STAGE + (wave * 4 + q) * 1024), 16, av[q], a_soff, 0, 0);
             }
         } else
@@ -249,9 +224,10 @@ __global__ __launch_bounds__(512) void cgemm_kernel(CgP p) {
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
     // Fragment reads are inline asm: the compiler's wait-count pass orders every ds_read it can see behind ALL outstanding LDS-DMA
-    // (it inserts s_waitcnt vmcnt(0) in front of the first read of each phase, which drains the tiles in flight); the ordering
+    // (it inserts a vmcnt(0) wait in front of the first read of each phase, which drains the tiles in flight); the ordering
     // that is actually needed -- the tile being read was waited for with the counted vmcnt below, by every wave, one barrier ago --
     // is kept by hand.  The values are consumed behind an explicit lgkmcnt(0) + sched_barrier (the pass does not see the reads).
+    // (literal offsets, not lds_read16: the operand form prints them in hex, so the device assembly would not stay identical)
     u32x4 fa[KSP][MI] = {}, fb[KSP][2] = {};  // [k-step of the phase][MFMA tile]
     const uint32_t lds0 = (uint32_t)(size_t)(lds_ptr)smem;
     auto read_frags = [&](int stage, int ph) {
@@ -272,8 +248,7 @@ __global__ __launch_bounds__(512) void cgemm_kernel(CgP p) {
     // the MFMA segment of a phase; `dma(u)` (u = 0..2) issues this wave's next DMA pieces BETWEEN the MFMAs (an LDS-DMA instruction
     // costs ~60 issue cycles among bare MFMAs and 100+ in a segment that also carries the fragment reads: MI355X_MICROARCH.md)
     auto mfmas = [&](auto&& dma) {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
+        wait_lgkm<0>(); SCHED_PIN();
         __builtin_amdgcn_s_setprio(1);
         int n = 0;
 #pragma unroll
@@ -301,10 +276,10 @@ __global__ __launch_bounds__(512) void cgemm_kernel(CgP p) {
 #pragma unroll
             for (int q = 0; q < P; ++q) issue(q, t, t);
         }
-    if (D > 1 && nk > 1) c_wait_vm<(D > 1 ? P : 0)>();  // (D == 2: the second tile's pieces may stay in flight)
-    else c_wait_vm<0>();
-    C_BARRIER();
-    if (grp == 1) C_BARRIER();  // the stagger
+    if (D > 1 && nk > 1) wait_vm<(D > 1 ? P : 0)>();  // (D == 2: the second tile's pieces may stay in flight)
+    else wait_vm<0>();
+    RAW_BARRIER();
+    if (grp == 1) RAW_BARRIER();  // the stagger
 
     // One k-tile.  Stage indices are compile-time (the loop is unrolled by the stage count).
     auto ktile = [&](int t, auto stage_tag) {
@@ -318,17 +293,17 @@ __global__ __launch_bounds__(512) void cgemm_kernel(CgP p) {
                 // tile t + 1 must have landed before anyone reads it behind the next barriers; with three stages the pieces of
                 // tile t + 2 issued in this tile's earlier phases may stay in flight
                 constexpr int inflight = NST == 3 ? (3 * (NPH - 1) < P ? 3 * (NPH - 1) : P) : 0;
-                if (NST == 3 && req) c_wait_vm<inflight>();
-                else c_wait_vm<0>();
+                if (NST == 3 && req) wait_vm<inflight>();
+                else wait_vm<0>();
                 // the last reads of stage S are complete before the barrier behind which the other half may overwrite it
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                wait_lgkm<0>();
             }
-            C_BARRIER();
+            RAW_BARRIER();
             mfmas([&](int u) {
                 const int q = ph * 3 + u;
                 if (q < P && req) issue(q, SR, t + D);
             });
-            C_BARRIER();
+            RAW_BARRIER();
         }
     };
     if constexpr (NST == 3) {
@@ -345,7 +320,7 @@ __global__ __launch_bounds__(512) void cgemm_kernel(CgP p) {
             if (t + 1 < nk) ktile(t + 1, std::integral_constant<int, 1>{});
         }
     }
-    if (grp == 0) C_BARRIER();
+    if (grp == 0) RAW_BARRIER();
     // (every wave is past its last fragment read and its last DMA wait: the stages are dead)
 
     // ---- epilogue, 128 tile rows at a time: acc + bias + time-embedding row -> storage type -> LDS tile -> + residual -> full-row
@@ -443,7 +418,7 @@ __global__ __launch_bounds__(256) void cconv_small_kernel(CgP p) {
         }
     }
     const int m0 = mt * SBM, n0 = nt * SBN;
-    const __amdgpu_buffer_rsrc_t ra = c_rsrc(p.a, p.a_bytes), rw = c_rsrc(p.w, p.w_bytes);
+    const __amdgpu_buffer_rsrc_t ra = buf_rsrc(p.a, p.a_bytes), rw = buf_rsrc(p.w, p.w_bytes);
     // DMA sources: wave w fills blocks 2w, 2w + 1 (8 rows each) of the A tile and of the W tile
     uint32_t aoff[2], amask[2], boff[2];
     uint32_t gyo[2][3], gxo[2][3], gok[2];  // (GEN only)
@@ -505,10 +480,10 @@ __global__ __launch_bounds__(256) void cconv_small_kernel(CgP p) {
     auto ktile = [&](int t, auto stage_tag) {
         constexpr int S = decltype(stage_tag)::value;
         // this wave's pieces of tile t have landed when at most the pieces of the (up to two) later tiles are outstanding
-        if (t + 2 < nk) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        else if (t + 1 < nk) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        C_BARRIER();  // everyone's pieces of tile t are in LDS, and everyone is past its reads of tile t - 1
+        if (t + 2 < nk) wait_vm<8>();
+        else if (t + 1 < nk) wait_vm<4>();
+        else wait_vm<0>();
+        RAW_BARRIER();  // everyone's pieces of tile t are in LDS, and everyone is past its reads of tile t - 1
         if (t + SNST - 1 < nk) request(t + SNST - 1, (S + SNST - 1) % SNST);
         u32x4 fa[4], fb[4];
 #pragma unroll
@@ -517,8 +492,7 @@ __global__ __launch_bounds__(256) void cconv_small_kernel(CgP p) {
             asm volatile("ds_read_b128 %0, %1" : "=v"(fa[ks]) : "v"(aa));
             asm volatile("ds_read_b128 %0, %1" : "=v"(fb[ks]) : "v"(bb));
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
+        wait_lgkm<0>(); SCHED_PIN();
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks)
             acc = E::mfma32(__builtin_bit_cast(typename E::v8, fa[ks]), __builtin_bit_cast(typename E::v8, fb[ks]), acc);

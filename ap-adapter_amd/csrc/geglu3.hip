@@ -41,25 +41,6 @@ struct G3P {
     float eps;
 };
 
-// the B operand (x) comes from AGPRs: 192 of them hold the two panels for the whole kernel
-template <int DT> struct G3Asm;
-template <> struct G3Asm<APAD_BF16> {
-    template <typename V8> static __device__ __forceinline__ void first(f32x16& d, const V8& a, const V8& b, const f32x16& c) {
-        asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_bf16 %0, %1, %2, %3" : "=&v"(d) : "v"(a), "a"(b), "v"(c));
-    }
-    template <typename V8> static __device__ __forceinline__ void acc(f32x16& d, const V8& a, const V8& b) {
-        asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(d) : "v"(a), "a"(b));
-    }
-};
-template <> struct G3Asm<APAD_F16> {
-    template <typename V8> static __device__ __forceinline__ void first(f32x16& d, const V8& a, const V8& b, const f32x16& c) {
-        asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_f16 %0, %1, %2, %3" : "=&v"(d) : "v"(a), "a"(b), "v"(c));
-    }
-    template <typename V8> static __device__ __forceinline__ void acc(f32x16& d, const V8& a, const V8& b) {
-        asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(d) : "v"(a), "a"(b));
-    }
-};
-
 template <int OFF> __device__ __forceinline__ void g3_write(uint32_t a, const u32x4& d) {
     asm volatile("ds_write_b128 %0, %1 offset:%2" ::"v"(a), "v"(d), "n"(OFF) : "memory");
 }
@@ -79,18 +60,14 @@ __global__ __launch_bounds__(512, 1) void geglu3_kernel(G3P p) {
     if (mtile >= p.ntile) return;
     const int64_t mw0 = ((int64_t)mtile * G3_NW + wave) * 32;
 
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(p.wpk), 0, G3_PARTS * G3_NCH * G3_STAGE, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rw = buf_rsrc(p.wpk, G3_PARTS * G3_NCH * G3_STAGE);
     const uint32_t dvoff = (uint32_t)(lane * 16);
     const int part_off = part * G3_NCH * G3_STAGE;
     auto dma = [&](int stage, int slot, int q) __attribute__((always_inline)) {
         // (the immediate offset moves the memory address AND the LDS address: the wave's three 1 KB pieces of a stage share one M0 / scalar offset)
-        const m3_lds_ptr lp = (m3_lds_ptr)(smem + slot * G3_STAGE + wave * 3072);
+        const lds_ptr lp = (lds_ptr)(smem + slot * G3_STAGE + wave * 3072);
         const int so = part_off + stage * G3_STAGE + wave * 3072;
-        switch (q) {
-            case 0: __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, lp, 16, dvoff, so, 0, 0); break;
-            case 1: __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, lp, 16, dvoff, so, 1024, 0); break;
-            default: __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, lp, 16, dvoff, so, 2048, 0); break;
-        }
+        dma_piece<3>(rw, lp, dvoff, so, q);
     };
 
     // ---- the wave's 32 rows of x: 24 COALESCED 16-byte loads per lane (a load instruction covers 1 KB in runs of 384 bytes; the fragment layout --
@@ -99,12 +76,9 @@ __global__ __launch_bounds__(512, 1) void geglu3_kernel(G3P p) {
     u32x4 stg[2][12];
     {
         // (scalar base + 32-bit lane offset form: 64-bit per-lane pointers for the 24 loads overflowed the 128-register budget of the prologue)
-        typedef const __attribute__((address_space(1))) uint8_t* g3_gptr;
-        typedef const __attribute__((address_space(1))) u32x4* g3_gptr16;
         const int64_t mb = mw0 < p.M ? mw0 : p.M - 1;  // (a wave wholly past the end re-reads the last row; mtile < ntile: M >= 1)
-        const uint64_t xa = reinterpret_cast<uint64_t>(p.x) + (uint64_t)mb * (G3_C * 2);
-        const uint32_t xlo = __builtin_amdgcn_readfirstlane((uint32_t)xa), xhi = __builtin_amdgcn_readfirstlane((uint32_t)(xa >> 32));  // (unsigned: no sign extension)
-        const g3_gptr xb = (g3_gptr)(((uint64_t)xhi << 32) | xlo);
+        // (the address in integer arithmetic: the pointer form swaps the operands of the 64-bit add)
+        const gptr xb = sgpr_ptr(reinterpret_cast<const uint8_t*>(reinterpret_cast<uint64_t>(p.x) + (uint64_t)mb * (G3_C * 2)));
         const int rmax = (int)(p.M - 1 - mb < 31 ? p.M - 1 - mb : 31);
         uint32_t go[12];
 #pragma unroll
@@ -115,12 +89,12 @@ __global__ __launch_bounds__(512, 1) void geglu3_kernel(G3P p) {
 #pragma unroll
         for (int h = 0; h < 2; ++h)
 #pragma unroll
-            for (int i = 0; i < 12; ++i) stg[h][i] = *(g3_gptr16)(xb + go[i] + h * 384);
+            for (int i = 0; i < 12; ++i) stg[h][i] = *(gptr16)(xb + go[i] + h * 384);
     }
     // this part's bias table (3 KB) -> LDS by the DMA as well (waves 0..2, one 1 KB piece each)
     if (wave < 3) {
-        const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.b1p), 0, G3_PARTS * G3_B1_BYTES, 0x00020000);
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, (m3_lds_ptr)(smem + G3_B1_OFF + wave * 1024), 16, dvoff, part * G3_B1_BYTES + wave * 1024, 0, 0);
+        const __amdgpu_buffer_rsrc_t rb = buf_rsrc(p.b1p, G3_PARTS * G3_B1_BYTES);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, (lds_ptr)(smem + G3_B1_OFF + wave * 1024), 16, dvoff, part * G3_B1_BYTES + wave * 1024, 0, 0);
     }
 #pragma unroll
     for (int s = 0; s < 2; ++s)
@@ -128,7 +102,7 @@ __global__ __launch_bounds__(512, 1) void geglu3_kernel(G3P p) {
         for (int q = 0; q < 3; ++q) dma(s, s, q);  // (stages 0, 1 -> slots 0, 1; slots 2.. hold the transposition until the barrier below)
     V8 xf[G3_KS];
     {
-        const uint32_t tw = (uint32_t)(size_t)(m3_lds_ptr)smem + (uint32_t)(2 * G3_STAGE + wave * G3_TROWS);
+        const uint32_t tw = (uint32_t)(size_t)(lds_ptr)smem + (uint32_t)(2 * G3_STAGE + wave * G3_TROWS);
         uint32_t wa[12];
 #pragma unroll
         for (int i = 0; i < 12; ++i) {
@@ -142,10 +116,10 @@ __global__ __launch_bounds__(512, 1) void geglu3_kernel(G3P p) {
 #pragma unroll
             for (int i = 0; i < 12; ++i) g3_write<0>(wa[i], stg[h][i]);
             u32x4 t[12];
-            m3_read<0>(t[0], ra); m3_read<32>(t[1], ra); m3_read<64>(t[2], ra); m3_read<96>(t[3], ra);
-            m3_read<128>(t[4], ra); m3_read<160>(t[5], ra); m3_read<192>(t[6], ra); m3_read<224>(t[7], ra);
-            m3_read<256>(t[8], ra); m3_read<288>(t[9], ra); m3_read<320>(t[10], ra); m3_read<352>(t[11], ra);
-            m3_wait_lgkm<0>();
+            lds_read16<0>(t[0], ra); lds_read16<32>(t[1], ra); lds_read16<64>(t[2], ra); lds_read16<96>(t[3], ra);
+            lds_read16<128>(t[4], ra); lds_read16<160>(t[5], ra); lds_read16<192>(t[6], ra); lds_read16<224>(t[7], ra);
+            lds_read16<256>(t[8], ra); lds_read16<288>(t[9], ra); lds_read16<320>(t[10], ra); lds_read16<352>(t[11], ra);
+            wait_lgkm<0>(); SCHED_PIN();
 #pragma unroll
             for (int k = 0; k < 12; ++k) xf[h * 12 + k] = __builtin_bit_cast(V8, t[k]);
         }
@@ -159,7 +133,7 @@ __global__ __launch_bounds__(512, 1) void geglu3_kernel(G3P p) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) a0[r] = b0[r] = 0.f;
 
-    const uint32_t lds0 = (uint32_t)(size_t)(m3_lds_ptr)smem;
+    const uint32_t lds0 = (uint32_t)(size_t)(lds_ptr)smem;
     const uint32_t fbase = lds0 + (uint32_t)(lane * 16);
     const uint32_t tbase = lds0 + (uint32_t)(G3_B1_OFF + half * 64);
     // this lane's output row pointer: token l31 of the wave's panel, the 16-byte piece of its half-wave
@@ -183,11 +157,10 @@ __global__ __launch_bounds__(512, 1) void geglu3_kernel(G3P p) {
     // iteration i: the 24 MFMAs of chunk i into `anxt` with the GEGLU of chunk i - 1 (`acur`) one phase behind each of the first 16, then the wave's
     // three DMA pieces of chunk i + 5 and the store of chunk i - 1.  Two waves share a SIMD: one wave's phase covers the other's MFMA.
     auto iteration = [&](int i, int slot, f32x16& acur, f32x16& anxt) __attribute__((always_inline)) {
-        asm volatile("s_waitcnt vmcnt(12)" ::: "memory");  // stage i has landed for this wave's pieces (stores only make the count stricter)
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
+        wait_vm<12>();  // stage i has landed for this wave's pieces (stores only make the count stricter)
+        wait_lgkm<0>(); SCHED_PIN();
         __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
+        SCHED_PIN();
         const uint32_t fa = fbase + (uint32_t)(slot * G3_STAGE);
         const uint32_t ta = tbase + (uint32_t)(i * 128);
         const int nstage = i + G3_NS - 1 < G3_NCH ? i + G3_NS - 1 : G3_NCH - 1;  // (past the end: a dummy re-load keeps the vmcnt arithmetic uniform)
@@ -196,10 +169,10 @@ __global__ __launch_bounds__(512, 1) void geglu3_kernel(G3P p) {
         u32x4 bq[4], f0[2], f1[2], f2[2];  // fragments two steps ahead (eight waves share the LDS pipe: one step ahead left every step waiting on it)
         V8 hn;
         M3Geglu<DT> gg;
-        m3_read<0>(bq[0], ta);
-        m3_read<16>(bq[1], ta);
-        m3_read<32>(bq[2], ta);
-        m3_read<48>(bq[3], ta);
+        lds_read16<0>(bq[0], ta);
+        lds_read16<16>(bq[1], ta);
+        lds_read16<32>(bq[2], ta);
+        lds_read16<48>(bq[3], ta);
         m3_read2<0>(f0, fa);
         m3_read2<2>(f1, fa);
         __builtin_amdgcn_sched_barrier(0);
@@ -220,10 +193,10 @@ __global__ __launch_bounds__(512, 1) void geglu3_kernel(G3P p) {
             }
         };
         auto mf = [&](int m, const V8& w) __attribute__((always_inline)) {
-            G3Asm<DT>::acc(anxt, w, xf[m]);
-            M3_PIN();
+            AsmMfma<DT, 'a'>::acc(anxt, w, xf[m]);
+            SCHED_PIN();
             after(m);
-            M3_PIN();
+            SCHED_PIN();
         };
         auto step = [&](const u32x4 (&f)[2], int ks) __attribute__((always_inline)) {
             mf(ks, __builtin_bit_cast(V8, f[0]));
@@ -232,50 +205,50 @@ __global__ __launch_bounds__(512, 1) void geglu3_kernel(G3P p) {
 
         // ---- step 0: b1 (C-layout register order) is the C operand of the first MFMA ----
         m3_read2<4>(f2, fa);
-        m3_wait_lgkm<4>();
+        wait_lgkm<4>(); SCHED_PIN();
         {
             f32x16 bias;
 #pragma unroll
             for (int qd = 0; qd < 4; ++qd)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) bias[qd * 4 + e] = __uint_as_float(bq[qd][e]);
-            G3Asm<DT>::first(anxt, __builtin_bit_cast(V8, f0[0]), xf[0], bias);
+            AsmMfma<DT, 'a'>::first(anxt, __builtin_bit_cast(V8, f0[0]), xf[0], bias);
             asm volatile("s_nop 7\n\ts_nop 6" ::: "memory");  // (the b1 registers may be recycled right here: 13 wait states behind an MFMA that reads them as C)
-            M3_PIN();
+            SCHED_PIN();
             after(0);
-            M3_PIN();
+            SCHED_PIN();
             mf(1, __builtin_bit_cast(V8, f0[1]));
         }
         m3_read2<6>(f0, fa);
-        m3_wait_lgkm<4>();
+        wait_lgkm<4>(); SCHED_PIN();
         step(f1, 2);
         m3_read2<8>(f1, fa);
-        m3_wait_lgkm<4>();
+        wait_lgkm<4>(); SCHED_PIN();
         step(f2, 4);
         m3_read2<10>(f2, fa);
-        m3_wait_lgkm<4>();
+        wait_lgkm<4>(); SCHED_PIN();
         step(f0, 6);
         m3_read2<12>(f0, fa);
-        m3_wait_lgkm<4>();
+        wait_lgkm<4>(); SCHED_PIN();
         step(f1, 8);
         m3_read2<14>(f1, fa);
-        m3_wait_lgkm<4>();
+        wait_lgkm<4>(); SCHED_PIN();
         step(f2, 10);
         m3_read2<16>(f2, fa);
-        m3_wait_lgkm<4>();
+        wait_lgkm<4>(); SCHED_PIN();
         step(f0, 12);
         m3_read2<18>(f0, fa);
-        m3_wait_lgkm<4>();
+        wait_lgkm<4>(); SCHED_PIN();
         step(f1, 14);
         m3_read2<20>(f1, fa);
-        m3_wait_lgkm<4>();
+        wait_lgkm<4>(); SCHED_PIN();
         step(f2, 16);
         m3_read2<22>(f2, fa);
-        m3_wait_lgkm<4>();
+        wait_lgkm<4>(); SCHED_PIN();
         step(f0, 18);
-        m3_wait_lgkm<2>();
+        wait_lgkm<2>(); SCHED_PIN();
         step(f1, 20);
-        m3_wait_lgkm<0>();
+        wait_lgkm<0>(); SCHED_PIN();
         step(f2, 22);
         if (i >= 1) store_h(hn, i - 1);
     };
@@ -303,7 +276,7 @@ __global__ __launch_bounds__(512, 1) void geglu3_kernel(G3P p) {
         }
         store_h(hn, G3_NCH - 1);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the tail's dummy re-loads must land before the workgroup's LDS is released)
+    wait_vm<0>();  // (the tail's dummy re-loads must land before the workgroup's LDS is released)
 }
 
 // ---- apad_geglu_pack: W1 [8C][C], b1 [8C] -> [4 parts][24 chunks][24 k-steps][64 lanes][8] + the fp32 bias table [4][24][2][16] ----

@@ -11,13 +11,12 @@
 // ds_read_b128 fragment reads); next K-tile's global loads are issued before the MFMAs of the current one.
 // Epilogue: accumulators -> LDS tile -> full-row 16 B stores (residual read with the same coalescing).
 #include <type_traits>
-#include "common.h"
+#include "gfx950_prims.h"
 #include "f32_ops.h"
 
 namespace {
 
 constexpr int BK = 64;
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 // TM = block tile edge: 128 (4 waves x 64x64) for big problems, 64 (4 waves x 32x32) when a 128-tiling would leave
 // most of the 256 CUs idle (the 64-token / 4096-row level of the UNet, 32x2 convolutions)
 // KG = K groups: KG x 4 waves per workgroup, group g reduces the k-tiles g, g + KG, ... of the SAME output tile from its own LDS
@@ -557,7 +556,6 @@ __global__ __launch_bounds__(256 * KG) void gemm_kernel(GemmP p) {
 // Where it is used: the TRAINING step (apad_set_gemm_ring(1), AdapterTrainer: ~2600 launches of <= 4000 rows per step on one stream);
 // in the denoise step the 64-token level runs on two streams and the ring's 66 KB of LDS per workgroup (tiled: 32 KB) costs their
 // co-residency: measured slower there (44.54 -> 44.83 ms), so inference keeps the tiled kernel.
-typedef __attribute__((address_space(3))) void* g_lds_ptr;
 constexpr int RSTAGE = 2 * 64 * BK * 2, RNST = 4, RSMEM = RNST * RSTAGE + 64 * 2 * 4;  // 16 384 per stage + the row statistics
 constexpr uint32_t R_OOB = 0x80000000u;
 
@@ -611,7 +609,7 @@ __global__ __launch_bounds__(256) void gemm_ring_kernel(GemmP p, uint32_t a_byte
     }
     // ---- DMA sources: wave w fills blocks 2w, 2w + 1 (8 rows each) of the A tile and of the W tile; lane -> (row, LDS slot), the
     //      slot holds source chunk slot ^ ((row >> 1) & 7) = lds_off's swizzle ----
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(p.w), 0, (int)w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rw = buf_rsrc(p.w, w_bytes);
     uint32_t aoff[2], aoff2[2], boff[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -629,19 +627,18 @@ __global__ __launch_bounds__(256) void gemm_ring_kernel(GemmP p, uint32_t a_byte
         const bool second = p.a2 != nullptr && kt * BK >= p.ksplit;  // wave-uniform
         const int soff = (second ? kt * BK - p.ksplit : kt * BK) * 2;
         // (the descriptor is rebuilt from scalar selects: two descriptors selected per call were kept in scratch)
-        const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(second ? p.a2 : p.a), 0,
-                                                                            (int)(second ? a2_bytes : a_bytes), 0x00020000);
+        const __amdgpu_buffer_rsrc_t ra = buf_rsrc(second ? p.a2 : p.a, second ? a2_bytes : a_bytes);
 #pragma unroll
         for (int i = 0; i < 2; ++i)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (g_lds_ptr)(st + (wave * 2 + i) * 1024), 16, second ? aoff2[i] : aoff[i], soff, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (lds_ptr)(st + (wave * 2 + i) * 1024), 16, second ? aoff2[i] : aoff[i], soff, 0, 0);
 #pragma unroll
         for (int i = 0; i < 2; ++i)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (g_lds_ptr)(st + 64 * BK * 2 + (wave * 2 + i) * 1024), 16, boff[i], kt * (BK * 2), 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_ptr)(st + 64 * BK * 2 + (wave * 2 + i) * 1024), 16, boff[i], kt * (BK * 2), 0, 0);
     };
     uint32_t fo[4];
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) fo[ks] = (uint32_t)(l31 * 128 + (((ks * 2 + half) ^ ((l31 >> 1) & 7)) << 4));
-    const uint32_t lds0 = (uint32_t)(size_t)(g_lds_ptr)smem;
+    const uint32_t lds0 = (uint32_t)(size_t)(lds_ptr)smem;
     const uint32_t abase = lds0 + (uint32_t)(wm * 32 * 128), bbase = lds0 + (uint32_t)(64 * BK * 2 + wn * 32 * 128);
     f32x16 acc, acc1;  // (named, not an array: a lambda-captured one-element array of vectors went to scratch)
 #pragma unroll
@@ -656,14 +653,10 @@ __global__ __launch_bounds__(256) void gemm_ring_kernel(GemmP p, uint32_t a_byte
         if (t < nk) request(t, t);
     auto ktile = [&](int t, auto stage_tag) {
         constexpr int S = decltype(stage_tag)::value;
-        if (t + 2 < nk) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        else if (t + 1 < nk) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_s_barrier();  // everyone's pieces of tile t are in LDS, everyone is past its reads of tile t - 1
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
+        if (t + 2 < nk) wait_vm<8>();
+        else if (t + 1 < nk) wait_vm<4>();
+        else wait_vm<0>();
+        RAW_BARRIER();  // everyone's pieces of tile t are in LDS, everyone is past its reads of tile t - 1
         if (t + RNST - 1 < nk) request(t + RNST - 1, (S + RNST - 1) % RNST);
         u32x4 fa[4], fb[4];
 #pragma unroll
@@ -672,8 +665,7 @@ __global__ __launch_bounds__(256) void gemm_ring_kernel(GemmP p, uint32_t a_byte
             asm volatile("ds_read_b128 %0, %1" : "=v"(fa[ks]) : "v"(aa));
             asm volatile("ds_read_b128 %0, %1" : "=v"(fb[ks]) : "v"(bb));
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
+        wait_lgkm<0>(); SCHED_PIN();
         // (RNST = 4 is even: the stage index parity is the k-tile parity, i.e. the K group of the tiled kernel)
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {

@@ -24,7 +24,7 @@
 //     round trip, no barrier
 #include <type_traits>
 #include <utility>
-#include "common.h"
+#include "gfx950_prims.h"
 
 namespace {
 
@@ -49,40 +49,8 @@ struct HcP {
     uint32_t a_bytes, w_bytes;
 };
 
-typedef __attribute__((address_space(3))) void* lds_ptr;
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t h_rsrc(const void* p, uint32_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
-}
-
-#define H_FENCE() asm volatile("" ::: "memory")
-#define H_BARRIER()                          \
-    do {                                     \
-        __builtin_amdgcn_sched_barrier(0);   \
-        H_FENCE();                           \
-        __builtin_amdgcn_s_barrier();        \
-        H_FENCE();                           \
-        __builtin_amdgcn_sched_barrier(0);   \
-    } while (0)
-
-template <int N_> __device__ __forceinline__ void h_wait_vm() {
-    if constexpr (N_ == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if constexpr (N_ == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-    else if constexpr (N_ == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    else if constexpr (N_ == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-    else if constexpr (N_ == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else if constexpr (N_ == 5) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-    else if constexpr (N_ == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    else static_assert(N_ == 0, "add the count");
-}
-
 template <int... S, class F> __device__ __forceinline__ void h_for_each(std::integer_sequence<int, S...>, F&& f) {
     (f(std::integral_constant<int, S>{}), ...);
-}
-
-template <int OFF> __device__ __forceinline__ void h_read(u32x4& dst, uint32_t addr) {
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "i"(OFF));
 }
 
 // WAVES_M x WAVES_N waves of (MI x 32 pixels) x (NJ x 32 channels); KS = MFMA steps (16 channels each) per weight stage (2: one 32-channel
@@ -120,7 +88,7 @@ __global__ __launch_bounds__(T::NT) void hconv_kernel(HcP p) {
 
     const int W = p.W, H = p.H, Wlog = p.Wlog;
     const int R = BM >> Wlog;  // image rows of a tile
-    const __amdgpu_buffer_rsrc_t ra = h_rsrc(p.a, p.a_bytes), rw = h_rsrc(p.wp, p.w_bytes);
+    const __amdgpu_buffer_rsrc_t ra = buf_rsrc(p.a, p.a_bytes), rw = buf_rsrc(p.wp, p.w_bytes);
     const uint32_t lds0 = (uint32_t)(size_t)(lds_ptr)smem;
 
     // ---- per tile: origin, halo DMA sources, the lanes' pixel records.  Persistent workgroups: tile tl, tl + gridDim.x, ... ----
@@ -219,10 +187,10 @@ __global__ __launch_bounds__(T::NT) void hconv_kernel(HcP p) {
         constexpr int SET = decltype(set_tag)::value, KSI = decltype(ks_tag)::value, IDX = decltype(idx_tag)::value;
         constexpr bool NEXT = decltype(next_tag)::value != 0;
         if constexpr (IDX < MI) {
-            h_read<0>(fa[SET][IDX], (NEXT ? a0n[IDX] : a0[IDX]) ^ (uint32_t)(KSI << 5));
+            lds_read16<0, 'i'>(fa[SET][IDX], (NEXT ? a0n[IDX] : a0[IDX]) ^ (uint32_t)(KSI << 5));
         } else if constexpr (IDX < MI + NJ) {
             constexpr int J = IDX - MI, SB = (KSI % KS) >> 1;  // sub-block of the stage
-            h_read<SB * T::SUBB + J * 2048>(fb[SET][J], bb);
+            lds_read16<SB * T::SUBB + J * 2048, 'i'>(fb[SET][J], bb);
         }
     };
     using I0 = std::integral_constant<int, 0>;
@@ -256,9 +224,9 @@ __global__ __launch_bounds__(T::NT) void hconv_kernel(HcP p) {
         for (int i = 0; i < MI; ++i)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[j][i][r] = 0.f;
-    h_wait_vm<2 * PBW>();  // the halo and stage 0 have landed (this wave's pieces; whatever the previous tile's epilogue left in flight is older)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    H_BARRIER();
+    wait_vm<2 * PBW>();  // the halo and stage 0 have landed (this wave's pieces; whatever the previous tile's epilogue left in flight is older)
+    wait_lgkm<0>();
+    RAW_BARRIER();
 #pragma unroll
     for (int i = 0; i < MI; ++i) a0[i] = a0n[i] = tap_address(i, 0, 0);
     h_for_each(std::make_integer_sequence<int, NRD>{}, [&](auto idx_tag) { read_one(I0{}, I0{}, idx_tag, I0{}, bfo[0]); });
@@ -275,11 +243,11 @@ __global__ __launch_bounds__(T::NT) void hconv_kernel(HcP p) {
             // (1) stage t + 1 has landed: at most what the previous iteration issued may be outstanding (the halo piece goes first in an
             //     iteration, so a halo piece is covered two iterations after its issue)
             constexpr bool prevA = S >= 1 && S - 1 < NLD;  // the previous iteration issued a halo piece (not in the last chunk)
-            if (!last) h_wait_vm<PBW + (prevA ? 1 : 0)>();
-            else if (S == 0 || S - 1 + 3 < SPC) h_wait_vm<PBW>();
-            else h_wait_vm<0>();
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            H_BARRIER();
+            if (!last) wait_vm<PBW + (prevA ? 1 : 0)>();
+            else if (S == 0 || S - 1 + 3 < SPC) wait_vm<PBW>();
+            else wait_vm<0>();
+            wait_lgkm<0>();
+            RAW_BARRIER();
             // (2) the MFMA steps.  Behind single MFMAs: the fragment reads of step k + 1 (of the next stage behind the last step: the barrier
             //     above certified it), the next tap's addresses, and this iteration's requests -- halo piece S of the next chunk, weight stage
             //     t + 3 (into the slot read in iteration t - 1)
@@ -318,8 +286,7 @@ __global__ __launch_bounds__(T::NT) void hconv_kernel(HcP p) {
                     __builtin_amdgcn_sched_barrier(0);
                 });
                 if constexpr (SAME) {
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                    __builtin_amdgcn_sched_barrier(0);
+                    wait_lgkm<0>(); SCHED_PIN();
                 }
                 if constexpr (NEWTAP) {
 #pragma unroll
@@ -356,7 +323,7 @@ __global__ __launch_bounds__(T::NT) void hconv_kernel(HcP p) {
             if (p.bias && p.ksplit == 1) braw[j][g] = *reinterpret_cast<const uint2*>(p.bias + (int64_t)n * 2);
             if (rg_table && p.ksplit == 1) traw[j][g] = *reinterpret_cast<const uint2*>(p.rg + (step * p.ld_rg + n) * 2);
         }
-    H_BARRIER();
+    RAW_BARRIER();
     // the next tile's setup + requests go out first: their DMA latency runs under this tile's epilogue.  (The 256 x 256 form keeps 164 bytes per lane of
     // loop-invariant addressing state in scratch -- written in the prologue, reloaded here: profiles/r06_pmc_hconv256_v6.txt shows it as 22 MB of WRITE_SIZE
     // beside the 32.8 MB output; moving this setup behind the epilogue or packing the results first did not remove it -- the main loop's 128 accumulators +
@@ -412,7 +379,7 @@ __global__ __launch_bounds__(T::NT) void hconv_kernel(HcP p) {
                 typename E::v4 h4;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) h4[e] = (elem)((acc[j][i][4 * g + e] + (float)b4[e]) + (float)t4[e]);
-                // (inline asm: an LDS access the compiler can see is ordered behind the next tile's DMA in flight -- s_waitcnt vmcnt(0))
+                // (inline asm: an LDS access the compiler can see is ordered behind the next tile's DMA in flight -- a vmcnt(0) wait)
                 const uint2 u2 = __builtin_bit_cast(uint2, h4);
                 asm volatile("ds_write_b64 %0, %1" ::"v"(stg_w + (uint32_t)((j * 32 + 8 * g) * 2)), "v"(u2) : "memory");
             }
@@ -420,8 +387,7 @@ __global__ __launch_bounds__(T::NT) void hconv_kernel(HcP p) {
         u32x4 orow[32 / RPI];
 #pragma unroll
         for (int k = 0; k < 32 / RPI; ++k) asm volatile("ds_read_b128 %0, %1" : "=v"(orow[k]) : "v"(stg_r + (uint32_t)(RPI * k * EROW)));
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
+        wait_lgkm<0>(); SCHED_PIN();
 #pragma unroll
         for (int k = 0; k < 32 / RPI; ++k) {
             const int rl = lane / LPR + RPI * k, m = mrow0 + rl;
@@ -491,7 +457,7 @@ __global__ __launch_bounds__(512) void hnarrow_kernel(HnP p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l15 = lane & 15, kg = lane >> 4;
     const int W = p.W, H = p.H, Wlog = p.Wlog, R = BM >> Wlog;
-    const __amdgpu_buffer_rsrc_t ra = h_rsrc(p.a, p.a_bytes);
+    const __amdgpu_buffer_rsrc_t ra = buf_rsrc(p.a, p.a_bytes);
     const uint32_t lds0 = (uint32_t)(size_t)(lds_ptr)smem;
 
     // the stationary operand
@@ -552,10 +518,10 @@ __global__ __launch_bounds__(512) void hnarrow_kernel(HnP p) {
             const int buf = gc % NBUF;
             // chunk gc has landed: only the pieces of chunk gc + 1 (if the stream has one) may still be outstanding
             const bool has_next = c + 1 < NCH || more;
-            if (has_next) h_wait_vm<NLD>();
-            else h_wait_vm<0>();
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            H_BARRIER();  // every wave's pieces of chunk gc are in LDS, and every wave is past its reads of chunk gc - 1: that buffer takes chunk gc + 2
+            if (has_next) wait_vm<NLD>();
+            else wait_vm<0>();
+            wait_lgkm<0>();
+            RAW_BARRIER();  // every wave's pieces of chunk gc are in LDS, and every wave is past its reads of chunk gc - 1: that buffer takes chunk gc + 2
             {
                 const int c2 = c + 2;  // chunk gc + 2 of the stream: of this tile, of the next one, or of the one after (NCH == 1)
                 const int nbuf = (gc + 2) % NBUF;
@@ -584,8 +550,7 @@ __global__ __launch_bounds__(512) void hnarrow_kernel(HnP p) {
                 for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
                     for (int b = 0; b < 2; ++b) asm volatile("ds_read_b128 %0, %1" : "=v"(fb[kk][b]) : "v"(a0[b] ^ (uint32_t)(kk << 6)));
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_sched_barrier(0);
+                wait_lgkm<0>(); SCHED_PIN();
 #pragma unroll
                 for (int kk = 0; kk < 2; ++kk)
 #pragma unroll

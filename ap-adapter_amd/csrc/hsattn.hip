@@ -26,11 +26,10 @@
 // bytes through the 64 B/clk path than the weights themselves); the launch boundary is the cheaper all-to-all (1.5 us, 20 KB per
 // workgroup each way).  A row's result never depends on its batch: one workgroup = one sample, fixed summation order.
 #include <stdlib.h>
-#include "common.h"
+#include "gfx950_prims.h"
 
 namespace {
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 constexpr float LOG2E = 1.4426950408889634f;
 constexpr float NEG_BIG = -1.0e30f;
 
@@ -39,16 +38,6 @@ constexpr float NEG_BIG = -1.0e30f;
 constexpr int HS_NSET = 8;  // register sets of weight fragments = k-steps a fragment is requested ahead of its use (per wave: NSET x NT KB in flight)
 constexpr int HS_PRE = 2;   // of those, the sets requested BEFORE the sample's rows are normalised (the rest right after: a wave that is still pushing 16 KB
                             // of weight requests into the memory pipe cannot start on rows that have long arrived)
-
-// wave-uniform global pointer pinned to SGPRs (xattn.hip): loads take the scalar base + 32-bit lane offset form
-typedef const __attribute__((address_space(1))) uint8_t* hs_gptr;
-typedef const __attribute__((address_space(1))) u32x4* hs_gptr16;
-__device__ __forceinline__ hs_gptr sgpr_ptr(const uint8_t* p) {
-    const uint64_t a = reinterpret_cast<uint64_t>(p);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a), hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
-    return (hs_gptr)(((uint64_t)hi << 32) | lo);
-}
-__device__ __forceinline__ u32x4 hs_ld16(hs_gptr base, uint32_t off) { return *(hs_gptr16)(base + off); }
 
 constexpr int HS_C = 640, HS_H = 8, HS_D = 80, HS_TM = 64, HS_KS = HS_C / 16, HS_PW = 160;  // PW: features of a head pair / output columns of a quarter
 constexpr int XROWB = HS_C * 2 + 16;   // X / O tile row stride: 81 sixteen-byte slots (odd: conflict-free ds_read_b128 over 32 rows)
@@ -138,8 +127,8 @@ __device__ __forceinline__ void hs_rows_store(const uint4 (&u)[HS_CH], float eps
 // CHAIN: a wave that runs several tile sets back to back (the GEGLU projection) requests the first NSET k-steps of the NEXT set (wbn) behind the
 // last NSET k-steps of this one, so the stream does not drain under the epilogue in between.
 template <int DT, int NT, int NSET, bool SWAP1, bool CHAIN = false>
-__device__ __forceinline__ void hs_project(const hs_gptr (&wb)[NT], uint32_t loff, const uint8_t* xs, typename ET<DT>::v8 (&wf)[NSET][NT], f32x16 (&acc)[NT][2],
-                                           const hs_gptr* wbn = nullptr) {
+__device__ __forceinline__ void hs_project(const gptr (&wb)[NT], uint32_t loff, const uint8_t* xs, typename ET<DT>::v8 (&wf)[NSET][NT], f32x16 (&acc)[NT][2],
+                                           const gptr* wbn = nullptr) {
     using E = ET<DT>;
     static_assert(HS_KS % NSET == 0, "the register sets of weight fragments rotate over the k-steps");
     typename E::v8 t[2][2];  // [k-step parity][panel]
@@ -164,7 +153,7 @@ __device__ __forceinline__ void hs_project(const hs_gptr (&wb)[NT], uint32_t lof
             HS_LDT(kk + i + 1, (i + 1) & 1);
             HS_MM(i, i & 1);
 #pragma unroll
-            for (int j = 0; j < NT; ++j) wf[i][j] = __builtin_bit_cast(typename E::v8, hs_ld16(wb[j] + (kk + i + NSET) * 1024, loff));
+            for (int j = 0; j < NT; ++j) wf[i][j] = __builtin_bit_cast(typename E::v8, ld16(wb[j] + (kk + i + NSET) * 1024, loff));
         }
 #pragma unroll
         for (int i = 0; i < NSET; ++i) {
@@ -179,7 +168,7 @@ __device__ __forceinline__ void hs_project(const hs_gptr (&wb)[NT], uint32_t lof
         HS_MM(i, i & 1);
         if (CHAIN) {
 #pragma unroll
-            for (int j = 0; j < NT; ++j) wf[i][j] = __builtin_bit_cast(typename E::v8, hs_ld16(wbn[j] + i * 1024, loff));
+            for (int j = 0; j < NT; ++j) wf[i][j] = __builtin_bit_cast(typename E::v8, ld16(wbn[j] + i * 1024, loff));
         }
     }
     if (CHAIN) {
@@ -240,7 +229,7 @@ __global__ __launch_bounds__(512) void hs_attn_kernel(HsP p) {
     hs_rows_load(xr, p.x + (int64_t)b * N * HS_C * 2, N, tid);
     const bool proj = SELF || wave < NTILE;
     const bool vslot = SELF && wave >= 2 && wave < 7;  // slot 1 of waves 2 .. 6 = tiles 10 .. 14 = the pair's V rows
-    hs_gptr wb[NT];
+    gptr wb[NT];
     typename E::v8 wf[NSET][NT];
     const uint32_t loff = (uint32_t)lane * 16u;
     int tile[NT];
@@ -255,7 +244,7 @@ __global__ __launch_bounds__(512) void hs_attn_kernel(HsP p) {
 #pragma unroll
         for (int i = 0; i < PRE; ++i)
 #pragma unroll
-            for (int j = 0; j < NT; ++j) wf[i][j] = __builtin_bit_cast(typename E::v8, hs_ld16(wb[j] + i * 1024, loff));
+            for (int j = 0; j < NT; ++j) wf[i][j] = __builtin_bit_cast(typename E::v8, ld16(wb[j] + i * 1024, loff));
     }
     if (tid < NTILE * 8 && p.wbias != nullptr)  // the pair's fp32 bias -> LDS (read by the projection epilogue)
         *reinterpret_cast<float4*>(BIAS + tid * 16) = *reinterpret_cast<const float4*>(p.wbias + pr * NTILE * 32 + tid * 4);
@@ -266,7 +255,7 @@ __global__ __launch_bounds__(512) void hs_attn_kernel(HsP p) {
 #pragma unroll
         for (int i = PRE; i < NSET; ++i)
 #pragma unroll
-            for (int j = 0; j < NT; ++j) wf[i][j] = __builtin_bit_cast(typename E::v8, hs_ld16(wb[j] + i * 1024, loff));
+            for (int j = 0; j < NT; ++j) wf[i][j] = __builtin_bit_cast(typename E::v8, ld16(wb[j] + i * 1024, loff));
     }
     __syncthreads();
 
@@ -451,27 +440,27 @@ __global__ __launch_bounds__(512) void hs_geglu_kernel(HgP p) {
     const int ntl = wave < 4 ? 3 : 2;
     const uint32_t loff = (uint32_t)lane * 16u;
     auto tile_base = [&](int t, int j) { return sgpr_ptr(p.w + ((int64_t)((hq * HG_TILES + t) * 2 + j) * HS_KS) * 1024); };
-    hs_gptr wb[2] = {tile_base(wave, 0), tile_base(wave, 1)};
+    gptr wb[2] = {tile_base(wave, 0), tile_base(wave, 1)};
     typename E::v8 wf[NSET][2];
     constexpr int PRE = HS_PRE < NSET ? HS_PRE : NSET;
 #pragma unroll
     for (int i = 0; i < PRE; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) wf[i][j] = __builtin_bit_cast(typename E::v8, hs_ld16(wb[j] + i * 1024, loff));
+        for (int j = 0; j < 2; ++j) wf[i][j] = __builtin_bit_cast(typename E::v8, ld16(wb[j] + i * 1024, loff));
     if (tid < HG_TILES * 2 * 8 && p.wbias != nullptr)
         *reinterpret_cast<float4*>(BIAS + tid * 16) = *reinterpret_cast<const float4*>(p.wbias + hq * HG_TILES * 2 * 32 + tid * 4);
     hs_rows_store<DT, NORM>(xr, p.eps, N, X, tid);
 #pragma unroll
     for (int i = PRE; i < NSET; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) wf[i][j] = __builtin_bit_cast(typename E::v8, hs_ld16(wb[j] + i * 1024, loff));
+        for (int j = 0; j < 2; ++j) wf[i][j] = __builtin_bit_cast(typename E::v8, ld16(wb[j] + i * 1024, loff));
     __syncthreads();
     uint8_t* const hb = p.out + ((int64_t)b * N * 4 * HS_C + hq * HS_C) * 2;
 #pragma unroll 1
     for (int it = 0; it < ntl; ++it) {
         const int t = wave + 8 * it;
         const int tn = it + 1 < ntl ? t + 8 : t;  // (after the last tile: its own first fragments once more, unused)
-        const hs_gptr wbn[2] = {tile_base(tn, 0), tile_base(tn, 1)};
+        const gptr wbn[2] = {tile_base(tn, 0), tile_base(tn, 1)};
         f32x16 acc[2][2];
 #pragma unroll
         for (int j = 0; j < 2; ++j)
@@ -549,7 +538,7 @@ __global__ __launch_bounds__(512) void hs_out_kernel(HoP p) {
     uint4 xr[HS_CH];
     hs_rows_load(xr, p.o + (int64_t)b * N * HS_C * 2, N, tid);
     const bool proj = wave < NTILE;
-    hs_gptr wb[1];
+    gptr wb[1];
     typename E::v8 wf[NSET][1];
     const uint32_t loff = (uint32_t)lane * 16u;
     wb[0] = sgpr_ptr(p.w + ((int64_t)(cq * NTILE + (proj ? wave : 0)) * HS_KS) * 1024);
@@ -557,12 +546,12 @@ __global__ __launch_bounds__(512) void hs_out_kernel(HoP p) {
     constexpr int PRE = HS_PRE < NSET ? HS_PRE : NSET;
     if (proj) {
 #pragma unroll
-        for (int i = 0; i < PRE; ++i) wf[i][0] = __builtin_bit_cast(typename E::v8, hs_ld16(wb[0] + i * 1024, loff));
+        for (int i = 0; i < PRE; ++i) wf[i][0] = __builtin_bit_cast(typename E::v8, ld16(wb[0] + i * 1024, loff));
     }
     hs_rows_store<DT, false>(xr, 0.f, N, X, tid);
     if (proj) {
 #pragma unroll
-        for (int i = PRE; i < NSET; ++i) wf[i][0] = __builtin_bit_cast(typename E::v8, hs_ld16(wb[0] + i * 1024, loff));
+        for (int i = PRE; i < NSET; ++i) wf[i][0] = __builtin_bit_cast(typename E::v8, ld16(wb[0] + i * 1024, loff));
 #pragma unroll
         for (int g = 0; g < 4; ++g) bq[g] = p.bo != nullptr ? *reinterpret_cast<const uint2*>(p.bo + (cq * HS_PW + wave * 32 + 8 * g + 4 * half) * 2) : make_uint2(0u, 0u);
     }
@@ -658,7 +647,7 @@ __device__ __forceinline__ void hf_body(const HfP& p, uint8_t* smem, int b, int 
     const int N = p.N;
     uint8_t* const T = smem + (HF_LDS - Q_BYTES);
     const uint32_t loff = (uint32_t)lane * 16u;
-    hs_gptr wb[NTW];
+    gptr wb[NTW];
 #pragma unroll
     for (int j = 0; j < NTW; ++j) wb[j] = sgpr_ptr(p.w + ((int64_t)((cq * 5 + t0 + j) * HF_KS + kq * 5)) * 1024);
     // H chunk staging: 64 rows x 40 sixteen-byte pieces = 5 per thread
@@ -688,7 +677,7 @@ __device__ __forceinline__ void hf_body(const HfP& p, uint8_t* smem, int b, int 
 #pragma unroll
     for (int s_ = 0; s_ < 5; ++s_)
 #pragma unroll
-        for (int j = 0; j < NTW; ++j) wf[s_][j] = __builtin_bit_cast(typename E::v8, hs_ld16(wb[j] + s_ * 1024, loff));
+        for (int j = 0; j < NTW; ++j) wf[s_][j] = __builtin_bit_cast(typename E::v8, ld16(wb[j] + s_ * 1024, loff));
     uint2 bq[NTW][4];
     if (kq == 0) {
 #pragma unroll
@@ -730,7 +719,7 @@ __device__ __forceinline__ void hf_body(const HfP& p, uint8_t* smem, int b, int 
                 acc[j][1] = E::mfma32(wf[s_][j], tb, acc[j][1]);
             }
 #pragma unroll
-            for (int j = 0; j < NTW; ++j) wf[s_][j] = __builtin_bit_cast(typename E::v8, hs_ld16(wb[j] + (cn * HF_CK + s_) * 1024, loff));
+            for (int j = 0; j < NTW; ++j) wf[s_][j] = __builtin_bit_cast(typename E::v8, ld16(wb[j] + (cn * HF_CK + s_) * 1024, loff));
         }
 #pragma unroll
         for (int s_ = 0; s_ < 5; ++s_) {

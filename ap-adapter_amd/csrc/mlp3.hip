@@ -59,20 +59,15 @@ __global__ __launch_bounds__(256, 1) void mlp3_kernel(Mlp3P p) {
     const int64_t mw0 = ((int64_t)blockIdx.x * 4 + wave) * 64;
 
     // ---- the weight stream: piece q (0..5) of this wave = 1 KB = one MFMA operand fragment; stage s -> ring slot s % 6 ----
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(p.wpk), 0, M3_NIT * M3_STAGE, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rw = buf_rsrc(p.wpk, M3_NIT * M3_STAGE);
     const uint32_t dvoff = (uint32_t)(lane * 16);
     auto dma = [&](int stage, int slot, int q) __attribute__((always_inline)) {
         // the instruction's immediate offset moves the memory address AND the LDS address: pieces 0..3 of the wave share one M0 / scalar offset,
         // pieces 4, 5 the next (the packed stream and the ring slot have the same piece order)
         const int grp = q >> 2;
-        const m3_lds_ptr lp = (m3_lds_ptr)(smem + slot * M3_STAGE + wave * 6144 + grp * 4096);
+        const lds_ptr lp = (lds_ptr)(smem + slot * M3_STAGE + wave * 6144 + grp * 4096);
         const int so = stage * M3_STAGE + wave * 6144 + grp * 4096;
-        switch (q & 3) {
-            case 0: __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, lp, 16, dvoff, so, 0, 0); break;
-            case 1: __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, lp, 16, dvoff, so, 1024, 0); break;
-            case 2: __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, lp, 16, dvoff, so, 2048, 0); break;
-            default: __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, lp, 16, dvoff, so, 3072, 0); break;
-        }
+        dma_piece<4>(rw, lp, dvoff, so, q & 3);
     };
 
     // ---- x panels -> registers (requested first: HBM latency), biases -> LDS (fp32; ahead of the first DMA: an LDS store the compiler can see is
@@ -105,7 +100,7 @@ __global__ __launch_bounds__(256, 1) void mlp3_kernel(Mlp3P p) {
 #pragma unroll
     for (int r = 0; r < 8; ++r) h0a[r] = h1a[r] = h0b[r] = h1b[r] = (typename E::elem)0.f;
 
-    const uint32_t lds0 = (uint32_t)(size_t)(m3_lds_ptr)smem;
+    const uint32_t lds0 = (uint32_t)(size_t)(lds_ptr)smem;
     const uint32_t fbase = lds0 + (uint32_t)(lane * 16);
     const uint32_t tbase = lds0 + (uint32_t)(M3_RING + half * 64);
     __syncthreads();  // the bias tables are in LDS (this also drains the prologue's DMA: the compiler waits vmcnt(0) here)
@@ -115,11 +110,10 @@ __global__ __launch_bounds__(256, 1) void mlp3_kernel(Mlp3P p) {
     auto iteration = [&](auto cfg, int i, int slot, f32x16& acur0, f32x16& acur1, f32x16& anxt0, f32x16& anxt1, const V8& hp0, const V8& hp1, V8& hn0, V8& hn1) __attribute__((always_inline)) {
         using CF = decltype(cfg);  // M3It<VM, DMA, G1, GG>: outstanding pieces allowed at the top, DMA issue / gemm1 / GEGLU of this iteration on or off
         // stage i has landed for this wave's pieces (VM younger requests may stay in flight); every wave is past its reads of stage i - 1
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CF::VM) : "memory");
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
+        wait_vm<CF::VM>();
+        wait_lgkm<0>(); SCHED_PIN();
         __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
+        SCHED_PIN();
         const uint32_t fa = fbase + (uint32_t)(slot * M3_STAGE);
         const uint32_t ta = tbase + (uint32_t)(i * 128);
         const int nstage = i + M3_NS - 1 < M3_NIT ? i + M3_NS - 1 : M3_NIT - 1;  // (past the end: a dummy re-load keeps the vmcnt arithmetic uniform)
@@ -135,70 +129,70 @@ __global__ __launch_bounds__(256, 1) void mlp3_kernel(Mlp3P p) {
         auto step2 = [&](const u32x4 (&f)[2], int ct, int r) __attribute__((always_inline)) {
             const V8 w0 = __builtin_bit_cast(V8, f[0]), w1 = __builtin_bit_cast(V8, f[1]);
             y0[ct] = E::mfma32(w0, hp0, y0[ct]);
-            M3_PIN();
+            SCHED_PIN();
             if (CF::GG) gg.ph1(acur0[8 + r], acur0[9 + r]);
-            M3_PIN();
+            SCHED_PIN();
             y1[ct] = E::mfma32(w0, hp1, y1[ct]);
-            M3_PIN();
+            SCHED_PIN();
             if (CF::GG) gg.ph2();
-            M3_PIN();
+            SCHED_PIN();
             y0[ct + 1] = E::mfma32(w1, hp0, y0[ct + 1]);
-            M3_PIN();
+            SCHED_PIN();
             if (CF::GG) gg.ph3();
-            M3_PIN();
+            SCHED_PIN();
             y1[ct + 1] = E::mfma32(w1, hp1, y1[ct + 1]);
-            M3_PIN();
+            SCHED_PIN();
             if (CF::GG) gg.template ph4<V8, EL>(acur0[r], acur0[r + 1], hn0, r);
-            M3_PIN();
+            SCHED_PIN();
         };
         // one step of gemm1 (chunk i): k-steps ks, ks + 1 x two panels; r >= 0: the GEGLU of hidden units r, r + 1 of panel 1 between the MFMAs
         auto step1 = [&](const u32x4 (&f)[2], int ks, int r, int q, int q2) __attribute__((always_inline)) {
             const V8 w0 = __builtin_bit_cast(V8, f[0]), w1 = __builtin_bit_cast(V8, f[1]);
-            if (CF::G1) M3Asm<DT>::acc(anxt0, w0, xf0[ks]);
-            M3_PIN();
+            if (CF::G1) AsmMfma<DT, 'v'>::acc(anxt0, w0, xf0[ks]);
+            SCHED_PIN();
             if (CF::DMA && q >= 0) dma(nstage, nslot, q);
             if (CF::GG && r >= 0) gg.ph1(acur1[8 + r], acur1[9 + r]);
-            M3_PIN();
-            if (CF::G1) M3Asm<DT>::acc(anxt1, w0, xf1[ks]);
-            M3_PIN();
+            SCHED_PIN();
+            if (CF::G1) AsmMfma<DT, 'v'>::acc(anxt1, w0, xf1[ks]);
+            SCHED_PIN();
             if (CF::GG && r >= 0) gg.ph2();
-            M3_PIN();
-            if (CF::G1) M3Asm<DT>::acc(anxt0, w1, xf0[ks + 1]);
-            M3_PIN();
+            SCHED_PIN();
+            if (CF::G1) AsmMfma<DT, 'v'>::acc(anxt0, w1, xf0[ks + 1]);
+            SCHED_PIN();
             if (CF::DMA && q2 >= 0) dma(nstage, nslot, q2);
             if (CF::GG && r >= 0) gg.ph3();
-            M3_PIN();
-            if (CF::G1) M3Asm<DT>::acc(anxt1, w1, xf1[ks + 1]);
-            M3_PIN();
+            SCHED_PIN();
+            if (CF::G1) AsmMfma<DT, 'v'>::acc(anxt1, w1, xf1[ks + 1]);
+            SCHED_PIN();
             if (CF::GG && r >= 0) gg.template ph4<V8, EL>(acur1[r], acur1[r + 1], hn1, r);
-            M3_PIN();
+            SCHED_PIN();
         };
 
         // ---- gemm2 of chunk i - 2 (4 steps) with the activation of panel 0 under it ----
         m3_read2<18>(fB, fa);
-        m3_wait_lgkm<2>();
+        wait_lgkm<2>(); SCHED_PIN();
         step2(fA, 0, 0);
         m3_read2<20>(fA, fa);
-        m3_wait_lgkm<2>();
+        wait_lgkm<2>(); SCHED_PIN();
         step2(fB, 2, 2);
         m3_read2<22>(fB, fa);
-        m3_wait_lgkm<2>();
+        wait_lgkm<2>(); SCHED_PIN();
         step2(fA, 4, 4);
         if (CF::G1) {
             m3_read2<0>(fA, fa);  // W1 k-steps 0, 1; then b1 of chunk i (C-layout register order): short-lived, read just ahead of its use
-            m3_read<0>(bq[0], ta);
-            m3_read<16>(bq[1], ta);
-            m3_read<32>(bq[2], ta);
-            m3_read<48>(bq[3], ta);
-            m3_wait_lgkm<6>();
+            lds_read16<0>(bq[0], ta);
+            lds_read16<16>(bq[1], ta);
+            lds_read16<32>(bq[2], ta);
+            lds_read16<48>(bq[3], ta);
+            wait_lgkm<6>(); SCHED_PIN();
         } else {
-            m3_wait_lgkm<0>();
+            wait_lgkm<0>(); SCHED_PIN();
             bq[0] = bq[1] = bq[2] = bq[3] = fA[0] = fA[1] = u32x4{0u, 0u, 0u, 0u};
         }
         step2(fB, 6, 6);
         // ---- gemm1 of chunk i (8 steps; b1 is the C operand of the first MFMA of each panel) with the activation of panel 1 under it ----
         if (CF::G1) m3_read2<2>(fB, fa);
-        m3_wait_lgkm<2>();
+        wait_lgkm<2>(); SCHED_PIN();
         {
             f32x16 bias;
 #pragma unroll
@@ -207,44 +201,44 @@ __global__ __launch_bounds__(256, 1) void mlp3_kernel(Mlp3P p) {
                 for (int e = 0; e < 4; ++e) bias[qd * 4 + e] = __uint_as_float(bq[qd][e]);
             const V8 w0 = __builtin_bit_cast(V8, fA[0]), w1 = __builtin_bit_cast(V8, fA[1]);
             if (CF::G1) {
-                M3Asm<DT>::first(anxt0, w0, xf0[0], bias);
-                M3Asm<DT>::first(anxt1, w0, xf1[0], bias);
+                AsmMfma<DT, 'v'>::first(anxt0, w0, xf0[0], bias);
+                AsmMfma<DT, 'v'>::first(anxt1, w0, xf1[0], bias);
                 // (a vector write to a register an in-flight MFMA still reads as its C operand is a software hazard -- 13 wait states for a 32x32
                 //  MFMA --, and the compiler, which does not see an MFMA in the asm, is free to recycle the b1 registers right here)
                 asm volatile("s_nop 7\n\ts_nop 6" ::: "memory");
             }
-            M3_PIN();
+            SCHED_PIN();
             if (CF::GG) gg.ph1(acur1[8], acur1[9]);
             if (CF::GG) gg.ph2();
-            M3_PIN();
-            if (CF::G1) M3Asm<DT>::acc(anxt0, w1, xf0[1]);
-            M3_PIN();
+            SCHED_PIN();
+            if (CF::G1) AsmMfma<DT, 'v'>::acc(anxt0, w1, xf0[1]);
+            SCHED_PIN();
             if (CF::GG) gg.ph3();
-            M3_PIN();
-            if (CF::G1) M3Asm<DT>::acc(anxt1, w1, xf1[1]);
-            M3_PIN();
+            SCHED_PIN();
+            if (CF::G1) AsmMfma<DT, 'v'>::acc(anxt1, w1, xf1[1]);
+            SCHED_PIN();
             if (CF::GG) gg.template ph4<V8, EL>(acur1[0], acur1[1], hn1, 0);
-            M3_PIN();
+            SCHED_PIN();
         }
         if (CF::G1) m3_read2<4>(fA, fa);
-        m3_wait_lgkm<2>();
+        wait_lgkm<2>(); SCHED_PIN();
         step1(fB, 2, -1, 0, 1);
         if (CF::G1) m3_read2<6>(fB, fa);
-        m3_wait_lgkm<2>();
+        wait_lgkm<2>(); SCHED_PIN();
         step1(fA, 4, 2, -1, -1);
         if (CF::G1) m3_read2<8>(fA, fa);
-        m3_wait_lgkm<2>();
+        wait_lgkm<2>(); SCHED_PIN();
         step1(fB, 6, -1, 2, 3);
         if (CF::G1) m3_read2<10>(fB, fa);
-        m3_wait_lgkm<2>();
+        wait_lgkm<2>(); SCHED_PIN();
         step1(fA, 8, 4, -1, -1);
         if (CF::G1) m3_read2<12>(fA, fa);
-        m3_wait_lgkm<2>();
+        wait_lgkm<2>(); SCHED_PIN();
         step1(fB, 10, -1, 4, 5);
         if (CF::G1) m3_read2<14>(fB, fa);
-        m3_wait_lgkm<2>();
+        wait_lgkm<2>(); SCHED_PIN();
         step1(fA, 12, 6, -1, -1);
-        m3_wait_lgkm<0>();
+        wait_lgkm<0>(); SCHED_PIN();
         step1(fB, 14, -1, -1, -1);
     };
 
@@ -270,7 +264,7 @@ __global__ __launch_bounds__(256, 1) void mlp3_kernel(Mlp3P p) {
     const int l31_e = lane_e & 31, half_e = lane_e >> 5;
     const int64_t nrow64 = p.M - mw0;
     const uint32_t nrow = (uint32_t)(nrow64 < 0 ? 0 : (nrow64 > 64 ? 64 : nrow64));
-    const __amdgpu_buffer_rsrc_t rres = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(p.x) + mw0 * (M3_C * 2), 0, (int)(nrow * (M3_C * 2)), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rres = buf_rsrc(p.x + mw0 * (M3_C * 2), nrow * (M3_C * 2));
     const uint32_t roff = (uint32_t)(lane_e * 16);
     const int rrow0 = half_e;
     const uint32_t rcol = (uint32_t)(l31_e * 16);
@@ -287,7 +281,7 @@ __global__ __launch_bounds__(256, 1) void mlp3_kernel(Mlp3P p) {
     __builtin_amdgcn_sched_barrier(0);
 
     // ---- epilogue: y + b2 -> storage type -> this wave's [64][256] tile in the dead ring -> + x (requested above) -> whole-row stores ----
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lgkm<0>();
 #pragma unroll
     for (int v = NEARLY; v < 32; ++v) res[v] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rres, roff, v * 1024, 0));
     __syncthreads();
@@ -309,7 +303,7 @@ __global__ __launch_bounds__(256, 1) void mlp3_kernel(Mlp3P p) {
             }
     // (a wave reads back only its own tile: its own LDS writes are ordered before its reads)
     {
-        const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc(p.out + mw0 * (M3_C * 2), 0, (int)(nrow * (M3_C * 2)), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rout = buf_rsrc(p.out + mw0 * (M3_C * 2), nrow * (M3_C * 2));
 #pragma unroll
         for (int v = 0; v < 32; ++v) {
             float f[8], r[8];

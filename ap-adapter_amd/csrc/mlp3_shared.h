@@ -1,24 +1,16 @@
 // Pieces shared by the 64-token register-block kernels (mlp3.hip: the whole feed-forward at C = 256; geglu3.hip: LayerNorm + GEGLU projection at
-// C = 384): inline-asm LDS fragment reads + counted waits beside an LDS-DMA ring, the GEGLU arithmetic in placeable phases, VGPR-accumulator MFMAs.
+// C = 384): the packed stage's fragment reads, the GEGLU arithmetic in placeable phases.  The hand-scheduling primitives are gfx950_prims.h's.
 #pragma once
+#include "gfx950_prims.h"
 #include "rp_shared.h"
 
 namespace {
 
-typedef __attribute__((address_space(3))) void* m3_lds_ptr;
-
-template <int OFF> __device__ __forceinline__ void m3_read(u32x4& d, uint32_t a) {
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(a), "n"(OFF));
-}
+// the two 1 KB fragments F0, F0 + 1 of a packed stage (fragment F at F KB)
 template <int F0> __device__ __forceinline__ void m3_read2(u32x4 (&f)[2], uint32_t a) {
-    m3_read<F0 * 1024>(f[0], a);
-    m3_read<(F0 + 1) * 1024>(f[1], a);
+    lds_read16<F0 * 1024>(f[0], a);
+    lds_read16<(F0 + 1) * 1024>(f[1], a);
 }
-template <int N> __device__ __forceinline__ void m3_wait_lgkm() {
-    asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
-#define M3_FENCE() asm volatile("" ::: "memory")
 
 // GEGLU of two hidden units (value v*, gate g*) in four phases of ~8 vector instructions, so that the phases can be placed between the MFMAs of a
 // step by hand (one wave per SIMD: an MFMA covers the few vector instructions issued right behind it, nothing else does).  gelu_erf_2's arithmetic
@@ -75,30 +67,5 @@ template <bool PRE> struct M3GegluT {
 };
 template <int DT> using M3Geglu = M3GegluT<DT == APAD_BF16>;
 template <int DT> constexpr float m3_value_scale() { return DT == APAD_BF16 ? 0.5f : 1.0f; }
-
-// gemm1's MFMAs are inline asm with VGPR accumulators: the compiler's MFMAs of this function are the AGPR form (the 256 output accumulators fill the
-// AGPR file), and an AGPR-form accumulator for gemm1 would have to be copied out through v_accvgpr_read for the GEGLU arithmetic (and, with 320
-// accumulator registers asked of a 256-entry file, shuffled between AGPR ranges: measured in the ISA, 8 copies per MFMA).  Hazards the compiler would
-// have covered: the accumulators are read by vector instructions only an LDS round trip (the next iteration's fragment wait) after the last MFMA
-// that writes them; the first MFMA's C operand (b1, straight from ds_read_b128) sits behind an explicit wait + s_nop.
-template <int DT> struct M3Asm;
-template <> struct M3Asm<APAD_BF16> {
-    template <typename V8> static __device__ __forceinline__ void first(f32x16& d, const V8& a, const V8& b, const f32x16& c) {
-        asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_bf16 %0, %1, %2, %3" : "=&v"(d) : "v"(a), "v"(b), "v"(c));
-    }
-    template <typename V8> static __device__ __forceinline__ void acc(f32x16& d, const V8& a, const V8& b) {
-        asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(d) : "v"(a), "v"(b));
-    }
-};
-template <> struct M3Asm<APAD_F16> {
-    template <typename V8> static __device__ __forceinline__ void first(f32x16& d, const V8& a, const V8& b, const f32x16& c) {
-        asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_f16 %0, %1, %2, %3" : "=&v"(d) : "v"(a), "v"(b), "v"(c));
-    }
-    template <typename V8> static __device__ __forceinline__ void acc(f32x16& d, const V8& a, const V8& b) {
-        asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(d) : "v"(a), "v"(b));
-    }
-};
-#define M3_PIN() __builtin_amdgcn_sched_barrier(0)
-
 
 }  // namespace

@@ -6,8 +6,6 @@
 
 namespace {
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 struct Seg {
     uint8_t* out;
     const uint8_t* bias;

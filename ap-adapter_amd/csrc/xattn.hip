@@ -22,6 +22,7 @@
 //     algorithmic bytes); phase 4 streams whole rows out
 //   * K / V of a (sample, head) are a few KB, fragment-packed at hoist time: coalesced 1 KB loads, L2-resident
 #include <type_traits>
+#include "gfx950_prims.h"
 #include "rp_shared.h"
 
 namespace {
@@ -55,20 +56,6 @@ struct XaP {
 // bytes of one (sample, head) block of a packed K/V set: [K fragments: nsub x 2][V^T fragments: nsub x 2], 1 KB each
 __host__ __device__ inline int64_t xa_kv_block(int L) { return (int64_t)((L + 31) / 32) * 4 * 1024; }
 
-// a wave-uniform pointer, pinned to SGPRs: loads through it take the (scalar base + 32-bit lane offset) form instead of a
-// 64-bit per-lane address -- the compiler otherwise hoists one such address per weight fragment out of the tile loop (24
-// registers per weight), which is what spilled in this 256-register kernel
-// (typed as a GLOBAL-address-space pointer: after the integer round trip the compiler no longer infers that, and a generic
-//  pointer turns the loads into flat_load, which also ticks lgkmcnt and makes every later wait a vmcnt(0))
-typedef const __attribute__((address_space(1))) uint8_t* xa_gptr;
-typedef const __attribute__((address_space(1))) u32x4* xa_gptr16;
-__device__ __forceinline__ xa_gptr sgpr_ptr(const uint8_t* p) {
-    const uint64_t a = reinterpret_cast<uint64_t>(p);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a), hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
-    return (xa_gptr)(((uint64_t)hi << 32) | lo);
-}
-__device__ __forceinline__ u32x4 xa_ld16(xa_gptr base, uint32_t off) { return *(xa_gptr16)(base + off); }
-
 __device__ __forceinline__ float oct_sum(float v) {
     // 8 consecutive lanes own one token row: two DPP quad permutes + one half-row mirror, no LDS
     v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0xB1, 0xf, 0xf, true));   // quad_perm [1,0,3,2]
@@ -86,17 +73,17 @@ template <int DT, int NS> struct XaFrags {
 
 // coalesced: fragment f of the block is 64 lanes x 16 bytes
 template <int DT, int NS> __device__ __forceinline__ void xa_fetch(XaFrags<DT, NS>& f, const uint8_t* blk_, int L, int lane) {
-    const xa_gptr blk = sgpr_ptr(blk_);
+    const gptr blk = sgpr_ptr(blk_);
 #pragma unroll
     for (int u = 0; u < NS; ++u) {
 #pragma unroll
-        for (int kk = 0; kk < 2; ++kk) f.kf[u][kk] = __builtin_bit_cast(typename ET<DT>::v8, xa_ld16(blk + (u * 2 + kk) * 1024, (uint32_t)(lane * 16)));
+        for (int kk = 0; kk < 2; ++kk) f.kf[u][kk] = __builtin_bit_cast(typename ET<DT>::v8, ld16(blk + (u * 2 + kk) * 1024, (uint32_t)(lane * 16)));
     }
-    const xa_gptr vb = blk + NS * 2 * 1024;
+    const gptr vb = blk + NS * 2 * 1024;
 #pragma unroll
     for (int st = 0; st < 2 * NS; ++st) {
         if (st * 16 >= L) break;
-        f.vf[st] = __builtin_bit_cast(typename ET<DT>::v8, xa_ld16(vb + st * 1024, (uint32_t)(lane * 16)));
+        f.vf[st] = __builtin_bit_cast(typename ET<DT>::v8, ld16(vb + st * 1024, (uint32_t)(lane * 16)));
     }
 }
 
@@ -428,9 +415,9 @@ __global__ __launch_bounds__(512) void xattn_kernel(XaP p) {
     //      temporaries, so that its 64 registers are not live (and spilled) during phase 1; the barrier hides the latency ----
     typename E::v8 wf[XKC];
     {
-        const xa_gptr wp = sgpr_ptr(p.wq + wave * (XKC * 1024));
+        const gptr wp = sgpr_ptr(p.wq + wave * (XKC * 1024));
 #pragma unroll
-        for (int kk = 0; kk < XKC; ++kk) wf[kk] = __builtin_bit_cast(typename ET<DT>::v8, xa_ld16(wp + kk * 1024, (uint32_t)(lane * 16)));
+        for (int kk = 0; kk < XKC; ++kk) wf[kk] = __builtin_bit_cast(typename ET<DT>::v8, ld16(wp + kk * 1024, (uint32_t)(lane * 16)));
     }
     __syncthreads();
 
@@ -565,8 +552,8 @@ __global__ __launch_bounds__(512) void xattn_kernel(XaP p) {
             constexpr int CNT = decltype(cnt_tag)::value;
             xa_fetch<DT, NS1>(f1, p.kv1 + ((int64_t)b * XH + h) * xa_kv_block(p.L1), p.L1, lane);
             const int nsub2 = p.L2 >> 5;
-            const xa_gptr kb = sgpr_ptr(p.kv2 + ((int64_t)b * XH + h) * xa_kv_block(p.L2));
-            const xa_gptr vb = kb + nsub2 * 2048;
+            const gptr kb = sgpr_ptr(p.kv2 + ((int64_t)b * XH + h) * xa_kv_block(p.L2));
+            const gptr vb = kb + nsub2 * 2048;
             f32x16 o2[CNT];
             float mx[CNT], l0[CNT], l1[CNT];
 #pragma unroll
@@ -590,12 +577,12 @@ __global__ __launch_bounds__(512) void xattn_kernel(XaP p) {
                 for (int u = 0; u < 2; ++u)
 #pragma unroll
                     for (int kk = 0; kk < 2; ++kk)
-                        kf[u][kk] = __builtin_bit_cast(typename E::v8, xa_ld16(kb + (c * 4 + u * 2 + kk) * 1024, (uint32_t)(lane * 16)));
+                        kf[u][kk] = __builtin_bit_cast(typename E::v8, ld16(kb + (c * 4 + u * 2 + kk) * 1024, (uint32_t)(lane * 16)));
             };
             auto load_v = [&](int c) {
                 c = c < nch ? c : nch - 1;
 #pragma unroll
-                for (int st = 0; st < 4; ++st) vf[st] = __builtin_bit_cast(typename E::v8, xa_ld16(vb + (c * 4 + st) * 1024, (uint32_t)(lane * 16)));
+                for (int st = 0; st < 4; ++st) vf[st] = __builtin_bit_cast(typename E::v8, ld16(vb + (c * 4 + st) * 1024, (uint32_t)(lane * 16)));
             };
             load_k(0);
             load_v(0);
@@ -668,9 +655,9 @@ __global__ __launch_bounds__(512) void xattn_kernel(XaP p) {
     }
     // ---- weights of this wave for phase 3: rows (output channels) wave*32.. of Wo ----
     {
-        const xa_gptr wp = sgpr_ptr(p.wo + wave * (XKC * 1024));
+        const gptr wp = sgpr_ptr(p.wo + wave * (XKC * 1024));
 #pragma unroll
-        for (int kk = 0; kk < XKC; ++kk) wf[kk] = __builtin_bit_cast(typename ET<DT>::v8, xa_ld16(wp + kk * 1024, (uint32_t)(lane * 16)));
+        for (int kk = 0; kk < XKC; ++kk) wf[kk] = __builtin_bit_cast(typename ET<DT>::v8, ld16(wp + kk * 1024, (uint32_t)(lane * 16)));
     }
     __syncthreads();  // O tile complete; the x^ tile is free
 
