@@ -53,3 +53,67 @@ def full_unet(scale):
         if hasattr(p, "to_k_ip"):
             p.scale = scale
     return u
+
+
+def exact_operand(*shape, seed=0, std=1.0, shift=None):
+    """fp32 N(0, std) (+ ``shift``, broadcast), rounded to bf16 and flushed to zero below 2^-14: every value is then exact in bf16,
+    f16 and fp32, so the three precision modes and an fp64 reference all see the same numbers"""
+    t = torch.randn(*shape, generator=torch.Generator().manual_seed(seed)) * std
+    if shift is not None:
+        t = t + shift
+    t = t.to(torch.bfloat16).float()
+    return torch.where(t.abs() < 2.0 ** -14, torch.zeros_like(t), t)
+
+
+def block_rel_err(out, ref, nblocks):
+    """(worst, index) of the max-abs error of each of ``nblocks`` equal blocks relative to that block's own max|ref| (the leading
+    dims of ``out`` / ``ref`` must enumerate the blocks).  A block whose reference is all zero must be exactly zero: its error is
+    0 or inf."""
+    e = (out.detach().double().cpu() - ref.detach().double().cpu()).reshape(nblocks, -1).abs().amax(1)
+    m = ref.detach().double().cpu().reshape(nblocks, -1).abs().amax(1)
+    r = torch.where(m > 0, e / m.clamp_min(1e-300), torch.where(e > 0, torch.full_like(e, float("inf")), torch.zeros_like(e)))
+    i = int(r.argmax())
+    return float(r[i]), i
+
+
+_HIP = []
+
+
+def _hip_runtime():
+    import ctypes
+    if not _HIP:
+        path = None
+        with open("/proc/self/maps") as f:  # the HIP runtime torch already loaded
+            for line in f:
+                if "libamdhip64.so" in line:
+                    path = line.split()[-1]
+                    break
+        lib = ctypes.CDLL(path or "libamdhip64.so")
+        lib.hipMemsetD32Async.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p]
+        lib.hipMemsetD32Async.restype = ctypes.c_int
+        _HIP.append(lib)
+    return _HIP[0]
+
+
+# one 32-bit word that is a NaN as fp32 and whose two halves are NaNs as bf16 and as f16
+NAN_WORD = 0x7FFF7FFF
+
+
+def nan_fill_free(dev):
+    """Fill every free block of torch's caching allocator on ``dev`` with NaN (NAN_WORD).  Outputs and scratch buffers the next
+    launches allocate come from these blocks, so an element, pad column or scratch entry a kernel fails to write reads as NaN
+    instead of as stale data of an earlier test.  (Only memory the allocator holds and no live tensor uses is written.)"""
+    import ctypes
+    torch.cuda.synchronize(dev)
+    lib = _hip_runtime()
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    for seg in torch.cuda.memory_snapshot():
+        if seg.get("device", dev.index or 0) != (dev.index or 0):
+            continue
+        addr = seg["address"]
+        for blk in seg["blocks"]:
+            if blk["state"] == "inactive" and blk["size"] >= 4:
+                rc = lib.hipMemsetD32Async(ctypes.c_void_p(addr), NAN_WORD, blk["size"] // 4, ctypes.c_void_p(stream))
+                assert rc == 0, f"hipMemsetD32Async: error {rc}"
+            addr += blk["size"]
+    torch.cuda.synchronize(dev)
