@@ -171,6 +171,8 @@ SYMBOLS = {
     # audio front-end (f-2)
     "apad_resample_fir": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp]),
     "apad_kaldi_fbank": (C.c_int, [_vp, _i64, _f32, _vp, _vp, _vp, _vp, _i32, _i32, _f32, _f32, _f32, _vp]),
+    "apad_wav_stats": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp]),
+    "apad_stft_logmel": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp]),
     "apad_adamw_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _vp]),
 }
 
@@ -206,7 +208,7 @@ def lib():
                 fn = getattr(h, name)  # AttributeError if the ABI lost a symbol
                 fn.restype = res
                 fn.argtypes = args
-            if h.apad_abi_version() != 10:
+            if h.apad_abi_version() != 11:
                 raise RuntimeError("libapadapter_hip.so ABI version mismatch")
             if h.apad_sizeof_gemm_desc() != C.sizeof(GemmDesc) or h.apad_sizeof_attn_desc() != C.sizeof(AttnDesc) \
                     or h.apad_sizeof_rp_desc() != C.sizeof(RpDesc) \

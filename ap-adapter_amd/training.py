@@ -387,19 +387,33 @@ def apply_condition_dropout(prompt_texts, mels, rng):
 class CollateFunction:
     """The reference's CollateFunction (:424-479) on this package's kernels.  ``encode_prompt(list_of_texts)`` must return
     (prompt_embeds, attention_mask, generated_prompt_embeds) -- the CLAP / T5 / GPT-2 encoders are third-party models
-    outside the hot path (SURVEY f-4); the audio condition (front-end + AudioMAE + pooling) runs here."""
+    outside the hot path (SURVEY f-4); the audio condition (front-end + AudioMAE + pooling) runs here.
 
-    def __init__(self, audiomae, encode_prompt, rng=None, device=None):
+    ``batch["mel"]`` (the VAE's input): stacked as given when every example carries a precomputed ``"mel"``; otherwise, when
+    every example has ``"mel"`` or ``"audio_path"``, fp32 [B, 1, int(duration * 102.4), 64] with the missing ones computed
+    in one ``frontend.wav_to_mel_batch`` call (the dataset's ``wav_to_mel``, :394-401).  Each wav is decoded once for both
+    front-ends."""
+
+    def __init__(self, audiomae, encode_prompt, rng=None, device=None, duration=10.0):
         import random
         self.model = audiomae
         self.encode_prompt = encode_prompt
         self.rng = rng or random.Random()
         self.device = device
+        self.duration = duration
 
     def __call__(self, examples):
-        from .frontend import load_mel
+        from .frontend import MEL_BINS, extract_kaldi_fbank_feature, load_wav, mel_target_frames, wav_to_mel_batch
+        decoded = {}
+
+        def wav(i):  # (waveform, sample rate), read once per example
+            if i not in decoded:
+                decoded[i] = load_wav(examples[i]["audio_path"])
+            return decoded[i]
+
         texts = [e["text"] for e in examples]
-        mel_spect = [e["fbank"] if "fbank" in e else load_mel(e["audio_path"], device=self.device)[0] for e in examples]
+        mel_spect = [e["fbank"] if "fbank" in e else extract_kaldi_fbank_feature(*wav(i), device=self.device)
+                     for i, e in enumerate(examples)]
         pooling_rate = self.rng.choice(POOL_LIST)  # ONE rate per batch (:443-444)
         texts, mel_spect = apply_condition_dropout(texts, mel_spect, self.rng)
         with torch.no_grad():
@@ -410,6 +424,15 @@ class CollateFunction:
                  "pooling_rate": pooling_rate}
         if all("mel" in e for e in examples):
             batch["mel"] = torch.stack([e["mel"] for e in examples]).float()
+        elif all("mel" in e or "audio_path" in e for e in examples):
+            need = [i for i, e in enumerate(examples) if "mel" not in e]
+            computed = wav_to_mel_batch([wav(i)[0] for i in need], [wav(i)[1] for i in need], self.duration, device=self.device)
+            if len(need) == len(examples):
+                batch["mel"] = computed
+            else:
+                target, rows = mel_target_frames(self.duration), iter(computed)
+                batch["mel"] = torch.stack([next(rows) if "mel" not in e else
+                                            e["mel"].to(computed.device, torch.float32).reshape(1, target, MEL_BINS) for e in examples])
         return batch
 
 

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define APAD_ABI_VERSION 10
+#define APAD_ABI_VERSION 11
 
 /* element types of activations / weights */
 enum { APAD_BF16 = 0, APAD_F16 = 1, APAD_F32 = 2 };
@@ -581,6 +581,24 @@ int apad_resample_fir(const float* x, const float* kernel, float* out, int64_t n
 int apad_kaldi_fbank(const float* x, int64_t n_samples, float dc, const float* window, const float* twiddle,
                      const float* mel, float* out, int32_t target_frames, int32_t num_mel_bins, float preemphasis,
                      float norm_mean, float norm_std, void* stream);
+
+/* VAE log-mel front-end ("next" rows f-2 / f-3; train_apadapter_v2.py:253-336 wav_to_mel -> audioldm TacotronSTFT) (ABI 11).
+   A ragged batch of `batch` mono 16 kHz clips: x = the clips' samples packed back to back, offsets [batch + 1] int64 in
+   DEVICE memory (clip b = x[offsets[b] .. offsets[b+1])), offsets_host = the same offsets in host memory (validation
+   only; the kernels read the device copy, so both launches are hipGraph-capturable).  Every clip must hold > 100 samples
+   and offsets[0] must be 0, else -1 and apad_last_error().  Per-clip results do not depend on the batch around the clip.
+
+   stats [batch][2] = {mean, scale}: mean of the clip, scale = 0.5 / max|x - mean| (0 for a constant or silent clip). */
+int apad_wav_stats(const float* x, const int64_t* offsets, const int64_t* offsets_host, float* stats, int32_t batch,
+                   void* stream);
+/* out [batch][target_frames][64] fp32 = log(max(mel @ |STFT|, 1e-5)) of y = clip((x - mean) * scale, -1, 1), zero-extended to
+   max(n, segment) samples (pad_wav; a longer clip is NOT truncated), reflect-padded by 512; frame f starts at f * 160.
+   window [1024] (periodic Hann), twiddle [512][2] = (cos, -sin)(2 pi k / 1024), mel [64][513] (Slaney), mel_range [64][2]
+   = each filter's non-zero bins [lo, hi) within [0, 513).  Rows past a clip's last frame (max(n, segment) / 160 + 1) are 0.
+   -1 when segment <= 512, target_frames <= 0 or a clip has <= 100 samples. */
+int apad_stft_logmel(const float* x, const int64_t* offsets, const int64_t* offsets_host, const float* stats,
+                     const float* window, const float* twiddle, const float* mel, const int32_t* mel_range, float* out,
+                     int32_t batch, int64_t segment, int32_t target_frames, void* stream);
 
 #ifdef __cplusplus
 }
