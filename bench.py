@@ -1,13 +1,15 @@
 """Benchmark of the AP-adapter hot path on MI355X: 10 s clips / second at 200 DDIM steps, AudioLDM2-large + AP.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--la La]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--la La] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A bench "step" is one DDIM step of the captured hot path over one batch: UNet on the CFG-duplicated batch (2B
 sample-forwards), CFG combine, DDIM update -- replayed as one hipGraph.  value = clips/s = (B * N) / (200 * t_step),
 t_step = max over ranks of (elapsed / K).  Inputs (latents, GPT-2 / T5 embeddings, audio tokens) are resident in HBM
 before the timed region; weights are random-init of the AudioLDM2-large geometry (no checkpoint offline).
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run does only what its headline needs: set-up, warm-up, the K timed steps, --dump-outputs.
+--full adds, after the timed steps, the side measurements: live rooflines, the MFMA ceiling, the attn2 grid, AudioMAE, the training
+step, the f16 / fp32 modes of the same step, the CPU baseline, and the figures read from the committed profiles/.
 """
 import argparse
 import json
@@ -769,15 +771,17 @@ def main():
     ap.add_argument("--guidance", type=float, default=9.5)
     ap.add_argument("--ap-scale", type=float, default=0.55)
     ap.add_argument("--low-res-streams", type=int, default=1, help="n > 0: run the two batch halves of the n lowest-resolution levels on two streams")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-fp32-leg", action="store_true", help="skip the fp32-precision-mode timing of the same step")
-    ap.add_argument("--step-only", action="store_true", help="only the timed step (for rocprofv3 runs: no roofline re-timings, no AudioMAE, no CPU leg)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run the side measurements (rooflines, MFMA ceiling, attn2 grid, "
+                                                        "AudioMAE, training step, f16 / fp32 modes, CPU baseline) and add them to the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-fp32-leg", action="store_true", help="with --full: skip the fp32-precision-mode timing of the same step")
+    ap.add_argument("--step-only", action="store_true", help="only the timed step even with --full (what a run without --full does)")
     ap.add_argument("--train", action="store_true", help="time BASELINE cfg 5 (the adapter's training step) instead of the denoise step")
     ap.add_argument("--train-batch", type=int, default=4)
     ap.add_argument("--train-dtype", choices=["bf16", "f16", "f32"], default="bf16", help="compute type of the training step (fp32 master weights in every mode)")
     ap.add_argument("--train-accum", type=int, default=4, help="also time an accumulation window of this many micro-batches, sequential and as one batch (0 = skip)")
-    ap.add_argument("--no-train-leg", action="store_true", help="skip the `train` sub-object (cfg 5: 5 optimizer steps at batch 4) of the default line")
-    ap.add_argument("--no-in-step", action="store_true", help="skip the live in-step kernel timing (roofline falls back to the isolated timing)")
+    ap.add_argument("--no-train-leg", action="store_true", help="with --full: skip the `train` sub-object (cfg 5: 5 optimizer steps at batch 4)")
+    ap.add_argument("--no-in-step", action="store_true", help="with --full: skip the live in-step kernel timing (roofline falls back to the isolated timing)")
     ap.add_argument("--stub-step-ms", type=float, default=None, help=argparse.SUPPRESS)
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step computed (rank 0) as DIR/<name>.npy, float32, at most 64 MB "
@@ -913,75 +917,73 @@ def main():
             # one-off per pipeline call, outside the timed region: time tables, K/V hoist + packing, warm-up step, graph capture
             "setup_ms": round(setup_ms, 1), "model_build_ms": round(build_ms, 1),
         }
-        if args.step_only:
-            print(json.dumps(line))
-            return
-        ins, how = {}, None
-        if not args.no_in_step:
-            with torch.no_grad():
-                ins, how = in_step_launch_times(step, ops, {
-                    # (only the launches at the full CFG batch: the shared prefix's transformer runs its self-attention at half the batch, and the FLOPs per
-                    #  launch below are those of 2B sample-forwards)
-                    "self_attn_1000": ("self_attention_fused", lambda x, *a, **kw: x.shape[1] == 1000 and x.shape[0] == 2 * B),
-                    "fused_attn2_ip": ("fused_cross_attention", lambda x, *a, **kw: kw.get("L2", 0) > 0),
-                    "fused_attn2_t5": ("fused_cross_attention", lambda x, *a, **kw: not kw.get("L2", 0))})
-        line["roofline"] = dominant_kernel_roofline(dev, dtype, 2 * B, ins.get("self_attn_1000"), how)
-        try:
-            line["mfma_ceiling"] = mfma_ceiling(dev)
-        except Exception as e:  # noqa: BLE001
-            line["mfma_ceiling"] = {"error": repr(e)}
-        line["roofline_top_line"] = profile_top_line()
-        nst = len(unet.low_res_streams) if getattr(unet, "low_res_streams", None) else 1
-        line["level64_kernels"] = level64_from_profile(2 * B, nst)
-        line["hbm_whole_step"] = whole_step_hbm(ms_per_step, 2 * B, args.la)
-        line["fused_attn2"] = fused_attn2_roofline(dev, dtype, 2 * B, args.la, args.ap_scale, ins.get("fused_attn2_ip"), how)
-        line["fused_attn2"]["t5_sites_in_step"] = ins.get("fused_attn2_t5")
-        try:
-            line["fused_attn2"]["grid"] = fused_attn2_grid(dev, dtype, 2 * B, args.ap_scale)
-        except Exception as e:  # noqa: BLE001
-            line["fused_attn2"]["grid"] = {"error": repr(e)}
-        # the audio-condition encoder (2 mels per call: clip + zeros) is outside the timed loop; reported
-        # separately and folded into a per-clip "included" figure (one pipeline call of B clips pays it once)
-        try:
-            mae_ms = audiomae_ms(dev)
-            per_call_s = DDIM_STEPS_PER_CLIP * ms_per_step * 1e-3 + mae_ms * 1e-3
-            line["audiomae"] = {"ms_per_call": round(mae_ms, 3), "mels": 2, "dtype": "f32 (exact-f32 MFMA; the reference's AudioMAE type)",
-                                "clips_per_s_including_it": round(B * world / per_call_s, 4)}
-        except Exception as e:  # never lose the headline line over the side measurement
-            line["audiomae"] = {"error": repr(e)}
-        if not args.no_train_leg and world == 1:
-            # BASELINE cfg 5 beside the headline (driver-observed): 5 graph-replayed optimizer steps at per-GPU batch 4
-            try:
-                targs = argparse.Namespace(**{**vars(args), "la": 32})
-                t_ = train_measure(targs, A, rank, world, dev, steps=5, warmup=2)
-                line["train"] = {k: t_[k] for k in ("metric", "value", "unit", "ms_per_step", "steps", "warmup", "dtype", "config", "loss_first",
-                                                     "loss_last", "finite", "accumulation")}
-            except Exception as e:  # noqa: BLE001
-                line["train"] = {"error": repr(e)}
-        if not args.no_fp32_leg and world == 1:
-            # the other two precision modes of the SAME step, beside the headline (all live): f16 -- what the reference ships (inference.py:13,
-            # torch_dtype=float16) --, graph-replayed like the bf16 line, and fp32 (exact-f32 MFMA, eager).  noise_pred (the guided epsilon of
-            # the first step, batch 32) of the 16-bit modes is compared with the fp32 mode's, which tests/test_gpu_unet.py holds within 1e-3
-            # (measured 1e-5) of the oracle chain at the same geometry
-            try:
+        if args.full and not args.step_only:  # the side measurements: after the timed steps, none of them feeds the headline
+            ins, how = {}, None
+            if not args.no_in_step:
                 with torch.no_grad():
-                    step_ptr.zero_()  # (the time tables are indexed by the device step counter: the first step, like the other modes below)
-                    e2 = unet.forward_nhwc(lat0.to(dtype), H, W, None, ge, pe, None, am, batch_repeat=2).float()
-                    np_bf16 = e2[:B] + args.guidance * (e2[B:] - e2[:B])
-                f16, np_f16 = precision_leg(A, unet, inp, args, dev, torch.float16, steps=10, graph=True)
-                f32, np_f32 = precision_leg(A, unet, inp, args, dev, torch.float32, steps=2, graph=False)
-                mx = float(np_f32.abs().max())
-                f16["noise_pred_max_abs_vs_fp32_mode"] = round(float((np_f16 - np_f32).abs().max()), 6)
-                f16["what"] = "the same batch-32 step in f16 storage (the reference's inference dtype, inference.py:13), hipGraph replay"
-                f32["what"] = ("the same batch-32 step with fp32 storage and exact-f32 MFMA (v_mfma_f32_32x32x2_f32, 1/16 of the bf16 rate), eager launches: "
-                               "the mode in which noise_pred is within 1e-3 of the oracle chain (measured 1e-5)")
-                line["f16_mode"], line["fp32_mode"] = f16, f32
-                line["noise_pred_vs_fp32_mode"] = {"bf16_max_abs": round(float((np_bf16 - np_f32).abs().max()), 6), "f16_max_abs": f16["noise_pred_max_abs_vs_fp32_mode"],
-                                                   "max_abs_noise_pred": round(mx, 4), "tensor": f"guided noise_pred of the first DDIM step, batch {B}, CFG {args.guidance}"}
+                    ins, how = in_step_launch_times(step, ops, {
+                        # (only the launches at the full CFG batch: the shared prefix's transformer runs its self-attention at half the batch, and the FLOPs per
+                        #  launch below are those of 2B sample-forwards)
+                        "self_attn_1000": ("self_attention_fused", lambda x, *a, **kw: x.shape[1] == 1000 and x.shape[0] == 2 * B),
+                        "fused_attn2_ip": ("fused_cross_attention", lambda x, *a, **kw: kw.get("L2", 0) > 0),
+                        "fused_attn2_t5": ("fused_cross_attention", lambda x, *a, **kw: not kw.get("L2", 0))})
+            line["roofline"] = dominant_kernel_roofline(dev, dtype, 2 * B, ins.get("self_attn_1000"), how)
+            try:
+                line["mfma_ceiling"] = mfma_ceiling(dev)
             except Exception as e:  # noqa: BLE001
-                line["fp32_mode"] = {"error": repr(e)}
-        if not args.no_cpu_baseline and world == 1:  # the host baseline is reported at N = 1 only
-            line["cpu_baseline"] = cpu_baseline()
+                line["mfma_ceiling"] = {"error": repr(e)}
+            line["roofline_top_line"] = profile_top_line()
+            nst = len(unet.low_res_streams) if getattr(unet, "low_res_streams", None) else 1
+            line["level64_kernels"] = level64_from_profile(2 * B, nst)
+            line["hbm_whole_step"] = whole_step_hbm(ms_per_step, 2 * B, args.la)
+            line["fused_attn2"] = fused_attn2_roofline(dev, dtype, 2 * B, args.la, args.ap_scale, ins.get("fused_attn2_ip"), how)
+            line["fused_attn2"]["t5_sites_in_step"] = ins.get("fused_attn2_t5")
+            try:
+                line["fused_attn2"]["grid"] = fused_attn2_grid(dev, dtype, 2 * B, args.ap_scale)
+            except Exception as e:  # noqa: BLE001
+                line["fused_attn2"]["grid"] = {"error": repr(e)}
+            # the audio-condition encoder (2 mels per call: clip + zeros) is outside the timed loop; reported
+            # separately and folded into a per-clip "included" figure (one pipeline call of B clips pays it once)
+            try:
+                mae_ms = audiomae_ms(dev)
+                per_call_s = DDIM_STEPS_PER_CLIP * ms_per_step * 1e-3 + mae_ms * 1e-3
+                line["audiomae"] = {"ms_per_call": round(mae_ms, 3), "mels": 2, "dtype": "f32 (exact-f32 MFMA; the reference's AudioMAE type)",
+                                    "clips_per_s_including_it": round(B * world / per_call_s, 4)}
+            except Exception as e:  # never lose the headline line over the side measurement
+                line["audiomae"] = {"error": repr(e)}
+            if not args.no_train_leg and world == 1:
+                # BASELINE cfg 5 beside the headline (driver-observed): 5 graph-replayed optimizer steps at per-GPU batch 4
+                try:
+                    targs = argparse.Namespace(**{**vars(args), "la": 32})
+                    t_ = train_measure(targs, A, rank, world, dev, steps=5, warmup=2)
+                    line["train"] = {k: t_[k] for k in ("metric", "value", "unit", "ms_per_step", "steps", "warmup", "dtype", "config", "loss_first",
+                                                         "loss_last", "finite", "accumulation")}
+                except Exception as e:  # noqa: BLE001
+                    line["train"] = {"error": repr(e)}
+            if not args.no_fp32_leg and world == 1:
+                # the other two precision modes of the SAME step, beside the headline (all live): f16 -- what the reference ships (inference.py:13,
+                # torch_dtype=float16) --, graph-replayed like the bf16 line, and fp32 (exact-f32 MFMA, eager).  noise_pred (the guided epsilon of
+                # the first step, batch 32) of the 16-bit modes is compared with the fp32 mode's, which tests/test_gpu_unet.py holds within 1e-3
+                # (measured 1e-5) of the oracle chain at the same geometry
+                try:
+                    with torch.no_grad():
+                        step_ptr.zero_()  # (the time tables are indexed by the device step counter: the first step, like the other modes below)
+                        e2 = unet.forward_nhwc(lat0.to(dtype), H, W, None, ge, pe, None, am, batch_repeat=2).float()
+                        np_bf16 = e2[:B] + args.guidance * (e2[B:] - e2[:B])
+                    f16, np_f16 = precision_leg(A, unet, inp, args, dev, torch.float16, steps=10, graph=True)
+                    f32, np_f32 = precision_leg(A, unet, inp, args, dev, torch.float32, steps=2, graph=False)
+                    mx = float(np_f32.abs().max())
+                    f16["noise_pred_max_abs_vs_fp32_mode"] = round(float((np_f16 - np_f32).abs().max()), 6)
+                    f16["what"] = "the same batch-32 step in f16 storage (the reference's inference dtype, inference.py:13), hipGraph replay"
+                    f32["what"] = ("the same batch-32 step with fp32 storage and exact-f32 MFMA (v_mfma_f32_32x32x2_f32, 1/16 of the bf16 rate), eager launches: "
+                                   "the mode in which noise_pred is within 1e-3 of the oracle chain (measured 1e-5)")
+                    line["f16_mode"], line["fp32_mode"] = f16, f32
+                    line["noise_pred_vs_fp32_mode"] = {"bf16_max_abs": round(float((np_bf16 - np_f32).abs().max()), 6), "f16_max_abs": f16["noise_pred_max_abs_vs_fp32_mode"],
+                                                       "max_abs_noise_pred": round(mx, 4), "tensor": f"guided noise_pred of the first DDIM step, batch {B}, CFG {args.guidance}"}
+                except Exception as e:  # noqa: BLE001
+                    line["fp32_mode"] = {"error": repr(e)}
+            if not args.no_cpu_baseline and world == 1:  # the host baseline is reported at N = 1 only
+                line["cpu_baseline"] = cpu_baseline()
         print(json.dumps(line))
     if world > 1:
         dist.barrier()
