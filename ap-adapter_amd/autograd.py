@@ -9,13 +9,12 @@ The un-fused training forward is taken only where a gradient is actually needed 
 first adapted attention nothing requires grad, so those layers keep running the fused inference kernels.
 Frozen weights need no weight gradient; their transposed / flipped copies for the dgrad GEMMs are cached.
 """
-import weakref
-
 import os as _os
 
 import torch
 
 from . import ops
+from .derived import derived
 
 
 def on(*tensors):
@@ -23,46 +22,25 @@ def on(*tensors):
     return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
 
 
-_wcache = {}
-
-
-def _psig(*ps):
-    """identity + storage + version + type + place of companion weights (the signature of a stacked copy, not its key)"""
-    return tuple((id(p), p.data_ptr(), p._version, p.dtype, p.device) for p in ps)
-
-
-def _cached(w, tag, make, extra=()):
-    """per-weight derived tensor (transposed / flipped copy), rebuilt when the weight is re-assigned or updated.  Only FROZEN
-    weights are cached: the optimizer kernel updates trainable ones through raw pointers, which no version counter sees."""
-    if w.requires_grad:
-        return make(w.detach())
-    key = (id(w), tag)  # ONE entry per (weight, kind): a changed companion (``extra``) overwrites it instead of piling up keys
-    sig = (w.data_ptr(), w._version, w.dtype, w.device) + tuple(extra)
-    hit = _wcache.get(key)
-    # the entry must belong to THIS tensor object: ids (and allocator addresses) are recycled once a model is freed, and a recycled
-    # id with an equal signature would otherwise serve another model's derived weight
-    if hit is None or hit[0] != sig or hit[2]() is not w:
-        if len(_wcache) > 4096:  # entries of freed models
-            for k in [k for k, v in _wcache.items() if v[2]() is None]:
-                del _wcache[k]
-        hit = (sig, make(w.detach()), weakref.ref(w))
-        _wcache[key] = hit
-    return hit[1]
+def _derived(w, tag, make, deps=()):
+    """derived() of a FROZEN weight.  A trainable one is re-derived on every call: the optimizer kernel updates it through raw pointers,
+    which no version counter sees."""
+    return make() if w.requires_grad else derived(w, tag, make, deps)
 
 
 def _wt(w):
     """W [N, K] -> W^T [K, N] contiguous: dx = dy . W is apad_gemm(a = dy, w = W^T)"""
-    return _cached(w, "T", lambda t: t.reshape(t.shape[0], -1).t().contiguous())
+    return _derived(w, "T", lambda: w.detach().reshape(w.shape[0], -1).t().contiguous())
 
 
 def _conv_dgrad_w(w):
     """conv weight [Cout, Cin, 3, 3] -> [Cin, 9*Cout] in (2-ky, 2-kx, cout) order: the stride-1 convolution of dy with
     it is the input gradient"""
-    return _cached(w, "dgrad", lambda t: t.flip(2, 3).permute(1, 2, 3, 0).reshape(t.shape[1], -1).contiguous())
+    return _derived(w, "dgrad", lambda: w.detach().flip(2, 3).permute(1, 2, 3, 0).reshape(w.shape[1], -1).contiguous())
 
 
 def _conv_fwd_w(w):
-    return _cached(w, "packed", lambda t: t.permute(0, 2, 3, 1).reshape(t.shape[0], -1).contiguous())
+    return ops.conv3x3_pack(w) if w.requires_grad else ops.conv3x3_weight(w)
 
 
 def _c(t):
@@ -137,7 +115,7 @@ class _QKV(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dq, dk, dv):
         wq, wk, wv = ctx.saved_tensors
-        wst = _cached(wq, "qkvT", lambda t: torch.cat([t, wk.detach(), wv.detach()], 0).t().contiguous(), extra=_psig(wk, wv))  # [C, 3C]
+        wst = _derived(wq, "qkvT", lambda: torch.cat([wq.detach(), wk.detach(), wv.detach()], 0).t().contiguous(), (wk, wv))  # [C, 3C]
         return ops.linear(_packed_grads(dq, dk, dv), wst), None, None, None
 
 
@@ -152,7 +130,7 @@ class _QKVT(_QKV):
         x = _c(x)
         B, N, Cc = x.shape
         ctx.save_for_backward(wq, wk, wv)
-        w = _cached(wq, "qkv", lambda t: torch.cat([t, wk.detach(), wv.detach()], 0).contiguous(), extra=_psig(wk, wv))
+        w = _derived(wq, "qkv_train", lambda: torch.cat([wq.detach(), wk.detach(), wv.detach()], 0).contiguous(), (wk, wv))
         q, k, v = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
         vt = vt_buffer("train_self", B, heads, Cc // heads, N, x.dtype, x.device)
         ops.linear_qkv(x, w, B, N, heads, q, k, vt, v=v)

@@ -10,6 +10,7 @@ import math
 import torch
 
 from . import _lib as L
+from .derived import derived
 
 _DT = {torch.bfloat16: L.BF16, torch.float16: L.F16, torch.float32: L.F32}
 _EPI = {None: L.EPI_NONE, "none": L.EPI_NONE, "silu": L.EPI_SILU, "gelu": L.EPI_GELU, "geglu": L.EPI_GEGLU, "tanh": L.EPI_TANH,
@@ -77,12 +78,9 @@ def gemm(a, w, *, M, N, K, lda, out, ldo, bias=None, residual=None, ldr=0, act=N
     return out
 
 
-import weakref as _weakref
-
 # LayerNorm folded into the Linear behind it where no fused row-panel kernel covers the width (the 640-wide level): the producing
 # GEMM emits row statistics, the consuming GEMM applies (x - mean) * rstd * gamma + beta by algebra
 LN_FOLD = True  # (module attribute only: no environment switch since round 5)
-_fold_cache = {}
 
 
 def rowstat_of(x):
@@ -94,22 +92,15 @@ def rowstat_of(x):
 def _ln_folded(w, bias, gamma, beta):
     """(w * gamma in the storage type, its fp32 row sums, fp32 beta . W^T + bias) of a Linear behind a LayerNorm; cached per weight,
     rebuilt when any of the four parameters is re-assigned or updated"""
-    ps = (w, bias, gamma, beta)
-    sig = tuple(None if p is None else (id(p), p.data_ptr(), p._version, p.dtype, p.device) for p in ps)
-    hit = _fold_cache.get(id(w))
-    if hit is None or hit[0] != sig or hit[2]() is not w:
-        if len(_fold_cache) > 1024:
-            for k in [k for k, v in _fold_cache.items() if v[2]() is None]:
-                del _fold_cache[k]
+    def make():
         wf = w.detach().float()
         wg = (wf * gamma.detach().float()).to(w.dtype).contiguous()
         cs = wg.float().sum(1).contiguous()
         bb = wf @ beta.detach().float()
         if bias is not None:
             bb = bb + bias.detach().float()
-        hit = (sig, (wg, cs, bb.contiguous()), _weakref.ref(w))
-        _fold_cache[id(w)] = hit
-    return hit[1]
+        return wg, cs, bb.contiguous()
+    return derived(w, "ln_fold", make, (bias, gamma, beta))
 
 
 def linear(x, w, bias=None, residual=None, act=None, out=None, rowgroup_bias=None, rows_per_group=0, step_ptr=None,
@@ -758,7 +749,6 @@ def linear_qkv(x, w_qkv, B, Lk, heads, q, k, vt, bias=None, ln=None, v=None):
 
 
 HCONV = True  # route eligible 3x3 convolutions through the halo-resident kernel (csrc/hconv.hip); a module attribute a test may flip
-_halo_cache = {}
 
 
 def conv_halo_eligible(Cin, Cout, Wout, stride, dtype, src_batch_mod=0, asym_pad=False):
@@ -770,20 +760,23 @@ def conv_halo_eligible(Cin, Cout, Wout, stride, dtype, src_batch_mod=0, asym_pad
 
 def conv_halo_weight(w_packed):
     """w_packed [Cout, 9 * Cin] -> apad_conv_halo_pack's form (same element count), cached per weight tensor version"""
-    key = id(w_packed)
-    sig = (w_packed.data_ptr(), w_packed._version, w_packed.dtype, w_packed.device, tuple(w_packed.shape))
-    hit = _halo_cache.get(key)
-    if hit is None or hit[0] != sig or hit[2]() is not w_packed:
-        if len(_halo_cache) > 512:
-            for k in [k for k, v in _halo_cache.items() if v[2]() is None]:
-                del _halo_cache[k]
+    def make():
         wc = w_packed.detach().contiguous()
         Cout, K = wc.shape
         out = torch.empty(L.lib().apad_conv_halo_packed_bytes(Cout, K // 9) // 2, dtype=wc.dtype, device=wc.device)
         L.check(L.lib().apad_conv_halo_pack(wc.data_ptr(), out.data_ptr(), Cout, K // 9, _DT[wc.dtype], _stream()), "apad_conv_halo_pack")
-        hit = (sig, out, _weakref.ref(w_packed))
-        _halo_cache[key] = hit
-    return hit[1]
+        return out
+    return derived(w_packed, "halo", make)
+
+
+def conv3x3_pack(w):
+    """conv weight [Cout, Cin, 3, 3] -> conv3x3's w_packed [Cout, 9*Cin] in (ky, kx, cin) order"""
+    return w.detach().permute(0, 2, 3, 1).reshape(w.shape[0], -1).contiguous()
+
+
+def conv3x3_weight(w):
+    """conv3x3_pack(w), cached per weight: the one copy the inference and the training forward share"""
+    return derived(w, "conv3x3", lambda: conv3x3_pack(w))
 
 
 def conv3x3(x, w_packed, bias, B, Hin, Win, stride=1, up=None, residual=None, rowgroup_bias=None, rows_per_group=0,

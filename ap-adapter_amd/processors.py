@@ -18,6 +18,7 @@ import torch.nn as nn
 
 from . import autograd as AG
 from . import ops
+from .derived import derived, signature
 
 _vt_pool = {}
 
@@ -49,22 +50,16 @@ def _xrows_ok(attn, hidden_states, residual, ln, L1, L2=0):
 
 def _xrows_weights(attn):
     """fragment-packed to_q / to_out[0] of apad_cross_attention_rows, cached like _xattn_weights"""
-    key = _pkey(attn.to_q.weight, attn.to_out[0].weight)
-    if getattr(attn, "_xrows_key", None) != key:
-        attn._xrows_w = (ops.xrows_pack_weight(attn.to_q.weight), ops.xrows_pack_weight(attn.to_out[0].weight))
-        attn._xrows_key = key
-    return attn._xrows_w
+    wq, wo = attn.to_q.weight, attn.to_out[0].weight
+    return derived(wq, "xrows", lambda: (ops.xrows_pack_weight(wq), ops.xrows_pack_weight(wo)), (wo,))
 
 
 def _xattn_weights(attn, ln):
     """(fragment-packed to_q with the block's LayerNorm folded in, its fold vectors, fragment-packed to_out[0]) of the fused kernel, cached on
-    the Attention module and re-packed when a parameter (the LayerNorm's included) is re-assigned, moved, cast or updated in place"""
-    key = (_pkey(attn.to_q.weight, attn.to_out[0].weight, ln[0], ln[1]), float(ln[2]))
-    if getattr(attn, "_xattn_key", None) != key:
-        wq_p, q_fold = ops.xattn_pack_weight(attn.to_q.weight.detach(), ln)
-        attn._xattn_w = (wq_p, q_fold, ops.xattn_pack_weight(attn.to_out[0].weight.detach()))
-        attn._xattn_key = key
-    return attn._xattn_w
+    to_q and re-packed when a parameter (the LayerNorm's included) is re-assigned, moved, cast or updated in place"""
+    wq, wo = attn.to_q.weight, attn.to_out[0].weight
+    return derived(wq, "xattn", lambda: ops.xattn_pack_weight(wq.detach(), ln) + (ops.xattn_pack_weight(wo.detach()),),
+                   (wo, ln[0], ln[1]), (float(ln[2]),))
 
 
 def _hs_route(attn, hidden_states, residual, ln):
@@ -86,19 +81,20 @@ def _rows_kv(pk, B, Lk, attn):
 
 
 def _hs_weights(attn, ln, self_attention):
-    """(packed projection weights, their fp32 bias, packed to_out[0]) of apad_hs_attention / apad_hs_out, cached on the Attention module and
-    re-packed when a parameter (the LayerNorm's included: it is folded into the projection) is re-assigned, moved, cast or updated in place"""
-    ps = (attn.to_q.weight, attn.to_out[0].weight) + ((attn.to_k.weight, attn.to_v.weight) if self_attention else ()) + (tuple(ln[:2]) if ln is not None else ())
-    key = (_pkey(*ps), self_attention, None if ln is None else float(ln[2]))
-    if getattr(attn, "_hs_key", None) != key:
+    """(packed projection weights, their fp32 bias, packed to_out[0]) of apad_hs_attention / apad_hs_out, cached on to_q and re-packed when a
+    parameter (the LayerNorm's included: it is folded into the projection) is re-assigned, moved, cast or updated in place"""
+    wq, wk, wv, wo = attn.to_q.weight, attn.to_k.weight, attn.to_v.weight, attn.to_out[0].weight
+    heads = attn.heads
+
+    def make():
         if self_attention:  # (the to_q rows carry log2(e) / sqrt(d): q is the softmax's base-2 exponent operand as projected)
-            d = attn.to_q.weight.shape[0] // attn.heads
-            pk, bb = ops.hs_pack_qkv(attn.to_q.weight, attn.to_k.weight, attn.to_v.weight, ln=ln, q_scale=ops.LOG2E / d ** 0.5)
+            d = wq.shape[0] // heads
+            pk, bb = ops.hs_pack_qkv(wq, wk, wv, ln=ln, q_scale=ops.LOG2E / d ** 0.5)
         else:
-            pk, bb = ops.hs_pack_rows(attn.to_q.weight, ln=ln)
-        attn._hs_w = (pk, bb, ops.hs_pack_rows(attn.to_out[0].weight)[0])
-        attn._hs_key = key
-    return attn._hs_w
+            pk, bb = ops.hs_pack_rows(wq, ln=ln)
+        return pk, bb, ops.hs_pack_rows(wo)[0]
+    deps = (wo,) + ((wk, wv) if self_attention else ()) + (tuple(ln[:2]) if ln is not None else ())
+    return derived(wq, "hs", make, deps, (self_attention, heads, None if ln is None else float(ln[2])))
 
 
 def _hs_sublayer(attn, hidden_states, residual, ln, **kv):
@@ -130,12 +126,6 @@ def vt_buffer(slot, B, heads, d, Lk, dtype, device):
 def clear_vt_pool():
     """Drop the V^T scratch pool.  Only when no captured hipGraph that used it is still going to be replayed."""
     _vt_pool.clear()
-
-
-def _pkey(*params):
-    """identity + storage + version of parameters: changes when a weight is re-assigned (inference.py:56-57 re-assigns
-    ``to_k_ip.weight`` / ``to_v_ip.weight``), moved, cast, or updated in place"""
-    return tuple((id(p), p.data_ptr(), p._version, p.dtype) for p in params)
 
 
 class _Hoist:
@@ -257,17 +247,16 @@ class AttnProcessor2_0(nn.Module):
         """to_q | to_k | to_v stacked for the one-launch projection.  prescale: the to_q rows carry log2(e) / sqrt(d) (scaled in
         fp32, rounded to the storage type once), so the projection writes q as the base-2 exponent operand of the softmax --
         rounded ONCE, like the reference's q -- and the attention kernel spends no instruction per score on the scale."""
-        ps = (attn.to_q.weight, attn.to_k.weight, attn.to_v.weight)
-        key = tuple((id(p), p.data_ptr(), p._version, p.dtype, p.device) for p in ps) + (bool(prescale),)
-        # cached on the Attention module (a processor instance may be shared by many sites)
-        if getattr(attn, "_qkv_key", None) != key:
-            wq = attn.to_q.weight.detach()
+        wq, wk, wv = attn.to_q.weight, attn.to_k.weight, attn.to_v.weight
+        heads = attn.heads
+
+        def make():
+            q = wq.detach()
             if prescale:
-                d = wq.shape[0] // attn.heads
-                wq = (wq.float() * (ops.LOG2E / d ** 0.5)).to(wq.dtype)
-            attn._qkv_w = torch.cat([wq, attn.to_k.weight.detach(), attn.to_v.weight.detach()], dim=0).contiguous()
-            attn._qkv_key = key
-        return attn._qkv_w
+                d = q.shape[0] // heads
+                q = (q.float() * (ops.LOG2E / d ** 0.5)).to(q.dtype)
+            return torch.cat([q, wk.detach(), wv.detach()], dim=0).contiguous()
+        return derived(wq, "qkv", make, (wk, wv), (bool(prescale), heads))
 
     def __call__(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None,
                  _residual=None, _ln=None):
@@ -296,11 +285,9 @@ class AttnProcessor2_0(nn.Module):
         if (encoder_hidden_states is None and attention_mask is None and _ln is not None and ops.sattn_ok(hidden_states, heads) and attn.to_q.bias is None
                 and tuple(attn.to_q.weight.shape) == (C_, C_)):
             # the two large levels: LayerNorm + q | k | v + attention in ONE launch (workgroup = (sample, head), K / V^T in LDS), then to_out
-            key = (_pkey(attn.to_q.weight, attn.to_k.weight, attn.to_v.weight, _ln[0], _ln[1]), float(_ln[2]))
-            if getattr(attn, "_sattn_key", None) != key:
-                attn._sattn_w = ops.sattn_pack(attn.to_q.weight, attn.to_k.weight, attn.to_v.weight, _ln, heads)
-                attn._sattn_key = key
-            o = ops.self_attention_fused(hidden_states, attn._sattn_w[0], attn._sattn_w[1], heads, _ln[2])
+            wq, wk, wv = attn.to_q.weight, attn.to_k.weight, attn.to_v.weight
+            w_p, csbb = derived(wq, "sattn", lambda: ops.sattn_pack(wq, wk, wv, _ln, heads), (wk, wv, _ln[0], _ln[1]), (float(_ln[2]), heads))
+            o = ops.self_attention_fused(hidden_states, w_p, csbb, heads, _ln[2])
             return ops.fused_linear(o, attn.to_out[0].weight, attn.to_out[0].bias, residual=_residual, rowstat=True)
         if encoder_hidden_states is None:
             Lk = N
@@ -344,7 +331,7 @@ class AttnProcessor2_0(nn.Module):
                 # packed with the projection: the weight-stationary kernel's layout, or the row-tile kernels' fragment sets
                 return (k_, vt_, ops.xattn_pack_kv(k_, vt_, ehs.shape[1]) if fused else (ops.rows_pack_kv(k_, vt_).data if rows else None))
 
-            k, vt, pk = self._hoisted(_loose_key(attn, ehs), lambda attn=attn, ehs=ehs: (ehs._version, _pkey(attn.to_k.weight, attn.to_v.weight)), make)
+            k, vt, pk = self._hoisted(_loose_key(attn, ehs), lambda attn=attn, ehs=ehs: (ehs._version, signature(attn.to_k.weight, attn.to_v.weight)), make)
         if attention_mask is not None:
             # the mask -> fp32 bias conversion is timestep-invariant too: hoisted with the K/V (two tiny torch kernels
             # per masked site per step otherwise)
@@ -489,7 +476,7 @@ class IPAttnProcessor2_0(nn.Module):
             return kv_
 
         sig = lambda attn=attn, ehs=ehs: (ehs._version, self.num_tokens,
-                                          _pkey(attn.to_k.weight, attn.to_v.weight, self.to_k_ip.weight, self.to_v_ip.weight))
+                                          signature(attn.to_k.weight, attn.to_v.weight, self.to_k_ip.weight, self.to_v_ip.weight))
         k_t, vt_t, Lt, k_a, vt_a, La, pk_t, pk_a = self._hoisted(_loose_key(attn, ehs), sig, make)
         bias = None
         if attention_mask is not None:

@@ -20,6 +20,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from .derived import derived
 
 NEG = float("-inf")
 
@@ -282,14 +283,11 @@ class T5Block(nn.Module):
         super().__init__()
         self.layer = nn.ModuleList([_T5LayerSelfAttention(cfg, has_bias), _T5LayerFF(cfg)])
         self.heads, self.eps = cfg.num_heads, cfg.layer_norm_epsilon
-        self._gate_key, self._gate = None, None
 
     def _value_gate(self):
         d = self.layer[1].DenseReluDense
-        key = tuple((id(p), p.data_ptr(), p._version) for p in (d.wi_0.weight, d.wi_1.weight))
-        if key != self._gate_key:  # rows value | gate, the layout of the gated epilogue
-            self._gate, self._gate_key = torch.cat([d.wi_1.weight.detach(), d.wi_0.weight.detach()], 0).contiguous(), key
-        return self._gate
+        value, gate = d.wi_1.weight, d.wi_0.weight  # rows value | gate, the layout of the gated epilogue
+        return derived(value, "value_gate", lambda: torch.cat([value.detach(), gate.detach()], 0).contiguous(), (gate,))
 
     def forward(self, x, bias, B, L):
         sa, H = self.layer[0], self.heads
@@ -391,13 +389,10 @@ class Conv1D(nn.Module):
         super().__init__()
         self.weight = nn.Parameter(torch.empty(nx, nf).normal_(std=0.02))
         self.bias = nn.Parameter(torch.zeros(nf))
-        self._key, self._wt = None, None
 
     def wt(self):
-        key = (id(self.weight), self.weight.data_ptr(), self.weight._version)
-        if key != self._key:
-            self._wt, self._key = self.weight.detach().t().contiguous(), key
-        return self._wt
+        w = self.weight
+        return derived(w, "T", lambda: w.detach().t().contiguous())
 
 
 class _GPT2Attention(nn.Module):

@@ -15,6 +15,7 @@ import torch.nn as nn
 
 from . import autograd as AG
 from . import ops
+from .derived import derived
 from .processors import AttnProcessor2_0
 
 
@@ -46,21 +47,6 @@ class UNetConfig:
                     up_block_types=tuple(self.up_block_types))
 
 
-class _Packed:
-    """Cache of a re-laid-out weight, invalidated when the parameter object, its storage or its version changes."""
-
-    def __init__(self):
-        self.key = None
-        self.val = None
-
-    def get(self, p, fn):
-        key = (id(p), p.data_ptr(), p._version, p.dtype, p.device)
-        if key != self.key:
-            self.val = fn(p.detach())
-            self.key = key
-        return self.val
-
-
 def _w2d(conv_or_linear):
     w = conv_or_linear.weight
     return w.detach().reshape(w.shape[0], -1) if w.dim() == 4 else w.detach()
@@ -73,15 +59,13 @@ class Conv3x3(nn.Module):
         super().__init__()
         self.conv = nn.Conv2d(cin, cout, 3, stride=stride, padding=1)
         self.stride = stride
-        self._pk = _Packed()
 
     def packed(self):
-        return self._pk.get(self.conv.weight, lambda w: w.permute(0, 2, 3, 1).reshape(w.shape[0], -1).contiguous())
+        return ops.conv3x3_weight(self.conv.weight)
 
 
-def _conv3x3(mod_conv, pk, x, B, H, W, stride=1, **kw):
-    wp = pk.get(mod_conv.weight, lambda w: w.permute(0, 2, 3, 1).reshape(w.shape[0], -1).contiguous())
-    return ops.conv3x3(x, wp, mod_conv.bias, B, H, W, stride=stride, **kw)
+def _conv3x3(mod_conv, x, B, H, W, stride=1, **kw):
+    return ops.conv3x3(x, ops.conv3x3_weight(mod_conv.weight), mod_conv.bias, B, H, W, stride=stride, **kw)
 
 
 class Attention(nn.Module):
@@ -148,21 +132,20 @@ class FeedForward(nn.Module):
 
     def _hs_weights(self, ln):
         """fragment-packed GEGLU projection (norm3 folded in) of apad_hs_geglu, re-packed when a parameter is re-assigned, moved, cast or updated"""
-        ps = (self.net[0].proj.weight, self.net[0].proj.bias, ln[0], ln[1], self.net[2].weight)
-        key = tuple((id(p), p.data_ptr(), p._version, p.dtype, p.device) for p in ps) + (float(ln[2]),)
-        if getattr(self, "_hs_key", None) != key:
-            self._hs_w = ops.hs_pack_geglu(self.net[0].proj.weight, self.net[0].proj.bias, ln=ln) + (ops.hs_pack_ff2(self.net[2].weight),)
-            self._hs_key = key
-        return self._hs_w
+        w1, b1, w2 = self.net[0].proj.weight, self.net[0].proj.bias, self.net[2].weight
+        return derived(w1, "hs_ff", lambda: ops.hs_pack_geglu(w1, b1, ln=ln) + (ops.hs_pack_ff2(w2),), (b1, ln[0], ln[1], w2), (float(ln[2]),))
 
-    def _packed_weights(self):
+    @property
+    def _mlp3_w(self):
         """the weight stream of apad_geglu_mlp_packed (ops.mlp_pack), re-packed when a parameter is re-assigned, moved, cast or updated"""
-        ps = (self.net[0].proj.weight, self.net[0].proj.bias, self.net[2].weight)  # (a bias-free GEGLU projection: ps[1] is None)
-        key = tuple(None if p is None else (id(p), p.data_ptr(), p._version, p.dtype, p.device) for p in ps)
-        if getattr(self, "_mlp3_key", None) != key:
-            self._mlp3_w = ops.mlp_pack(ps[0].detach(), None if ps[1] is None else ps[1].detach(), ps[2].detach())
-            self._mlp3_key = key
-        return self._mlp3_w
+        w1, b1, w2 = self.net[0].proj.weight, self.net[0].proj.bias, self.net[2].weight  # (a bias-free GEGLU projection: b1 is None)
+        return derived(w1, "mlp3", lambda: ops.mlp_pack(w1.detach(), None if b1 is None else b1.detach(), w2.detach()), (b1, w2))
+
+    @property
+    def _geglu3_w(self):
+        """the weight stream of apad_layernorm_geglu_packed (ops.geglu_pack), re-packed like _mlp3_w"""
+        w1, b1 = self.net[0].proj.weight, self.net[0].proj.bias
+        return derived(w1, "geglu3", lambda: ops.geglu_pack(w1.detach(), None if b1 is None else b1.detach()), (b1,))
 
     def forward(self, x, ln):
         """x un-normalised; ln = norm3.  C in ops.MLP_C: the whole feed-forward + residual in one launch (the 4C-wide
@@ -181,18 +164,14 @@ class FeedForward(nn.Module):
             return ops.linear(h, self.net[2].weight, self.net[2].bias, residual=x, rowstat=True)
         if x.shape[-1] in ops.MLP_C and x.dtype in ops.FUSED_DTYPES:
             if ops.MLP_PACKED and x.numel() // x.shape[-1] >= ops.MLP_PACKED_MIN_M and x.is_contiguous():
-                wp, bp = self._packed_weights()
+                wp, bp = self._mlp3_w
                 return ops.geglu_mlp_packed(x, wp, bp, self.net[2].bias, ln=ln)
             return ops.geglu_mlp(x, self.net[0].proj.weight, self.net[0].proj.bias, self.net[2].weight, self.net[2].bias, ln=ln)
         if (ops.MLP_PACKED and x.shape[-1] in ops.GEGLU_PACKED_C and x.dtype in ops.FUSED_DTYPES and x.is_contiguous()
                 and x.numel() // x.shape[-1] >= ops.GEGLU_PACKED_MIN_M):
             # the 384-wide level at full size: LayerNorm + GEGLU projection on the 64-token register-block kernel from packed weights
-            ps = (self.net[0].proj.weight, self.net[0].proj.bias)
-            key = tuple(None if p is None else (id(p), p.data_ptr(), p._version, p.dtype, p.device) for p in ps)
-            if getattr(self, "_geglu3_key", None) != key:
-                self._geglu3_w = ops.geglu_pack(ps[0].detach(), None if ps[1] is None else ps[1].detach())
-                self._geglu3_key = key
-            h = ops.layernorm_geglu_packed(x, self._geglu3_w[0], self._geglu3_w[1], ln=ln)
+            wp, bp = self._geglu3_w
+            h = ops.layernorm_geglu_packed(x, wp, bp, ln=ln)
         else:
             h = ops.fused_linear(x, self.net[0].proj.weight, self.net[0].proj.bias, ln=ln, act="geglu")
         return ops.linear(h, self.net[2].weight, self.net[2].bias, residual=x, rowstat=True)  # (the next block's norm1 folds into its q|k|v)
@@ -252,11 +231,7 @@ class Transformer2DModel(nn.Module):
     def _hs_packed(self, which):
         """fragment-packed proj_in / proj_out weight for apad_hs_out, re-packed when the parameter is re-assigned, moved, cast or updated"""
         w = (self.proj_in if which == "in" else self.proj_out).weight
-        key = (id(w), w.data_ptr(), w._version, w.dtype, w.device)
-        cache = self.__dict__.setdefault("_hs_pk", {})
-        if cache.get(which, (None,))[0] != key:
-            cache[which] = (key, ops.hs_pack_rows(w.detach().reshape(w.shape[0], -1))[0])
-        return cache[which][1]
+        return derived(w, "hs_rows", lambda: ops.hs_pack_rows(w.detach().reshape(w.shape[0], -1))[0])
 
     def forward(self, x, ehs, emask):
         if AG.on(x):
@@ -294,7 +269,6 @@ class ResnetBlock2D(nn.Module):
         self.norm2 = nn.GroupNorm(groups, cout, eps=eps)
         self.conv2 = nn.Conv2d(cout, cout, 3, padding=1)
         self.conv_shortcut = nn.Conv2d(cin, cout, 1) if cin != cout else None
-        self._pk1, self._pk2 = _Packed(), _Packed()
 
     def time_proj(self, emb_act):
         """emb_act = SiLU(time embedding) [rows, 512] -> [rows, Cout]"""
@@ -307,10 +281,10 @@ class ResnetBlock2D(nn.Module):
         if skip is not None:
             h = ops.group_norm2(x, skip, self.norm1.weight, self.norm1.bias, self.groups, self.norm1.eps, silu=True)
             B = h.shape[0]
-            h, _, _ = _conv3x3(self.conv1, self._pk1, h, B, H, W, rowgroup_bias=tproj, rows_per_group=rows_per_group, step_ptr=step_ptr)
+            h, _, _ = _conv3x3(self.conv1, h, B, H, W, rowgroup_bias=tproj, rows_per_group=rows_per_group, step_ptr=step_ptr)
             h = ops.group_norm(h, self.norm2.weight, self.norm2.bias, self.groups, self.norm2.eps, silu=True)
             sc = ops.linear2(x, skip, _w2d(self.conv_shortcut), self.conv_shortcut.bias)
-            out, _, _ = _conv3x3(self.conv2, self._pk2, h, B, H, W, residual=sc)
+            out, _, _ = _conv3x3(self.conv2, h, B, H, W, residual=sc)
             return out
         if AG.on(x):
             h = AG.group_norm(x, self.norm1.weight, self.norm1.bias, self.groups, self.norm1.eps, True)
@@ -320,11 +294,11 @@ class ResnetBlock2D(nn.Module):
             out, _, _ = AG.conv3x3(h, self.conv2.weight, self.conv2.bias, B, H, W, residual=sc)
             return out
         h = ops.group_norm(x, self.norm1.weight, self.norm1.bias, self.groups, self.norm1.eps, silu=True)
-        h, _, _ = _conv3x3(self.conv1, self._pk1, h, B, H, W, rowgroup_bias=tproj, rows_per_group=rows_per_group,
+        h, _, _ = _conv3x3(self.conv1, h, B, H, W, rowgroup_bias=tproj, rows_per_group=rows_per_group,
                            step_ptr=step_ptr)
         h = ops.group_norm(h, self.norm2.weight, self.norm2.bias, self.groups, self.norm2.eps, silu=True)
         sc = x if self.conv_shortcut is None else ops.linear(x, _w2d(self.conv_shortcut), self.conv_shortcut.bias)
-        out, _, _ = _conv3x3(self.conv2, self._pk2, h, B, H, W, residual=sc)
+        out, _, _ = _conv3x3(self.conv2, h, B, H, W, residual=sc)
         return out
 
 
@@ -332,25 +306,23 @@ class Downsample2D(nn.Module):
     def __init__(self, channels):
         super().__init__()
         self.conv = nn.Conv2d(channels, channels, 3, stride=2, padding=1)
-        self._pk = _Packed()
 
     def forward(self, x, B, H, W):
         if AG.on(x):
             return AG.conv3x3(x, self.conv.weight, self.conv.bias, B, H, W, stride=2)
-        return _conv3x3(self.conv, self._pk, x, B, H, W, stride=2)
+        return _conv3x3(self.conv, x, B, H, W, stride=2)
 
 
 class Upsample2D(nn.Module):
     def __init__(self, channels):
         super().__init__()
         self.conv = nn.Conv2d(channels, channels, 3, padding=1)
-        self._pk = _Packed()
 
     def forward(self, x, B, H, W, output_size=None):
         up = tuple(output_size) if output_size is not None else (2 * H, 2 * W)
         if AG.on(x):
             return AG.conv3x3(x, self.conv.weight, self.conv.bias, B, H, W, up=up)
-        return _conv3x3(self.conv, self._pk, x, B, H, W, up=up)
+        return _conv3x3(self.conv, x, B, H, W, up=up)
 
 
 class _Block(nn.Module):
@@ -437,7 +409,6 @@ class AudioLDM2UNet2DConditionModel(nn.Module):
             self.up_blocks.append(UpBlock(cfg, in_ch, out_ch, prev, typ == "CrossAttnUpBlock2D", i != len(boc) - 1, temb_dim))
         self.conv_norm_out = nn.GroupNorm(cfg.norm_num_groups, boc[0], eps=cfg.norm_eps)
         self.conv_out = nn.Conv2d(boc[0], cfg.out_channels, 3, padding=1)
-        self._pk_in, self._pk_out = _Packed(), _Packed()
         self._time_tables = None
         self.low_res_streams = None  # optional (stream, stream): see forward_nhwc
         self.low_res_levels = 1      # how many of the lowest-resolution levels run on the two streams
@@ -584,7 +555,7 @@ class AudioLDM2UNet2DConditionModel(nn.Module):
             tab, rpg = tp(name, m)
             return m(x, B_of(x), H, W, tab, rpg if rpg is not None else H * W, step_ptr, skip=skip)
 
-        wp = self._pk_in.get(self.conv_in.weight, lambda w: w.permute(0, 2, 3, 1).reshape(w.shape[0], -1).contiguous())
+        wp = ops.conv3x3_weight(self.conv_in.weight)
         if share:
             x, _, _ = ops.conv3x3(x, wp, self.conv_in.bias, Bs, H, W)
         else:
@@ -692,8 +663,7 @@ class AudioLDM2UNet2DConditionModel(nn.Module):
             return x
         x = ops.group_norm(x, self.conv_norm_out.weight, self.conv_norm_out.bias, cfg.norm_num_groups,
                            self.conv_norm_out.eps, silu=True)
-        wp = self._pk_out.get(self.conv_out.weight, lambda w: w.permute(0, 2, 3, 1).reshape(w.shape[0], -1).contiguous())
-        x, _, _ = ops.conv3x3(x, wp, self.conv_out.bias, B, H, W)
+        x, _, _ = _conv3x3(self.conv_out, x, B, H, W)
         return x
 
 

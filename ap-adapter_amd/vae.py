@@ -27,7 +27,8 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .unet import _Packed, _conv3x3, _w2d
+from .derived import derived
+from .unet import _conv3x3, _w2d
 
 
 @dataclass
@@ -57,14 +58,13 @@ class VaeResnetBlock(nn.Module):
         self.norm2 = nn.GroupNorm(groups, cout, eps=EPS)
         self.conv2 = nn.Conv2d(cout, cout, 3, padding=1)
         self.conv_shortcut = nn.Conv2d(cin, cout, 1) if cin != cout else None
-        self._pk1, self._pk2 = _Packed(), _Packed()
 
     def forward(self, x, B, H, W):
         h = ops.group_norm(x, self.norm1.weight, self.norm1.bias, self.groups, EPS, silu=True)
-        h, _, _ = _conv3x3(self.conv1, self._pk1, h, B, H, W)
+        h, _, _ = _conv3x3(self.conv1, h, B, H, W)
         h = ops.group_norm(h, self.norm2.weight, self.norm2.bias, self.groups, EPS, silu=True)
         sc = x if self.conv_shortcut is None else ops.linear(x, _w2d(self.conv_shortcut), self.conv_shortcut.bias)
-        out, _, _ = _conv3x3(self.conv2, self._pk2, h, B, H, W, residual=sc)
+        out, _, _ = _conv3x3(self.conv2, h, B, H, W, residual=sc)
         return out
 
 
@@ -80,15 +80,11 @@ class VaeAttention(nn.Module):
         self.to_k = nn.Linear(channels, channels)
         self.to_v = nn.Linear(channels, channels)
         self.to_out = nn.ModuleList([nn.Linear(channels, channels), nn.Dropout(0.0)])
-        self._pk = _Packed()
 
     def _qk(self):
         ws = (self.to_q.weight, self.to_k.weight, self.to_q.bias, self.to_k.bias)
-        key = tuple((id(p), p.data_ptr(), p._version, p.dtype, p.device) for p in ws)
-        if getattr(self, "_qk_key", None) != key:
-            self._qk_val = (torch.cat([ws[0].detach(), ws[1].detach()], 0).contiguous(), torch.cat([ws[2].detach(), ws[3].detach()], 0).contiguous())
-            self._qk_key = key
-        return self._qk_val
+        return derived(ws[0], "qk", lambda: (torch.cat([ws[0].detach(), ws[1].detach()], 0).contiguous(),
+                                             torch.cat([ws[2].detach(), ws[3].detach()], 0).contiguous()), ws[1:])
 
     def forward(self, x, B, H, W):
         HW, C = H * W, x.shape[-1]
@@ -127,7 +123,6 @@ class _Resample(nn.Module):
     def __init__(self, channels, stride=1):
         super().__init__()
         self.conv = nn.Conv2d(channels, channels, 3, stride=stride, padding=1 if stride == 1 else 0)
-        self._pk = _Packed()
 
 
 class UpDecoderBlock(nn.Module):
@@ -141,7 +136,7 @@ class UpDecoderBlock(nn.Module):
             x = r(x, B, H, W)
         if self.upsamplers is not None:
             u = self.upsamplers[0]
-            x, H, W = _conv3x3(u.conv, u._pk, x, B, H, W, up=(2 * H, 2 * W))  # nearest x2 folded into the conv's gather
+            x, H, W = _conv3x3(u.conv, x, B, H, W, up=(2 * H, 2 * W))  # nearest x2 folded into the conv's gather
         return x, H, W
 
 
@@ -156,7 +151,7 @@ class DownEncoderBlock(nn.Module):
             x = r(x, B, H, W)
         if self.downsamplers is not None:
             d = self.downsamplers[0]
-            x, H, W = _conv3x3(d.conv, d._pk, x, B, H, W, stride=2, asym_pad=True)  # F.pad(x, (0,1,0,1)) + stride-2 conv
+            x, H, W = _conv3x3(d.conv, x, B, H, W, stride=2, asym_pad=True)  # F.pad(x, (0,1,0,1)) + stride-2 conv
         return x, H, W
 
 
@@ -186,7 +181,6 @@ class Encoder(nn.Module):
         self.mid_block = VaeMidBlock(w[-1], g)
         self.conv_norm_out = nn.GroupNorm(g, w[-1], eps=EPS)
         self.conv_out = nn.Conv2d(w[-1], 2 * cfg.latent_channels, 3, padding=1)
-        self._pk_in, self._pk_out = _Packed(), _Packed()
 
     def forward(self, x):
         """x [B, Cin, H, W] -> moments [B, h*w, 2*latent] (NHWC), h, w"""
@@ -194,12 +188,14 @@ class Encoder(nn.Module):
         cp = ops.round_up(Cin, 8)
         xin = torch.zeros(B, H * W, cp, dtype=x.dtype, device=x.device)  # layout: NCHW -> NHWC, channels widened to one 16-byte vector
         xin[..., :Cin] = x.permute(0, 2, 3, 1).reshape(B, H * W, Cin)
-        h, _, _ = ops.conv3x3(xin, self._pk_in.get(self.conv_in.weight, lambda w: _pack_wide_in(w, cp)), self.conv_in.bias, B, H, W)
+        w = self.conv_in.weight
+        wp = derived(w, "conv3x3_wide_in", lambda: _pack_wide_in(w.detach(), cp), extra=(cp,))
+        h, _, _ = ops.conv3x3(xin, wp, self.conv_in.bias, B, H, W)
         for blk in self.down_blocks:
             h, H, W = blk(h, B, H, W)
         h = self.mid_block(h, B, H, W)
         h = ops.group_norm(h, self.conv_norm_out.weight, self.conv_norm_out.bias, self.groups, EPS, silu=True)
-        h, _, _ = _conv3x3(self.conv_out, self._pk_out, h, B, H, W)
+        h, _, _ = _conv3x3(self.conv_out, h, B, H, W)
         return h, H, W
 
 
@@ -214,19 +210,19 @@ class Decoder(nn.Module):
         self.up_blocks = nn.ModuleList([UpDecoderBlock(rw[max(i - 1, 0)], rw[i], cfg.layers_per_block + 1, g, i != len(w) - 1) for i in range(len(w))])
         self.conv_norm_out = nn.GroupNorm(g, w[0], eps=EPS)
         self.conv_out = nn.Conv2d(w[0], cfg.out_channels, 3, padding=1)
-        self._pk_in, self._pk_out, self._pk_bias = _Packed(), _Packed(), _Packed()
 
     def forward(self, z, B, H, W):
         """z [B, h*w, latent] NHWC (after post_quant_conv) -> [B, out_channels, H', W']"""
-        h, _, _ = _conv3x3(self.conv_in, self._pk_in, z, B, H, W)
+        h, _, _ = _conv3x3(self.conv_in, z, B, H, W)
         h = self.mid_block(h, B, H, W)
         for blk in self.up_blocks:
             h, H, W = blk(h, B, H, W)
         h = ops.group_norm(h, self.conv_norm_out.weight, self.conv_norm_out.bias, self.groups, EPS, silu=True)
         co = self.out_channels
         cp = ops.round_up(co, 8)  # the GEMM stores 16-byte vectors: zero weight rows up to 8 output channels
-        wp = self._pk_out.get(self.conv_out.weight, lambda w: _pack_wide_out(w, cp))
-        bp = self._pk_bias.get(self.conv_out.bias, lambda b: torch.cat([b, b.new_zeros(cp - co)]).contiguous())
+        w, b = self.conv_out.weight, self.conv_out.bias
+        wp = derived(w, "conv3x3_wide_out", lambda: _pack_wide_out(w.detach(), cp), extra=(cp,))
+        bp = derived(b, "zero_padded", lambda: torch.cat([b.detach(), b.new_zeros(cp - co)]).contiguous(), extra=(cp,))
         out, _, _ = ops.conv3x3(h, wp, bp, B, H, W)
         return out[..., :co].permute(0, 2, 1).reshape(B, co, H, W).contiguous()  # layout: NHWC -> NCHW
 

@@ -16,7 +16,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .unet import _Packed
+from .derived import derived
 
 
 @dataclass
@@ -41,31 +41,32 @@ class HifiGanResidualBlock(nn.Module):
         pad = lambda d: (kernel_size * d - d) // 2
         self.convs1 = nn.ModuleList([nn.Conv1d(channels, channels, kernel_size, dilation=d, padding=pad(d)) for d in dilation])
         self.convs2 = nn.ModuleList([nn.Conv1d(channels, channels, kernel_size, dilation=1, padding=pad(1)) for _ in dilation])
-        self._pk1 = [_Packed() for _ in dilation]
-        self._pk2 = [_Packed() for _ in dilation]
 
     def forward(self, h):
         """h [B, T, C] channels-last"""
         k, s = self.kernel_size, self.leaky_relu_slope
-        for c1, c2, d, p1, p2 in zip(self.convs1, self.convs2, self.dilation, self._pk1, self._pk2):
-            t = ops.conv1d(h, _pack1d(c1, p1), c1.bias, k, dilation=d, pre_slope=s)
-            h = ops.conv1d(t, _pack1d(c2, p2), c2.bias, k, pre_slope=s, residual=h)
+        for c1, c2, d in zip(self.convs1, self.convs2, self.dilation):
+            t = ops.conv1d(h, _pack1d(c1), c1.bias, k, dilation=d, pre_slope=s)
+            h = ops.conv1d(t, _pack1d(c2), c2.bias, k, pre_slope=s, residual=h)
         return h
 
 
-def _pack1d(conv, pk, pad_out=0):
+def _pack1d(conv, pad_out=0):
     """Conv1d weight [Cout, Cin, k] -> [Cout (+ zero rows), k * Cin] in (tap, cin) order"""
-    def f(w):
-        w2 = w.permute(0, 2, 1).reshape(w.shape[0], -1)
+    w = conv.weight
+
+    def make():
+        w2 = w.detach().permute(0, 2, 1).reshape(w.shape[0], -1)
         if pad_out > w.shape[0]:
             w2 = torch.cat([w2, w2.new_zeros(pad_out - w.shape[0], w2.shape[1])], 0)
         return w2.contiguous()
-    return pk.get(conv.weight, f)
+    return derived(w, "conv1d", make, extra=(pad_out,))
 
 
-def _pack1d_t(conv, pk):
+def _pack1d_t(conv):
     """ConvTranspose1d weight [Cin, Cout, k] -> [Cout, k * Cin] in (tap, cin) order"""
-    return pk.get(conv.weight, lambda w: w.permute(1, 2, 0).reshape(w.shape[1], -1).contiguous())
+    w = conv.weight
+    return derived(w, "conv1d_t", lambda: w.detach().permute(1, 2, 0).reshape(w.shape[1], -1).contiguous())
 
 
 class SpeechT5HifiGan(nn.Module):
@@ -88,8 +89,6 @@ class SpeechT5HifiGan(nn.Module):
         self.conv_post = nn.Conv1d(ch, 1, 7, padding=3)
         self.register_buffer("mean", torch.zeros(cfg.model_in_dim))
         self.register_buffer("scale", torch.ones(cfg.model_in_dim))
-        self._pk_pre, self._pk_post, self._pk_postb = _Packed(), _Packed(), _Packed()
-        self._pk_up = [_Packed() for _ in self.upsampler]
 
     @torch.no_grad()
     def forward(self, spectrogram):
@@ -102,14 +101,15 @@ class SpeechT5HifiGan(nn.Module):
         x = spectrogram if batched else spectrogram.unsqueeze(0)
         dtype = self.conv_pre.weight.dtype
         x = x.to(dtype).contiguous()  # channels-last already: [B, T, mel bins] (the reference transposes to [B, C, T] here)
-        h = ops.conv1d(x, _pack1d(self.conv_pre, self._pk_pre), self.conv_pre.bias, 7)
+        h = ops.conv1d(x, _pack1d(self.conv_pre), self.conv_pre.bias, 7)
         for i, (up, rate, k) in enumerate(zip(self.upsampler, cfg.upsample_rates, cfg.upsample_kernel_sizes)):
-            h = ops.conv1d(h, _pack1d_t(up, self._pk_up[i]), up.bias, k, transposed_stride=rate, pre_slope=cfg.leaky_relu_slope)
+            h = ops.conv1d(h, _pack1d_t(up), up.bias, k, transposed_stride=rate, pre_slope=cfg.leaky_relu_slope)
             r = [self.resblocks[i * 3 + j](h) for j in range(3)]
             h = ops.mix3(r[0], r[1], r[2], 1.0 / 3.0)
         # conv_post has ONE output channel: padded to 8 zero-extended rows (the GEMM's 16-byte output rows), column 0 is the wave
-        wp = _pack1d(self.conv_post, self._pk_post, pad_out=8)
-        bp = self._pk_postb.get(self.conv_post.bias, lambda b: torch.cat([b, b.new_zeros(7)]).contiguous())
+        wp = _pack1d(self.conv_post, pad_out=8)
+        b = self.conv_post.bias
+        bp = derived(b, "zero_padded", lambda: torch.cat([b.detach(), b.new_zeros(7)]).contiguous())
         y = ops.conv1d(h, wp, bp, 7, pre_slope=0.01, act="tanh")  # F.leaky_relu's default slope, then conv_post, then tanh
         wave = y[:, :, 0].contiguous()
         return wave if batched else wave[0]
