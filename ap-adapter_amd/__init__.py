@@ -13,5 +13,6 @@ from .text_encoders import (PromptEncoder, ClapTextModelWithProjection, T5Encode
 from .wiring import install_ap_adapter, build_processors, ip_layer_names, adapter_state_dict, save_adapter, load_adapter  # noqa: F401
 from . import ops, distributed, autograd, config, sharded  # noqa: F401
 from .config import get_config  # noqa: F401
+from .ops import set_float32_matmul_precision, get_float32_matmul_precision  # noqa: F401
 from .training import AdapterTrainer, add_noise  # noqa: F401
 from ._lib import build, lib  # noqa: F401

@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("APAD_LIB_PATH") or os.path.join(_HERE, "libapadapter_hip.so")  # override: kernel A/B experiments
 CSRC = os.path.join(_HERE, "csrc")
 
-BF16, F16, F32 = 0, 1, 2
+BF16, F16, F32, F32_BF16X3 = 0, 1, 2, 3
 A_PLAIN, A_CONV3X3, A_PATCH16, A_CONV1D = 0, 1, 2, 4
 EPI_NONE, EPI_SILU, EPI_GELU, EPI_GEGLU, EPI_TANH, EPI_RELU, EPI_GELU_TANH, EPI_GEGLU_TANH = 0, 1, 2, 3, 4, 5, 6, 7
 OUT_ROWMAJOR, OUT_VT, OUT_QKV = 0, 1, 2
@@ -132,6 +132,8 @@ SYMBOLS = {
     "apad_gemm": (C.c_int, [C.POINTER(GemmDesc), _vp]),
     "apad_conv_halo_pack": (C.c_int, [_vp, _vp, _i64, _i64, _i32, _vp]),
     "apad_hconv_launch_count": (_i64, []),
+    "apad_f32_split_weight": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _vp]),
+    "apad_f32x3_launch_count": (_i64, []),
     "apad_probe_mfma": (C.c_int, [_vp, _i32, _i32, C.POINTER(C.c_double), _vp]),
     "apad_conv_halo_packed_bytes": (_i64, [_i64, _i64]),
     "apad_conv_halo_workspace_bytes": (_i64, [_i64, _i64, _i64, _i32]),
@@ -208,7 +210,7 @@ def lib():
                 fn = getattr(h, name)  # AttributeError if the ABI lost a symbol
                 fn.restype = res
                 fn.argtypes = args
-            if h.apad_abi_version() != 11:
+            if h.apad_abi_version() != 12:
                 raise RuntimeError("libapadapter_hip.so ABI version mismatch")
             if h.apad_sizeof_gemm_desc() != C.sizeof(GemmDesc) or h.apad_sizeof_attn_desc() != C.sizeof(AttnDesc) \
                     or h.apad_sizeof_rp_desc() != C.sizeof(RpDesc) \

@@ -47,6 +47,15 @@ def _c(t):
     return t if t.is_contiguous() else t.contiguous()
 
 
+def _exact(backward):
+    """the input-gradient GEMMs of a backward stay on the exact-f32 kernel under set_float32_matmul_precision("high"): only the
+    training forward follows the setting"""
+    def run(ctx, *grads):
+        with ops.exact_f32():
+            return backward(ctx, *grads)
+    return run
+
+
 class _Linear(torch.autograd.Function):
     """y = x W^T (+ b) (+ residual)"""
 
@@ -59,9 +68,11 @@ class _Linear(torch.autograd.Function):
         # gradients are, instead of being rounded to the storage type once per micro-batch
         ctx.sink = getattr(w, "_apad_grad_sink", None)
         w2 = w.reshape(w.shape[0], -1)
-        return ops.linear(_c(x), w2, b, residual=None if residual is None else _c(residual))
+        with ops.recorded_forward():  # (fp32 "high": a trainable w is split by this call, inside a captured step)
+            return ops.linear(_c(x), w2, b, residual=None if residual is None else _c(residual))
 
     @staticmethod
+    @_exact
     def backward(ctx, dy):
         x, w = ctx.saved_tensors
         dy = _c(dy)
@@ -110,9 +121,11 @@ class _QKV(torch.autograd.Function):
     def forward(ctx, x, wq, wk, wv):
         x = _c(x)
         ctx.save_for_backward(wq, wk, wv)
-        return ops.linear(x, wq), ops.linear(x, wk), ops.linear(x, wv)
+        with ops.recorded_forward():
+            return ops.linear(x, wq), ops.linear(x, wk), ops.linear(x, wv)
 
     @staticmethod
+    @_exact
     def backward(ctx, dq, dk, dv):
         wq, wk, wv = ctx.saved_tensors
         wst = _derived(wq, "qkvT", lambda: torch.cat([wq.detach(), wk.detach(), wv.detach()], 0).t().contiguous(), (wk, wv))  # [C, 3C]
@@ -138,6 +151,7 @@ class _QKVT(_QKV):
         return q, k, v, vt
 
     @staticmethod
+    @_exact
     def backward(ctx, dq, dk, dv, _dvt):
         return _QKV.backward(ctx, dq, dk, dv) + (None,)
 
@@ -165,6 +179,7 @@ class _LayerNorm(torch.autograd.Function):
         return ops.layer_norm(x, g, b, eps)
 
     @staticmethod
+    @_exact
     def backward(ctx, dy):
         x, g = ctx.saved_tensors
         return ops.layer_norm_bwd(x, g, _c(dy), ctx.eps), None, None, None
@@ -188,6 +203,7 @@ class _LayerNormRes(torch.autograd.Function):
         return ops.layer_norm(x, g, b, eps), x.view_as(x)
 
     @staticmethod
+    @_exact
     def backward(ctx, dy, dres):
         x, g = ctx.saved_tensors
         if dy is None:
@@ -214,6 +230,7 @@ class _GroupNorm(torch.autograd.Function):
         return ops.group_norm(x, g, b, groups, eps, silu=silu)
 
     @staticmethod
+    @_exact
     def backward(ctx, dy):
         x, g, b = ctx.saved_tensors
         groups, eps, silu = ctx.cfg
@@ -241,6 +258,7 @@ class _Conv3x3(torch.autograd.Function):
         return out
 
     @staticmethod
+    @_exact
     def backward(ctx, dy):
         (w,) = ctx.saved_tensors
         B, H, W, stride, up, _ = ctx.geom
@@ -276,6 +294,7 @@ class _Geglu(torch.autograd.Function):
         return ops.geglu(proj)
 
     @staticmethod
+    @_exact
     def backward(ctx, dh):
         (proj,) = ctx.saved_tensors
         return ops.geglu_bwd(proj, _c(dh))
@@ -299,6 +318,7 @@ class _Attention(torch.autograd.Function):
         return o
 
     @staticmethod
+    @_exact
     def backward(ctx, do):
         q, k, v, o, lse, key_bias = ctx.saved_tensors
         need_kv = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
@@ -330,6 +350,7 @@ class _IPAttention(torch.autograd.Function):
         return o
 
     @staticmethod
+    @_exact
     def backward(ctx, do):
         q, k_t, v_t, k_a, v_a, o_t, o_a, lse_t, lse_a, key_bias = ctx.saved_tensors
         do = _c(do)
@@ -354,6 +375,7 @@ class _MSE(torch.autograd.Function):
         return loss.reshape(())
 
     @staticmethod
+    @_exact
     def backward(ctx, g):
         (dpred,) = ctx.saved_tensors
         # g is 1 for loss.backward(); applied as a device-side scalar multiply of a [B, 8, 250, 16] tensor (no host

@@ -1,5 +1,5 @@
 // Internal entry points of the fp32 precision mode (f32_ops.hip).  The C-ABI functions dispatch here when the
-// descriptor's dtype is APAD_F32; arguments are validated inside.
+// descriptor's dtype is APAD_F32 (or APAD_F32_BF16X3 for apad_gemm / apad_attention); arguments are validated inside.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "../../include/apadapter_hip.h"

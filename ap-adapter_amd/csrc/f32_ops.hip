@@ -10,6 +10,13 @@
 // B[l / 32][l % 32], C/D lane l, register r = C[8 * (r / 4) + 4 * (l / 32) + r % 4][l % 32] -- the C layout of every
 // 32x32 MFMA, so the transposed-score trick of attention.hip (C layout re-used as the next B operand) carries over:
 // register r of the score tile is the B element of k-step r when V^T is read with the same key permutation.
+//
+// The "high" form of the mode (dtype APAD_F32_BF16X3; gemm_f32x3_kernel, attn_f32x3_kernel): same storage, same gathers,
+// same epilogues and softmax, but every contraction runs on v_mfma_f32_32x32x16_bf16 over split operands, x = hi + lo with
+// hi = bf16(x), lo = bf16(x - hi) (x - hi is exact in fp32).  A product is lo.hi + hi.lo + hi.hi, accumulated in fp32 in that
+// fixed order per 16-wide k step; the dropped lo.lo term is below 2^-16 relative and lo's own rounding about 2^-17.  Three
+// 32x32x16 MFMAs replace eight 32x32x2_f32 per 16 k.  Activations are split in registers on their way into LDS (an LDS-DMA
+// copy cannot split); weights arrive as the two bf16 planes of apad_f32_split_weight.
 #include <math.h>
 #include "common.h"
 #include "f32_ops.h"
@@ -26,6 +33,48 @@ __device__ __forceinline__ float gelu_p(float x) { return 0.5f * x * (1.0f + erf
 // "gelu_new" of GPT-2 / T5's gated-gelu (transformers NewGELUActivation)
 __device__ __forceinline__ float gelu_tanh_p(float x) { return 0.5f * x * (1.0f + tanhf(0.7978845608028654f * (x + 0.044715f * x * x * x))); }
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+int64_t g_f32x3_launches = 0;  // (tests assert the route with it; not synchronised: a diagnostic)
+
+__device__ __forceinline__ f32x16 mfma16(bf16x8_t a, bf16x8_t b, f32x16 c) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+}
+// acc += A . B on split operands, the fixed order lo.hi, hi.lo, hi.hi (a row's result must not depend on its tile)
+__device__ __forceinline__ f32x16 mfma3(bf16x8_t ah, bf16x8_t al, bf16x8_t bh, bf16x8_t bl, f32x16 c) {
+    c = mfma16(al, bh, c);
+    c = mfma16(ah, bl, c);
+    return mfma16(ah, bh, c);
+}
+// x = hi + lo: hi = bf16(x) (round to nearest even), lo = bf16(x - hi); x - hi is exact in fp32
+__device__ __forceinline__ void split_bf16(float x, __bf16& hi, __bf16& lo) {
+    hi = (__bf16)x;
+    lo = (__bf16)(x - (float)hi);
+}
+__device__ __forceinline__ void split4(f4 x, uint2& hi, uint2& lo) {
+    bf16x4_t h, l;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        __bf16 a, b;
+        split_bf16(x[e], a, b);
+        h[e] = a;
+        l[e] = b;
+    }
+    hi = __builtin_bit_cast(uint2, h);
+    lo = __builtin_bit_cast(uint2, l);
+}
+// 8 consecutive floats (two 16-byte loads) -> the hi and lo MFMA fragments
+__device__ __forceinline__ void split8(f4 x0, f4 x1, bf16x8_t& hi, bf16x8_t& lo) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        __bf16 a, b;
+        split_bf16(x0[e], a, b);
+        hi[e] = a;
+        lo[e] = b;
+        split_bf16(x1[e], a, b);
+        hi[4 + e] = a;
+        lo[4 + e] = b;
+    }
+}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // GEMM: out = epilogue(A . W^T + bias + rowgroup_bias) + residual, all A modes / epilogues / output modes of apad_gemm
@@ -51,10 +100,14 @@ struct G32P {
     int32_t taps, dilation, pad, transposed, pre_act;  // APAD_A_CONV1D
     float pre_slope;
     int32_t lead;  // conv3x3: zero rows / columns before the first source row / column (1, or 0 with conv_asym_pad)
+    int64_t wplane;  // APAD_F32_BF16X3: bf16 elements from the hi plane of w to its lo plane
 };
 
 // float offset of 16-byte chunk `chunk` (0..7) of tile row `row` (the swizzle of gemm.hip's lds_off)
 __device__ __forceinline__ int lds32(int row, int chunk) { return row * BKF + ((chunk ^ ((row >> 1) & 7)) << 2); }
+// bf16 planes of the split form: 64-byte rows of BKF elements, 16-byte chunk c16 (0..3) stored at c16 ^ ((row >> 2) & 3) -- the
+// fragment reads (32 rows at one chunk) are then conflict-free in each of ds_read_b128's 16-lane groups
+__device__ __forceinline__ int ldsx(int row, int c16) { return row * BKF + ((c16 ^ ((row >> 2) & 3)) << 3); }
 
 struct Row32 {
     int64_t base;  // PLAIN: element offset of the row; CONV / PATCH: source batch index
@@ -101,8 +154,8 @@ template <int AMODE> __device__ __forceinline__ f4 load_a32(const G32P& p, const
     }
 }
 
-template <int AMODE> __global__ __launch_bounds__(256) void gemm_f32_kernel(G32P p) {
-    __shared__ __attribute__((aligned(16))) float smem[TB * CLD];  // staging: 2 x 64 x 32 floats; epilogue: 64 x 68
+template <int AMODE, bool X3> __device__ __forceinline__ void gemm_f32_body(const G32P& p) {
+    __shared__ __attribute__((aligned(16))) float smem[TB * CLD];  // staging: 2 x 64 x 32 floats (X3: 4 x 64 x 32 bf16); epilogue: 64 x 68
     float* const sA = smem;
     float* const sB = smem + TB * BKF;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -160,35 +213,80 @@ template <int AMODE> __global__ __launch_bounds__(256) void gemm_f32_kernel(G32P
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
     const int nk = (int)((p.K + BKF - 1) / BKF);
-    f4 ga[2], gb[2];
-    auto gload = [&](int kt) {
-        const int k = kt * BKF + chunk * 4;
+    if constexpr (X3) {
+        // hi / lo planes of A and W: 4 x 64 rows x 32 bf16 = 16 KB of the staging buffer
+        __bf16* const xAh = reinterpret_cast<__bf16*>(smem);
+        __bf16* const xAl = xAh + TB * BKF;
+        __bf16* const xBh = xAl + TB * BKF;
+        __bf16* const xBl = xBh + TB * BKF;
+        const __bf16* const wx = reinterpret_cast<const __bf16*>(p.w);
+        f4 ga[2];
+        uint2 gbh[2], gbl[2];
+        auto gload = [&](int kt) {
+            const int k = kt * BKF + chunk * 4;
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            ga[i] = load_a32<AMODE>(p, ra[i], k);
-            const f4 z = {0.f, 0.f, 0.f, 0.f};
-            gb[i] = (wv[i] && k < p.K) ? *reinterpret_cast<const f4*>(p.w + wb[i] + k) : z;
+            for (int i = 0; i < 2; ++i) {
+                ga[i] = load_a32<AMODE>(p, ra[i], k);
+                const bool ok = wv[i] && k < p.K;
+                gbh[i] = ok ? *reinterpret_cast<const uint2*>(wx + wb[i] + k) : make_uint2(0u, 0u);
+                gbl[i] = ok ? *reinterpret_cast<const uint2*>(wx + p.wplane + wb[i] + k) : make_uint2(0u, 0u);
+            }
+        };
+        gload(0);
+        for (int kt = 0; kt < nk; ++kt) {
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const int rl = (tid >> 3) + 32 * i;
+                const int o = ldsx(rl, chunk >> 1) + (chunk & 1) * 4;
+                uint2 ah, al;
+                split4(ga[i], ah, al);
+                *reinterpret_cast<uint2*>(xAh + o) = ah;
+                *reinterpret_cast<uint2*>(xAl + o) = al;
+                *reinterpret_cast<uint2*>(xBh + o) = gbh[i];
+                *reinterpret_cast<uint2*>(xBl + o) = gbl[i];
+            }
+            __syncthreads();
+            if (kt + 1 < nk) gload(kt + 1);  // in flight under the MFMAs of this k-tile
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) {  // k = kt*32 + ks*16 + half*8 + j in both operands
+                const int oa = ldsx(wm * 32 + l31, ks * 2 + half), ob = ldsx(wn * 32 + l31, ks * 2 + half);
+                const bf16x8_t ah = *reinterpret_cast<const bf16x8_t*>(xAh + oa), al = *reinterpret_cast<const bf16x8_t*>(xAl + oa);
+                const bf16x8_t bh = *reinterpret_cast<const bf16x8_t*>(xBh + ob), bl = *reinterpret_cast<const bf16x8_t*>(xBl + ob);
+                acc = mfma3(ah, al, bh, bl, acc);
+            }
+            __syncthreads();
         }
-    };
-    gload(0);
-    for (int kt = 0; kt < nk; ++kt) {
+    } else {
+        f4 ga[2], gb[2];
+        auto gload = [&](int kt) {
+            const int k = kt * BKF + chunk * 4;
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int rl = (tid >> 3) + 32 * i;
-            *reinterpret_cast<f4*>(sA + lds32(rl, chunk)) = ga[i];
-            *reinterpret_cast<f4*>(sB + lds32(rl, chunk)) = gb[i];
+            for (int i = 0; i < 2; ++i) {
+                ga[i] = load_a32<AMODE>(p, ra[i], k);
+                const f4 z = {0.f, 0.f, 0.f, 0.f};
+                gb[i] = (wv[i] && k < p.K) ? *reinterpret_cast<const f4*>(p.w + wb[i] + k) : z;
+            }
+        };
+        gload(0);
+        for (int kt = 0; kt < nk; ++kt) {
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const int rl = (tid >> 3) + 32 * i;
+                *reinterpret_cast<f4*>(sA + lds32(rl, chunk)) = ga[i];
+                *reinterpret_cast<f4*>(sB + lds32(rl, chunk)) = gb[i];
+            }
+            __syncthreads();
+            if (kt + 1 < nk) gload(kt + 1);  // in flight under the MFMAs of this k-tile
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) {
+                const int ch = ks * 2 + half;
+                const f4 af = *reinterpret_cast<const f4*>(sA + lds32(wm * 32 + l31, ch));
+                const f4 bf = *reinterpret_cast<const f4*>(sB + lds32(wn * 32 + l31, ch));
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc = mfma2(af[j], bf[j], acc);  // k = kt*32 + ch*4 + j in both operands
+            }
+            __syncthreads();
         }
-        __syncthreads();
-        if (kt + 1 < nk) gload(kt + 1);  // in flight under the MFMAs of this k-tile
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            const int ch = ks * 2 + half;
-            const f4 af = *reinterpret_cast<const f4*>(sA + lds32(wm * 32 + l31, ch));
-            const f4 bf = *reinterpret_cast<const f4*>(sB + lds32(wn * 32 + l31, ch));
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc = mfma2(af[j], bf[j], acc);  // k = kt*32 + ch*4 + j in both operands
-        }
-        __syncthreads();
     }
 
     // ---- epilogue: acc (+ bias, + rowgroup bias, activation) -> LDS tile ----
@@ -258,6 +356,9 @@ template <int AMODE> __global__ __launch_bounds__(256) void gemm_f32_kernel(G32P
     }
 }
 
+template <int AMODE> __global__ __launch_bounds__(256) void gemm_f32_kernel(G32P p) { gemm_f32_body<AMODE, false>(p); }
+template <int AMODE> __global__ __launch_bounds__(256) void gemm_f32x3_kernel(G32P p) { gemm_f32_body<AMODE, true>(p); }
+
 // ---------------------------------------------------------------------------------------------------------------------
 // Attention: softmax(Q K^T * scale + bias) V, one or two independently normalised key segments (attention.hip's
 // operator).  One wave = 32 queries of one (batch, head); waves are independent; K fragments (A operand, rows = keys)
@@ -280,10 +381,19 @@ struct A32P {
 constexpr float LOG2E_F = 1.4426950408889634f;
 constexpr float NEG_BIG_F = -1.0e30f;
 
+// Q^T B-operand fragments of one wave: exact form, lane holds Q[qi][cc*8 + half*4 .. +4); split form (X3), lane holds the hi / lo
+// parts of Q[qi][cc*16 + half*8 .. +8), split once
+template <int D, bool X3> struct QFrag {
+    float f[D / 8][4];
+};
+template <int D> struct QFrag<D, true> {
+    bf16x8_t hi[D / 16], lo[D / 16];
+};
+
 // un-normalised O^T (o), running max m (scaled log2 domain) and denominator of ONE softmax segment over L keys
-template <int D>
+template <int D, bool X3>
 __device__ __forceinline__ void segment32(const float* kbase, int64_t k_sl, const float* vbase, int L, int Lpad, const float* bias,
-                                          float c, const float (&qf)[D / 8][4], f32x16 (&o)[(D + 31) / 32], float& den, float& m,
+                                          float c, const QFrag<D, X3>& q, f32x16 (&o)[(D + 31) / 32], float& den, float& m,
                                           int l31, int half) {
     constexpr int DT_TILES = (D + 31) / 32;
     float sum = 0.f;
@@ -295,15 +405,25 @@ __device__ __forceinline__ void segment32(const float* kbase, int64_t k_sl, cons
     for (int key0 = 0; key0 < L; key0 += 32) {
         // S^T (32 keys x 32 queries) = K . Q^T
         const int krow = key0 + l31 < L ? key0 + l31 : L - 1;  // rows past L are masked below
-        const float* kp = kbase + (int64_t)krow * k_sl + half * 4;
         f32x16 s;
 #pragma unroll
         for (int r = 0; r < 16; ++r) s[r] = 0.f;
+        if constexpr (X3) {
+            const float* kp = kbase + (int64_t)krow * k_sl + half * 8;
 #pragma unroll
-        for (int cc = 0; cc < D / 8; ++cc) {
-            const f4 kf = *reinterpret_cast<const f4*>(kp + cc * 8);
+            for (int cc = 0; cc < D / 16; ++cc) {  // K split as it loads: d = cc*16 + half*8 + j
+                bf16x8_t kh, kl;
+                split8(*reinterpret_cast<const f4*>(kp + cc * 16), *reinterpret_cast<const f4*>(kp + cc * 16 + 4), kh, kl);
+                s = mfma3(kh, kl, q.hi[cc], q.lo[cc], s);
+            }
+        } else {
+            const float* kp = kbase + (int64_t)krow * k_sl + half * 4;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) s = mfma2(kf[j], qf[cc][j], s);
+            for (int cc = 0; cc < D / 8; ++cc) {
+                const f4 kf = *reinterpret_cast<const f4*>(kp + cc * 8);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) s = mfma2(kf[j], q.f[cc][j], s);
+            }
         }
         float tmax = NEG_BIG_F;
 #pragma unroll
@@ -330,22 +450,51 @@ __device__ __forceinline__ void segment32(const float* kbase, int64_t k_sl, cons
             sum += s[r];
         }
         // O^T += V^T . P^T : register r of the score tile is the B element of k-step r
+        if constexpr (X3) {
+            // 16-key step t: B element j of lane (l31, half) is register 8t + j = key 16t + 8(j / 4) + 4 half + j % 4, so V^T is
+            // read at the same keys; P and V^T split into hi / lo like every other operand of this form
 #pragma unroll
-        for (int g = 0; g < 4; ++g) {
+            for (int t = 0; t < 2; ++t) {
+                bf16x8_t ph, pl;
 #pragma unroll
-            for (int dt = 0; dt < DT_TILES; ++dt) {
-                const int d = dt * 32 + l31;
-                f4 vf = {0.f, 0.f, 0.f, 0.f};
-                if (d < D) vf = *reinterpret_cast<const f4*>(vbase + (int64_t)d * Lpad + key0 + 8 * g + 4 * half);
+                for (int j = 0; j < 8; ++j) {
+                    __bf16 a, b;
+                    split_bf16(s[8 * t + j], a, b);
+                    ph[j] = a;
+                    pl[j] = b;
+                }
 #pragma unroll
-                for (int j = 0; j < 4; ++j) o[dt] = mfma2(vf[j], s[g * 4 + j], o[dt]);
+                for (int dt = 0; dt < DT_TILES; ++dt) {
+                    const int d = dt * 32 + l31;
+                    f4 v0 = {0.f, 0.f, 0.f, 0.f}, v1 = v0;
+                    if (d < D) {
+                        const float* vp = vbase + (int64_t)d * Lpad + key0 + 16 * t + 4 * half;
+                        v0 = *reinterpret_cast<const f4*>(vp);
+                        v1 = *reinterpret_cast<const f4*>(vp + 8);
+                    }
+                    bf16x8_t vh, vl;
+                    split8(v0, v1, vh, vl);
+                    o[dt] = mfma3(vh, vl, ph, pl, o[dt]);
+                }
+            }
+        } else {
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+#pragma unroll
+                for (int dt = 0; dt < DT_TILES; ++dt) {
+                    const int d = dt * 32 + l31;
+                    f4 vf = {0.f, 0.f, 0.f, 0.f};
+                    if (d < D) vf = *reinterpret_cast<const f4*>(vbase + (int64_t)d * Lpad + key0 + 8 * g + 4 * half);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) o[dt] = mfma2(vf[j], s[g * 4 + j], o[dt]);
+                }
             }
         }
     }
     den = half_sum(sum);
 }
 
-template <int D> __global__ __launch_bounds__(256) void attn_f32_kernel(A32P p) {
+template <int D, bool X3> __device__ __forceinline__ void attn_f32_body(const A32P& p) {
     constexpr int DT_TILES = (D + 31) / 32;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int half = lane >> 5, l31 = lane & 31;
@@ -355,20 +504,27 @@ template <int D> __global__ __launch_bounds__(256) void attn_f32_kernel(A32P p) 
     int qi = q0 + l31;
     const bool qvalid = qi < p.N;
     qi = qvalid ? qi : p.N - 1;
-    float qf[D / 8][4];  // Q^T B-operand fragments: lane holds Q[qi][cc*8 + half*4 .. +4)
-    const float* qp = p.q + (int64_t)b * p.q_sb + (int64_t)qi * p.q_sn + h * D + half * 4;
+    QFrag<D, X3> qf;
+    if constexpr (X3) {
+        const float* qp = p.q + (int64_t)b * p.q_sb + (int64_t)qi * p.q_sn + h * D + half * 8;
 #pragma unroll
-    for (int cc = 0; cc < D / 8; ++cc) {
-        const f4 v = *reinterpret_cast<const f4*>(qp + cc * 8);
+        for (int cc = 0; cc < D / 16; ++cc)
+            split8(*reinterpret_cast<const f4*>(qp + cc * 16), *reinterpret_cast<const f4*>(qp + cc * 16 + 4), qf.hi[cc], qf.lo[cc]);
+    } else {
+        const float* qp = p.q + (int64_t)b * p.q_sb + (int64_t)qi * p.q_sn + h * D + half * 4;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) qf[cc][j] = v[j];
+        for (int cc = 0; cc < D / 8; ++cc) {
+            const f4 v = *reinterpret_cast<const f4*>(qp + cc * 8);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) qf.f[cc][j] = v[j];
+        }
     }
     f32x16 o[DT_TILES];
     float den, m;
     {
         const int bk = b / p.kvdiv;
         const float* bias = p.key_bias ? p.key_bias + (int64_t)b * p.L : nullptr;
-        segment32<D>(p.k + (int64_t)bk * p.k_sb + h * D, p.k_sl, p.vt + (int64_t)bk * p.vt_sb + (int64_t)h * D * p.Lpad, p.L, p.Lpad,
+        segment32<D, X3>(p.k + (int64_t)bk * p.k_sb + h * D, p.k_sl, p.vt + (int64_t)bk * p.vt_sb + (int64_t)h * D * p.Lpad, p.L, p.Lpad,
                      bias, p.scale_log2, qf, o, den, m, l31, half);
     }
     if (p.lse != nullptr && half == 0 && q0 + l31 < ((p.N + 31) & ~31))  // (pad entries: 0, see attention.hip)
@@ -382,7 +538,7 @@ template <int D> __global__ __launch_bounds__(256) void attn_f32_kernel(A32P p) 
         f32x16 o2[DT_TILES];
         float den2, m2;
         const int bk = b / p.kvdiv2;
-        segment32<D>(p.k2 + (int64_t)bk * p.k2_sb + h * D, p.k2_sl, p.vt2 + (int64_t)bk * p.vt2_sb + (int64_t)h * D * p.Lpad2, p.L2,
+        segment32<D, X3>(p.k2 + (int64_t)bk * p.k2_sb + h * D, p.k2_sl, p.vt2 + (int64_t)bk * p.vt2_sb + (int64_t)h * D * p.Lpad2, p.L2,
                      p.Lpad2, nullptr, p.scale_log2, qf, o2, den2, m2, l31, half);
         const float inv2 = 1.0f / den2;
 #pragma unroll
@@ -404,9 +560,17 @@ template <int D> __global__ __launch_bounds__(256) void attn_f32_kernel(A32P p) 
         }
 }
 
-template <int D> int attn_launch(const A32P& p, hipStream_t s) {
+template <int D> __global__ __launch_bounds__(256) void attn_f32_kernel(A32P p) { attn_f32_body<D, false>(p); }
+template <int D> __global__ __launch_bounds__(256) void attn_f32x3_kernel(A32P p) { attn_f32_body<D, true>(p); }
+
+template <int D> int attn_launch(const A32P& p, bool x3, hipStream_t s) {
     dim3 grid((unsigned)((p.N + 127) / 128), (unsigned)(p.B * p.H));
-    hipLaunchKernelGGL((attn_f32_kernel<D>), grid, dim3(256), 0, s, p);
+    if (x3) {
+        hipLaunchKernelGGL((attn_f32x3_kernel<D>), grid, dim3(256), 0, s, p);
+        ++g_f32x3_launches;
+    } else {
+        hipLaunchKernelGGL((attn_f32_kernel<D>), grid, dim3(256), 0, s, p);
+    }
     return apad_check_launch("apad_attention(f32)");
 }
 
@@ -644,7 +808,32 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_f32_kernel(BwdF p) {
     }
 }
 
+// w [N][ldw] fp32 -> [2][N][K] bf16 (hi plane, then lo plane); 4 elements per thread
+__global__ __launch_bounds__(256) void split_weight_kernel(const float* w, __bf16* out, int64_t N, int64_t K, int64_t ldw) {
+    const int64_t kq = K / 4, total = N * kq;
+    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
+        const int64_t n = idx / kq, k = (idx - n * kq) * 4;
+        uint2 hi, lo;
+        split4(*reinterpret_cast<const f4*>(w + n * ldw + k), hi, lo);
+        *reinterpret_cast<uint2*>(out + n * K + k) = hi;
+        *reinterpret_cast<uint2*>(out + N * K + n * K + k) = lo;
+    }
+}
+
 }  // namespace
+
+extern "C" int apad_f32_split_weight(const void* w, void* out, int64_t N, int64_t K, int64_t ldw, void* stream) {
+    APAD_CHECK(w && out, "apad_f32_split_weight: null operand");
+    APAD_CHECK(N > 0 && K > 0 && K % 4 == 0 && ldw >= K && ldw % 4 == 0, "apad_f32_split_weight: needs N > 0, K %% 4 == 0, ldw >= K, ldw %% 4 == 0 "
+               "(N=%lld K=%lld ldw=%lld)", (long long)N, (long long)K, (long long)ldw);
+    APAD_CHECK(al16(w) && al16(out), "apad_f32_split_weight: pointers must be 16-byte aligned");
+    int64_t blocks = (N * (K / 4) + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(split_weight_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const float*)w, (__bf16*)out, N, K, ldw);
+    return apad_check_launch("apad_f32_split_weight");
+}
+
+extern "C" int64_t apad_f32x3_launch_count(void) { return g_f32x3_launches; }
 
 int apad_f32_gemm(const apad_gemm_desc* d, hipStream_t s) {
     APAD_CHECK(d->a && d->w && d->out, "apad_gemm(f32): null operand");
@@ -652,6 +841,7 @@ int apad_f32_gemm(const apad_gemm_desc* d, hipStream_t s) {
                (long long)d->K);
     APAD_CHECK(d->K % 4 == 0 && d->ldw % 4 == 0, "apad_gemm(f32): K and ldw must be multiples of 4 (K=%lld ldw=%lld)", (long long)d->K,
                (long long)d->ldw);
+    const bool x3 = d->dtype == APAD_F32_BF16X3;  // w: the split planes of apad_f32_split_weight, ldw in bf16 elements
     APAD_CHECK(al16(d->a) && al16(d->w) && al16(d->out) && al16(d->residual), "apad_gemm(f32): pointers must be 16-byte aligned");
     G32P p;
     p.a = (const float*)d->a; p.w = (const float*)d->w; p.out = (float*)d->out; p.out2 = (float*)d->out2; p.out3 = (float*)d->out3;
@@ -719,6 +909,18 @@ int apad_f32_gemm(const apad_gemm_desc* d, hipStream_t s) {
     p.n_tiles = (int)((d->N + bn_out - 1) / bn_out);
     const int64_t m_tiles = (d->M + TB - 1) / TB;
     dim3 grid((unsigned)(p.n_tiles * m_tiles));
+    if (x3) {
+        p.wplane = (bn_out == TB ? d->N : 2 * d->N) * d->ldw;  // the lo plane follows the hi plane of all the rows the GEMM reads
+        switch (d->a_mode) {
+            case APAD_A_PLAIN: hipLaunchKernelGGL((gemm_f32x3_kernel<APAD_A_PLAIN>), grid, dim3(256), 0, s, p); break;
+            case APAD_A_CONV3X3: hipLaunchKernelGGL((gemm_f32x3_kernel<APAD_A_CONV3X3>), grid, dim3(256), 0, s, p); break;
+            case APAD_A_CONV1D: hipLaunchKernelGGL((gemm_f32x3_kernel<APAD_A_CONV1D>), grid, dim3(256), 0, s, p); break;
+            default: hipLaunchKernelGGL((gemm_f32x3_kernel<APAD_A_PATCH16>), grid, dim3(256), 0, s, p); break;
+        }
+        ++g_f32x3_launches;
+        return apad_check_launch("apad_gemm(f32 bf16x3)");
+    }
+    p.wplane = 0;
     switch (d->a_mode) {
         case APAD_A_PLAIN: hipLaunchKernelGGL((gemm_f32_kernel<APAD_A_PLAIN>), grid, dim3(256), 0, s, p); break;
         case APAD_A_CONV3X3: hipLaunchKernelGGL((gemm_f32_kernel<APAD_A_CONV3X3>), grid, dim3(256), 0, s, p); break;
@@ -758,14 +960,15 @@ int apad_f32_attention(const apad_attn_desc* d, hipStream_t s) {
     p.kvdiv = d->kv_batch_div; p.kvdiv2 = dual ? d->kv2_batch_div : 1;
     p.scale_log2 = d->q_prescaled ? 1.0f : d->softmax_scale * LOG2E_F;
     p.scale2 = d->scale2;
+    const bool x3 = d->dtype == APAD_F32_BF16X3;
     switch (d->D) {
-        case 16: return attn_launch<16>(p, s);
-        case 32: return attn_launch<32>(p, s);
-        case 48: return attn_launch<48>(p, s);
-        case 64: return attn_launch<64>(p, s);
-        case 80: return attn_launch<80>(p, s);
-        case 96: return attn_launch<96>(p, s);
-        case 128: return attn_launch<128>(p, s);
+        case 16: return attn_launch<16>(p, x3, s);
+        case 32: return attn_launch<32>(p, x3, s);
+        case 48: return attn_launch<48>(p, x3, s);
+        case 64: return attn_launch<64>(p, x3, s);
+        case 80: return attn_launch<80>(p, x3, s);
+        case 96: return attn_launch<96>(p, x3, s);
+        case 128: return attn_launch<128>(p, x3, s);
     }
     apad_set_error("apad_attention(f32): head dim %d not supported (16,32,48,64,80,96,128)", d->D);
     return -1;

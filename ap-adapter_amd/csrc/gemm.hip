@@ -945,7 +945,7 @@ extern "C" int apad_set_gemm_ring(int32_t mode) {
 
 extern "C" int apad_gemm(const apad_gemm_desc* d, void* stream) {
     APAD_CHECK(d != nullptr, "apad_gemm: null descriptor");
-    if (d->dtype == APAD_F32) return apad_f32_gemm(d, (hipStream_t)stream);  // fp32 precision mode (f32_ops.hip)
+    if (d->dtype == APAD_F32 || d->dtype == APAD_F32_BF16X3) return apad_f32_gemm(d, (hipStream_t)stream);  // fp32 precision modes (f32_ops.hip)
     APAD_CHECK(d->dtype == APAD_BF16 || d->dtype == APAD_F16, "apad_gemm: dtype %d not supported (bf16/f16/f32)", d->dtype);
     APAD_CHECK(d->a && d->w && d->out, "apad_gemm: null operand");
     APAD_CHECK(d->M > 0 && d->N > 0 && d->K > 0, "apad_gemm: empty problem M=%lld N=%lld K=%lld", (long long)d->M,

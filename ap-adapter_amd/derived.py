@@ -5,9 +5,11 @@ keyed by its identity) and is replaced -- its old value released -- when the sig
 built from or of the settings it was built with changes.  Nothing else drops a value: a captured hipGraph holds the raw addresses of
 the derived weights it was recorded with, and the pipeline re-captures whenever a parameter changes (pipeline._weights_signature).
 """
+import torch
 from torch.utils.weak import WeakIdKeyDictionary
 
 _store = WeakIdKeyDictionary()  # key tensor -> {tag: (signature, value)}
+_values = WeakIdKeyDictionary()  # every tensor a make() returned (alone or in a tuple / list) -> True
 
 
 def signature(*tensors):
@@ -24,5 +26,15 @@ def derived(key, tag, make, deps=(), extra=()):
     entries = _store.setdefault(key, {})
     hit = entries.get(tag)
     if hit is None or hit[0] != sig:
-        hit = entries[tag] = (sig, make())
+        value = make()
+        for t in (value if isinstance(value, (tuple, list)) else (value,)):
+            if isinstance(t, torch.Tensor):
+                _values[t] = True
+        hit = entries[tag] = (sig, value)
     return hit[1]
+
+
+def is_derived(t):
+    """True when ``t`` is a value this store built: a tensor nothing writes into after make(), replaced (as a new tensor) when what it
+    derives from changes"""
+    return t in _values

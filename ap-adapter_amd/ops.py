@@ -10,7 +10,7 @@ import math
 import torch
 
 from . import _lib as L
-from .derived import derived
+from .derived import derived, is_derived
 
 _DT = {torch.bfloat16: L.BF16, torch.float16: L.F16, torch.float32: L.F32}
 _EPI = {None: L.EPI_NONE, "none": L.EPI_NONE, "silu": L.EPI_SILU, "gelu": L.EPI_GELU, "geglu": L.EPI_GEGLU, "tanh": L.EPI_TANH,
@@ -45,24 +45,114 @@ def set_gemm_ring(mode):
     return int(L.lib().apad_set_gemm_ring(int(mode)))
 
 
+# fp32 matmul precision of the fp32-storage modules (torch.set_float32_matmul_precision's names): "highest" runs every contraction
+# of apad_gemm / apad_attention on the exact-f32 MFMA (APAD_F32), "high" on three bf16 MFMAs over hi / lo splits of the operands
+# (APAD_F32_BF16X3, about 2^-16 relative).  The 16-bit modes never read it; neither do the backward kernels of the training step
+# (attention backward and the weight gradients stay exact fp32, and so do the input gradients: autograd runs them under exact_f32()).
+_F32_PRECISIONS = ("highest", "high")
+_f32_precision = ["highest"]
+_exact_depth = [0]
+
+
+def set_float32_matmul_precision(precision):
+    """"highest" (default) | "high".  Process-wide; "medium" (TF32) does not exist on this device and raises like any other string."""
+    if precision not in _F32_PRECISIONS:
+        raise ValueError(f"set_float32_matmul_precision: {precision!r} is not one of {_F32_PRECISIONS}")
+    _f32_precision[0] = precision
+
+
+def get_float32_matmul_precision():
+    return _f32_precision[0]
+
+
+class exact_f32:
+    """context: the fp32 contractions inside run exact (APAD_F32) whatever the precision setting -- the training step's backward"""
+    def __enter__(self):
+        _exact_depth[0] += 1
+
+    def __exit__(self, *exc):
+        _exact_depth[0] -= 1
+
+
+def _f32_dtype(dtype, exact=False):
+    """the descriptor dtype of an fp32 contraction under the current setting (16-bit dtypes map as always)"""
+    if dtype == torch.float32 and not exact and _exact_depth[0] == 0 and _f32_precision[0] == "high":
+        return L.F32_BF16X3
+    return _DT[dtype]
+
+
+def f32_split_weight(w, rows, K, ldw):
+    """the [2][rows][K] bf16 hi / lo planes (apad_f32_split_weight) of the fp32 weight rows w[:rows, :K] (row stride ldw) an
+    APAD_F32_BF16X3 GEMM reads.
+
+    Cached (on the tensor that owns the storage: a view's base, with the view's place in the tag; rebuilt when its signature changes)
+    only for a frozen operand: a module parameter or a derived weight, read outside an autograd recording of it.  Everything else is
+    split afresh by every call, so that a captured step splits it inside the graph and reads what the tensor holds at replay: the
+    trainable adapter weights in the training forward (the optimizer writes them through raw pointers between replays) and
+    activations used as the second operand (the VAE / T5 attention), whose buffers kernels write without a version bump."""
+    def make():
+        wv = w.detach()
+        out = torch.empty(2, rows, K, dtype=torch.bfloat16, device=w.device)
+        L.check(L.lib().apad_f32_split_weight(wv.data_ptr(), out.data_ptr(), rows, K, ldw, _stream()), "apad_f32_split_weight")
+        return out
+    if not split_cacheable(w):
+        return make()
+    base = w if w._base is None else w._base
+    off = w.storage_offset() - base.storage_offset()
+    return derived(base, ("bf16x3", off, rows, K, ldw), make)
+
+
+_in_recorded_forward = [0]
+
+
+class recorded_forward:
+    """context: the forward of an autograd Function (where grad mode is off): a trainable weight read inside is split per call"""
+    def __enter__(self):
+        _in_recorded_forward[0] += 1
+
+    def __exit__(self, *exc):
+        _in_recorded_forward[0] -= 1
+
+
+def split_cacheable(w):
+    """whether f32_split_weight may keep the planes of w: a module parameter or a derived weight (or a view of one), unless it is a
+    trainable weight read by the training forward"""
+    base = w if w._base is None else w._base
+    recording = torch.is_grad_enabled() or _in_recorded_forward[0] > 0
+    if recording and (w.requires_grad or base.requires_grad):
+        return False
+    return isinstance(base, torch.nn.Parameter) or is_derived(base)
+
+
+def _set_w(d, w, rows, K, ldw, exact=False):
+    """fills the descriptor's w / ldw / dtype: fp32 in "high" precision reads the split planes of w (ldw in bf16 elements)"""
+    d.dtype = _f32_dtype(w.dtype, exact)
+    if d.dtype == L.F32_BF16X3:
+        d.w, d.ldw = f32_split_weight(w, rows, K, ldw).data_ptr(), K
+    else:
+        d.w, d.ldw = w.data_ptr(), ldw
+
+
 def gemm(a, w, *, M, N, K, lda, out, ldo, bias=None, residual=None, ldr=0, act=None, rowgroup_bias=None, ld_rg=0,
          rows_per_group=0, step_ptr=None, a_mode=L.A_PLAIN, out_mode=L.OUT_ROWMAJOR, conv=None, vt=None, ldw=None,
          residual_row_mod=0, asym_pad=False, rowstat_out=None, ln_fold=None, a2=None, lda2=0, k_split=0, a_row_mod=0, a2_row_mod=0,
-         w_halo=None, workspace=None):
+         w_halo=None, workspace=None, exact=False):
     """Raw descriptor call; the typed helpers below are what the model code uses.  rowstat_out: fp32 [M, N/64, 2] side output
-    (row statistics of the stored rows); ln_fold = (rowstat_in [M, T, 2], colsum, bias_fp32, eps): LayerNorm by algebra."""
+    (row statistics of the stored rows); ln_fold = (rowstat_in [M, T, 2], colsum, bias_fp32, eps): LayerNorm by algebra.
+    exact: an fp32 product stays on the exact-f32 kernel whatever the precision setting."""
     d = L.GemmDesc()
     if rowstat_out is not None:
         d.rowstat_out = rowstat_out.data_ptr()
     if ln_fold is not None:
         rs, cs, bb, eps = ln_fold
         d.rowstat_in, d.ln_colsum, d.ln_bias, d.rowstat_in_tiles, d.ln_eps = rs.data_ptr(), cs.data_ptr(), bb.data_ptr(), rs.shape[-2], float(eps)
-    d.a, d.w, d.out = a.data_ptr(), w.data_ptr(), out.data_ptr()
+    d.a, d.out = a.data_ptr(), out.data_ptr()
     d.bias, d.residual, d.rowgroup_bias, d.step_ptr = _ptr(bias), _ptr(residual), _ptr(rowgroup_bias), _ptr(step_ptr)
-    d.M, d.N, d.K, d.lda, d.ldw, d.ldo, d.ldr, d.ld_rg = M, N, K, lda, (K if ldw is None else ldw), ldo, ldr, ld_rg
+    d.M, d.N, d.K, d.lda, d.ldo, d.ldr, d.ld_rg = M, N, K, lda, ldo, ldr, ld_rg
+    _set_w(d, w, 2 * N if act in ("geglu", "geglu_tanh") else N, K, K if ldw is None else ldw, exact)
     d.rows_per_group = rows_per_group
     d.residual_row_mod = residual_row_mod
-    d.a_mode, d.epilogue, d.out_mode, d.dtype = a_mode, _EPI[act], out_mode, _DT[w.dtype]
+    d.a_mode, d.epilogue, d.out_mode = a_mode, _EPI[act], out_mode
     if conv is not None:
         (d.Hin, d.Win, d.Cin, d.Hout, d.Wout, d.stride, d.Hup, d.Wup, d.src_batch_mod) = conv
     if vt is not None:
@@ -735,11 +825,12 @@ def linear_qkv(x, w_qkv, B, Lk, heads, q, k, vt, bias=None, ln=None, v=None):
     Cc = C3 // 3
     x2 = x.reshape(B * Lk, K)
     d = L.GemmDesc()
-    d.a, d.w, d.out, d.out2, d.out3 = x2.data_ptr(), w_qkv.data_ptr(), q.data_ptr(), k.data_ptr(), vt.data_ptr()
+    d.a, d.out, d.out2, d.out3 = x2.data_ptr(), q.data_ptr(), k.data_ptr(), vt.data_ptr()
     d.out4 = _ptr(v)  # v row-major [B*Lk, C] as well (the training step's backward reads it)
     d.bias = _ptr(bias)
-    d.M, d.N, d.K, d.lda, d.ldw, d.ldo = B * Lk, C3, K, x2.stride(0), w_qkv.stride(0), Cc
-    d.a_mode, d.epilogue, d.out_mode, d.dtype = L.A_PLAIN, L.EPI_NONE, L.OUT_QKV, _DT[w_qkv.dtype]
+    d.M, d.N, d.K, d.lda, d.ldo = B * Lk, C3, K, x2.stride(0), Cc
+    _set_w(d, w_qkv, C3, K, w_qkv.stride(0))
+    d.a_mode, d.epilogue, d.out_mode = L.A_PLAIN, L.EPI_NONE, L.OUT_QKV
     d.heads, d.head_dim, d.L, d.Lpad = heads, Cc // heads, Lk, vt.shape[-1]
     if fold is not None:
         rs, cs, bb, eps = fold
@@ -823,9 +914,10 @@ def conv1d(x, w_packed, bias, taps, dilation=1, transposed_stride=0, pad=None, p
     if out is None:
         out = torch.empty(B, Tout, Cout, dtype=x.dtype, device=x.device)
     d = L.GemmDesc()
-    d.a, d.w, d.out, d.bias, d.residual = x.data_ptr(), w_packed.data_ptr(), out.data_ptr(), _ptr(bias), _ptr(residual)
-    d.M, d.N, d.K, d.lda, d.ldw, d.ldo, d.ldr = B * Tout, Cout, taps * Cin, 0, w_packed.stride(0), Cout, Cout
-    d.a_mode, d.epilogue, d.out_mode, d.dtype = L.A_CONV1D, _EPI[act], L.OUT_ROWMAJOR, _DT[w_packed.dtype]
+    d.a, d.out, d.bias, d.residual = x.data_ptr(), out.data_ptr(), _ptr(bias), _ptr(residual)
+    d.M, d.N, d.K, d.lda, d.ldo, d.ldr = B * Tout, Cout, taps * Cin, 0, Cout, Cout
+    _set_w(d, w_packed, Cout, taps * Cin, w_packed.stride(0))
+    d.a_mode, d.epilogue, d.out_mode = L.A_CONV1D, _EPI[act], L.OUT_ROWMAJOR
     d.Hin, d.Hout, d.Cin, d.stride = T, Tout, Cin, max(s_, 1)
     d.taps, d.dilation, d.pad, d.transposed = taps, dilation, pad, 1 if s_ else 0
     if pre_slope is not None:
@@ -943,7 +1035,7 @@ def attention(q, k, vt, Lk, heads, key_bias=None, k2=None, vt2=None, L2=0, scale
     d.o_stride_b, d.o_stride_n = out.stride(0), out.stride(1)
     d.B, d.N, d.H, d.D, d.L, d.Lpad = B, N, heads, d_head, Lk, vt.shape[-1]
     d.kv_batch_div, d.kv2_batch_div = kv_batch_div, kv2_batch_div
-    d.dtype = _DT[q.dtype]
+    d.dtype = _f32_dtype(q.dtype)
     d.softmax_scale = 1.0 / math.sqrt(d_head)
     d.scale2 = float(scale2)
     d.q_prescaled = 1 if q_prescaled else 0
@@ -1055,7 +1147,7 @@ def attention_lse(q, k, vt, Lk, heads, key_bias=None):
     d.o_stride_b, d.o_stride_n = out.stride(0), out.stride(1)
     d.B, d.N, d.H, d.D = B, N, heads, Cc // heads
     d.L, d.Lpad, d.L2, d.Lpad2 = Lk, vt.shape[-1], 0, 0
-    d.kv_batch_div, d.kv2_batch_div, d.dtype = 1, 1, _DT[q.dtype]
+    d.kv_batch_div, d.kv2_batch_div, d.dtype = 1, 1, _f32_dtype(q.dtype)
     d.softmax_scale, d.scale2 = 1.0 / math.sqrt(Cc // heads), 0.0
     L.check(L.lib().apad_attention(C.byref(d), _stream()), "apad_attention")
     return out, lse
@@ -1218,10 +1310,10 @@ def weight_grad(dy, x, fp32=False, acc=None):
     if acc is not None:
         if not (fp32 and acc.dtype == torch.float32 and acc.is_contiguous() and tuple(acc.shape) == (N, K)):
             raise ValueError("weight_grad(acc=...): needs fp32=True and a contiguous fp32 [N, K] accumulator")
-        gemm(dyt, xt, M=N, N=K, K=Mpad, lda=Mpad, out=acc, ldo=K, ldw=Mpad, residual=acc, ldr=K)
+        gemm(dyt, xt, M=N, N=K, K=Mpad, lda=Mpad, out=acc, ldo=K, ldw=Mpad, residual=acc, ldr=K, exact=True)
         return None
     out = torch.empty(N, K, dtype=dyt.dtype, device=dy.device)
-    gemm(dyt, xt, M=N, N=K, K=Mpad, lda=Mpad, out=out, ldo=K, ldw=Mpad)
+    gemm(dyt, xt, M=N, N=K, K=Mpad, lda=Mpad, out=out, ldo=K, ldw=Mpad, exact=True)
     return out
 
 

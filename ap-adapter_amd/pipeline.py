@@ -184,7 +184,8 @@ class AudioLDM2Pipeline:
         graphed = use_graph and callback is None
         key = (B, Cc, H, W, tuple(generated_prompt_embeds.shape), tuple(prompt_embeds.shape),
                None if attention_mask is None else (tuple(attention_mask.shape), attention_mask.dtype), num_inference_steps,
-               float(guidance_scale), dtype, bool(keep_noise_pred), str(dev))
+               float(guidance_scale), dtype, bool(keep_noise_pred), str(dev),
+               ops.get_float32_matmul_precision() if dtype == torch.float32 else None)  # (a step captured in one precision never replays in the other)
         e = None
         if graphed:
             wsig = self._weights_signature()

@@ -160,6 +160,12 @@ class _Hoist:
 HOIST_OWNER = [None]  # set by the pipeline around a call (see AudioLDM2Pipeline.denoise)
 
 
+def _precision_of(w):
+    """the fp32 matmul precision hoisted K/V of an fp32 module were projected in (part of their signature: K/V projected in one
+    precision never serve the other); None for the 16-bit modes, which do not read it"""
+    return ops.get_float32_matmul_precision() if w.dtype == torch.float32 else None
+
+
 def _loose_key(attn, t):
     """which (site, condition BUFFER) a hoisted result belongs to; the content is tracked by _Hoist.sig"""
     return (id(attn), t.data_ptr(), tuple(t.shape), tuple(t.stride()), t.dtype)
@@ -331,7 +337,8 @@ class AttnProcessor2_0(nn.Module):
                 # packed with the projection: the weight-stationary kernel's layout, or the row-tile kernels' fragment sets
                 return (k_, vt_, ops.xattn_pack_kv(k_, vt_, ehs.shape[1]) if fused else (ops.rows_pack_kv(k_, vt_).data if rows else None))
 
-            k, vt, pk = self._hoisted(_loose_key(attn, ehs), lambda attn=attn, ehs=ehs: (ehs._version, signature(attn.to_k.weight, attn.to_v.weight)), make)
+            k, vt, pk = self._hoisted(_loose_key(attn, ehs), lambda attn=attn, ehs=ehs: (ehs._version, signature(attn.to_k.weight, attn.to_v.weight),
+                                                                                      _precision_of(attn.to_k.weight)), make)
         if attention_mask is not None:
             # the mask -> fp32 bias conversion is timestep-invariant too: hoisted with the K/V (two tiny torch kernels
             # per masked site per step otherwise)
@@ -476,7 +483,8 @@ class IPAttnProcessor2_0(nn.Module):
             return kv_
 
         sig = lambda attn=attn, ehs=ehs: (ehs._version, self.num_tokens,
-                                          signature(attn.to_k.weight, attn.to_v.weight, self.to_k_ip.weight, self.to_v_ip.weight))
+                                          signature(attn.to_k.weight, attn.to_v.weight, self.to_k_ip.weight, self.to_v_ip.weight),
+                                          _precision_of(attn.to_k.weight))
         k_t, vt_t, Lt, k_a, vt_a, La, pk_t, pk_a = self._hoisted(_loose_key(attn, ehs), sig, make)
         bias = None
         if attention_mask is not None:

@@ -34,10 +34,14 @@
 extern "C" {
 #endif
 
-#define APAD_ABI_VERSION 11
+#define APAD_ABI_VERSION 12
 
 /* element types of activations / weights */
-enum { APAD_BF16 = 0, APAD_F16 = 1, APAD_F32 = 2 };
+/* APAD_F32_BF16X3: fp32 storage, each contraction of apad_gemm / apad_attention as three bf16 MFMAs on split operands
+   (x = hi + lo, hi = bf16(x), lo = bf16(x - hi); lo.hi + hi.lo + hi.hi accumulated in fp32) -- torch's "high" fp32 matmul
+   precision.  apad_gemm then reads w as the [2][rows][ldw] bf16 planes of apad_f32_split_weight (rows = 2N for GEGLU, else N;
+   ldw in bf16 elements).  Every other entry point rejects it. */
+enum { APAD_BF16 = 0, APAD_F16 = 1, APAD_F32 = 2, APAD_F32_BF16X3 = 3 };
 
 /* apad_gemm_desc.a_mode: how row m / column k of the A operand is fetched */
 enum {
@@ -419,6 +423,11 @@ int64_t apad_conv_halo_workspace_bytes(int64_t M, int64_t N, int64_t Cin, int32_
 int apad_probe_mfma(void* sink, int32_t mode, int32_t iters, double* flops, void* stream);
 /* diagnostic: how many apad_gemm calls of this process went to the halo kernel (tests assert the route with it) */
 int64_t apad_hconv_launch_count(void);
+/* w [N][ldw] fp32 -> out [2][N][K] bf16: the hi plane bf16(w), then the lo plane bf16(w - hi) (APAD_F32_BF16X3's weight form;
+   once per parameter version).  K % 4 == 0, ldw % 4 == 0, 16-byte aligned pointers. */
+int apad_f32_split_weight(const void* w, void* out, int64_t N, int64_t K, int64_t ldw, void* stream);
+/* diagnostic: how many apad_gemm / apad_attention launches of this process ran on the APAD_F32_BF16X3 kernels */
+int64_t apad_f32x3_launch_count(void);
 int apad_attention(const apad_attn_desc* d, void* stream);
 /* returns -3 (and sets the error text) when the shape is outside the kernel's envelope; callers then use apad_gemm */
 int apad_rowpanel_gemm(const apad_rp_desc* d, void* stream);
