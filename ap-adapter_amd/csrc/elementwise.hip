@@ -89,6 +89,70 @@ __global__ __launch_bounds__(256) void cfg_ddim_kernel(const uint8_t* eps2, floa
     }
 }
 
+// V consecutive elements <-> registers: V = 8 moves 16 bytes per access (two for fp32), V = 1 is the scalar form
+template <int V> __device__ __forceinline__ void ld_f32v(const float* p, int64_t i, float* v) {
+    if constexpr (V == 8) {
+        const float4 a = *reinterpret_cast<const float4*>(p + i), b = *reinterpret_cast<const float4*>(p + i + 4);
+        v[0] = a.x, v[1] = a.y, v[2] = a.z, v[3] = a.w, v[4] = b.x, v[5] = b.y, v[6] = b.z, v[7] = b.w;
+    } else {
+        v[0] = p[i];
+    }
+}
+template <int V> __device__ __forceinline__ void st_f32v(float* p, int64_t i, const float* v) {
+    if constexpr (V == 8) {
+        *reinterpret_cast<float4*>(p + i) = make_float4(v[0], v[1], v[2], v[3]);
+        *reinterpret_cast<float4*>(p + i + 4) = make_float4(v[4], v[5], v[6], v[7]);
+    } else {
+        p[i] = v[0];
+    }
+}
+template <int DT, int V> __device__ __forceinline__ void ld_elemv(const uint8_t* p, int64_t i, float* v) {
+    if constexpr (DT == APAD_F32) ld_f32v<V>(reinterpret_cast<const float*>(p), i, v);
+    else if constexpr (V == 8) unpack8<DT>(*reinterpret_cast<const uint4*>(p + i * 2), v);
+    else v[0] = ld_elem<DT>(p, i);
+}
+template <int DT, int V> __device__ __forceinline__ void st_elemv(uint8_t* p, int64_t i, const float* v) {
+    if constexpr (DT == APAD_F32) st_f32v<V>(reinterpret_cast<float*>(p), i, v);
+    else if constexpr (V == 8) *reinterpret_cast<uint4*>(p + i * 2) = pack8<DT>(v);
+    else st_elem<DT>(p, i, v[0]);
+}
+
+// The guided noise as in cfg_ddim_kernel, then a sampler whose update is linear in (x, eps, m1, z): row r = coef + 6 * step
+// (scheduler.py SAMPLER_COLS),  x' = r0 x + r1 eps + r2 m1 + r3 z[step],  m0 = r4 x + r5 eps -> hist (the next step's m1).
+// DPM-Solver++ 2M: r3 = 0;  DDIM eta > 0: r2 = 0, no hist.  m1 / z are not read on a step whose coefficient is 0 (wave-uniform).
+template <int DT, int V>
+__global__ __launch_bounds__(256) void cfg_sampler_kernel(const uint8_t* eps2, float* latents, uint8_t* unet_in, float* eps_out, float* hist,
+                                                          const float* noise, const float* coef, const int32_t* step_ptr, int n_steps, float gs,
+                                                          int64_t total) {
+    int step = step_ptr ? *step_ptr : 0;
+    step = step < 0 ? 0 : (step >= n_steps ? n_steps - 1 : step);  // the table and the noise buffer have n_steps rows
+    const float* r = coef + 6 * step;
+    const float c_x = r[0], c_e = r[1], c_m = r[2], c_z = r[3], d_x = r[4], d_e = r[5];
+    const bool use_m1 = hist && c_m != 0.f, use_z = noise && c_z != 0.f;
+    const float* z = noise + (use_z ? (int64_t)step * total : 0);
+    for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * V; i < total; i += (int64_t)gridDim.x * 256 * V) {
+        float eu[V], ec[V], x[V], m1[V], zz[V], e[V], m0[V];
+        ld_elemv<DT, V>(eps2, i, eu);
+        ld_elemv<DT, V>(eps2, total + i, ec);
+        ld_f32v<V>(latents, i, x);
+#pragma unroll
+        for (int j = 0; j < V; ++j) m1[j] = zz[j] = 0.f;
+        if (use_m1) ld_f32v<V>(hist, i, m1);
+        if (use_z) ld_f32v<V>(z, i, zz);
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            // the reference forms the guided noise in the model dtype: one fp32 fma (what cfg_ddim_kernel's expression compiles to), one rounding
+            e[j] = (float)(typename ET<DT>::elem)fmaf(gs, ec[j] - eu[j], eu[j]);
+            m0[j] = d_x * x[j] + d_e * e[j];
+            x[j] = c_x * x[j] + c_e * e[j] + c_m * m1[j] + c_z * zz[j];
+        }
+        st_f32v<V>(latents, i, x);
+        st_elemv<DT, V>(unet_in, i, x);
+        if (hist) st_f32v<V>(hist, i, m0);
+        if (eps_out) st_f32v<V>(eps_out, i, e);
+    }
+}
+
 __global__ void step_advance_kernel(int32_t* p) { *p = *p + 1; }
 
 template <int DT> __global__ __launch_bounds__(256) void mix3_kernel(const uint8_t* a, const uint8_t* b, const uint8_t* c, uint8_t* out, int64_t n,
@@ -232,6 +296,41 @@ extern "C" int apad_cfg_ddim_step(const void* eps2, float* latents, void* unet_i
         hipLaunchKernelGGL((cfg_ddim_kernel<APAD_F16>), dim3((unsigned)blocks), dim3(256), 0, s, (const uint8_t*)eps2, latents,
                            (uint8_t*)unet_in, eps_out, coef, step_ptr, guidance_scale, total);
     return apad_check_launch("apad_cfg_ddim_step");
+}
+
+namespace {
+template <int DT>
+void launch_cfg_sampler(bool vec, unsigned blocks, hipStream_t s, const void* eps2, float* latents, void* unet_in, float* eps_out, float* history,
+                        const float* noise, const float* coef, const int32_t* step_ptr, int32_t n_steps, float gs, int64_t total) {
+    if (vec)
+        hipLaunchKernelGGL((cfg_sampler_kernel<DT, 8>), dim3(blocks), dim3(256), 0, s, (const uint8_t*)eps2, latents, (uint8_t*)unet_in, eps_out,
+                           history, noise, coef, step_ptr, n_steps, gs, total);
+    else
+        hipLaunchKernelGGL((cfg_sampler_kernel<DT, 1>), dim3(blocks), dim3(256), 0, s, (const uint8_t*)eps2, latents, (uint8_t*)unet_in, eps_out,
+                           history, noise, coef, step_ptr, n_steps, gs, total);
+}
+}  // namespace
+
+extern "C" int apad_cfg_sampler_step(const void* eps2, float* latents, void* unet_in, float* eps_out, float* history, const float* noise,
+                                     const float* coef, const int32_t* step_ptr, int32_t n_steps, float guidance_scale, int32_t B, int64_t n,
+                                     int32_t dtype, void* stream) {
+    APAD_CHECK(eps2 && latents && unet_in && coef, "apad_cfg_sampler_step: null operand");
+    APAD_CHECK(dtype == APAD_BF16 || dtype == APAD_F16 || dtype == APAD_F32, "apad_cfg_sampler_step: dtype %d not supported", dtype);
+    APAD_CHECK(B > 0 && n > 0 && n_steps > 0, "apad_cfg_sampler_step: empty problem");
+    const int64_t total = (int64_t)B * n;
+    // 16-byte accesses need every base 16-byte aligned and 8 | total (then the second CFG half and every noise row are aligned too)
+    const uintptr_t bases = (uintptr_t)eps2 | (uintptr_t)latents | (uintptr_t)unet_in | (uintptr_t)eps_out | (uintptr_t)history | (uintptr_t)noise;
+    const bool vec = total % 8 == 0 && bases % 16 == 0;
+    int64_t blocks = ((vec ? total / 8 : total) + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == APAD_F32)
+        launch_cfg_sampler<APAD_F32>(vec, (unsigned)blocks, s, eps2, latents, unet_in, eps_out, history, noise, coef, step_ptr, n_steps, guidance_scale, total);
+    else if (dtype == APAD_BF16)
+        launch_cfg_sampler<APAD_BF16>(vec, (unsigned)blocks, s, eps2, latents, unet_in, eps_out, history, noise, coef, step_ptr, n_steps, guidance_scale, total);
+    else
+        launch_cfg_sampler<APAD_F16>(vec, (unsigned)blocks, s, eps2, latents, unet_in, eps_out, history, noise, coef, step_ptr, n_steps, guidance_scale, total);
+    return apad_check_launch("apad_cfg_sampler_step");
 }
 
 extern "C" int apad_mix3(const void* a, const void* b, const void* c, void* out, int64_t n, float scale, int32_t dtype, void* stream) {

@@ -1127,6 +1127,26 @@ def cfg_ddim_step(eps2, latents, unet_in, coef, step_ptr, guidance_scale, eps_ou
                                        _stream()), "apad_cfg_ddim_step")
 
 
+def cfg_sampler_step(eps2, latents, unet_in, coef, step_ptr, guidance_scale, eps_out=None, history=None, noise=None):
+    """cfg_ddim_step for a sampler with a six-column table (scheduler.SAMPLER_COLS): coef fp32 [steps, 6]; history fp32 like latents
+    (read as m1, overwritten with this step's data prediction); noise fp32 [steps, B, n...] (row *step_ptr is added, scaled)."""
+    _req(latents, "cfg_sampler_step.latents", torch.float32)
+    _req(coef, "cfg_sampler_step.coef", torch.float32)
+    if coef.dim() != 2 or coef.shape[1] != 6 or not coef.is_contiguous():
+        raise RuntimeError(f"cfg_sampler_step.coef: expected a contiguous [steps, 6] table, got {tuple(coef.shape)}")
+    steps = coef.shape[0]
+    B = latents.shape[0]
+    n = latents.numel() // B
+    if eps2.dtype != unet_in.dtype or eps2.numel() != 2 * latents.numel() or unet_in.numel() != latents.numel():
+        raise RuntimeError("cfg_sampler_step: eps2 [2B, n] and unet_in [B, n] must share the model dtype and match latents [B, n]")
+    for t, name, numel in ((eps_out, "eps_out", latents.numel()), (history, "history", latents.numel()), (noise, "noise", steps * latents.numel())):
+        if t is not None and (_req(t, "cfg_sampler_step." + name, torch.float32).numel() != numel or not t.is_contiguous()):
+            raise RuntimeError(f"cfg_sampler_step.{name}: expected {numel} contiguous fp32 values, got {tuple(t.shape)}")
+    L.check(L.lib().apad_cfg_sampler_step(eps2.data_ptr(), latents.data_ptr(), unet_in.data_ptr(), _ptr(eps_out), _ptr(history), _ptr(noise),
+                                          coef.data_ptr(), _ptr(step_ptr), steps, float(guidance_scale), B, n, _DT[eps2.dtype], _stream()),
+            "apad_cfg_sampler_step")
+
+
 def step_advance(step_ptr):
     L.check(L.lib().apad_step_advance(step_ptr.data_ptr(), _stream()), "apad_step_advance")
 

@@ -8,17 +8,18 @@ precomputed-embedding arguments the reference already accepts.
 MI355X-first structure of the loop:
   * K/V of all 64 cross-attention sites are projected once per call (timestep-invariant), not once per step
   * the time-embedding MLP and every resnet's time_emb_proj are tabulated for all steps before the loop
-  * DDIM coefficients live in a device table; CFG combine + DDIM update are one kernel; the step index is a device
-    counter -> zero host synchronisation inside the loop
+  * the scheduler's coefficients live in a device table; CFG combine + scheduler update are one kernel (deterministic DDIM, DDIM with
+    eta > 0 from pre-drawn noise, DPM-Solver++ 2M with its history buffer); the step index is a device counter -> zero host
+    synchronisation inside the loop
   * the whole step (UNet on the duplicated batch, CFG, DDIM, counter) is captured once as a hipGraph and replayed
 """
 from dataclasses import dataclass
-from typing import Optional
+from typing import Optional, Union
 
 import torch
 
 from . import ops
-from .scheduler import DDIMScheduler
+from .scheduler import DDIMScheduler, DPMSolverMultistepScheduler
 
 
 @dataclass
@@ -31,7 +32,7 @@ class AudioLDM2Pipeline:
     vocoder_model_in_dim = 64      # mel bins
     vocoder_upsample_factor = 0.01  # prod(upsample_rates) / sampling_rate = 160 / 16000
 
-    def __init__(self, unet, scheduler: Optional[DDIMScheduler] = None, audiomae=None, vocoder=None, vae=None, prompt_encoder=None,
+    def __init__(self, unet, scheduler: Optional[Union[DDIMScheduler, DPMSolverMultistepScheduler]] = None, audiomae=None, vocoder=None, vae=None, prompt_encoder=None,
                  tokenizer=None, tokenizer_2=None):
         self.unet = unet
         self.vocoder = vocoder  # vocoder.SpeechT5HifiGan (HIP) -- mel -> waveform
@@ -124,6 +125,22 @@ class AudioLDM2Pipeline:
             latents = latents.to(device)
         return latents * self.scheduler.init_noise_sigma
 
+    def prepare_step_noise(self, batch_size, num_channels_latents, latent_height, latent_width, num_inference_steps, generator, device=None,
+                           out=None):
+        """The noise a stochastic sampler consumes, drawn BEFORE the loop so that the captured step has no host involvement: one
+        ``randn`` of the latent shape [B, C, H, W] per step, in the order the reference draws them (``randn_tensor(model_output.shape,
+        generator=generator)`` inside ``DDIMScheduler.step``, after the initial latents), on the generator's own device like
+        ``prepare_latents``.  Returned in the loop's layout, fp32 [steps, B, H * W, C]; ``out`` is refilled in place."""
+        shape = (batch_size, num_channels_latents, latent_height, latent_width)
+        gdev = generator.device if generator is not None else torch.device("cpu")
+        if out is None:
+            out = torch.empty(num_inference_steps, batch_size, latent_height * latent_width, num_channels_latents, dtype=torch.float32,
+                              device=device if device is not None else gdev)
+        for i in range(num_inference_steps):
+            z = torch.randn(shape, generator=generator, device=gdev, dtype=torch.float32)
+            out[i].copy_(z.permute(0, 2, 3, 1).reshape(batch_size, latent_height * latent_width, num_channels_latents))
+        return out
+
     def encode_audio(self, mel, time_pooling, freq_pooling):
         """AudioMAE over the prompt mel and over zeros_like(mel) (:928-929); the zero-mel result depends only on the
         weights and the pooling setting and is cached."""
@@ -169,10 +186,13 @@ class AudioLDM2Pipeline:
 
     @torch.no_grad()
     def denoise(self, latents_nchw, generated_prompt_embeds, prompt_embeds, attention_mask, num_inference_steps,
-                guidance_scale, use_graph=True, callback=None, callback_steps=1, keep_noise_pred=False):
-        """CFG + DDIM loop (:983-1031).  With ``use_graph`` the step is captured ONCE per (batch, token counts, steps, guidance,
-        weights) and kept: later calls copy their latents / conditions into the graph's static buffers, refresh the hoisted
-        K/V in place and replay -- no warm-up step, no re-capture (a sharded job runs many batches through one pipeline)."""
+                guidance_scale, use_graph=True, callback=None, callback_steps=1, keep_noise_pred=False, eta=0.0, generator=None):
+        """CFG + scheduler loop (:983-1031).  With ``use_graph`` the step is captured ONCE per (batch, token counts, steps, guidance,
+        weights, sampler) and kept: later calls copy their latents / conditions into the graph's static buffers, refresh the hoisted
+        K/V in place and replay -- no warm-up step, no re-capture (a sharded job runs many batches through one pipeline).
+        ``self.scheduler.sampler_plan(eta)`` names the update kernel, its coefficient table and the per-sampler state that lives with the
+        captured step: the data-prediction history of the multistep solver (zeroed before every run) and the per-step noise of DDIM
+        with ``eta`` > 0 (drawn from ``generator`` before the loop, ``prepare_step_noise``)."""
         unet = self.unet
         dev = latents_nchw.device
         dtype = unet.conv_in.weight.dtype
@@ -181,11 +201,13 @@ class AudioLDM2Pipeline:
             raise NotImplementedError("the audio-conditioned path requires classifier-free guidance (:941 chunk(2))")
         sched = self.scheduler
         sched.set_timesteps(num_inference_steps)
+        plan = sched.sampler_plan(eta)
         graphed = use_graph and callback is None
         key = (B, Cc, H, W, tuple(generated_prompt_embeds.shape), tuple(prompt_embeds.shape),
                None if attention_mask is None else (tuple(attention_mask.shape), attention_mask.dtype), num_inference_steps,
                float(guidance_scale), dtype, bool(keep_noise_pred), str(dev),
-               ops.get_float32_matmul_precision() if dtype == torch.float32 else None)  # (a step captured in one precision never replays in the other)
+               ops.get_float32_matmul_precision() if dtype == torch.float32 else None,  # (a step captured in one precision never replays in the other)
+               plan.key)  # (... nor one captured for another sampler / eta: the table and the update kernel are baked in)
         e = None
         if graphed:
             wsig = self._weights_signature()
@@ -202,6 +224,10 @@ class AudioLDM2Pipeline:
             if attention_mask is not None:
                 e["mask"].copy_(attention_mask)
             e["step_ptr"].zero_()
+            if e["hist"] is not None:
+                e["hist"].zero_()
+            if e["noise"] is not None:
+                self.prepare_step_noise(B, Cc, H, W, num_inference_steps, generator, out=e["noise"])
             unet.set_kv_cache(True, clear=False)
             try:
                 unet.refresh_kv_cache()  # hoisted K/V of the new conditions, recomputed into the buffers the graph reads
@@ -214,10 +240,13 @@ class AudioLDM2Pipeline:
             e = {"lat": latents_nchw.float().permute(0, 2, 3, 1).reshape(B, H * W, Cc).contiguous(),  # fp32 master, NHWC
                  "gen": generated_prompt_embeds.to(dtype).contiguous().clone(), "pe": prompt_embeds.to(dtype).contiguous().clone(),
                  "mask": None if attention_mask is None else attention_mask.clone(),
-                 "coef": sched.coef_table().to(dev), "step_ptr": torch.zeros(1, dtype=torch.int32, device=dev)}
+                 "coef": plan.table.to(dev), "step_ptr": torch.zeros(1, dtype=torch.int32, device=dev)}
             e["unet_in"] = e["lat"].to(dtype).clone() if dtype == torch.float32 else e["lat"].to(dtype)
             e["eps_out"] = torch.empty_like(e["lat"]) if keep_noise_pred else None
+            e["hist"] = torch.zeros_like(e["lat"]) if plan.needs_history else None
+            e["noise"] = self.prepare_step_noise(B, Cc, H, W, num_inference_steps, generator, device=dev) if plan.needs_noise else None
             lat, unet_in, gen, pe, mask, coef, step_ptr, eps_out = (e[k] for k in ("lat", "unet_in", "gen", "pe", "mask", "coef", "step_ptr", "eps_out"))
+            hist, noise = e["hist"], e["noise"]
             from . import processors as P_
             owner = key if graphed else ("eager", id(e))
             P_.HOIST_OWNER[0] = owner  # hoisted K/V created below belong to this call (graph: until the graph is evicted)
@@ -230,8 +259,18 @@ class AudioLDM2Pipeline:
 
             def step():
                 eps2 = unet.forward_nhwc(unet_in, H, W, None, gen, pe, None, mask, batch_repeat=2)
-                ops.cfg_ddim_step(eps2, lat, unet_in, coef, step_ptr, guidance_scale, eps_out)
+                if plan.legacy:
+                    ops.cfg_ddim_step(eps2, lat, unet_in, coef, step_ptr, guidance_scale, eps_out)
+                else:
+                    ops.cfg_sampler_step(eps2, lat, unet_in, coef, step_ptr, guidance_scale, eps_out, hist, noise)
                 ops.step_advance(step_ptr)
+
+            def reset():  # back to step 0 of this call (after the warm-up step and after the capture)
+                lat.copy_(lat0)
+                unet_in.copy_(lat0)
+                step_ptr.zero_()
+                if hist is not None:
+                    hist.zero_()
 
             try:
                 if graphed:
@@ -244,15 +283,11 @@ class AudioLDM2Pipeline:
                     with torch.cuda.stream(s):
                         step()
                     torch.cuda.current_stream().wait_stream(s)
-                    lat.copy_(lat0)
-                    unet_in.copy_(lat0)
-                    step_ptr.zero_()
+                    reset()
                     g = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(g, stream=s):
                         step()
-                    lat.copy_(lat0)
-                    unet_in.copy_(lat0)
-                    step_ptr.zero_()
+                    reset()
                     e["graph"], e["wsig"] = g, wsig
                     while len(self._graphs) >= self.MAX_CACHED_GRAPHS:
                         self._evict(next(iter(self._graphs)))
@@ -292,8 +327,6 @@ class AudioLDM2Pipeline:
         if output_type != "latent" and (self.vae is None or self.vocoder is None):
             raise NotImplementedError("waveform output needs latents -> mel (vae=ap_adapter_amd.AutoencoderKL) and mel -> waveform "
                                       "(vocoder=ap_adapter_amd.SpeechT5HifiGan); or use output_type='latent'")
-        if eta != 0.0:
-            raise NotImplementedError("eta != 0 is not used by the reference drivers")
         if num_waveforms_per_prompt > 1 and prompt is not None and output_type != "latent":
             # pipeline_audioldm2.py:1048-1056 re-orders the candidates by CLAP text-audio similarity (score_waveforms); the CLAP audio
             # tower is outside this path, and returning them un-ranked would silently differ from the reference
@@ -330,8 +363,9 @@ class AudioLDM2Pipeline:
             ge = self.assemble_condition(ge, tokens, uncond, dtype)
         lat = self.prepare_latents(batch_size * num_waveforms_per_prompt, self.unet.config.in_channels, height, dtype,
                                    dev, generator, latents)
+        # prepare_extra_step_kwargs (:617-632): eta reaches a scheduler whose step takes it (DDIM) and is ignored by the others
         out = self.denoise(lat, ge, pe, am, num_inference_steps, guidance_scale, use_graph=use_graph, callback=callback,
-                           callback_steps=callback_steps)
+                           callback_steps=callback_steps, eta=eta, generator=generator)
         if output_type != "latent":  # :1036-1044
             scaling = getattr(getattr(self.vae, "config", None), "scaling_factor", 1.0)
             mel = self.vae.decode(out / scaling)

@@ -1,10 +1,51 @@
-"""DDIM scheduler state for the denoise loop (diffusers==0.21.2 DDIMScheduler semantics with the AudioLDM2
-scheduler_config: scaled_linear betas 0.0015..0.0195, 1000 train steps, leading spacing, steps_offset 1,
-set_alpha_to_one False, epsilon prediction, eta 0; call sites /root/reference/pipeline/pipeline_audioldm2.py:983-984,
-:1007, :1025).  The per-step update itself runs in apad_cfg_ddim_step from a device-resident coefficient table, which
-removes the reference's per-step host<->device sync inside ``scheduler.step``."""
+"""Scheduler state for the denoise loop.
+
+``DDIMScheduler``: diffusers==0.21.2 DDIMScheduler semantics with the AudioLDM2 scheduler_config: scaled_linear betas
+0.0015..0.0195, 1000 train steps, leading spacing, steps_offset 1, set_alpha_to_one False, epsilon prediction; call sites
+/root/reference/pipeline/pipeline_audioldm2.py:983-984, :1007, :1025.  ``eta`` is a per-call value as in the reference
+(``prepare_extra_step_kwargs``, :617-632).
+
+``DPMSolverMultistepScheduler``: DPM-Solver++ (2M), data-prediction form, midpoint (Lu et al. 2022), in diffusers'
+conventions.  The reference pipeline accepts any ``KarrasDiffusionSchedulers`` member (:158); this is the second one here.
+
+The per-step update itself runs on the device from a coefficient table (``apad_cfg_ddim_step`` for deterministic DDIM,
+``apad_cfg_sampler_step`` for everything else), which removes the reference's per-step host<->device sync inside
+``scheduler.step``.  Every update here is LINEAR in (x, eps, previous data prediction m1, fresh noise z), so one row of six
+coefficients per step describes it (``SAMPLER_COLS``); ``sampler_plan`` tells the loop which kernel, table and per-sampler buffers
+a call needs.
+
+PARITY UNPINNED: the ``eta`` arithmetic and the multistep solver are restated from the published formulas (diffusers is not
+vendored and not installable offline); ``tests/sampler_oracle.py`` restates them a second time, independently, in float64."""
+import math
+from dataclasses import dataclass
+
 import numpy as np
 import torch
+
+# one table row: x' = c_x x + c_eps eps + c_m1 m1 + c_z z ;  m0 = d_x x + d_eps eps (the data prediction kept for the next step)
+SAMPLER_COLS = ("c_x", "c_eps", "c_m1", "c_z", "d_x", "d_eps")
+
+
+@dataclass
+class SamplerPlan:
+    """what one denoise call asks of the loop: ``table`` fp32 [steps, 2] for apad_cfg_ddim_step when ``legacy`` (the deterministic
+    DDIM path every earlier caller takes), else fp32 [steps, 6] for apad_cfg_sampler_step; whether a data-prediction history buffer
+    and a per-step noise buffer are needed; ``key`` is the scheduler's share of the captured graph's cache key"""
+    table: torch.Tensor
+    legacy: bool
+    needs_history: bool
+    needs_noise: bool
+    key: tuple
+
+
+def _scaled_linear_acp(num_train_timesteps, beta_start, beta_end):
+    betas = torch.linspace(beta_start ** 0.5, beta_end ** 0.5, num_train_timesteps, dtype=torch.float32) ** 2
+    return torch.cumprod(1.0 - betas, dim=0)
+
+
+def _leading_timesteps(num_train_timesteps, num_inference_steps, steps_offset):
+    ratio = num_train_timesteps // num_inference_steps
+    return (np.arange(0, num_inference_steps) * ratio).round()[::-1].copy().astype(np.int64) + steps_offset
 
 
 class DDIMScheduler:
@@ -15,16 +56,15 @@ class DDIMScheduler:
                  set_alpha_to_one=False):
         self.num_train_timesteps = num_train_timesteps
         self.steps_offset = steps_offset
-        betas = torch.linspace(beta_start ** 0.5, beta_end ** 0.5, num_train_timesteps, dtype=torch.float32) ** 2
-        self.alphas_cumprod = torch.cumprod(1.0 - betas, dim=0)
+        self._betas = (beta_start, beta_end, bool(set_alpha_to_one))
+        self.alphas_cumprod = _scaled_linear_acp(num_train_timesteps, beta_start, beta_end)
         self.final_alpha_cumprod = torch.tensor(1.0) if set_alpha_to_one else self.alphas_cumprod[0]
         self.timesteps = None
         self.num_inference_steps = None
 
     def set_timesteps(self, num_inference_steps, device=None):
         self.num_inference_steps = num_inference_steps
-        ratio = self.num_train_timesteps // num_inference_steps
-        ts = (np.arange(0, num_inference_steps) * ratio).round()[::-1].copy().astype(np.int64) + self.steps_offset
+        ts = _leading_timesteps(self.num_train_timesteps, num_inference_steps, self.steps_offset)
         self.timesteps = torch.from_numpy(ts).to(device) if device is not None else torch.from_numpy(ts)
 
     def scale_model_input(self, sample, timestep=None):
@@ -44,3 +84,108 @@ class DDIMScheduler:
             c_e = (1 - a_p).sqrt() - (a_p / a_t).sqrt() * (1 - a_t).sqrt()
             rows.append([float(c_x), float(c_e)])
         return torch.tensor(rows, dtype=torch.float32)
+
+    def sampler_rows(self, eta=0.0, timesteps=None):
+        """[steps, 6] float64 rows (``SAMPLER_COLS``) of diffusers' ``DDIMScheduler.step`` with ``eta``:
+        var = (1 - a_p) / (1 - a_t) * (1 - a_t / a_p), std = eta sqrt(var),
+        x_prev = sqrt(a_p) x0 + sqrt(1 - a_p - std^2) eps + std z, x0 = (x - sqrt(1 - a_t) eps) / sqrt(a_t).
+        The previous timestep is t - num_train_timesteps // steps (``final_alpha_cumprod`` below 0).  At eta = 0 the first two
+        columns are the float64 values ``coef_table`` rounds.  ``timesteps`` (a list) replaces the scheduler's own grid."""
+        acp = self.alphas_cumprod.double()
+        ts = self.timesteps.tolist() if timesteps is None else [int(t) for t in timesteps]
+        ratio = self.num_train_timesteps // len(ts)
+        rows = []
+        for t in ts:
+            a_t = acp[t]
+            p = t - ratio
+            a_p = acp[p] if p >= 0 else self.final_alpha_cumprod.double()
+            std = eta * ((1 - a_p) / (1 - a_t) * (1 - a_t / a_p)).sqrt()
+            c_x = (a_p / a_t).sqrt()
+            c_e = (1 - a_p - std ** 2).sqrt() - (a_p / a_t).sqrt() * (1 - a_t).sqrt()
+            rows.append([float(c_x), float(c_e), 0.0, float(std), 0.0, 0.0])
+        return torch.tensor(rows, dtype=torch.float64)
+
+    def sampler_plan(self, eta=0.0):
+        """eta = 0 keeps the two-column table and apad_cfg_ddim_step; eta > 0 needs one fresh noise tensor per step"""
+        eta = float(eta)
+        key = ("DDIMScheduler", self.order, "leading", self.num_train_timesteps, self.steps_offset, self._betas, eta)
+        if eta == 0.0:
+            return SamplerPlan(self.coef_table(), True, False, False, key)
+        return SamplerPlan(self.sampler_rows(eta).float(), False, False, True, key)
+
+
+class DPMSolverMultistepScheduler:
+    """DPM-Solver++ multistep (2M), epsilon prediction, data-prediction form, midpoint -- diffusers' class name, constructor keywords
+    and attributes as far as they apply.  alpha_t = sqrt(acp_t), sigma_t = sqrt(1 - acp_t), lambda_t = log alpha_t - log sigma_t, all
+    indexed by integer timestep; a step goes from ``timesteps[i]`` to ``timesteps[i + 1]`` and the last one to timestep 0 (the alpha of
+    DDIMScheduler's ``final_alpha_cumprod``).
+
+    Timestep grid -- a deliberate, UNPINNED choice: ``timesteps`` is DDIMScheduler's grid at the same step count (leading spacing,
+    ratio ``num_train_timesteps // N``, ``steps_offset`` 1).  From memory diffusers 0.21.2 divides by ``N + 1`` for this class, which
+    cannot be checked offline and would start a 200-step run at t = 801 instead of 996; sharing DDIM's grid makes both samplers visit the
+    same timesteps and keeps the UNet's time tables identical.
+
+    Not implemented (raise, name the argument): other ``algorithm_type`` / ``solver_type`` / ``timestep_spacing`` / ``prediction_type``,
+    ``solver_order`` > 2, ``use_karras_sigmas``, ``thresholding``."""
+    init_noise_sigma = 1.0
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.0015, beta_end=0.0195, solver_order=2, prediction_type="epsilon",
+                 thresholding=False, algorithm_type="dpmsolver++", solver_type="midpoint", lower_order_final=True,
+                 use_karras_sigmas=False, timestep_spacing="leading", steps_offset=1):
+        for name, value, ok in (("algorithm_type", algorithm_type, ("dpmsolver++",)), ("solver_type", solver_type, ("midpoint",)),
+                                ("timestep_spacing", timestep_spacing, ("leading",)), ("solver_order", solver_order, (1, 2)),
+                                ("prediction_type", prediction_type, ("epsilon",)), ("use_karras_sigmas", use_karras_sigmas, (False,)),
+                                ("thresholding", thresholding, (False,))):
+            if value not in ok:
+                raise NotImplementedError(f"DPMSolverMultistepScheduler: {name}={value!r} is not implemented (supported: "
+                                          f"{', '.join(repr(o) for o in ok)})")
+        self.num_train_timesteps = num_train_timesteps
+        self.steps_offset = steps_offset
+        self.solver_order = int(solver_order)
+        self.order = 1  # diffusers: ``order`` counts model evaluations per step, 1 for a multistep solver
+        self.algorithm_type, self.solver_type, self.timestep_spacing = algorithm_type, solver_type, timestep_spacing
+        self.lower_order_final = bool(lower_order_final)
+        self.prediction_type = prediction_type
+        self._betas = (beta_start, beta_end)
+        self.alphas_cumprod = _scaled_linear_acp(num_train_timesteps, beta_start, beta_end)
+        self.timesteps = None
+        self.num_inference_steps = None
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        self.num_inference_steps = num_inference_steps
+        ts = _leading_timesteps(self.num_train_timesteps, num_inference_steps, self.steps_offset)
+        self.timesteps = torch.from_numpy(ts).to(device) if device is not None else torch.from_numpy(ts)
+
+    def scale_model_input(self, sample, timestep=None):
+        return sample
+
+    def sampler_rows(self, timesteps=None):
+        """[steps, 6] float64 rows (``SAMPLER_COLS``).  With m0 = (x - sigma_t eps) / alpha_t = d_x x + d_eps eps, h = lambda_prev -
+        lambda_t, A = sigma_prev / sigma_t and E = -alpha_prev (exp(-h) - 1):
+          first order  (step 0, solver_order 1, the last step under lower_order_final with fewer than 15 steps):  x' = A x + E m0
+          second order:  x' = A x + E (m0 + 0.5 (m0 - m1) / r0),  r0 = (lambda_t - lambda_tprev) / h
+        expanded into c_x = A + E (1 + k) d_x, c_eps = E (1 + k) d_eps, c_m1 = -E k with k = 0.5 / r0 (0 on a first-order step).
+        ``timesteps`` (a list) replaces the scheduler's own grid."""
+        acp = self.alphas_cumprod.double()
+        ts = self.timesteps.tolist() if timesteps is None else [int(t) for t in timesteps]
+        n = len(ts)
+        al = lambda t: math.sqrt(float(acp[t]))
+        sg = lambda t: math.sqrt(1.0 - float(acp[t]))
+        lam = lambda t: math.log(al(t)) - math.log(sg(t))
+        rows = []
+        for i, t in enumerate(ts):
+            prev = ts[i + 1] if i + 1 < n else 0
+            h = lam(prev) - lam(t)
+            A = sg(prev) / sg(t)
+            E = -al(prev) * math.expm1(-h)
+            first = i == 0 or self.solver_order == 1 or (self.lower_order_final and n < 15 and i == n - 1)
+            k = 0.0 if first else 0.5 * h / (lam(t) - lam(ts[i - 1]))
+            d_x, d_e = 1.0 / al(t), -sg(t) / al(t)
+            rows.append([A + E * (1.0 + k) * d_x, E * (1.0 + k) * d_e, -E * k, 0.0, d_x, d_e])
+        return torch.tensor(rows, dtype=torch.float64)
+
+    def sampler_plan(self, eta=0.0):
+        """``eta`` is ignored, as the reference's ``prepare_extra_step_kwargs`` drops it for a scheduler whose ``step`` has none"""
+        key = ("DPMSolverMultistepScheduler", self.solver_order, self.timestep_spacing, self.lower_order_final, self.num_train_timesteps,
+               self.steps_offset, self._betas)
+        return SamplerPlan(self.sampler_rows().float(), False, self.solver_order > 1, False, key)

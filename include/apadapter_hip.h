@@ -24,6 +24,8 @@
  *   apad_timestep_embedding  diffusers Timesteps (pipeline/modeling_audioldm2.py:317, :761)
  *   apad_cfg_ddim_step / apad_step_advance  CFG combine + DDIMScheduler.step
  *                       (pipeline/pipeline_audioldm2.py:1020-1025)
+ *   apad_cfg_sampler_step  CFG combine + the step of any other scheduler the pipeline is built with (:158, :1025):
+ *                       DDIMScheduler.step with eta > 0, DPMSolverMultistepScheduler.step (DPM-Solver++ 2M)
  */
 #ifndef APADAPTER_HIP_H
 #define APADAPTER_HIP_H
@@ -464,6 +466,15 @@ int apad_cfg_ddim_step(const void* eps2, float* latents, void* unet_in, float* e
                        const int32_t* step_ptr, float guidance_scale, int32_t B, int64_t n, int32_t dtype,
                        void* stream);
 int apad_step_advance(int32_t* step_ptr, void* stream);
+/* The general form of apad_cfg_ddim_step for samplers whose update is linear in (x, eps, m1, z): the same CFG combine (guided noise
+   rounded to `dtype`), then with row r = coef + 6 * s, s = *step_ptr clamped to [0, n_steps):
+     x' = r[0] x + r[1] eps + r[2] m1 + r[3] z[s] ,   m0 = r[4] x + r[5] eps
+   latents / unet_in / eps_out as above; history (optional, fp32 [B][n]): read as m1 -- only when r[2] != 0 -- and overwritten with
+   m0, the data prediction the next step reads (DPM-Solver++ 2M); noise (optional, fp32 [n_steps][B][n]): z[s], read only when
+   r[3] != 0 (DDIM eta > 0).  A null history / noise contributes 0.  One launch, no host involvement: hipGraph-capturable. */
+int apad_cfg_sampler_step(const void* eps2, float* latents, void* unet_in, float* eps_out, float* history, const float* noise,
+                          const float* coef, const int32_t* step_ptr, int32_t n_steps, float guidance_scale, int32_t B, int64_t n,
+                          int32_t dtype, void* stream);
 /* out = (a + b + c) * scale, element-wise over n values of `dtype` (HiFi-GAN: mean of the three residual-block branches,
    SpeechT5HifiGan.forward) */
 int apad_mix3(const void* a, const void* b, const void* c, void* out, int64_t n, float scale, int32_t dtype, void* stream);

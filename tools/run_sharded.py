@@ -64,7 +64,10 @@ def build_decoder(dev, dtype, small=False, seed=300):
     return vae.to(dev, dtype).requires_grad_(False), voc.to(dev, dtype).requires_grad_(False)
 
 
-def build_job(dev, dtype, task_cfg, small=False, seed=100, adapter_ckpt=None):
+SAMPLERS = {"ddim": "DDIMScheduler", "dpmsolver++": "DPMSolverMultistepScheduler"}  # --sampler -> scheduler class of ap_adapter_amd
+
+
+def build_job(dev, dtype, task_cfg, small=False, seed=100, adapter_ckpt=None, sampler="ddim"):
     """UNet + adapter + AudioMAE (fp32, the reference's type) on ``dev``; random-init weights of the real shapes unless an adapter
     checkpoint (reference key scheme) is given"""
     import ap_adapter_amd as A
@@ -83,7 +86,7 @@ def build_job(dev, dtype, task_cfg, small=False, seed=100, adapter_ckpt=None):
                 p.to_k_ip.weight = torch.nn.Parameter(sd[n + ".to_k_ip.weight"].to(dev))
                 p.to_v_ip.weight = torch.nn.Parameter(sd[n + ".to_v_ip.weight"].to(dev))
     unet = unet.to(dev, dtype).requires_grad_(False)
-    return A.AudioLDM2Pipeline(unet, audiomae=mae.to(dev, torch.float32))
+    return A.AudioLDM2Pipeline(unet, scheduler=getattr(A, SAMPLERS[sampler])(), audiomae=mae.to(dev, torch.float32))
 
 
 def main():
@@ -93,6 +96,8 @@ def main():
     ap.add_argument("--clips", type=int, default=None, help="number of clips (default: files x prompts)")
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--sampler", choices=sorted(SAMPLERS), default="ddim", help="ddim: the reference's scheduler; dpmsolver++: DPM-Solver++ (2M), "
+                                                                                "meant for 20 - 25 steps")
     ap.add_argument("--small", action="store_true", help="small UNet / 2-block AudioMAE (smoke runs)")
     ap.add_argument("--seconds", type=float, default=10.0)
     ap.add_argument("--adapter-ckpt", default=None)
@@ -118,7 +123,7 @@ def main():
     else:
         files = write_synthetic_wavs(os.path.join(tempfile.gettempdir(), "apad_synth_wavs"), seconds=args.seconds)
     clips = S.list_clips(files, cfg, args.clips)
-    pipe = build_job(dev, dtype, cfg, small=args.small, adapter_ckpt=args.adapter_ckpt)
+    pipe = build_job(dev, dtype, cfg, small=args.small, adapter_ckpt=args.adapter_ckpt, sampler=args.sampler)
     H = int(args.seconds / pipe.vocoder_upsample_factor) // pipe.vae_scale_factor  # latent frames: 10 s -> 250 (pipeline_audioldm2.py:872-880)
 
     def encode_audio(path, tp, fp):
@@ -149,7 +154,7 @@ def main():
     if rank == 0:
         finite = all(bool(torch.isfinite(x).all()) for x in allc)
         print(json.dumps({"task": args.task, "clips": len(clips), "world": world, "batch": args.batch, "steps": args.steps,
-                          "La": A.config.audio_tokens(cfg), "seconds_rank0": round(dt, 2), "clips_per_s": round(len(clips) / dt, 4),
+                          "sampler": args.sampler, "La": A.config.audio_tokens(cfg), "seconds_rank0": round(dt, 2), "clips_per_s": round(len(clips) / dt, 4),
                           "graph_captures": pipe.graph_captures, "graph_hits": pipe.graph_hits, "finite": finite,
                           "wavs_written_rank0": n_wavs}))
         if args.out:
