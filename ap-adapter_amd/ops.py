@@ -170,7 +170,6 @@ def gemm(a, w, *, M, N, K, lda, out, ldo, bias=None, residual=None, ldr=0, act=N
 
 # LayerNorm folded into the Linear behind it where no fused row-panel kernel covers the width (the 640-wide level): the producing
 # GEMM emits row statistics, the consuming GEMM applies (x - mean) * rstd * gamma + beta by algebra
-LN_FOLD = True  # (module attribute only: no environment switch since round 5)
 
 
 def rowstat_of(x):
@@ -214,7 +213,7 @@ def linear(x, w, bias=None, residual=None, act=None, out=None, rowgroup_bias=Non
             raise RuntimeError("linear(ln=...): no row statistics for x (use fused_linear, which falls back to apad_layernorm)")
         w, cs, bb = _ln_folded(w, bias, ln[0], ln[1])
         bias, fold = None, (rs, cs, bb, ln[2])
-    if rowstat and LN_FOLD and N % 64 == 0 and N not in RP_K and act in (None, "none") and w.dtype in FUSED_DTYPES:
+    if rowstat and N % 64 == 0 and N not in RP_K and act in (None, "none") and w.dtype in FUSED_DTYPES:
         rs_out = torch.empty(M, N // 64, 2, dtype=torch.float32, device=x.device)
     gemm(x2, w, M=M, N=N, K=K, lda=x2.stride(0), out=out, ldo=N, bias=bias, residual=r2, ldr=N, act=act,
          rowgroup_bias=rowgroup_bias, ld_rg=(rowgroup_bias.stride(0) if rowgroup_bias is not None else 0),
@@ -248,12 +247,10 @@ def linear2(xa, xb, w, bias=None, out=None):
 
 def ln_foldable(x, w):
     """a LayerNorm in front of this Linear can be folded: 16-bit, statistics available, a width the row-panel kernel does not cover"""
-    return LN_FOLD and x.dtype in FUSED_DTYPES and not rp_ok(x) and rowstat_of(x) is not None and w.shape[1] == x.shape[-1]
+    return x.dtype in FUSED_DTYPES and not rp_ok(x) and rowstat_of(x) is not None and w.shape[1] == x.shape[-1]
 
 
 RP_K = (256, 384)  # reduction dims the row-panel kernel covers
-CGEMM_LINEAR = False  # (measured in round 3: no gain on the HBM-bound to_out / proj launches; module attribute only)
-CGEMM_MIN_M = 16000  # the row threshold of csrc/cgemm.hip
 FUSED_DTYPES = (torch.bfloat16, torch.float16)  # the fused kernels (row-panel, feed-forward, cross-attention) are 16-bit only;
 # the fp32 precision mode (exact-f32 MFMA, csrc/f32_ops.hip) runs the un-fused apad_layernorm / apad_gemm / apad_attention chain
 
@@ -293,11 +290,6 @@ def fused_linear(x, w, bias=None, ln=None, residual=None, act=None, out=None, ro
     apad_layernorm + apad_gemm."""
     K = x.shape[-1]
     N = w.shape[0] // 2 if act == "geglu" else w.shape[0]
-    if (CGEMM_LINEAR and ln is None and act is None and x.dtype in FUSED_DTYPES and N % 128 == 0 and K % 64 == 0
-            and x.numel() // K >= CGEMM_MIN_M):
-        # plain projections of the large levels (to_out + residual, proj_in / proj_out at >= 16000 rows): apad_gemm's big-tile
-        # LDS-DMA kernel (csrc/cgemm.hip) instead of the weight-stationary row-panel kernel
-        return linear(x, w, bias, residual=residual, out=out)
     if rp_ok(x, K) and N % 64 == 0:
         if out is None:
             out = torch.empty(*x.shape[:-1], N, dtype=w.dtype, device=x.device)
@@ -397,9 +389,6 @@ def xrows_pack_weight(w):
     if N % 32 or K % 16:
         raise ValueError(f"xrows_pack_weight: {tuple(w.shape)}")
     return w.detach().reshape(N // 32, 32, K // 16, 2, 8).permute(0, 2, 3, 1, 4).contiguous().reshape(-1)
-
-
-ROWS_KV_PACKED = True  # the processors hand the row-tile cross-attention kernels fragment-packed key / value sets (False: the (k, vt) pair; module attribute only)
 
 
 class RowsKV:
@@ -528,17 +517,13 @@ def self_attention_fused(x, w_packed, csbb, heads, ln_eps, out=None):
 
 # ---- the 64-token level's attention sub-layers (csrc/hsattn.hip): head-sliced LayerNorm + projections + attention, then to_out + residual ----
 HS_C, HS_HEADS, HS_MAXN = 640, 8, 64
-HS_ATTN = True  # False: the LN-folded q|k|v GEMM -> attention -> to_out chain
+HS_ATTN = True  # False: the LN-folded q|k|v GEMM -> attention -> to_out chain (and the level's 1x1 projections and feed-forward on the tiled GEMM)
 
 
 def hs_ok(x, heads, n_q_rows):
     """envelope of apad_hs_attention / apad_hs_out: [B, <= 64, 640], 8 heads, 16-bit, a square to_q"""
     return (HS_ATTN and x.dim() == 3 and x.shape[-1] == HS_C and x.shape[1] <= HS_MAXN and heads == HS_HEADS and n_q_rows == HS_C
             and x.dtype in FUSED_DTYPES and x.is_contiguous())
-
-
-HS_FF2 = True  # its second Linear through apad_hs_ff2 (False: the tiled GEMM); module attribute only
-HS_FF = True  # the feed-forward of that level through apad_hs_geglu (+ apad_hs_ff2); follows HS_ATTN (unet.FeedForward); module attribute only
 
 
 def hs_rows_ok(x):
@@ -637,7 +622,7 @@ def hs_ff2(h, w2_packed, bias, residual, rowstat=False, out=None):
             raise ValueError(f"hs_ff2: residual {tuple(residual.shape)} must be contiguous [B, N, 640]")
     if out is None:
         out = torch.empty(B, N, HS_C, dtype=h.dtype, device=h.device)
-    rs = torch.empty(B * N, 20, 2, dtype=torch.float32, device=h.device) if (rowstat and LN_FOLD) else None
+    rs = torch.empty(B * N, 20, 2, dtype=torch.float32, device=h.device) if rowstat else None
     d = L.HsOutDesc()
     d.o, d.w_packed, d.bias, d.residual, d.out, d.rowstat_out = h.data_ptr(), w2_packed.data_ptr(), _ptr(bias), _ptr(residual), out.data_ptr(), _ptr(rs)
     d.B, d.N, d.C, d.dtype = B, N, HS_C, _DT[h.dtype]
@@ -693,7 +678,7 @@ def hs_out(o, wo_packed, bias, residual, rowstat=False, out=None):
             raise ValueError(f"hs_out: residual {tuple(residual.shape)} must be contiguous with the shape of o")
     if out is None:
         out = torch.empty_like(o)
-    rs = torch.empty(B * N, 20, 2, dtype=torch.float32, device=o.device) if (rowstat and LN_FOLD) else None
+    rs = torch.empty(B * N, 20, 2, dtype=torch.float32, device=o.device) if rowstat else None
     d = L.HsOutDesc()
     d.o, d.w_packed, d.bias, d.residual, d.out, d.rowstat_out = o.data_ptr(), wo_packed.data_ptr(), _ptr(bias), _ptr(residual), out.data_ptr(), _ptr(rs)
     d.B, d.N, d.C, d.dtype = B, N, Cc, _DT[o.dtype]

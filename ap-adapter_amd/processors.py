@@ -13,6 +13,8 @@ Weights are read through the attributes at call time.  The timestep-invariant K/
 out of the denoise loop with ``kv_cache_enabled`` (the pipeline switches it on and clears it per call); with it
 off every call recomputes them exactly like the reference.
 """
+from typing import NamedTuple, Optional
+
 import torch
 import torch.nn as nn
 
@@ -22,30 +24,50 @@ from .derived import derived, signature
 
 _vt_pool = {}
 
-# Route the C = 256 / 8-head cross-attention sub-layers (<= 64 keys per segment) through the single-launch
-# apad_fused_cross_attention kernel (LN + to_q + decoupled attention + to_out + residual).  False selects the
-# three-kernel chain it replaces (tests).
+# The one-launch cross-attention kernels (apad_fused_cross_attention at C = 256, apad_cross_attention_rows at C = 384).  False selects the chain
+# they replace (tests).
 USE_FUSED_XATTN = True
-# Self-attention behind the row-panel projection: scale the to_q rows by log2(e) / sqrt(d) once (cached with the stacked weight) so
-# that apad_attention takes q as the base-2 exponent operand (q_prescaled)
-PRESCALE_Q = True
+USE_XATTN_ROWS = True  # the 384-wide level's kernel alone (follows USE_FUSED_XATTN)
 
 
-def _fused_xattn_ok(attn, hidden_states, residual, ln, L1, L2=0, masked=False):
-    C_ = hidden_states.shape[-1]
-    return (USE_FUSED_XATTN and residual is hidden_states and ln is not None and C_ == ops.XATTN_C and attn.heads == ops.XATTN_HEADS
-            and tuple(attn.to_q.weight.shape) == (C_, C_) and ops.xattn_lengths_ok(L1, L2, masked)
-            and hidden_states.is_contiguous() and hidden_states.dtype in ops.FUSED_DTYPES)
+def route(kind, attn, hidden_states, residual=None, ln=None, L1=0, L2=0, masked=False, same_batch=True):
+    """Which kernels run this attention sub-layer.  Decided ONCE per call, before the hoist, from shapes, dtypes, strides and module attributes
+    only (CPU tensors do; nothing is launched); both the packing of the hoisted key / value sets and the dispatch read the answer.
 
+    ``kind``: "self", "cross" (AttnProcessor2_0 over a condition) or "decoupled" (IPAttnProcessor2_0); ``residual`` / ``ln``: what the caller
+    fuses (the block entry passes ``residual is hidden_states`` and its LayerNorm); ``L1`` / ``L2``: key counts of the one or two segments;
+    ``masked``: a key bias will be passed; ``same_batch``: the condition has the batch of the hidden states.
 
-USE_XATTN_ROWS = True  # the 384-wide level's single-launch route (follows USE_FUSED_XATTN; module attribute only)
-
-
-def _xrows_ok(attn, hidden_states, residual, ln, L1, L2=0):
-    """the 384-wide cross-attention sub-layers with <= 64 keys per segment: apad_cross_attention_rows (masked or not)"""
-    C_ = hidden_states.shape[-1]
-    return (USE_FUSED_XATTN and USE_XATTN_ROWS and residual is hidden_states and ln is not None and ops.xrows_ok(C_, attn.heads, L1, L2)
-            and tuple(attn.to_q.weight.shape) == (C_, C_) and hidden_states.is_contiguous() and hidden_states.dtype in ops.FUSED_DTYPES)
+      "fused"  apad_fused_cross_attention: LayerNorm + to_q + attention + to_out + residual in one launch (C = 256)
+      "rows"   apad_cross_attention_rows: the same sub-layer in one launch on row tiles (C = 384)
+      "hs"     apad_hs_attention + apad_hs_out: the 64-token level's head-sliced pair (csrc/hsattn.hip), self or cross
+      "sattn"  apad_self_attention_fused + to_out: LayerNorm + q | k | v + attention in one launch at the two large levels
+      "chain"  projection(s) + apad_attention + to_out: every other geometry, every masked self-attention (the fused self-attention
+               kernels carry no key bias; the reference applies attention_mask to attn1 too, attention_processor.py:245-249), all of fp32
+    """
+    x, heads, wq = hidden_states, attn.heads, attn.to_q.weight
+    C_ = x.shape[-1]
+    square_q = tuple(wq.shape) == (C_, C_)
+    # [B, <= 64, 640], 8 heads, a bias-free square to_q; entered with or without the block's LayerNorm / residual
+    hs = (ops.hs_ok(x, heads, wq.shape[0]) and attn.to_q.bias is None and attn.to_out[0].weight.shape[0] == ops.HS_C
+          and (residual is None or (residual.shape == x.shape and residual.is_contiguous())))
+    if kind == "self":
+        if masked:
+            return "chain"
+        if hs:
+            return "hs"
+        if ln is not None and ops.sattn_ok(x, heads) and attn.to_q.bias is None and square_q:
+            return "sattn"
+        return "chain"
+    # the one-launch kernels take the block entry only: they apply its LayerNorm and add x itself
+    entry = USE_FUSED_XATTN and residual is x and ln is not None and square_q and x.is_contiguous() and x.dtype in ops.FUSED_DTYPES
+    if entry and C_ == ops.XATTN_C and heads == ops.XATTN_HEADS and ops.xattn_lengths_ok(L1, L2, masked):
+        return "fused"
+    if entry and USE_XATTN_ROWS and same_batch and ops.xrows_ok(C_, heads, L1, L2):
+        return "rows"
+    if hs and same_batch and ops.hs_cross_lengths_ok(L1, L2):
+        return "hs"
+    return "chain"
 
 
 def _xrows_weights(attn):
@@ -60,20 +82,6 @@ def _xattn_weights(attn, ln):
     wq, wo = attn.to_q.weight, attn.to_out[0].weight
     return derived(wq, "xattn", lambda: ops.xattn_pack_weight(wq.detach(), ln) + (ops.xattn_pack_weight(wo.detach()),),
                    (wo, ln[0], ln[1]), (float(ln[2]),))
-
-
-def _hs_route(attn, hidden_states, residual, ln):
-    """the 64-token level's two-launch route (csrc/hsattn.hip): [B, <= 64, 640], 8 heads, a bias-free square to_q; entered with or without
-    the block's LayerNorm / residual (the reference call has neither)"""
-    return (ops.hs_ok(hidden_states, attn.heads, attn.to_q.weight.shape[0]) and attn.to_q.bias is None and attn.to_out[0].weight.shape[0] == ops.HS_C
-            and (residual is None or (residual.shape == hidden_states.shape and residual.is_contiguous())))
-
-
-def _rows_kv_route(attn, hidden_states, residual, ln, L1, L2=0):
-    """the site's cross-attention runs on a row-tile kernel that reads fragment-packed key / value sets (ops.rows_pack_kv): the 384-wide level's
-    one-launch kernel or the 64-token level's head-sliced pair"""
-    return ops.ROWS_KV_PACKED and (_xrows_ok(attn, hidden_states, residual, ln, L1, L2)
-                                   or (_hs_route(attn, hidden_states, residual, ln) and ops.hs_cross_lengths_ok(L1, L2)))
 
 
 def _rows_kv(pk, B, Lk, attn):
@@ -203,13 +211,36 @@ def _as_image(out, shape4):
     return out if shape4 is None else out.transpose(-1, -2).reshape(*shape4)
 
 
-class AttnProcessor2_0(nn.Module):
-    """Plain scaled-dot-product attention (reference :199-294).  Accepts dummy hidden_size / cross_attention_dim
-    like the reference so it can live in AttnProcsLayers."""
+class _KV(NamedTuple):
+    """the hoisted key / value sets of one cross-attention call, per segment: k [B, L, C] row-major, vt [B, heads, d, Lpad] per-head transposed,
+    pk = the fragment packing the call's route reads (ops.xattn_pack_kv for "fused", ops.rows_pack_kv for "rows" / "hs", None for "chain");
+    a call without a second segment leaves its three fields None"""
+    k1: torch.Tensor
+    vt1: torch.Tensor
+    pk1: Optional[torch.Tensor] = None
+    k2: Optional[torch.Tensor] = None
+    vt2: Optional[torch.Tensor] = None
+    pk2: Optional[torch.Tensor] = None
+
+
+def _pack_kv(r, k, vt):
+    if r == "fused":
+        return ops.xattn_pack_kv(k, vt, k.shape[1])
+    if r in ("rows", "hs"):
+        return ops.rows_pack_kv(k, vt).data
+    return None
+
+
+class _Processor(nn.Module):
+    """What the two processors share: the entry of the reference's processors (guards, the 4-D form), the hoist of timestep-invariant results
+    and the dispatch over ``route``.  Adds no parameter, buffer or sub-module.  A subclass describes its condition: ``_lengths`` (key counts of
+    the one or two segments), ``_segments`` (source rows and projection weights of each), ``_kv_signature`` (what the hoisted sets were
+    computed from), ``_bias`` (its mask rule) and ``_scale2`` (the weight of the second segment)."""
 
     fuses_residual = True
+    kind = None
 
-    def __init__(self, hidden_size=None, cross_attention_dim=None):
+    def __init__(self):
         super().__init__()
         self.kv_cache_enabled = False
         self._kv_cache = None
@@ -238,15 +269,16 @@ class AttnProcessor2_0(nn.Module):
             return e.out
         return e.get()
 
-    def _project_kv(self, attn, src, slot):
+    def _project_kv(self, attn, src, wk, wv, slot):
+        """one key / value segment: k row-major, vt per-head transposed; slot None: a persistent (hoisted) value owns its buffer"""
         B, Lk, _ = src.shape
-        C_ = attn.to_k.weight.shape[0]
-        k = ops.linear(src, attn.to_k.weight)
-        if slot is None:  # persistent (cached) values own their buffer
-            vt = torch.zeros(B, attn.heads, C_ // attn.heads, ops.round_up(Lk, 32), dtype=src.dtype, device=src.device)
+        d = attn.to_k.weight.shape[0] // attn.heads
+        k = ops.linear(src, wk)
+        if slot is None:
+            vt = torch.zeros(B, attn.heads, d, ops.round_up(Lk, 32), dtype=src.dtype, device=src.device)
         else:
-            vt = vt_buffer(slot, B, attn.heads, C_ // attn.heads, Lk, src.dtype, src.device)
-        ops.linear_vt(src, attn.to_v.weight, B, Lk, attn.heads, vt)
+            vt = vt_buffer(slot, B, attn.heads, d, Lk, src.dtype, src.device)
+        ops.linear_vt(src, wv, B, Lk, attn.heads, vt)
         return k, vt
 
     def _qkv_weight(self, attn, prescale=False):
@@ -264,8 +296,36 @@ class AttnProcessor2_0(nn.Module):
             return torch.cat([q, wk.detach(), wv.detach()], dim=0).contiguous()
         return derived(wq, "qkv", make, (wk, wv), (bool(prescale), heads))
 
-    def __call__(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None,
-                 _residual=None, _ln=None):
+    def _project_qkv(self, attn, x, ln):
+        """LayerNorm? + q | k | v of a self-attention on the "chain" route -> (q, k, vt, q is pre-scaled)"""
+        B, N, C_ = x.shape
+        heads = attn.heads
+
+        def outputs():
+            q = torch.empty(B, N, C_, dtype=x.dtype, device=x.device)
+            return q, torch.empty_like(q), vt_buffer("self", B, heads, C_ // heads, N, x.dtype, x.device)
+
+        if ops.rp_ok(x) and attn.to_q.weight.shape[0] == C_:
+            # LayerNorm + q|k|v in ONE launch: x is read once, V lands per-head transposed; the to_q rows carry log2(e) / sqrt(d), so
+            # apad_attention takes q as the base-2 exponent operand
+            q, k, vt = outputs()
+            prescaled = attn.to_q.bias is None
+            ops.rowpanel(x, self._qkv_weight(attn, prescaled), [(q, None, C_, "row"), (k, None, C_, "row"), (vt, None, C_, "vt")],
+                         ln=ln, vt_geom=(heads, C_ // heads, N, vt.shape[-1]))
+            return q, k, vt, prescaled
+        if attn.to_q.weight.shape[0] == C_ and C_ % 128 == 0:  # (fp32 mode: every width whose C % 128 == 0)
+            # widths outside the row-panel envelope (the 640-wide level): q|k|v in ONE tiled launch, the LayerNorm folded into
+            # it when the GEMM that produced x left its row statistics, else a LayerNorm launch first
+            qkv_w = self._qkv_weight(attn)
+            fold = ln is not None and ops.ln_foldable(x, qkv_w)
+            hs = x if (ln is None or fold) else ops.layer_norm(x, *ln)
+            q, k, vt = outputs()
+            ops.linear_qkv(hs, qkv_w, B, N, heads, q, k, vt, ln=ln if fold else None)
+            return q, k, vt, False
+        hs = x if ln is None else ops.layer_norm(x, *ln)
+        return (ops.linear(hs, attn.to_q.weight),) + self._project_kv(attn, hs, attn.to_k.weight, attn.to_v.weight, "self") + (False,)
+
+    def _sublayer(self, attn, hidden_states, encoder_hidden_states, attention_mask, _residual, _ln):
         """``_residual`` (added after to_out) and ``_ln`` = (gamma, beta, eps) (LayerNorm applied to hidden_states
         first) are private fusion hooks used by this package's BasicTransformerBlock; without them the call is the
         reference's."""
@@ -273,131 +333,123 @@ class AttnProcessor2_0(nn.Module):
             raise NotImplementedError("spatial_norm / group_norm / norm_cross are not on the AudioLDM2 path")
         if hidden_states.ndim == 4:
             tok, res, shape4 = _as_tokens(hidden_states, _residual)
-            return _as_image(self(attn, tok, encoder_hidden_states, attention_mask, temb, _residual=res, _ln=_ln), shape4)
+            return _as_image(self._sublayer(attn, tok, encoder_hidden_states, attention_mask, res, _ln), shape4)
         if hidden_states.ndim != 3:
             raise ValueError("hidden_states must be [batch, tokens, channels] or [batch, channels, height, width]")
-        B, N, C_ = hidden_states.shape
-        heads = attn.heads
-        if AG.on(hidden_states, encoder_hidden_states):
-            return self._call_train(attn, hidden_states, encoder_hidden_states, attention_mask, _residual, _ln)
-        prescaled = False
+        if encoder_hidden_states is None and self.kind == "decoupled":
+            raise ValueError("IPAttnProcessor2_0 needs encoder_hidden_states = [text tokens | audio tokens]")
         if attn.residual_connection or attn.rescale_output_factor != 1.0:
             raise NotImplementedError("residual_connection / rescale_output_factor are not on the AudioLDM2 path")
-        hs_route = _hs_route(attn, hidden_states, _residual, _ln)
-        # (a masked self-attention -- the reference applies attention_mask to attn1 too, attention_processor.py:245-249 -- takes the generic
-        #  q|k|v + apad_attention(key_bias) route below: the two fused self-attention kernels carry no key bias)
-        if encoder_hidden_states is None and attention_mask is None and hs_route:
-            return _hs_sublayer(attn, hidden_states, _residual, _ln)
-        if (encoder_hidden_states is None and attention_mask is None and _ln is not None and ops.sattn_ok(hidden_states, heads) and attn.to_q.bias is None
-                and tuple(attn.to_q.weight.shape) == (C_, C_)):
-            # the two large levels: LayerNorm + q | k | v + attention in ONE launch (workgroup = (sample, head), K / V^T in LDS), then to_out
-            wq, wk, wv = attn.to_q.weight, attn.to_k.weight, attn.to_v.weight
-            w_p, csbb = derived(wq, "sattn", lambda: ops.sattn_pack(wq, wk, wv, _ln, heads), (wk, wv, _ln[0], _ln[1]), (float(_ln[2]), heads))
-            o = ops.self_attention_fused(hidden_states, w_p, csbb, heads, _ln[2])
-            return ops.fused_linear(o, attn.to_out[0].weight, attn.to_out[0].bias, residual=_residual, rowstat=True)
-        if encoder_hidden_states is None:
-            Lk = N
-            if ops.rp_ok(hidden_states) and attn.to_q.weight.shape[0] == C_:
-                # LayerNorm + q|k|v in ONE launch: x is read once, V lands per-head transposed
-                q = torch.empty(B, N, C_, dtype=hidden_states.dtype, device=hidden_states.device)
-                k = torch.empty_like(q)
-                vt = vt_buffer("self", B, heads, C_ // heads, N, hidden_states.dtype, hidden_states.device)
-                prescaled = PRESCALE_Q and attn.to_q.bias is None
-                ops.rowpanel(hidden_states, self._qkv_weight(attn, prescaled), [(q, None, C_, "row"), (k, None, C_, "row"), (vt, None, C_, "vt")],
-                             ln=_ln, vt_geom=(heads, C_ // heads, N, vt.shape[-1]))
-            elif attn.to_q.weight.shape[0] == C_ and C_ % 128 == 0:  # (fp32 mode: every width whose C % 128 == 0)
-                # widths outside the row-panel envelope (the 640-wide level): q|k|v in ONE tiled launch, the LayerNorm folded into
-                # it when the GEMM that produced hidden_states left its row statistics (ops.LN_FOLD), else a LayerNorm launch first
-                qkv_w = self._qkv_weight(attn)
-                fold = _ln is not None and ops.ln_foldable(hidden_states, qkv_w)
-                hs = hidden_states if (_ln is None or fold) else ops.layer_norm(hidden_states, *_ln)
-                q = torch.empty(B, N, C_, dtype=hidden_states.dtype, device=hidden_states.device)
-                k = torch.empty_like(q)
-                vt = vt_buffer("self", B, heads, C_ // heads, N, hidden_states.dtype, hidden_states.device)
-                ops.linear_qkv(hs, qkv_w, B, N, heads, q, k, vt, ln=_ln if fold else None)
-            else:
-                hs = hidden_states if _ln is None else ops.layer_norm(hidden_states, *_ln)
-                q = ops.linear(hs, attn.to_q.weight)
-                k, vt = self._project_kv(attn, hs, "self")
-        else:
-            q = None  # projected below, unless the single-launch kernel takes the whole sub-layer
-            ehs = encoder_hidden_states
-            if ehs.dim() < 3:
-                ehs = ehs.unsqueeze(0)
-            Lk = ehs.shape[1]
-            # hoisted K/V belong to ONE (Attention site, condition buffer) -- a processor instance may be shared by every site
-            # (set_attn_processor(proc)) -- and are valid for one condition content and one pair of to_k / to_v weights
-            # (re-assigned or stepped weights, an in-place update of the condition -> recomputed, in place)
-            fused = _fused_xattn_ok(attn, hidden_states, _residual, _ln, Lk)
-            rows = not fused and ehs.shape[0] == B and _rows_kv_route(attn, hidden_states, _residual, _ln, Lk)
-            persistent = self.kv_cache_enabled
+        x, ehs, residual, ln = hidden_states, encoder_hidden_states, _residual, _ln
+        if ehs is not None and ehs.dim() < 3:
+            ehs = ehs.unsqueeze(0)
+        if AG.on(x, ehs, *self.parameters()):
+            return self._call_train(attn, x, ehs, attention_mask, residual, ln)
+        B, N, _ = x.shape
+        heads, wo, bo = attn.heads, attn.to_out[0].weight, attn.to_out[0].bias
+        masked = attention_mask is not None
+        if ehs is None:
+            r = route("self", attn, x, residual, ln, masked=masked)
+            if r == "hs":
+                return _hs_sublayer(attn, x, residual, ln)
+            if r == "sattn":  # workgroup = (sample, head), K / V^T in LDS; then to_out
+                wq, wk, wv = attn.to_q.weight, attn.to_k.weight, attn.to_v.weight
+                w_p, csbb = derived(wq, "sattn", lambda: ops.sattn_pack(wq, wk, wv, ln, heads), (wk, wv, ln[0], ln[1]), (float(ln[2]), heads))
+                o = ops.self_attention_fused(x, w_p, csbb, heads, ln[2])
+                return ops.fused_linear(o, wo, bo, residual=residual, rowstat=True)
+            q, k, vt, prescaled = self._project_qkv(attn, x, ln)
+            o = ops.attention(q, k, vt, N, heads, key_bias=self._bias(attention_mask, B, N), q_prescaled=prescaled)
+            return ops.fused_linear(o, wo, bo, residual=residual, rowstat=True)
+        L1, L2 = self._lengths(ehs)
+        r = route(self.kind, attn, x, residual, ln, L1, L2, masked, ehs.shape[0] == B)
+        persistent = self.kv_cache_enabled
 
-            def make(attn=attn, ehs=ehs, fused=fused, rows=rows, persistent=persistent):
-                k_, vt_ = self._project_kv(attn, ehs, None if persistent else "cross")
-                # packed with the projection: the weight-stationary kernel's layout, or the row-tile kernels' fragment sets
-                return (k_, vt_, ops.xattn_pack_kv(k_, vt_, ehs.shape[1]) if fused else (ops.rows_pack_kv(k_, vt_).data if rows else None))
+        def make():  # the projections, packed with them into what the route's kernel reads
+            kv = [self._project_kv(attn, src, wk, wv, None if persistent else slot) for src, wk, wv, slot in self._segments(attn, ehs)]
+            return _KV(*(t for k, vt in kv for t in (k, vt, _pack_kv(r, k, vt))))
 
-            k, vt, pk = self._hoisted(_loose_key(attn, ehs), lambda attn=attn, ehs=ehs: (ehs._version, signature(attn.to_k.weight, attn.to_v.weight),
-                                                                                      _precision_of(attn.to_k.weight)), make)
-        if attention_mask is not None:
-            # the mask -> fp32 bias conversion is timestep-invariant too: hoisted with the K/V (two tiny torch kernels
-            # per masked site per step otherwise)
-            (bias,) = self._hoisted(("bias",) + _loose_key(None, attention_mask) + (Lk,), lambda m=attention_mask: m._version,
-                                    lambda m=attention_mask: (_key_bias(m, B, Lk),))
-        else:
-            bias = None
-        if encoder_hidden_states is not None and fused and pk is not None:
-            wq_p, q_fold, wo_p = _xattn_weights(attn, _ln)
-            return ops.fused_cross_attention(hidden_states, wq_p, wo_p, attn.to_out[0].bias, pk, Lk, heads, ln=_ln, key_bias=bias, q_fold=q_fold)
-        if encoder_hidden_states is not None and rows and pk is not None:
-            k, vt = _rows_kv(pk, B, Lk, attn), None
-        if encoder_hidden_states is not None and _xrows_ok(attn, hidden_states, _residual, _ln, Lk) and k.shape[0] == B:
+        # hoisted K/V belong to ONE (Attention site, condition buffer) -- a processor instance may be shared by every site
+        # (set_attn_processor(proc)) -- and are valid for one condition content and one set of projection weights (re-assigned or
+        # stepped weights, an in-place update of the condition -> recomputed, in place); packed for one route
+        kv = self._hoisted(_loose_key(attn, ehs) + (r,), lambda: self._kv_signature(attn, ehs), make)
+        bias = self._bias(attention_mask, B, L1)
+        scale2 = self._scale2()
+        if r == "fused":
+            wq_p, q_fold, wo_p = _xattn_weights(attn, ln)
+            return ops.fused_cross_attention(x, wq_p, wo_p, bo, kv.pk1, L1, heads, ln=ln, key_bias=bias, kv2_packed=kv.pk2, L2=L2, scale2=scale2,
+                                             q_fold=q_fold)
+        if r in ("rows", "hs"):
+            k1 = _rows_kv(kv.pk1, B, L1, attn)
+            k2 = _rows_kv(kv.pk2, B, L2, attn) if L2 > 0 else None
+            if r == "hs":
+                return _hs_sublayer(attn, x, residual, ln, k1=k1, vt1=None, key_bias=bias, k2=k2, vt2=None, scale2=scale2)
             wq_p, wo_p = _xrows_weights(attn)
-            return ops.cross_attention_rows(hidden_states, wq_p, wo_p, attn.to_out[0].bias, k, vt, heads, ln=_ln, key_bias=bias)
-        if encoder_hidden_states is not None and hs_route and ops.hs_cross_lengths_ok(Lk) and k.shape[0] == B:
-            return _hs_sublayer(attn, hidden_states, _residual, _ln, k1=k, vt1=vt, key_bias=bias)
-        if q is None:
-            q = ops.fused_linear(hidden_states, attn.to_q.weight, ln=_ln)
-        o = ops.attention(q, k, vt, Lk, heads, key_bias=bias, q_prescaled=prescaled)
-        return ops.fused_linear(o, attn.to_out[0].weight, attn.to_out[0].bias, residual=_residual, rowstat=True)
+            return ops.cross_attention_rows(x, wq_p, wo_p, bo, k1, None, heads, ln=ln, key_bias=bias, k2=k2, vt2=None, scale2=scale2)
+        q = ops.fused_linear(x, attn.to_q.weight, ln=ln)
+        o = ops.attention(q, kv.k1, kv.vt1, L1, heads, key_bias=bias, k2=kv.k2, vt2=kv.vt2, L2=L2, scale2=scale2)
+        return ops.fused_linear(o, wo, bo, residual=residual, rowstat=True)
 
 
-def _train_common(attn):
-    if attn.residual_connection or attn.rescale_output_factor != 1.0:
-        raise NotImplementedError("residual_connection / rescale_output_factor are not on the AudioLDM2 path")
+class AttnProcessor2_0(_Processor):
+    """Plain scaled-dot-product attention (reference :199-294).  Accepts dummy hidden_size / cross_attention_dim
+    like the reference so it can live in AttnProcsLayers."""
+
+    kind = "cross"
+
+    def __init__(self, hidden_size=None, cross_attention_dim=None):
+        super().__init__()
+
+    def __call__(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None,
+                 _residual=None, _ln=None):
+        return self._sublayer(attn, hidden_states, encoder_hidden_states, attention_mask, _residual, _ln)
+
+    def _lengths(self, ehs):
+        return ehs.shape[1], 0
+
+    def _segments(self, attn, ehs):
+        return [(ehs, attn.to_k.weight, attn.to_v.weight, "cross")]
+
+    def _kv_signature(self, attn, ehs):
+        return (ehs._version, signature(attn.to_k.weight, attn.to_v.weight), _precision_of(attn.to_k.weight))
+
+    def _bias(self, attention_mask, B, Lk):
+        """the whole mask as a key bias.  The mask -> fp32 bias conversion is timestep-invariant too: hoisted with the K/V (two tiny torch
+        kernels per masked site per step otherwise)"""
+        if attention_mask is None:
+            return None
+        m = attention_mask
+        return self._hoisted(("bias",) + _loose_key(None, m) + (Lk,), lambda: m._version, lambda: (_key_bias(m, B, Lk),))[0]
+
+    def _scale2(self):
+        return 0.0
+
+    def _call_train(self, attn, hidden_states, ehs, attention_mask, _residual, _ln):
+        """Training mode (gradients flow to hidden_states; autograd.py): the un-fused chain LayerNorm ->
+        to_q / to_k / to_v -> attention -> to_out (+ residual), every node a HIP forward with a HIP backward."""
+        B, N, _ = hidden_states.shape
+        if _ln is not None and _residual is hidden_states:
+            hs, _residual = AG.layer_norm_res(hidden_states, *_ln)  # (the residual gradient joins the LayerNorm backward launch)
+        else:
+            hs = hidden_states if _ln is None else AG.layer_norm(hidden_states, *_ln)
+        if ehs is None:  # self-attention: one input-gradient GEMM for the three projections
+            src = hs
+            q, k, v, vt = AG.qkv(hs, attn.to_q.weight, attn.to_k.weight, attn.to_v.weight, attn.heads)
+        else:
+            src = ehs
+            q = AG.linear(hs, attn.to_q.weight)
+            k = AG.linear(src, attn.to_k.weight)
+            v = AG.linear(src, attn.to_v.weight)
+            vt = None
+        o = AG.attention(q, k, v, attn.heads, _key_bias(attention_mask, B, src.shape[1]), vt=vt)
+        return AG.linear(o, attn.to_out[0].weight, attn.to_out[0].bias, residual=_residual)
 
 
-def _attn_call_train(self, attn, hidden_states, encoder_hidden_states, attention_mask, _residual, _ln):
-    """Training-mode AttnProcessor2_0 (gradients flow to hidden_states; autograd.py): the un-fused chain LayerNorm ->
-    to_q / to_k / to_v -> attention -> to_out (+ residual), every node a HIP forward with a HIP backward."""
-    _train_common(attn)
-    B, N, _ = hidden_states.shape
-    if _ln is not None and _residual is hidden_states:
-        hs, _residual = AG.layer_norm_res(hidden_states, *_ln)  # (the residual gradient joins the LayerNorm backward launch)
-    else:
-        hs = hidden_states if _ln is None else AG.layer_norm(hidden_states, *_ln)
-    src = hs if encoder_hidden_states is None else (encoder_hidden_states if encoder_hidden_states.dim() == 3
-                                                    else encoder_hidden_states.unsqueeze(0))
-    if encoder_hidden_states is None:  # self-attention: one input-gradient GEMM for the three projections
-        q, k, v, vt = AG.qkv(hs, attn.to_q.weight, attn.to_k.weight, attn.to_v.weight, attn.heads)
-    else:
-        q = AG.linear(hs, attn.to_q.weight)
-        k = AG.linear(src, attn.to_k.weight)
-        v = AG.linear(src, attn.to_v.weight)
-        vt = None
-    o = AG.attention(q, k, v, attn.heads, _key_bias(attention_mask, B, src.shape[1]), vt=vt)
-    return AG.linear(o, attn.to_out[0].weight, attn.to_out[0].bias, residual=_residual)
-
-
-AttnProcessor2_0._call_train = _attn_call_train
-
-
-class IPAttnProcessor2_0(nn.Module):
+class IPAttnProcessor2_0(_Processor):
     """Decoupled cross-attention (reference :297-470): text branch over the first ``num_tokens`` tokens with the frozen
     ``attn.to_k/to_v``, audio branch over the remaining tokens with the trainable ``to_k_ip/to_v_ip``, blended
     ``text + scale * audio`` inside one fused kernel."""
 
-    fuses_residual = True
+    kind = "decoupled"
 
     def __init__(self, hidden_size, name, cross_attention_dim=None, num_tokens=4, scale=1.0, do_copy=False,
                  copy_dir=None):
@@ -409,114 +461,47 @@ class IPAttnProcessor2_0(nn.Module):
         self.name = name
         self.to_k_ip = nn.Linear(cross_attention_dim or hidden_size, hidden_size, bias=False)
         self.to_v_ip = nn.Linear(cross_attention_dim or hidden_size, hidden_size, bias=False)
-        self.kv_cache_enabled = False
-        self._kv_cache = None
         if do_copy:
             # reference :328-344 warm-starts from copied_cross_attention/{name}_{k,v}.bin
             from .wiring import load_copied_cross_attention
             load_copied_cross_attention(self, copy_dir)
-
-    def clear_kv_cache(self):
-        self._kv_cache = None
-
-    refresh_kv_cache = AttnProcessor2_0.refresh_kv_cache
-    drop_kv_owner = AttnProcessor2_0.drop_kv_owner
-    _hoisted = AttnProcessor2_0._hoisted
-
-    def _project(self, attn, ehs):
-        B = ehs.shape[0]
-        nt = self.num_tokens
-        txt = ehs[:, :nt, :]
-        aud = ehs[:, nt:, :]
-        Lt, La = txt.shape[1], aud.shape[1]
-        C_ = attn.to_k.weight.shape[0]
-        d = C_ // attn.heads
-        persistent = self.kv_cache_enabled
-        # ragged views -> dense rows for the GEMM A operand (plumbing copies of <= 520 x 768 tokens)
-        txt = txt.contiguous()
-        k_t = ops.linear(txt, attn.to_k.weight)
-        vt_t = (torch.zeros(B, attn.heads, d, ops.round_up(Lt, 32), dtype=ehs.dtype, device=ehs.device) if persistent
-                else vt_buffer("ip_txt", B, attn.heads, d, Lt, ehs.dtype, ehs.device))
-        ops.linear_vt(txt, attn.to_v.weight, B, Lt, attn.heads, vt_t)
-        k_a = vt_a = None
-        if La > 0:
-            aud = aud.contiguous()
-            k_a = ops.linear(aud, self.to_k_ip.weight)
-            vt_a = (torch.zeros(B, attn.heads, d, ops.round_up(La, 32), dtype=ehs.dtype, device=ehs.device)
-                    if persistent else vt_buffer("ip_aud", B, attn.heads, d, La, ehs.dtype, ehs.device))
-            ops.linear_vt(aud, self.to_v_ip.weight, B, La, attn.heads, vt_a)
-        return k_t, vt_t, Lt, k_a, vt_a, La, None, None
 
     def __call__(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None, scale=1.0,
                  _residual=None, _ln=None):
         if scale != 1.0:
             # the reference dereferences an undefined ``logger`` here (:356-357) -> NameError; reject loudly instead
             raise ValueError("`scale` of IPAttnProcessor2_0 is set through the `scale` attribute, not the call kwarg")
-        if attn.spatial_norm is not None or attn.group_norm is not None or attn.norm_cross:
-            raise NotImplementedError("spatial_norm / group_norm / norm_cross are not on the AudioLDM2 path")
-        if hidden_states.ndim == 4:
-            tok, res, shape4 = _as_tokens(hidden_states, _residual)
-            return _as_image(self(attn, tok, encoder_hidden_states, attention_mask, temb, _residual=res, _ln=_ln), shape4)
-        if hidden_states.ndim != 3:
-            raise ValueError("hidden_states must be [batch, tokens, channels] or [batch, channels, height, width]")
-        if encoder_hidden_states is None:
-            raise ValueError("IPAttnProcessor2_0 needs encoder_hidden_states = [text tokens | audio tokens]")
-        ehs = encoder_hidden_states
-        if ehs.dim() < 3:
-            ehs = ehs.unsqueeze(0)
-        B, N, _ = hidden_states.shape
-        if AG.on(hidden_states, ehs, self.to_k_ip.weight, self.to_v_ip.weight):
-            return self._call_train(attn, hidden_states, ehs, attention_mask, _residual, _ln)
-        # see AttnProcessor2_0: one entry per (site, condition buffer), valid for one condition content and one set of the four
-        # projection weights, so a re-assigned to_k_ip / to_v_ip (inference.py:56-57) or an optimizer step is never served stale K/V
-        Lt0 = min(self.num_tokens, ehs.shape[1])
-        fused = _fused_xattn_ok(attn, hidden_states, _residual, _ln, Lt0, ehs.shape[1] - Lt0, attention_mask is not None)  # (no activation captured below)
-        rows = not fused and ehs.shape[0] == B and _rows_kv_route(attn, hidden_states, _residual, _ln, Lt0, ehs.shape[1] - Lt0)
+        return self._sublayer(attn, hidden_states, encoder_hidden_states, attention_mask, _residual, _ln)
 
-        def make(attn=attn, ehs=ehs, fused=fused, rows=rows):
-            kv_ = self._project(attn, ehs)
-            k_t_, vt_t_, Lt_, k_a_, vt_a_, La_ = kv_[:6]
-            if fused:  # packed once, with the hoisted projection
-                kv_ = kv_[:6] + (ops.xattn_pack_kv(k_t_, vt_t_, Lt_), ops.xattn_pack_kv(k_a_, vt_a_, La_) if La_ > 0 else None)
-            elif rows:  # ... or into the fragment sets the row-tile kernels of the 384- / 640-wide levels read
-                kv_ = kv_[:6] + (ops.rows_pack_kv(k_t_, vt_t_).data, ops.rows_pack_kv(k_a_, vt_a_).data if La_ > 0 else None)
-            return kv_
+    def _lengths(self, ehs):
+        Lt = min(self.num_tokens, ehs.shape[1])
+        return Lt, ehs.shape[1] - Lt
 
-        sig = lambda attn=attn, ehs=ehs: (ehs._version, self.num_tokens,
-                                          signature(attn.to_k.weight, attn.to_v.weight, self.to_k_ip.weight, self.to_v_ip.weight),
-                                          _precision_of(attn.to_k.weight))
-        k_t, vt_t, Lt, k_a, vt_a, La, pk_t, pk_a = self._hoisted(_loose_key(attn, ehs), sig, make)
-        bias = None
-        if attention_mask is not None:
-            # reference :424-428 keeps only mask column 0 (split by the singleton query dim) and broadcasts it
-            # over the text keys
-            m = attention_mask.reshape(B, -1)[:, :1].float()
-            bias = m.expand(B, Lt).contiguous()
-        if pk_t is not None and _fused_xattn_ok(attn, hidden_states, _residual, _ln, Lt, La, bias is not None):
-            wq_p, q_fold, wo_p = _xattn_weights(attn, _ln)
-            return ops.fused_cross_attention(hidden_states, wq_p, wo_p, attn.to_out[0].bias, pk_t, Lt, attn.heads, ln=_ln,
-                                             key_bias=bias, kv2_packed=pk_a, L2=La, scale2=self.scale, q_fold=q_fold)
-        if rows and pk_t is not None:
-            k_t, vt_t = _rows_kv(pk_t, B, Lt, attn), None
-            if La > 0:
-                k_a, vt_a = _rows_kv(pk_a, B, La, attn), None
-        if _xrows_ok(attn, hidden_states, _residual, _ln, Lt, La) and k_t.shape[0] == B:
-            wq_p, wo_p = _xrows_weights(attn)
-            return ops.cross_attention_rows(hidden_states, wq_p, wo_p, attn.to_out[0].bias, k_t, vt_t, attn.heads, ln=_ln, key_bias=bias,
-                                            k2=k_a, vt2=vt_a, scale2=self.scale)
-        if attn.residual_connection or attn.rescale_output_factor != 1.0:
-            raise NotImplementedError("residual_connection / rescale_output_factor are not on the AudioLDM2 path")
-        if _hs_route(attn, hidden_states, _residual, _ln) and ops.hs_cross_lengths_ok(Lt, La) and k_t.shape[0] == B:
-            return _hs_sublayer(attn, hidden_states, _residual, _ln, k1=k_t, vt1=vt_t, key_bias=bias, k2=k_a, vt2=vt_a, scale2=self.scale)
-        q = ops.fused_linear(hidden_states, attn.to_q.weight, ln=_ln)
-        o = ops.attention(q, k_t, vt_t, Lt, attn.heads, key_bias=bias, k2=k_a, vt2=vt_a, L2=La, scale2=self.scale)
-        return ops.fused_linear(o, attn.to_out[0].weight, attn.to_out[0].bias, residual=_residual, rowstat=True)
+    def _segments(self, attn, ehs):
+        # ragged views -> dense rows for the GEMM A operand (plumbing copies of <= 520 x 768 tokens)
+        nt = self.num_tokens
+        segs = [(ehs[:, :nt, :].contiguous(), attn.to_k.weight, attn.to_v.weight, "ip_txt")]
+        if ehs.shape[1] > nt:
+            segs.append((ehs[:, nt:, :].contiguous(), self.to_k_ip.weight, self.to_v_ip.weight, "ip_aud"))
+        return segs
 
+    def _kv_signature(self, attn, ehs):
+        # all four projection weights: a re-assigned to_k_ip / to_v_ip (inference.py:56-57) or an optimizer step is never served stale K/V
+        return (ehs._version, self.num_tokens, signature(attn.to_k.weight, attn.to_v.weight, self.to_k_ip.weight, self.to_v_ip.weight),
+                _precision_of(attn.to_k.weight))
+
+    def _bias(self, attention_mask, B, Lt):
+        """reference :424-428 keeps only mask column 0 (split by the singleton query dim) and broadcasts it over the text keys"""
+        if attention_mask is None:
+            return None
+        return attention_mask.reshape(B, -1)[:, :1].float().expand(B, Lt).contiguous()
+
+    def _scale2(self):
+        return self.scale
 
     def _call_train(self, attn, hidden_states, ehs, attention_mask, _residual, _ln):
         """Training mode (reference :347-470 under autograd; train_apadapter_v2.py:941-957): gradients w.r.t.
         hidden_states, to_k_ip.weight and to_v_ip.weight (and the condition tokens if they require grad)."""
-        _train_common(attn)
         B = hidden_states.shape[0]
         nt = self.num_tokens
         txt, aud = ehs[:, :nt, :].contiguous(), ehs[:, nt:, :].contiguous()
@@ -526,9 +511,7 @@ class IPAttnProcessor2_0(nn.Module):
             hs = hidden_states if _ln is None else AG.layer_norm(hidden_states, *_ln)
         q = AG.linear(hs, attn.to_q.weight)
         k_t, v_t = AG.linear(txt, attn.to_k.weight), AG.linear(txt, attn.to_v.weight)
-        bias = None
-        if attention_mask is not None:
-            bias = attention_mask.reshape(B, -1)[:, :1].float().expand(B, txt.shape[1]).contiguous()
+        bias = self._bias(attention_mask, B, txt.shape[1])
         if aud.shape[1] == 0:  # no audio tokens: the text branch alone (reference :435-445 on an empty slice contributes 0)
             o = AG.attention(q, k_t, v_t, attn.heads, bias)
         else:

@@ -155,26 +155,28 @@ class FeedForward(nn.Module):
             xn, xr = AG.layer_norm_res(x, *ln)  # (the residual gradient joins the LayerNorm backward launch)
             h = AG.geglu(AG.linear(xn, self.net[0].proj.weight, self.net[0].proj.bias))
             return AG.linear(h, self.net[2].weight, self.net[2].bias, residual=xr)
-        if ops.HS_FF and ops.HS_ATTN and ops.hs_rows_ok(x) and self.net[0].proj.weight.shape[0] == 8 * ops.HS_C:
-            # the 64-token level: LayerNorm + GEGLU projection in ONE launch, workgroup = (sample, hidden quarter) (csrc/hsattn.hip)
+        C_, rows = x.shape[-1], x.numel() // x.shape[-1]
+        w1, b1, w2, b2 = self.net[0].proj.weight, self.net[0].proj.bias, self.net[2].weight, self.net[2].bias
+        hs_level = ops.HS_ATTN and ops.hs_rows_ok(x) and w1.shape[0] == 8 * ops.HS_C
+        one_launch = C_ in ops.MLP_C and x.dtype in ops.FUSED_DTYPES
+        packed = ops.MLP_PACKED and x.dtype in ops.FUSED_DTYPES and x.is_contiguous()
+        if hs_level:
+            # the 64-token level: LayerNorm + GEGLU projection in ONE launch, workgroup = (sample, hidden quarter), then the second Linear +
+            # residual on the same row tiles (csrc/hsattn.hip)
             pk, bb, w2p = self._hs_weights(ln)
-            h = ops.hs_geglu(x, pk, bb, ln_eps=ln[2])
-            if ops.HS_FF2:
-                return ops.hs_ff2(h, w2p, self.net[2].bias, x, rowstat=True)
-            return ops.linear(h, self.net[2].weight, self.net[2].bias, residual=x, rowstat=True)
-        if x.shape[-1] in ops.MLP_C and x.dtype in ops.FUSED_DTYPES:
-            if ops.MLP_PACKED and x.numel() // x.shape[-1] >= ops.MLP_PACKED_MIN_M and x.is_contiguous():
-                wp, bp = self._mlp3_w
-                return ops.geglu_mlp_packed(x, wp, bp, self.net[2].bias, ln=ln)
-            return ops.geglu_mlp(x, self.net[0].proj.weight, self.net[0].proj.bias, self.net[2].weight, self.net[2].bias, ln=ln)
-        if (ops.MLP_PACKED and x.shape[-1] in ops.GEGLU_PACKED_C and x.dtype in ops.FUSED_DTYPES and x.is_contiguous()
-                and x.numel() // x.shape[-1] >= ops.GEGLU_PACKED_MIN_M):
+            return ops.hs_ff2(ops.hs_geglu(x, pk, bb, ln_eps=ln[2]), w2p, b2, x, rowstat=True)
+        elif one_launch and packed and rows >= ops.MLP_PACKED_MIN_M:
+            wp, bp = self._mlp3_w
+            return ops.geglu_mlp_packed(x, wp, bp, b2, ln=ln)
+        elif one_launch:
+            return ops.geglu_mlp(x, w1, b1, w2, b2, ln=ln)
+        elif packed and C_ in ops.GEGLU_PACKED_C and rows >= ops.GEGLU_PACKED_MIN_M:
             # the 384-wide level at full size: LayerNorm + GEGLU projection on the 64-token register-block kernel from packed weights
             wp, bp = self._geglu3_w
             h = ops.layernorm_geglu_packed(x, wp, bp, ln=ln)
         else:
-            h = ops.fused_linear(x, self.net[0].proj.weight, self.net[0].proj.bias, ln=ln, act="geglu")
-        return ops.linear(h, self.net[2].weight, self.net[2].bias, residual=x, rowstat=True)  # (the next block's norm1 folds into its q|k|v)
+            h = ops.fused_linear(x, w1, b1, ln=ln, act="geglu")
+        return ops.linear(h, w2, b2, residual=x, rowstat=True)  # (the next block's norm1 folds into its q|k|v)
 
 
 def cfg_expand(x, cond):
@@ -233,21 +235,24 @@ class Transformer2DModel(nn.Module):
         w = (self.proj_in if which == "in" else self.proj_out).weight
         return derived(w, "hs_rows", lambda: ops.hs_pack_rows(w.detach().reshape(w.shape[0], -1))[0])
 
+    def _hs_io(self, h):
+        """proj_in / proj_out of these rows run on apad_hs_out: the 64-token level, both weights 640 x 640"""
+        return (ops.HS_ATTN and ops.hs_rows_ok(h)
+                and tuple(self.proj_in.weight.shape[:2]) == (ops.HS_C, ops.HS_C) == tuple(self.proj_out.weight.shape[:2]))
+
     def forward(self, x, ehs, emask):
         if AG.on(x):
             h = AG.group_norm(x, self.norm.weight, self.norm.bias, self.groups, self.norm.eps, False)
             h = AG.linear(h, self.proj_in.weight, self.proj_in.bias)
         else:
             h = ops.group_norm(x, self.norm.weight, self.norm.bias, self.groups, self.norm.eps, silu=False)
-            hs_io = ops.HS_ATTN and ops.hs_rows_ok(h) and tuple(self.proj_in.weight.shape[:2]) == (ops.HS_C, ops.HS_C) == tuple(self.proj_out.weight.shape[:2])
-            if hs_io:  # the 64-token level: the 1x1 projections on the row-tile kernel of its attention sub-layers (csrc/hsattn.hip, apad_hs_out)
+            if self._hs_io(h):  # the 64-token level: the 1x1 projections on the row-tile kernel of its attention sub-layers (csrc/hsattn.hip, apad_hs_out)
                 h = ops.hs_out(h, self._hs_packed("in"), self.proj_in.bias, None, rowstat=True)
             else:
                 h = ops.fused_linear(h, _w2d(self.proj_in), self.proj_in.bias, rowstat=True)
         for blk in self.transformer_blocks:
             h = blk(h, ehs, emask)
-        if not AG.on(h, x) and h.shape[0] == x.shape[0] and ops.HS_ATTN and ops.hs_rows_ok(h) and ops.hs_rows_ok(x) \
-                and tuple(self.proj_in.weight.shape[:2]) == (ops.HS_C, ops.HS_C) == tuple(self.proj_out.weight.shape[:2]):
+        if not AG.on(h, x) and h.shape[0] == x.shape[0] and self._hs_io(h) and ops.hs_rows_ok(x):
             return ops.hs_out(h, self._hs_packed("out"), self.proj_out.bias, x)
         if h.shape[0] != x.shape[0]:  # the CFG batch was expanded inside (cfg_expand): the residual rows are the same for both halves
             if h.dtype in ops.FUSED_DTYPES and not AG.on(h, x):  # read modulo its rows by the GEMM's epilogue: no copy
