@@ -1,5 +1,5 @@
 // Small HBM-bound kernels of the path: AudioMAE token pooling, sinusoidal timestep embedding, fused
-// classifier-free-guidance + DDIM update, device-side step counter.
+// classifier-free-guidance + DDIM / sampler update, the edit step (sampler update + region blend) and its start, device-side step counter.
 #include "common.h"
 #include "f32_ops.h"
 
@@ -150,6 +150,123 @@ __global__ __launch_bounds__(256) void cfg_sampler_kernel(const uint8_t* eps2, f
         st_elemv<DT, V>(unet_in, i, x);
         if (hist) st_f32v<V>(hist, i, m0);
         if (eps_out) st_f32v<V>(eps_out, i, e);
+    }
+}
+
+// cfg_sampler_kernel's update with every rounding spelled out.  That kernel leaves the fusing of its multiply-adds to the compiler, which settled
+// on three forms (read off its gfx950 code): the 16-byte form fuses everything but c_e * e and d_e * e, the scalar fp32 form everything but c_x * x
+// and none of m0, the scalar 16-bit forms fuse nothing.  apad_cfg_edit_step promises the bits of apad_cfg_sampler_step where the mask is 1
+// (tests/test_gpu_edit.py::test_mask_of_ones_is_cfg_sampler_step_bit_for_bit holds the two together), so here nothing is left to the compiler:
+// contraction is off and each fused multiply-add is written as one.
+template <int DT, int V>
+__device__ __forceinline__ void sampler_update(float c_x, float c_e, float c_m, float c_z, float d_x, float d_e, float x, float e, float m1, float zz,
+                                               float& xn, float& m0) {
+#pragma clang fp contract(off)
+    if constexpr (V == 8) {
+        xn = fmaf(c_z, zz, fmaf(c_m, m1, fmaf(c_x, x, c_e * e)));
+        m0 = fmaf(d_x, x, d_e * e);
+    } else if constexpr (DT == APAD_F32) {
+        xn = fmaf(c_z, zz, fmaf(c_m, m1, fmaf(c_e, e, c_x * x)));
+        m0 = d_x * x + d_e * e;
+    } else {
+        xn = ((c_x * x + c_e * e) + c_m * m1) + c_z * zz;
+        m0 = d_x * x + d_e * e;
+    }
+}
+
+// known = fma(kx, x0, kz * z0);  x' = fma(m, g, (1 - m) * known): m = 1 leaves the bits of g, m = 0 those of known, (kx, kz) = (1, 0) makes known x0
+__device__ __forceinline__ float edit_known(float kx, float kz, float x0, float z0) {
+#pragma clang fp contract(off)
+    return fmaf(kx, x0, kz * z0);
+}
+__device__ __forceinline__ float edit_blend(float m, float g, float kx, float kz, float x0, float z0) {
+#pragma clang fp contract(off)
+    return fmaf(m, g, (1.0f - m) * edit_known(kx, kz, x0, z0));
+}
+
+// cfg_sampler_kernel's step followed by the edit blend (scheduler.py ``keep`` table, row s = (kx, kz)): with g the sampler's update,
+//   known = fma(kx, x0, kz * z0)   -- the source at the noise level the step lands on ((1, 0) on the last step: the bits of x0)
+//   x'    = fma(m, g, (1 - m) * known),  m = mask[pixel] in [0, 1]  -- m = 1 leaves the bits of g, m = 0 those of known
+// mask fp32 [mask_batch][n / C], element j of a clip belongs to pixel j / C (NHWC, channel fastest).  V = 8 requires C == 8: one vector is one
+// pixel and takes one mask value.  The data prediction m0 is formed from the pre-blend x and eps, as in cfg_sampler_kernel.  A null mask is
+// m = 1 everywhere (the plain sampler step).
+template <int DT, int V>
+__global__ __launch_bounds__(256) void cfg_edit_kernel(const uint8_t* eps2, float* latents, uint8_t* unet_in, float* eps_out, float* hist,
+                                                       const float* noise, const float* coef, const float* keep, const float* x0, const float* z0,
+                                                       const float* mask, int mask_per_clip, int C, int64_t n, const int32_t* step_ptr, int n_steps,
+                                                       float gs, int64_t total) {
+    int step = step_ptr ? *step_ptr : 0;
+    step = step < 0 ? 0 : (step >= n_steps ? n_steps - 1 : step);  // the tables and the noise buffer have n_steps rows
+    const float* r = coef + 6 * step;
+    const float c_x = r[0], c_e = r[1], c_m = r[2], c_z = r[3], d_x = r[4], d_e = r[5];
+    const float kx = mask ? keep[2 * step] : 0.f, kz = mask ? keep[2 * step + 1] : 0.f;
+    const bool use_m1 = hist && c_m != 0.f, use_z = noise && c_z != 0.f;
+    const float* z = noise + (use_z ? (int64_t)step * total : 0);
+    const int64_t npix = n / C;  // pixels per clip
+    for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * V; i < total; i += (int64_t)gridDim.x * 256 * V) {
+        float eu[V], ec[V], x[V], m1[V], zz[V], e[V], m0[V];
+        ld_elemv<DT, V>(eps2, i, eu);
+        ld_elemv<DT, V>(eps2, total + i, ec);
+        ld_f32v<V>(latents, i, x);
+#pragma unroll
+        for (int j = 0; j < V; ++j) m1[j] = zz[j] = 0.f;
+        if (use_m1) ld_f32v<V>(hist, i, m1);
+        if (use_z) ld_f32v<V>(z, i, zz);
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            e[j] = (float)(typename ET<DT>::elem)fmaf(gs, ec[j] - eu[j], eu[j]);
+            float xn;
+            sampler_update<DT, V>(c_x, c_e, c_m, c_z, d_x, d_e, x[j], e[j], m1[j], zz[j], xn, m0[j]);
+            x[j] = xn;
+        }
+        if (mask) {
+            const int64_t pix = V == 8 ? (i >> 3) : i / C;  // over the whole batch: clip * npix + pixel
+            const float m = mask[mask_per_clip ? pix : pix % npix];
+            float a[V], b[V];
+            ld_f32v<V>(x0, i, a);
+            ld_f32v<V>(z0, i, b);
+#pragma unroll
+            for (int j = 0; j < V; ++j) x[j] = edit_blend(m, x[j], kx, kz, a[j], b[j]);
+        }
+        st_f32v<V>(latents, i, x);
+        st_elemv<DT, V>(unet_in, i, x);
+        if (hist) st_f32v<V>(hist, i, m0);
+        if (eps_out) st_f32v<V>(eps_out, i, e);
+    }
+}
+
+// The three buffers an edit run starts from, in the loop's layout (NHWC, [rows = B * h * w][Lc]), in one pass:
+//   x0 = (mean + exp(0.5 * clamp(logvar, -30, 20)) * post_noise) * scale   (gaussian_sample_kernel's draw, kept in fp32; or, with null moments,
+//        the x0 already there),   latents = fma(a, x0, s * z0)   (add_noise at the start timestep),   unet_in = latents in the model dtype.
+// V = 8 requires Lc == 8: one vector is one latent pixel, its mean at moments + 16 * row and its logvar 8 elements further.
+template <int DT, int V>
+__global__ __launch_bounds__(256) void edit_start_kernel(const uint8_t* moments, const float* post_noise, const float* z0, float* x0, float* latents,
+                                                         uint8_t* unet_in, float a, float s, float scale, int64_t total, int Lc) {
+    for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * V; i < total; i += (int64_t)gridDim.x * 256 * V) {
+        float x[V], zz[V];
+        if (moments) {
+            const int64_t row = V == 8 ? (i >> 3) : i / Lc;
+            const int64_t mo = row * 2 * Lc + (i - row * Lc);
+            float mean[V], lv[V], pn[V];
+            ld_elemv<DT, V>(moments, mo, mean);
+            ld_elemv<DT, V>(moments, mo + Lc, lv);
+            ld_f32v<V>(post_noise, i, pn);
+#pragma unroll
+            for (int j = 0; j < V; ++j) x[j] = (mean[j] + expf(0.5f * fminf(fmaxf(lv[j], -30.0f), 20.0f)) * pn[j]) * scale;
+            st_f32v<V>(x0, i, x);
+        } else {
+            ld_f32v<V>(x0, i, x);
+        }
+        ld_f32v<V>(z0, i, zz);
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            x[j] = edit_known(a, s, x[j], zz[j]);  // the source at the start timestep's noise level
+            // unet_in is the copy of the fp32 master: keep the compiler from folding the f16 store into the multiply-add (v_fma_mixlo_f16
+            // rounds the exact sum once, and the copy would differ from the rounded master in the last f16 bit)
+            asm volatile("" : "+v"(x[j]));
+        }
+        st_f32v<V>(latents, i, x);
+        st_elemv<DT, V>(unet_in, i, x);
     }
 }
 
@@ -331,6 +448,82 @@ extern "C" int apad_cfg_sampler_step(const void* eps2, float* latents, void* une
     else
         launch_cfg_sampler<APAD_F16>(vec, (unsigned)blocks, s, eps2, latents, unet_in, eps_out, history, noise, coef, step_ptr, n_steps, guidance_scale, total);
     return apad_check_launch("apad_cfg_sampler_step");
+}
+
+namespace {
+template <int DT>
+void launch_cfg_edit(bool vec, unsigned blocks, hipStream_t s, const void* eps2, float* latents, void* unet_in, float* eps_out, float* history,
+                     const float* noise, const float* coef, const float* keep, const float* x0, const float* z0, const float* mask, int per_clip, int C,
+                     int64_t n, const int32_t* step_ptr, int32_t n_steps, float gs, int64_t total) {
+    if (vec)
+        hipLaunchKernelGGL((cfg_edit_kernel<DT, 8>), dim3(blocks), dim3(256), 0, s, (const uint8_t*)eps2, latents, (uint8_t*)unet_in, eps_out, history,
+                           noise, coef, keep, x0, z0, mask, per_clip, C, n, step_ptr, n_steps, gs, total);
+    else
+        hipLaunchKernelGGL((cfg_edit_kernel<DT, 1>), dim3(blocks), dim3(256), 0, s, (const uint8_t*)eps2, latents, (uint8_t*)unet_in, eps_out, history,
+                           noise, coef, keep, x0, z0, mask, per_clip, C, n, step_ptr, n_steps, gs, total);
+}
+template <int DT>
+void launch_edit_start(bool vec, unsigned blocks, hipStream_t s, const void* moments, const float* post_noise, const float* z0, float* x0, float* latents,
+                       void* unet_in, float a, float sg, float scale, int64_t total, int Lc) {
+    if (vec)
+        hipLaunchKernelGGL((edit_start_kernel<DT, 8>), dim3(blocks), dim3(256), 0, s, (const uint8_t*)moments, post_noise, z0, x0, latents,
+                           (uint8_t*)unet_in, a, sg, scale, total, Lc);
+    else
+        hipLaunchKernelGGL((edit_start_kernel<DT, 1>), dim3(blocks), dim3(256), 0, s, (const uint8_t*)moments, post_noise, z0, x0, latents,
+                           (uint8_t*)unet_in, a, sg, scale, total, Lc);
+}
+}  // namespace
+
+extern "C" int apad_cfg_edit_step(const void* eps2, float* latents, void* unet_in, float* eps_out, float* history, const float* noise,
+                                  const float* coef, const float* keep, const float* x0, const float* z0, const float* mask, int32_t mask_batch,
+                                  int32_t C, const int32_t* step_ptr, int32_t n_steps, float guidance_scale, int32_t B, int64_t n, int32_t dtype,
+                                  void* stream) {
+    APAD_CHECK(eps2 && latents && unet_in && coef, "apad_cfg_edit_step: null operand");
+    APAD_CHECK(dtype == APAD_BF16 || dtype == APAD_F16 || dtype == APAD_F32, "apad_cfg_edit_step: dtype %d not supported", dtype);
+    APAD_CHECK(B > 0 && n > 0 && n_steps > 0, "apad_cfg_edit_step: empty problem");
+    if (mask) {
+        APAD_CHECK(keep && x0 && z0, "apad_cfg_edit_step: a mask needs the keep table, x0 and z0 (null operand)");
+        APAD_CHECK(mask_batch == 1 || mask_batch == B, "apad_cfg_edit_step: mask_batch %d must be 1 or B = %d", mask_batch, B);
+        APAD_CHECK(C > 0 && n % C == 0, "apad_cfg_edit_step: n = %lld is not a multiple of C = %d", (long long)n, C);
+    }
+    const int64_t total = (int64_t)B * n;
+    // cfg_sampler_step's rule (every base 16-byte aligned, 8 | total) plus C == 8, which makes one 8-element vector one pixel
+    const uintptr_t bases = (uintptr_t)eps2 | (uintptr_t)latents | (uintptr_t)unet_in | (uintptr_t)eps_out | (uintptr_t)history | (uintptr_t)noise |
+                            (uintptr_t)x0 | (uintptr_t)z0;
+    const bool vec = total % 8 == 0 && bases % 16 == 0 && (!mask || C == 8);
+    int64_t blocks = ((vec ? total / 8 : total) + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    hipStream_t s = (hipStream_t)stream;
+    const int per_clip = mask_batch == B && B > 1;
+    const int Cc = mask ? C : 1;
+    if (dtype == APAD_F32)
+        launch_cfg_edit<APAD_F32>(vec, (unsigned)blocks, s, eps2, latents, unet_in, eps_out, history, noise, coef, keep, x0, z0, mask, per_clip, Cc, n,
+                                  step_ptr, n_steps, guidance_scale, total);
+    else if (dtype == APAD_BF16)
+        launch_cfg_edit<APAD_BF16>(vec, (unsigned)blocks, s, eps2, latents, unet_in, eps_out, history, noise, coef, keep, x0, z0, mask, per_clip, Cc, n,
+                                   step_ptr, n_steps, guidance_scale, total);
+    else
+        launch_cfg_edit<APAD_F16>(vec, (unsigned)blocks, s, eps2, latents, unet_in, eps_out, history, noise, coef, keep, x0, z0, mask, per_clip, Cc, n,
+                                  step_ptr, n_steps, guidance_scale, total);
+    return apad_check_launch("apad_cfg_edit_step");
+}
+
+extern "C" int apad_edit_start(const void* moments, const float* post_noise, const float* z0, float* x0_out, float* latents, void* unet_in, float a,
+                               float s, float scale, int64_t rows, int32_t Lc, int32_t dtype, void* stream) {
+    APAD_CHECK(z0 && x0_out && latents && unet_in, "apad_edit_start: null operand");
+    APAD_CHECK(!moments || post_noise, "apad_edit_start: moments need post_noise (null operand)");
+    APAD_CHECK(dtype == APAD_BF16 || dtype == APAD_F16 || dtype == APAD_F32, "apad_edit_start: dtype %d not supported", dtype);
+    APAD_CHECK(rows > 0 && Lc > 0, "apad_edit_start: empty problem (rows=%lld Lc=%d)", (long long)rows, Lc);
+    const int64_t total = rows * Lc;
+    const uintptr_t bases = (uintptr_t)moments | (uintptr_t)post_noise | (uintptr_t)z0 | (uintptr_t)x0_out | (uintptr_t)latents | (uintptr_t)unet_in;
+    const bool vec = Lc == 8 && bases % 16 == 0;
+    int64_t blocks = ((vec ? total / 8 : total) + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == APAD_F32) launch_edit_start<APAD_F32>(vec, (unsigned)blocks, st, moments, post_noise, z0, x0_out, latents, unet_in, a, s, scale, total, Lc);
+    else if (dtype == APAD_BF16) launch_edit_start<APAD_BF16>(vec, (unsigned)blocks, st, moments, post_noise, z0, x0_out, latents, unet_in, a, s, scale, total, Lc);
+    else launch_edit_start<APAD_F16>(vec, (unsigned)blocks, st, moments, post_noise, z0, x0_out, latents, unet_in, a, s, scale, total, Lc);
+    return apad_check_launch("apad_edit_start");
 }
 
 extern "C" int apad_mix3(const void* a, const void* b, const void* c, void* out, int64_t n, float scale, int32_t dtype, void* stream) {

@@ -1132,6 +1132,64 @@ def cfg_sampler_step(eps2, latents, unet_in, coef, step_ptr, guidance_scale, eps
             "apad_cfg_sampler_step")
 
 
+def cfg_edit_step(eps2, latents, unet_in, coef, keep, step_ptr, guidance_scale, x0, z0, mask, channels=8, eps_out=None, history=None, noise=None):
+    """cfg_sampler_step followed by the edit blend: keep fp32 [steps, 2] (scheduler ``SamplerPlan.keep``), x0 / z0 fp32 like latents (the
+    source latents and the noise that built the start), mask fp32 [1 or B, n / channels] with 1 = regenerate and 0 = keep;
+    latents [B, n...] are NHWC with ``channels`` fastest.  mask = None is cfg_sampler_step."""
+    _req(latents, "cfg_edit_step.latents", torch.float32)
+    _req(coef, "cfg_edit_step.coef", torch.float32)
+    if coef.dim() != 2 or coef.shape[1] != 6 or not coef.is_contiguous():
+        raise RuntimeError(f"cfg_edit_step.coef: expected a contiguous [steps, 6] table, got {tuple(coef.shape)}")
+    steps = coef.shape[0]
+    B = latents.shape[0]
+    n = latents.numel() // B
+    if eps2.dtype != unet_in.dtype or eps2.numel() != 2 * latents.numel() or unet_in.numel() != latents.numel():
+        raise RuntimeError("cfg_edit_step: eps2 [2B, n] and unet_in [B, n] must share the model dtype and match latents [B, n]")
+    for t, name, numel in ((eps_out, "eps_out", latents.numel()), (history, "history", latents.numel()), (noise, "noise", steps * latents.numel()),
+                           (x0, "x0", latents.numel()), (z0, "z0", latents.numel()), (keep, "keep", 2 * steps)):
+        if t is not None and (_req(t, "cfg_edit_step." + name, torch.float32).numel() != numel or not t.is_contiguous()):
+            raise RuntimeError(f"cfg_edit_step.{name}: expected {numel} contiguous fp32 values, got {tuple(t.shape)}")
+    mask_batch = 0
+    if mask is not None:
+        _req(mask, "cfg_edit_step.mask", torch.float32)
+        channels = int(channels)
+        # (n % channels != 0 and a mask batch other than 1 or B are the entry point's own checks)
+        if mask.dim() != 2 or not mask.is_contiguous() or (channels > 0 and n % channels == 0 and mask.shape[1] != n // channels):
+            raise RuntimeError(f"cfg_edit_step.mask: expected a contiguous [1 or B, n / channels] table with n = {n}, channels = {channels}, "
+                               f"got {tuple(mask.shape)}")
+        mask_batch = mask.shape[0]  # 1 or B: the entry point checks it
+    L.check(L.lib().apad_cfg_edit_step(eps2.data_ptr(), latents.data_ptr(), unet_in.data_ptr(), _ptr(eps_out), _ptr(history), _ptr(noise),
+                                       coef.data_ptr(), _ptr(keep), _ptr(x0), _ptr(z0), _ptr(mask), mask_batch, int(channels), _ptr(step_ptr), steps,
+                                       float(guidance_scale), B, n, _DT[eps2.dtype], _stream()), "apad_cfg_edit_step")
+
+
+def edit_start(z0, x0, latents, unet_in, a, s, moments=None, post_noise=None, scale=1.0):
+    """the start of an edit run, written into the loop's buffers: with ``moments`` [rows, 2L] = (mean | logvar) in unet_in's dtype and
+    ``post_noise`` fp32 [rows, L], x0 <- (mean + exp(0.5 clamp(logvar, -30, 20)) post_noise) * scale; without, x0 holds the source latents
+    already.  Then latents <- a x0 + s z0 (fp32) and unet_in <- latents.  z0 / x0 / latents fp32 [rows, L] (any shape of that size)."""
+    _req(z0, "edit_start.z0", torch.float32)
+    numel = z0.numel()
+    for t, name in ((x0, "x0"), (latents, "latents")):
+        if _req(t, "edit_start." + name, torch.float32).numel() != numel or not t.is_contiguous():
+            raise RuntimeError(f"edit_start.{name}: expected {numel} contiguous fp32 values, got {tuple(t.shape)}")
+    _req(unet_in, "edit_start.unet_in")
+    if unet_in.numel() != numel or not unet_in.is_contiguous() or not z0.is_contiguous():
+        raise RuntimeError(f"edit_start: z0 and unet_in must be contiguous with {numel} values")
+    if moments is None:
+        Lc = z0.shape[-1]
+        if post_noise is not None:
+            raise RuntimeError("edit_start.post_noise: given without moments")
+    else:
+        _req(moments, "edit_start.moments", unet_in.dtype)
+        if moments.dim() != 2 or not moments.is_contiguous() or moments.numel() != 2 * numel:
+            raise RuntimeError(f"edit_start.moments: expected a contiguous [rows, 2L] tensor of {2 * numel} values, got {tuple(moments.shape)}")
+        Lc = moments.shape[1] // 2
+        if post_noise is None or _req(post_noise, "edit_start.post_noise", torch.float32).numel() != numel or not post_noise.is_contiguous():
+            raise RuntimeError(f"edit_start.post_noise: expected {numel} contiguous fp32 values")
+    L.check(L.lib().apad_edit_start(_ptr(moments), _ptr(post_noise), z0.data_ptr(), x0.data_ptr(), latents.data_ptr(), unet_in.data_ptr(), float(a),
+                                    float(s), float(scale), numel // Lc, Lc, _DT[unet_in.dtype], _stream()), "apad_edit_start")
+
+
 def step_advance(step_ptr):
     L.check(L.lib().apad_step_advance(step_ptr.data_ptr(), _stream()), "apad_step_advance")
 

@@ -12,6 +12,12 @@ MI355X-first structure of the loop:
     eta > 0 from pre-drawn noise, DPM-Solver++ 2M with its history buffer); the step index is a device counter -> zero host
     synchronisation inside the loop
   * the whole step (UNet on the duplicated batch, CFG, DDIM, counter) is captured once as a hipGraph and replayed
+
+Editing from a source clip (``source_audio`` / ``source_mel`` / ``source_latents``, ``strength``, ``edit_mask`` / ``edit_region``; no working
+counterpart in the reference -- its pipeline/style_transfer_pipeline.py:908-936 starts on it and does not import; diffusers' img2img / inpaint
+conventions, PARITY UNPINNED): the VAE posterior draw, ``add_noise`` to the start timestep and the loop's three buffers are one launch
+(``apad_edit_start``), the run visits ``timesteps[k:]``, and with a mask the captured step's update kernel is ``apad_cfg_edit_step``, which
+re-imposes the kept region at every step's noise level.  A call without a source takes none of this.
 """
 from dataclasses import dataclass
 from typing import Optional, Union
@@ -19,7 +25,7 @@ from typing import Optional, Union
 import torch
 
 from . import ops
-from .scheduler import DDIMScheduler, DPMSolverMultistepScheduler
+from .scheduler import DDIMScheduler, DPMSolverMultistepScheduler, edit_start_index
 
 
 @dataclass
@@ -27,10 +33,26 @@ class AudioPipelineOutput:
     audios: torch.Tensor = None
 
 
+@dataclass
+class EditSource:
+    """what ``denoise(source=)`` starts an edit run from.  ``z0`` fp32 [B, C, H, W]: the noise of the start, and of the kept region at
+    every step.  The source latents: either ``x0`` fp32 [B, C, H, W] (already multiplied by the VAE's scaling_factor), or the VAE
+    posterior ``moments`` [B * H * W, 2 C] (mean | logvar per latent pixel, NHWC, as ``vae.encode(mel).latent_dist`` holds them) with
+    ``post_noise`` fp32 [B, C, H, W] and ``scale`` = scaling_factor.  ``mask`` fp32 [1 or B, 1, H, W] in [0, 1], 1 = regenerate,
+    0 = keep; None = no region (strength only)."""
+    z0: torch.Tensor
+    x0: torch.Tensor = None
+    moments: torch.Tensor = None
+    post_noise: torch.Tensor = None
+    scale: float = 1.0
+    mask: torch.Tensor = None
+
+
 class AudioLDM2Pipeline:
     vae_scale_factor = 4           # AutoencoderKL of AudioLDM2: 2 ** (len(block_out_channels) - 1)
     vocoder_model_in_dim = 64      # mel bins
     vocoder_upsample_factor = 0.01  # prod(upsample_rates) / sampling_rate = 160 / 16000
+    latent_row_seconds = 0.04      # one latent row = vae_scale_factor mel frames of vocoder_upsample_factor seconds
 
     def __init__(self, unet, scheduler: Optional[Union[DDIMScheduler, DPMSolverMultistepScheduler]] = None, audiomae=None, vocoder=None, vae=None, prompt_encoder=None,
                  tokenizer=None, tokenizer_2=None):
@@ -163,6 +185,128 @@ class AudioLDM2Pipeline:
         neg, pos = generated_prompt_embeds.to(dtype).chunk(2)
         return torch.cat([torch.cat([neg, u], dim=1), torch.cat([pos, a], dim=1)], dim=0).contiguous()
 
+    # ---- editing from a source clip ----
+    def check_edit_arguments(self, batch, height, num_inference_steps, audio_length_in_s, latents, source_audio, source_mel, source_latents,
+                             strength, edit_mask, edit_region):
+        """every argument check of an edit call, on the host, before any device work; each ValueError names the offending argument.
+        Returns (k, mask): the start index into the timestep grid and the fp32 mask [1 or B, 1, H, W] (None without one)."""
+        H, W = height // self.vae_scale_factor, self.vocoder_model_in_dim // self.vae_scale_factor
+        try:
+            ok = 0.0 < float(strength) <= 1.0
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError(f"strength={strength!r} must lie in (0, 1]")
+        given = [n for n, v in (("source_audio", source_audio), ("source_mel", source_mel), ("source_latents", source_latents)) if v is not None]
+        if not given:
+            for n, bad in (("strength", float(strength) != 1.0), ("edit_mask", edit_mask is not None), ("edit_region", edit_region is not None)):
+                if bad:
+                    raise ValueError(f"{n} needs a source clip (source_audio=, source_mel= or source_latents=)")
+            return 0, None
+        if len(given) > 1:
+            raise ValueError(f"{' and '.join(given)} are both given: pass one form of the source")
+        if latents is not None:
+            raise ValueError("latents= cannot be combined with a source clip: the run starts from the noised source")
+        if edit_mask is not None and edit_region is not None:
+            raise ValueError("edit_mask and edit_region are both given: pass one of them")
+        if source_latents is None and self.vae is None:
+            raise ValueError(f"{given[0]} needs vae=ap_adapter_amd.AutoencoderKL to encode the clip (or pass source_latents=)")
+        if source_mel is not None:
+            shp = tuple(source_mel.shape)
+            if len(shp) not in (2, 3, 4) or shp[-1] != self.vocoder_model_in_dim or (len(shp) == 4 and shp[1] != 1):
+                raise ValueError(f"source_mel {shp}: expected [frames, {self.vocoder_model_in_dim}], [b, frames, ...] or [b, 1, frames, ...]")
+            if shp[-2] != height:
+                raise ValueError(f"source_mel has {shp[-2]} frames; this call's height (audio_length_in_s={audio_length_in_s}) is {height}")
+            b = 1 if len(shp) == 2 else shp[0]
+            if b != 1 and batch % b != 0:
+                raise ValueError(f"source_mel holds {b} clips for a batch of {batch}")
+        if source_latents is not None:
+            shp = tuple(source_latents.shape)
+            C = self.unet.config.in_channels
+            if len(shp) != 4 or shp[1] != C or shp[3] != W:
+                raise ValueError(f"source_latents {shp}: expected [b, {C}, rows, {W}]")
+            if shp[2] != H:
+                raise ValueError(f"source_latents has {shp[2]} rows; this call's height {height} (audio_length_in_s={audio_length_in_s}) is {H} rows")
+            if shp[0] != 1 and batch % shp[0] != 0:
+                raise ValueError(f"source_latents holds {shp[0]} clips for a batch of {batch}")
+        if source_audio is not None and not isinstance(source_audio, str):
+            if len(source_audio) == 0 or (len(source_audio) != 1 and batch % len(source_audio) != 0):
+                raise ValueError(f"source_audio holds {len(source_audio)} files for a batch of {batch}")
+        mask = None
+        if edit_region is not None:
+            try:
+                t0, t1 = (float(v) for v in edit_region)
+            except (TypeError, ValueError):
+                raise ValueError(f"edit_region={edit_region!r}: expected (start_s, end_s)") from None
+            r0, r1 = int(round(t0 / self.latent_row_seconds)), int(round(t1 / self.latent_row_seconds))
+            if not (0.0 <= t0 < t1 and r0 < r1 <= H):
+                raise ValueError(f"edit_region={edit_region!r}: expected 0 <= start_s < end_s <= {H * self.latent_row_seconds:.2f} s, at "
+                                 f"least one latent row ({self.latent_row_seconds} s) apart")
+            mask = torch.zeros(1, 1, H, W, dtype=torch.float32)
+            mask[:, :, r0:r1] = 1.0
+        if edit_mask is not None:
+            mask = torch.as_tensor(edit_mask).detach().to(torch.float32)
+            if mask.dim() > 4:
+                raise ValueError(f"edit_mask {tuple(mask.shape)} is not broadcastable to [{batch}, 1, {H}, {W}]")
+            mask = mask.reshape((1,) * (4 - mask.dim()) + tuple(mask.shape))
+            try:
+                ok = torch.broadcast_shapes(tuple(mask.shape), (batch, 1, H, W)) == (batch, 1, H, W)
+            except RuntimeError:
+                ok = False
+            if not ok:
+                raise ValueError(f"edit_mask {tuple(edit_mask.shape) if hasattr(edit_mask, 'shape') else tuple(mask.shape)} is not broadcastable "
+                                 f"to [{batch}, 1, {H}, {W}]")
+            if mask.numel() and not (float(mask.min()) >= 0.0 and float(mask.max()) <= 1.0):  # (also false for NaN)
+                raise ValueError("edit_mask values must lie in [0, 1] (1 = regenerate, 0 = keep)")
+            mask = mask.expand(mask.shape[0], 1, H, W).contiguous()
+        return edit_start_index(num_inference_steps, strength), mask
+
+    def prepare_edit_source(self, batch, height, device, generator, source_audio=None, source_mel=None, source_latents=None, mask=None):
+        """The ``EditSource`` of a call.  Generator draw order, each on the generator's own device like ``prepare_latents``: the posterior
+        noise [B, C, H, W] (skipped for ``source_latents``), then z0 [B, C, H, W]; a stochastic sampler's per-step noise follows in
+        ``denoise``.  A source of fewer clips than the batch is repeated per clip (``num_waveforms_per_prompt``)."""
+        C, H, W = self.unet.config.in_channels, height // self.vae_scale_factor, self.vocoder_model_in_dim // self.vae_scale_factor
+        shape = (batch, C, H, W)
+        gdev = generator.device if generator is not None else torch.device("cpu")
+        rep = lambda t: t.repeat_interleave(batch // t.shape[0], dim=0) if t.shape[0] != batch else t
+        src = EditSource(z0=None, mask=mask)
+        if source_latents is not None:
+            src.x0 = rep(source_latents.to(device, torch.float32))
+        else:
+            if source_audio is not None:
+                from .frontend import wav_to_mel
+                paths = [source_audio] if isinstance(source_audio, str) else list(source_audio)
+                # target_length = int(duration * 102.4): (height + 0.5) / 102.4 lands on ``height`` frames whatever the rounding
+                source_mel = torch.stack([wav_to_mel(p, (height + 0.5) / 102.4, device=device) for p in paths])
+            mel = rep(source_mel.to(device).reshape(-1, 1, height, self.vocoder_model_in_dim))
+            dist = self.vae.encode(mel).latent_dist
+            if tuple(dist._geom) != (batch, H, W, C):
+                raise ValueError(f"the VAE encodes the source to (B, H, W, C) = {tuple(dist._geom)}; the UNet's latents are {(batch, H, W, C)}")
+            src.moments = dist._m.reshape(batch * H * W, 2 * C)
+            src.scale = float(getattr(getattr(self.vae, "config", None), "scaling_factor", 1.0))
+            src.post_noise = torch.randn(shape, generator=generator, device=gdev, dtype=torch.float32)
+        src.z0 = torch.randn(shape, generator=generator, device=gdev, dtype=torch.float32)
+        return src
+
+    def _fill_edit_buffers(self, e, src, a, s):
+        """x0 / z0 / mask and the start (fp32 master + model-dtype copy) of an edit run, written in place into the loop's static buffers"""
+        lat, unet_in = e["lat"], e["unet_in"]
+        B, HW, C = lat.shape
+        nhwc = lambda t: t.to(lat.device, torch.float32).permute(0, 2, 3, 1).reshape(B, HW, C)
+        e["z0"].copy_(nhwc(src.z0))
+        if src.moments is not None:
+            m = src.moments.to(lat.device).contiguous()
+            # the kernel reads the moments and writes unet_in in ONE dtype: a VAE held in another precision than the UNet keeps its own
+            out = unet_in if m.dtype == unet_in.dtype else torch.empty_like(lat, dtype=m.dtype)
+            ops.edit_start(e["z0"], e["x0"], lat, out, a, s, moments=m, post_noise=nhwc(src.post_noise).contiguous(), scale=src.scale)
+            if out is not unet_in:
+                unet_in.copy_(lat)
+        else:
+            e["x0"].copy_(nhwc(src.x0))
+            ops.edit_start(e["z0"], e["x0"], lat, unet_in, a, s)
+        if e["emask"] is not None:
+            e["emask"].copy_(src.mask.to(lat.device, torch.float32).reshape(e["emask"].shape))
+
     # ---- the loop ----
     MAX_CACHED_GRAPHS = 4  # each holds its activation pool (GBs at batch 32): least-recently-used entries are dropped
 
@@ -186,28 +330,54 @@ class AudioLDM2Pipeline:
 
     @torch.no_grad()
     def denoise(self, latents_nchw, generated_prompt_embeds, prompt_embeds, attention_mask, num_inference_steps,
-                guidance_scale, use_graph=True, callback=None, callback_steps=1, keep_noise_pred=False, eta=0.0, generator=None):
+                guidance_scale, use_graph=True, callback=None, callback_steps=1, keep_noise_pred=False, eta=0.0, generator=None, *,
+                source=None, start=0):
         """CFG + scheduler loop (:983-1031).  With ``use_graph`` the step is captured ONCE per (batch, token counts, steps, guidance,
         weights, sampler) and kept: later calls copy their latents / conditions into the graph's static buffers, refresh the hoisted
         K/V in place and replay -- no warm-up step, no re-capture (a sharded job runs many batches through one pipeline).
         ``self.scheduler.sampler_plan(eta)`` names the update kernel, its coefficient table and the per-sampler state that lives with the
         captured step: the data-prediction history of the multistep solver (zeroed before every run) and the per-step noise of DDIM
-        with ``eta`` > 0 (drawn from ``generator`` before the loop, ``prepare_step_noise``)."""
+        with ``eta`` > 0 (drawn from ``generator`` before the loop, ``prepare_step_noise``).
+
+        ``source`` (an ``EditSource``, or the fp32 (x0, z0, mask) triple, each [B, C, H, W] / mask [1 or B, 1, H, W] or None) makes this
+        an edit run entering the timestep grid at index ``start``: ``latents_nchw`` is then unused (pass None) -- the run starts from
+        ``add_noise(x0, z0, timesteps[start])`` -- it visits ``timesteps[start:]``, and with a mask every step re-imposes the kept
+        region.  x0 / z0 / mask live with the captured step as static buffers, refilled in place on a cache hit."""
         unet = self.unet
-        dev = latents_nchw.device
         dtype = unet.conv_in.weight.dtype
-        B, Cc, H, W = latents_nchw.shape
+        src = None
+        if source is not None:
+            src = source if isinstance(source, EditSource) else EditSource(x0=source[0], z0=source[1], mask=source[2])
+            if latents_nchw is not None:
+                raise ValueError("latents_nchw must be None when source= is given: the run starts from the noised source")
+            dev = unet.conv_in.weight.device
+            B, Cc, H, W = src.z0.shape
+        elif start:
+            raise ValueError(f"start={start} needs source=")
+        else:
+            dev = latents_nchw.device
+            B, Cc, H, W = latents_nchw.shape
         if not guidance_scale > 1.0:
             raise NotImplementedError("the audio-conditioned path requires classifier-free guidance (:941 chunk(2))")
         sched = self.scheduler
         sched.set_timesteps(num_inference_steps)
-        plan = sched.sampler_plan(eta)
+        if src is None:
+            plan, n_run, emask_shape = sched.sampler_plan(eta), num_inference_steps, None
+        else:
+            plan = sched.sampler_plan(eta, start=start, masked=src.mask is not None)
+            n_run = num_inference_steps - plan.start
+            noise_a, noise_s = sched.add_noise_coefs(plan.start)
+            emask_shape = None if src.mask is None else (src.mask.shape[0], H * W)
+            if emask_shape is not None and (tuple(src.mask.shape[1:]) != (1, H, W) or emask_shape[0] not in (1, B)):
+                raise ValueError(f"source mask {tuple(src.mask.shape)}: expected [1 or {B}, 1, {H}, {W}]")
         graphed = use_graph and callback is None
         key = (B, Cc, H, W, tuple(generated_prompt_embeds.shape), tuple(prompt_embeds.shape),
                None if attention_mask is None else (tuple(attention_mask.shape), attention_mask.dtype), num_inference_steps,
                float(guidance_scale), dtype, bool(keep_noise_pred), str(dev),
                ops.get_float32_matmul_precision() if dtype == torch.float32 else None,  # (a step captured in one precision never replays in the other)
                plan.key)  # (... nor one captured for another sampler / eta: the table and the update kernel are baked in)
+        if src is not None:  # an edit run: start index and masked flag are in plan.key; the mask's batch form selects the kernel's indexing
+            key += (("edit", emask_shape),)
         e = None
         if graphed:
             wsig = self._weights_signature()
@@ -217,8 +387,11 @@ class AudioLDM2Pipeline:
                 e = None
         if e is not None:
             self._graphs[key] = self._graphs.pop(key)  # most recently used last
-            e["lat"].copy_(latents_nchw.float().permute(0, 2, 3, 1).reshape(B, H * W, Cc))
-            e["unet_in"].copy_(e["lat"])
+            if src is None:
+                e["lat"].copy_(latents_nchw.float().permute(0, 2, 3, 1).reshape(B, H * W, Cc))
+                e["unet_in"].copy_(e["lat"])
+            else:
+                self._fill_edit_buffers(e, src, noise_a, noise_s)
             e["gen"].copy_(generated_prompt_embeds)
             e["pe"].copy_(prompt_embeds)
             if attention_mask is not None:
@@ -227,31 +400,38 @@ class AudioLDM2Pipeline:
             if e["hist"] is not None:
                 e["hist"].zero_()
             if e["noise"] is not None:
-                self.prepare_step_noise(B, Cc, H, W, num_inference_steps, generator, out=e["noise"])
+                self.prepare_step_noise(B, Cc, H, W, n_run, generator, out=e["noise"])
             unet.set_kv_cache(True, clear=False)
             try:
                 unet.refresh_kv_cache()  # hoisted K/V of the new conditions, recomputed into the buffers the graph reads
             finally:
                 unet.set_kv_cache(False, clear=False)  # (see the end of the capture branch)
-            for _ in range(num_inference_steps):
+            for _ in range(n_run):
                 e["graph"].replay()
             self.graph_hits += 1
         else:
-            e = {"lat": latents_nchw.float().permute(0, 2, 3, 1).reshape(B, H * W, Cc).contiguous(),  # fp32 master, NHWC
+            e = {"lat": (latents_nchw.float().permute(0, 2, 3, 1).reshape(B, H * W, Cc).contiguous() if src is None  # fp32 master, NHWC
+                         else torch.empty(B, H * W, Cc, dtype=torch.float32, device=dev)),
                  "gen": generated_prompt_embeds.to(dtype).contiguous().clone(), "pe": prompt_embeds.to(dtype).contiguous().clone(),
                  "mask": None if attention_mask is None else attention_mask.clone(),
                  "coef": plan.table.to(dev), "step_ptr": torch.zeros(1, dtype=torch.int32, device=dev)}
             e["unet_in"] = e["lat"].to(dtype).clone() if dtype == torch.float32 else e["lat"].to(dtype)
+            if src is not None:
+                e["x0"], e["z0"] = torch.empty_like(e["lat"]), torch.empty_like(e["lat"])
+                e["emask"] = None if emask_shape is None else torch.empty(emask_shape, dtype=torch.float32, device=dev)
+                e["keep"] = None if plan.keep is None else plan.keep.to(dev)
+                self._fill_edit_buffers(e, src, noise_a, noise_s)
             e["eps_out"] = torch.empty_like(e["lat"]) if keep_noise_pred else None
             e["hist"] = torch.zeros_like(e["lat"]) if plan.needs_history else None
-            e["noise"] = self.prepare_step_noise(B, Cc, H, W, num_inference_steps, generator, device=dev) if plan.needs_noise else None
+            e["noise"] = self.prepare_step_noise(B, Cc, H, W, n_run, generator, device=dev) if plan.needs_noise else None
             lat, unet_in, gen, pe, mask, coef, step_ptr, eps_out = (e[k] for k in ("lat", "unet_in", "gen", "pe", "mask", "coef", "step_ptr", "eps_out"))
             hist, noise = e["hist"], e["noise"]
             from . import processors as P_
             owner = key if graphed else ("eager", id(e))
             P_.HOIST_OWNER[0] = owner  # hoisted K/V created below belong to this call (graph: until the graph is evicted)
             unet.set_kv_cache(True, clear=False)
-            unet.precompute_time_tables(sched.timesteps.to(dev), step_ptr)
+            unet.precompute_time_tables((sched.timesteps if src is None else sched.timesteps[plan.start:]).to(dev), step_ptr)
+            masked = src is not None and src.mask is not None
             e["tables"] = unet._time_tables  # the captured step keeps reading these
             # (the 64-token section stays on the one captured stream: four sub-layer workgroups per sample fill the chip at the CFG batch
             #  -- same-box A/B 37.35 vs 37.49 ms with two half-batch streams -- and this is the configuration bench.py measures;
@@ -259,7 +439,9 @@ class AudioLDM2Pipeline:
 
             def step():
                 eps2 = unet.forward_nhwc(unet_in, H, W, None, gen, pe, None, mask, batch_repeat=2)
-                if plan.legacy:
+                if masked:
+                    ops.cfg_edit_step(eps2, lat, unet_in, coef, e["keep"], step_ptr, guidance_scale, e["x0"], e["z0"], e["emask"], Cc, eps_out, hist, noise)
+                elif plan.legacy:
                     ops.cfg_ddim_step(eps2, lat, unet_in, coef, step_ptr, guidance_scale, eps_out)
                 else:
                     ops.cfg_sampler_step(eps2, lat, unet_in, coef, step_ptr, guidance_scale, eps_out, hist, noise)
@@ -293,13 +475,13 @@ class AudioLDM2Pipeline:
                         self._evict(next(iter(self._graphs)))
                     self._graphs[key] = e
                     self.graph_captures += 1
-                    for _ in range(num_inference_steps):
+                    for _ in range(n_run):
                         g.replay()
                 else:
-                    for i in range(num_inference_steps):
+                    for i in range(n_run):
                         step()
                         if callback is not None and i % callback_steps == 0:
-                            callback(i, int(sched.timesteps[i]), lat.reshape(B, H, W, Cc).permute(0, 3, 1, 2))
+                            callback(i, int(sched.timesteps[plan.start + i if src is not None else i]), lat.reshape(B, H, W, Cc).permute(0, 3, 1, 2))
             finally:
                 P_.HOIST_OWNER[0] = None
                 unet.clear_time_tables()  # (a captured step keeps reading its own tables: e["tables"])
@@ -320,10 +502,16 @@ class AudioLDM2Pipeline:
                  negative_prompt_embeds=None, generated_prompt_embeds=None, negative_generated_prompt_embeds=None,
                  attention_mask=None, negative_attention_mask=None, max_new_tokens=None, return_dict=True,
                  callback=None, callback_steps=1, cross_attention_kwargs=None, output_type="np", mel=None,
-                 use_graph=True):
+                 use_graph=True, source_audio=None, source_mel=None, source_latents=None, strength=1.0, edit_mask=None, edit_region=None):
         """Same keyword surface and defaults as the reference (pipeline_audioldm2.py:748-775, ``output_type="np"`` included): a
         pipeline built with ``vae=`` and ``vocoder=`` returns waveforms by default; ``output_type="latent"`` is the exit for a pipeline
-        that holds the denoise path only."""
+        that holds the denoise path only.
+
+        Beyond the reference -- editing a source clip: ``source_audio`` (a wav path, or one per clip; through ``frontend.wav_to_mel``),
+        ``source_mel`` (the 64-bin log-mel [b, 1, height, 64]) or ``source_latents`` ([b, C, height / 4, 16], scaled) is encoded, noised
+        to the interior timestep that ``strength`` in (0, 1] selects (diffusers' img2img convention: the last int(N * strength) steps
+        run) and denoised from there.  ``edit_mask`` (broadcastable to [B, 1, height / 4, 16]; 1 = regenerate, 0 = keep) or
+        ``edit_region`` = (start_s, end_s) restricts the change: the rest of the returned latents is the source's, bit for bit."""
         if output_type != "latent" and (self.vae is None or self.vocoder is None):
             raise NotImplementedError("waveform output needs latents -> mel (vae=ap_adapter_amd.AutoencoderKL) and mel -> waveform "
                                       "(vocoder=ap_adapter_amd.SpeechT5HifiGan); or use output_type='latent'")
@@ -339,20 +527,23 @@ class AudioLDM2Pipeline:
                          ("attention_mask", attention_mask), ("negative_attention_mask", negative_attention_mask)):
                 if v is None:
                     raise ValueError(f"{n} is required when no text prompt is given")
-        if audio_file is not None and mel is None:
-            from .frontend import load_mel  # "next" row f-2
-            mel = load_mel(audio_file)
         if audio_length_in_s is None:
             audio_length_in_s = 10.24
         height = int(audio_length_in_s / self.vocoder_upsample_factor)
         if height % self.vae_scale_factor != 0:
             height = -(-height // self.vae_scale_factor) * self.vae_scale_factor
-        dev = self.unet.conv_in.weight.device
-        dtype = self.unet.conv_in.weight.dtype
         if prompt is not None:
             batch_size = 1 if isinstance(prompt, str) else len(prompt)
         else:
             batch_size = prompt_embeds.shape[0]
+        edit_k, edit_mask = self.check_edit_arguments(batch_size * num_waveforms_per_prompt, height, num_inference_steps, audio_length_in_s, latents,
+                                                      source_audio, source_mel, source_latents, strength, edit_mask, edit_region)
+        editing = source_audio is not None or source_mel is not None or source_latents is not None
+        if audio_file is not None and mel is None:
+            from .frontend import load_mel  # "next" row f-2
+            mel = load_mel(audio_file)
+        dev = self.unet.conv_in.weight.device
+        dtype = self.unet.conv_in.weight.dtype
         # encode_prompt (:272-580): text prompts through the HIP prompt encoder, or the precomputed embeddings; [negative; positive]
         pe, am, ge = self.encode_prompt(prompt, dev, num_waveforms_per_prompt, True, negative_prompt, prompt_embeds=prompt_embeds,
                                         negative_prompt_embeds=negative_prompt_embeds, generated_prompt_embeds=generated_prompt_embeds,
@@ -361,11 +552,17 @@ class AudioLDM2Pipeline:
         if mel is not None:
             tokens, uncond = self.encode_audio(mel.to(dev), time_pooling, freq_pooling)
             ge = self.assemble_condition(ge, tokens, uncond, dtype)
-        lat = self.prepare_latents(batch_size * num_waveforms_per_prompt, self.unet.config.in_channels, height, dtype,
-                                   dev, generator, latents)
         # prepare_extra_step_kwargs (:617-632): eta reaches a scheduler whose step takes it (DDIM) and is ignored by the others
-        out = self.denoise(lat, ge, pe, am, num_inference_steps, guidance_scale, use_graph=use_graph, callback=callback,
-                           callback_steps=callback_steps, eta=eta, generator=generator)
+        if editing:
+            src = self.prepare_edit_source(batch_size * num_waveforms_per_prompt, height, dev, generator, source_audio, source_mel, source_latents,
+                                           edit_mask)
+            out = self.denoise(None, ge, pe, am, num_inference_steps, guidance_scale, use_graph=use_graph, callback=callback,
+                               callback_steps=callback_steps, eta=eta, generator=generator, source=src, start=edit_k)
+        else:
+            lat = self.prepare_latents(batch_size * num_waveforms_per_prompt, self.unet.config.in_channels, height, dtype,
+                                       dev, generator, latents)
+            out = self.denoise(lat, ge, pe, am, num_inference_steps, guidance_scale, use_graph=use_graph, callback=callback,
+                               callback_steps=callback_steps, eta=eta, generator=generator)
         if output_type != "latent":  # :1036-1044
             scaling = getattr(getattr(self.vae, "config", None), "scaling_factor", 1.0)
             mel = self.vae.decode(out / scaling)

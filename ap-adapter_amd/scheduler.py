@@ -14,6 +14,9 @@ The per-step update itself runs on the device from a coefficient table (``apad_c
 coefficients per step describes it (``SAMPLER_COLS``); ``sampler_plan`` tells the loop which kernel, table and per-sampler buffers
 a call needs.
 
+An edit run (a source clip noised to an interior timestep, optionally with a region mask; ``edit_start_index``, ``_EditSchedule``,
+``sampler_plan(start=, masked=)``) enters the same grid at index k and uses rows ``k:`` of the same tables.
+
 PARITY UNPINNED: the ``eta`` arithmetic and the multistep solver are restated from the published formulas (diffusers is not
 vendored and not installable offline); ``tests/sampler_oracle.py`` restates them a second time, independently, in float64."""
 import math
@@ -30,12 +33,55 @@ SAMPLER_COLS = ("c_x", "c_eps", "c_m1", "c_z", "d_x", "d_eps")
 class SamplerPlan:
     """what one denoise call asks of the loop: ``table`` fp32 [steps, 2] for apad_cfg_ddim_step when ``legacy`` (the deterministic
     DDIM path every earlier caller takes), else fp32 [steps, 6] for apad_cfg_sampler_step; whether a data-prediction history buffer
-    and a per-step noise buffer are needed; ``key`` is the scheduler's share of the captured graph's cache key"""
+    and a per-step noise buffer are needed; ``key`` is the scheduler's share of the captured graph's cache key.  An edit run
+    (``sampler_plan(start=, masked=)``) visits ``timesteps[start:]``: ``table`` then holds the rows of those steps only, and with
+    ``masked`` ``keep`` is the fp32 [steps - start, 2] table of apad_cfg_edit_step"""
     table: torch.Tensor
     legacy: bool
     needs_history: bool
     needs_noise: bool
     key: tuple
+    keep: torch.Tensor = None
+    start: int = 0
+
+
+def edit_start_index(num_inference_steps, strength):
+    """diffusers' img2img ``get_timesteps``: an edit of ``strength`` in (0, 1] runs the last ``min(int(N * strength), N)`` of the N steps,
+    i.e. starts at index k = N - that.  strength 0.5 with 4 | N is the k = N // 4 * 2 of the reference's unfinished style-transfer loop
+    (pipeline/style_transfer_pipeline.py:908-936)."""
+    n = int(num_inference_steps)
+    if not 0.0 < float(strength) <= 1.0:
+        raise ValueError(f"strength={strength!r} must lie in (0, 1]")
+    run = min(int(n * float(strength)), n)
+    if run == 0:
+        raise ValueError(f"strength={strength!r} leaves no step to run at num_inference_steps={n} (int(N * strength) == 0)")
+    return n - run
+
+
+class _EditSchedule:
+    """what an edit run needs of either scheduler (both share the timestep grid and alphas_cumprod): where it starts, the add_noise
+    coefficients of the start and the per-step (kx, kz) of the kept region.  PARITY UNPINNED, like the samplers: diffusers' img2img /
+    inpaint conventions restated from memory; tests/edit_oracle.py restates them a second time, independently, in float64."""
+    edit_start_index = staticmethod(edit_start_index)
+
+    def _check_start(self, start):
+        n = len(self.timesteps)
+        if not 0 <= int(start) < n:
+            raise ValueError(f"start={start!r} must lie in [0, {n})")
+        return int(start)
+
+    def add_noise_coefs(self, start):
+        """(a, s) of x_start = a x0 + s z0 at ``timesteps[start]``: (sqrt(acp_t), sqrt(1 - acp_t)), float64"""
+        acp_t = float(self.alphas_cumprod.double()[int(self.timesteps[self._check_start(start)])])
+        return math.sqrt(acp_t), math.sqrt(1.0 - acp_t)
+
+    def keep_table(self, start=0):
+        """fp32 [N - start, 2]: row i = (sqrt(acp_t), sqrt(1 - acp_t)) at t = timesteps[start + i + 1], the noise level step i lands
+        on; the last row is (1, 0) -- the kept region ends as the source latents themselves"""
+        acp = self.alphas_cumprod.double()
+        ts = self.timesteps.tolist()[self._check_start(start) + 1:]
+        rows = [[math.sqrt(float(acp[t])), math.sqrt(1.0 - float(acp[t]))] for t in ts] + [[1.0, 0.0]]
+        return torch.tensor(rows, dtype=torch.float64).float()
 
 
 def _scaled_linear_acp(num_train_timesteps, beta_start, beta_end):
@@ -48,7 +94,7 @@ def _leading_timesteps(num_train_timesteps, num_inference_steps, steps_offset):
     return (np.arange(0, num_inference_steps) * ratio).round()[::-1].copy().astype(np.int64) + steps_offset
 
 
-class DDIMScheduler:
+class DDIMScheduler(_EditSchedule):
     order = 1
     init_noise_sigma = 1.0
 
@@ -105,16 +151,22 @@ class DDIMScheduler:
             rows.append([float(c_x), float(c_e), 0.0, float(std), 0.0, 0.0])
         return torch.tensor(rows, dtype=torch.float64)
 
-    def sampler_plan(self, eta=0.0):
-        """eta = 0 keeps the two-column table and apad_cfg_ddim_step; eta > 0 needs one fresh noise tensor per step"""
+    def sampler_plan(self, eta=0.0, start=0, masked=False):
+        """eta = 0 keeps the two-column table and apad_cfg_ddim_step; eta > 0 needs one fresh noise tensor per step.  ``start`` > 0: rows
+        ``start:`` of the FULL table (the previous timestep stays t - num_train_timesteps // N).  ``masked``: always the six-column
+        table, plus ``keep``."""
         eta = float(eta)
+        start, masked = self._check_start(start), bool(masked)
         key = ("DDIMScheduler", self.order, "leading", self.num_train_timesteps, self.steps_offset, self._betas, eta)
-        if eta == 0.0:
-            return SamplerPlan(self.coef_table(), True, False, False, key)
-        return SamplerPlan(self.sampler_rows(eta).float(), False, False, True, key)
+        if start or masked:
+            key += (start, masked)
+        if eta == 0.0 and not masked:
+            return SamplerPlan(self.coef_table()[start:].contiguous(), True, False, False, key, None, start)
+        return SamplerPlan(self.sampler_rows(eta)[start:].float().contiguous(), False, False, eta != 0.0, key,
+                           self.keep_table(start) if masked else None, start)
 
 
-class DPMSolverMultistepScheduler:
+class DPMSolverMultistepScheduler(_EditSchedule):
     """DPM-Solver++ multistep (2M), epsilon prediction, data-prediction form, midpoint -- diffusers' class name, constructor keywords
     and attributes as far as they apply.  alpha_t = sqrt(acp_t), sigma_t = sqrt(1 - acp_t), lambda_t = log alpha_t - log sigma_t, all
     indexed by integer timestep; a step goes from ``timesteps[i]`` to ``timesteps[i + 1]`` and the last one to timestep 0 (the alpha of
@@ -159,13 +211,15 @@ class DPMSolverMultistepScheduler:
     def scale_model_input(self, sample, timestep=None):
         return sample
 
-    def sampler_rows(self, timesteps=None):
-        """[steps, 6] float64 rows (``SAMPLER_COLS``).  With m0 = (x - sigma_t eps) / alpha_t = d_x x + d_eps eps, h = lambda_prev -
+    def sampler_rows(self, timesteps=None, start=0):
+        """[steps - start, 6] float64 rows (``SAMPLER_COLS``).  With m0 = (x - sigma_t eps) / alpha_t = d_x x + d_eps eps, h = lambda_prev -
         lambda_t, A = sigma_prev / sigma_t and E = -alpha_prev (exp(-h) - 1):
           first order  (step 0, solver_order 1, the last step under lower_order_final with fewer than 15 steps):  x' = A x + E m0
           second order:  x' = A x + E (m0 + 0.5 (m0 - m1) / r0),  r0 = (lambda_t - lambda_tprev) / h
         expanded into c_x = A + E (1 + k) d_x, c_eps = E (1 + k) d_eps, c_m1 = -E k with k = 0.5 / r0 (0 on a first-order step).
-        ``timesteps`` (a list) replaces the scheduler's own grid."""
+        ``timesteps`` (a list) replaces the scheduler's own grid.  ``start`` > 0 (an edit run entering the grid at that index): rows
+        ``start:`` of the same table, except that the history is empty on entry, so row ``start`` is first order; ``lower_order_final``
+        keeps judging by the full step count."""
         acp = self.alphas_cumprod.double()
         ts = self.timesteps.tolist() if timesteps is None else [int(t) for t in timesteps]
         n = len(ts)
@@ -173,19 +227,25 @@ class DPMSolverMultistepScheduler:
         sg = lambda t: math.sqrt(1.0 - float(acp[t]))
         lam = lambda t: math.log(al(t)) - math.log(sg(t))
         rows = []
-        for i, t in enumerate(ts):
+        for i in range(start, n):
+            t = ts[i]
             prev = ts[i + 1] if i + 1 < n else 0
             h = lam(prev) - lam(t)
             A = sg(prev) / sg(t)
             E = -al(prev) * math.expm1(-h)
-            first = i == 0 or self.solver_order == 1 or (self.lower_order_final and n < 15 and i == n - 1)
+            first = i == start or self.solver_order == 1 or (self.lower_order_final and n < 15 and i == n - 1)
             k = 0.0 if first else 0.5 * h / (lam(t) - lam(ts[i - 1]))
             d_x, d_e = 1.0 / al(t), -sg(t) / al(t)
             rows.append([A + E * (1.0 + k) * d_x, E * (1.0 + k) * d_e, -E * k, 0.0, d_x, d_e])
         return torch.tensor(rows, dtype=torch.float64)
 
-    def sampler_plan(self, eta=0.0):
-        """``eta`` is ignored, as the reference's ``prepare_extra_step_kwargs`` drops it for a scheduler whose ``step`` has none"""
+    def sampler_plan(self, eta=0.0, start=0, masked=False):
+        """``eta`` is ignored, as the reference's ``prepare_extra_step_kwargs`` drops it for a scheduler whose ``step`` has none.
+        ``start`` / ``masked``: see ``sampler_rows`` and ``DDIMScheduler.sampler_plan``."""
+        start, masked = self._check_start(start), bool(masked)
         key = ("DPMSolverMultistepScheduler", self.solver_order, self.timestep_spacing, self.lower_order_final, self.num_train_timesteps,
                self.steps_offset, self._betas)
-        return SamplerPlan(self.sampler_rows().float(), False, self.solver_order > 1, False, key)
+        if start or masked:
+            key += (start, masked)
+        return SamplerPlan(self.sampler_rows(start=start).float(), False, self.solver_order > 1, False, key,
+                           self.keep_table(start) if masked else None, start)

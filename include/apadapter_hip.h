@@ -26,6 +26,9 @@
  *                       (pipeline/pipeline_audioldm2.py:1020-1025)
  *   apad_cfg_sampler_step  CFG combine + the step of any other scheduler the pipeline is built with (:158, :1025):
  *                       DDIMScheduler.step with eta > 0, DPMSolverMultistepScheduler.step (DPM-Solver++ 2M)
+ *   apad_edit_start / apad_cfg_edit_step  editing from a source clip (no working counterpart in the reference; diffusers' img2img /
+ *                       inpaint conventions): posterior draw + add_noise at the start timestep, and apad_cfg_sampler_step's step
+ *                       followed by the re-imposition of the kept region
  */
 #ifndef APADAPTER_HIP_H
 #define APADAPTER_HIP_H
@@ -475,6 +478,25 @@ int apad_step_advance(int32_t* step_ptr, void* stream);
 int apad_cfg_sampler_step(const void* eps2, float* latents, void* unet_in, float* eps_out, float* history, const float* noise,
                           const float* coef, const int32_t* step_ptr, int32_t n_steps, float guidance_scale, int32_t B, int64_t n,
                           int32_t dtype, void* stream);
+/* apad_cfg_sampler_step followed by the edit blend.  With g the update above, row s of keep [n_steps][2] fp32 = (kx, kz) and
+   m = mask[pixel] in [0, 1] (1 = regenerate, 0 = keep):
+     known = fma(kx, x0, kz * z0) ,   x' = fma(m, g, (1 - m) * known)
+   so m = 1 leaves the bits of g, m = 0 those of known, and a keep row (1, 0) -- the last step's -- makes known the bits of x0.
+   x0 / z0 fp32 [B][n]: the source latents and the noise that built the start (apad_edit_start).  mask fp32 [mask_batch][n / C],
+   mask_batch 1 (shared) or B; element j of a clip belongs to pixel j / C (NHWC, channel fastest).  m0 -> history is formed from the
+   pre-blend x and eps.  16-byte accesses under apad_cfg_sampler_step's rule plus C == 8 (one vector = one pixel), a scalar form
+   otherwise.  A null mask makes this apad_cfg_sampler_step (keep / x0 / z0 unread).  One launch, hipGraph-capturable. */
+int apad_cfg_edit_step(const void* eps2, float* latents, void* unet_in, float* eps_out, float* history, const float* noise,
+                       const float* coef, const float* keep, const float* x0, const float* z0, const float* mask, int32_t mask_batch,
+                       int32_t C, const int32_t* step_ptr, int32_t n_steps, float guidance_scale, int32_t B, int64_t n, int32_t dtype,
+                       void* stream);
+/* The buffers an edit run starts from, in the loop's layout ([rows = B * h * w][Lc], NHWC), in one pass:
+     x0_out  = (mean + exp(0.5 * clamp(logvar, -30, 20)) * post_noise) * scale   fp32; moments [rows][2 * Lc] = (mean | logvar) in `dtype`
+               as apad_gaussian_sample reads them, post_noise fp32 [rows][Lc].  Null moments: x0_out already holds the source latents.
+     latents = fma(a, x0, s * z0)   fp32 (add_noise at the start timestep: a = sqrt(acp_t), s = sqrt(1 - acp_t)), z0 fp32 [rows][Lc]
+     unet_in = latents in `dtype`. */
+int apad_edit_start(const void* moments, const float* post_noise, const float* z0, float* x0_out, float* latents, void* unet_in, float a,
+                    float s, float scale, int64_t rows, int32_t Lc, int32_t dtype, void* stream);
 /* out = (a + b + c) * scale, element-wise over n values of `dtype` (HiFi-GAN: mean of the three residual-block branches,
    SpeechT5HifiGan.forward) */
 int apad_mix3(const void* a, const void* b, const void* c, void* out, int64_t n, float scale, int32_t dtype, void* stream);

@@ -6,6 +6,12 @@ gathered in clip order on every rank; rank 0 writes them.
     python tools/run_sharded.py --task style_transfer --clips 256 --batch 32 --steps 200 [--audio-dir DIR] [--out latents.pt]
     python tools/run_sharded.py --gpus 8 --clips 256 ...        (starts its 8 ranks itself; equivalent to the line below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 tools/run_sharded.py --clips 256 ...
+
+Editing instead of generating (--strength S and / or --edit-region A:B, optionally --source-dir DIR): every clip starts from its source
+wav -- the file of the same name in DIR, by default the audio prompt itself -- encoded by the VAE (random-init weights here), noised to
+the interior timestep S selects, and only seconds A..B are regenerated.  Each clip's noise is seeded by its index, so a clip's result
+does not depend on the batch or rank it lands in.
+    python tools/run_sharded.py --clips 64 --steps 50 --strength 0.6 --edit-region 4:7
 """
 import argparse
 import glob
@@ -104,6 +110,10 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--wav-dir", default=None, help="decode every clip (VAE + vocoder on the HIP path) and write 16 kHz wavs named as "
                                                      "inference.py:79 names them")
+    ap.add_argument("--source-dir", default=None, help="edit: directory holding each clip's source wav under the audio prompt's file name "
+                                                        "(default: the audio prompt itself)")
+    ap.add_argument("--strength", type=float, default=None, help="edit: in (0, 1], the share of the schedule that is run from the noised source")
+    ap.add_argument("--edit-region", default=None, metavar="A:B", help="edit: regenerate seconds A..B only, keep the rest of the source")
     ap.add_argument("--gpus", type=int, default=1, help="N > 1 without a launcher: this script starts its N ranks itself (one per GPU)")
     args = ap.parse_args()
 
@@ -130,12 +140,36 @@ def main():
         tok, unc = pipe.encode_audio(load_mel(path, device=dev), tp, fp)
         return tok[0], unc[0]
 
-    def denoise(lat, gen, t5, mask, gs):
-        return pipe.denoise(lat, gen, t5, mask, args.steps, gs)
+    editing = args.strength is not None or args.edit_region is not None or args.source_dir is not None
+    if editing:
+        height = H * pipe.vae_scale_factor
+        pipe.vae = build_decoder(dev, dtype, small=args.small)[0]
+        region = tuple(float(v) for v in args.edit_region.split(":")) if args.edit_region else None
+        # the pipeline's own argument checks, once, on a stand-in source of the right shape
+        start, region_mask = pipe.check_edit_arguments(args.batch, height, args.steps, args.seconds, None, None, None, torch.empty(1, 8, H, 16),
+                                                       1.0 if args.strength is None else args.strength, None, region)
+        moments = {}
+
+        def source_moments(path):
+            from ap_adapter_amd.frontend import wav_to_mel
+            src = os.path.join(args.source_dir, os.path.basename(path)) if args.source_dir else path
+            if src not in moments:
+                mel = wav_to_mel(src, (height + 0.5) / 102.4, device=dev)
+                moments[src] = pipe.vae.encode(mel[None]).latent_dist._m.reshape(H * 16, 16)
+            return moments[src]
+
+    def denoise(lat, gen, t5, mask, gs, clips=None):
+        if not editing:
+            return pipe.denoise(lat, gen, t5, mask, args.steps, gs)
+        # z0 = the clip's seeded latents (what a generation run would start from); the posterior draw is seeded by the clip index too
+        post = torch.stack([torch.randn(8, H, 16, generator=torch.Generator().manual_seed(7919 * c["index"] + 1)) for c in clips])
+        src = A.EditSource(z0=lat, moments=torch.cat([source_moments(c["audio"]) for c in clips]), post_noise=post,
+                           scale=pipe.vae.config.scaling_factor, mask=region_mask)
+        return pipe.denoise(None, gen, t5, mask, args.steps, gs, source=src, start=start)
 
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    local_out = S.run_sharded(clips, cfg, encode_audio, denoise, args.batch, rank, world, latent_shape=(8, H, 16), device=dev)
+    local_out = S.run_sharded(clips, cfg, encode_audio, denoise, args.batch, rank, world, latent_shape=(8, H, 16), device=dev, pass_clips=True)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     n_wavs = 0
@@ -154,7 +188,7 @@ def main():
     if rank == 0:
         finite = all(bool(torch.isfinite(x).all()) for x in allc)
         print(json.dumps({"task": args.task, "clips": len(clips), "world": world, "batch": args.batch, "steps": args.steps,
-                          "sampler": args.sampler, "La": A.config.audio_tokens(cfg), "seconds_rank0": round(dt, 2), "clips_per_s": round(len(clips) / dt, 4),
+                          "sampler": args.sampler, "strength": args.strength, "edit_region": args.edit_region, "La": A.config.audio_tokens(cfg), "seconds_rank0": round(dt, 2), "clips_per_s": round(len(clips) / dt, 4),
                           "graph_captures": pipe.graph_captures, "graph_hits": pipe.graph_hits, "finite": finite,
                           "wavs_written_rank0": n_wavs}))
         if args.out:
