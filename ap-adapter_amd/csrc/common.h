@@ -136,6 +136,25 @@ void apad_set_error(const char* fmt, ...);
         }                                \
     } while (0)
 int apad_check_launch(const char* what);
+// The dtype ladder of the 256-thread element-wise launches, for the `dtype` (APAD_BF16 / APAD_F16 / APAD_F32, checked by the caller) and the
+// stream `s` of the calling scope: kern<DT> (LAUNCH_DT), kern<DT, F> (LAUNCH_DT_F), kern<DT, vec ? 8 : 1> (LAUNCH_DT_V)
+#define LAUNCH_DT(kern, grid, ...)                                                                                \
+    do {                                                                                                          \
+        if (dtype == APAD_BF16) hipLaunchKernelGGL((kern<APAD_BF16>), grid, dim3(256), 0, s, __VA_ARGS__);        \
+        else if (dtype == APAD_F32) hipLaunchKernelGGL((kern<APAD_F32>), grid, dim3(256), 0, s, __VA_ARGS__);     \
+        else hipLaunchKernelGGL((kern<APAD_F16>), grid, dim3(256), 0, s, __VA_ARGS__);                            \
+    } while (0)
+#define LAUNCH_DT_F(kern, F, grid, ...)                                                                           \
+    do {                                                                                                          \
+        if (dtype == APAD_BF16) hipLaunchKernelGGL((kern<APAD_BF16, F>), grid, dim3(256), 0, s, __VA_ARGS__);     \
+        else if (dtype == APAD_F32) hipLaunchKernelGGL((kern<APAD_F32, F>), grid, dim3(256), 0, s, __VA_ARGS__);  \
+        else hipLaunchKernelGGL((kern<APAD_F16, F>), grid, dim3(256), 0, s, __VA_ARGS__);                         \
+    } while (0)
+#define LAUNCH_DT_V(kern, vec, grid, ...)                          \
+    do {                                                           \
+        if (vec) LAUNCH_DT_F(kern, 8, grid, __VA_ARGS__);          \
+        else LAUNCH_DT_F(kern, 1, grid, __VA_ARGS__);              \
+    } while (0)
 // dynamic LDS above 64 KB needs hipFuncAttributeMaxDynamicSharedMemorySize once per (kernel, DEVICE): *devmask = the devices it has been set on
 // (one static word per kernel at the call site); thread-safe, the return code of hipFuncSetAttribute is checked.  0 = ok, -1 = error set
 int apad_ensure_dyn_lds(const void* kern, int bytes, unsigned* devmask);

@@ -1,5 +1,6 @@
 // Small HBM-bound kernels of the path: AudioMAE token pooling, sinusoidal timestep embedding, fused
-// classifier-free-guidance + DDIM / sampler update, the edit step (sampler update + region blend) and its start, device-side step counter.
+// classifier-free-guidance + sampler update (one kernel behind apad_cfg_ddim_step / apad_cfg_sampler_step / apad_cfg_edit_step) and the edit
+// run's start, device-side step counter.
 #include "common.h"
 #include "f32_ops.h"
 
@@ -72,23 +73,6 @@ __global__ void timestep_kernel(const float* t, uint8_t* out, int n, int dim, in
     }
 }
 
-// eps = e_u + g (e_c - e_u); x_prev = c0 * x + c1 * eps   (pipeline_audioldm2.py:1020-1025, DDIM eta = 0)
-template <int DT>
-__global__ __launch_bounds__(256) void cfg_ddim_kernel(const uint8_t* eps2, float* latents, uint8_t* unet_in, float* eps_out,
-                                                       const float* coef, const int32_t* step_ptr, float gs, int64_t total) {
-    const int step = step_ptr ? *step_ptr : 0;
-    const float c0 = coef[2 * step], c1 = coef[2 * step + 1];
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const float eu = ld_elem<DT>(eps2, i), ec = ld_elem<DT>(eps2, total + i);
-        // the reference forms the guided noise in the model dtype
-        const float e = (float)(typename ET<DT>::elem)(eu + gs * (ec - eu));
-        const float x = c0 * latents[i] + c1 * e;
-        latents[i] = x;
-        st_elem<DT>(unet_in, i, x);
-        if (eps_out) eps_out[i] = e;
-    }
-}
-
 // V consecutive elements <-> registers: V = 8 moves 16 bytes per access (two for fp32), V = 1 is the scalar form
 template <int V> __device__ __forceinline__ void ld_f32v(const float* p, int64_t i, float* v) {
     if constexpr (V == 8) {
@@ -117,52 +101,29 @@ template <int DT, int V> __device__ __forceinline__ void st_elemv(uint8_t* p, in
     else st_elem<DT>(p, i, v[0]);
 }
 
-// The guided noise as in cfg_ddim_kernel, then a sampler whose update is linear in (x, eps, m1, z): row r = coef + 6 * step
-// (scheduler.py SAMPLER_COLS),  x' = r0 x + r1 eps + r2 m1 + r3 z[step],  m0 = r4 x + r5 eps -> hist (the next step's m1).
-// DPM-Solver++ 2M: r3 = 0;  DDIM eta > 0: r2 = 0, no hist.  m1 / z are not read on a step whose coefficient is 0 (wave-uniform).
-template <int DT, int V>
-__global__ __launch_bounds__(256) void cfg_sampler_kernel(const uint8_t* eps2, float* latents, uint8_t* unet_in, float* eps_out, float* hist,
-                                                          const float* noise, const float* coef, const int32_t* step_ptr, int n_steps, float gs,
-                                                          int64_t total) {
-    int step = step_ptr ? *step_ptr : 0;
-    step = step < 0 ? 0 : (step >= n_steps ? n_steps - 1 : step);  // the table and the noise buffer have n_steps rows
-    const float* r = coef + 6 * step;
-    const float c_x = r[0], c_e = r[1], c_m = r[2], c_z = r[3], d_x = r[4], d_e = r[5];
-    const bool use_m1 = hist && c_m != 0.f, use_z = noise && c_z != 0.f;
-    const float* z = noise + (use_z ? (int64_t)step * total : 0);
-    for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * V; i < total; i += (int64_t)gridDim.x * 256 * V) {
-        float eu[V], ec[V], x[V], m1[V], zz[V], e[V], m0[V];
-        ld_elemv<DT, V>(eps2, i, eu);
-        ld_elemv<DT, V>(eps2, total + i, ec);
-        ld_f32v<V>(latents, i, x);
-#pragma unroll
-        for (int j = 0; j < V; ++j) m1[j] = zz[j] = 0.f;
-        if (use_m1) ld_f32v<V>(hist, i, m1);
-        if (use_z) ld_f32v<V>(z, i, zz);
-#pragma unroll
-        for (int j = 0; j < V; ++j) {
-            // the reference forms the guided noise in the model dtype: one fp32 fma (what cfg_ddim_kernel's expression compiles to), one rounding
-            e[j] = (float)(typename ET<DT>::elem)fmaf(gs, ec[j] - eu[j], eu[j]);
-            m0[j] = d_x * x[j] + d_e * e[j];
-            x[j] = c_x * x[j] + c_e * e[j] + c_m * m1[j] + c_z * zz[j];
-        }
-        st_f32v<V>(latents, i, x);
-        st_elemv<DT, V>(unet_in, i, x);
-        if (hist) st_f32v<V>(hist, i, m0);
-        if (eps_out) st_f32v<V>(eps_out, i, e);
-    }
-}
+// The forms of the step kernel: the 16-byte form (8 elements per access), the scalar form, and apad_cfg_ddim_step's (scalar, two-column table)
+enum { STEP_DDIM = 0, STEP_SCALAR = 1, STEP_VEC = 8 };
+static_assert(STEP_VEC == 8 && STEP_SCALAR == 1, "LAUNCH_DT_V passes 8 / 1 as the form");
 
-// cfg_sampler_kernel's update with every rounding spelled out.  That kernel leaves the fusing of its multiply-adds to the compiler, which settled
-// on three forms (read off its gfx950 code): the 16-byte form fuses everything but c_e * e and d_e * e, the scalar fp32 form everything but c_x * x
-// and none of m0, the scalar 16-bit forms fuse nothing.  apad_cfg_edit_step promises the bits of apad_cfg_sampler_step where the mask is 1
-// (tests/test_gpu_edit.py::test_mask_of_ones_is_cfg_sampler_step_bit_for_bit holds the two together), so here nothing is left to the compiler:
-// contraction is off and each fused multiply-add is written as one.
-template <int DT, int V>
+// The sampler's update, linear in (x, eps, m1, z), with every rounding spelled out: contraction is off and each fused multiply-add is written
+// as one.  The forms are the ones hipcc once chose for three separately compiled kernels, read off their gfx950 code (v_fma / v_fmac = fused,
+// v_mul / v_pk_mul + v_add = not) and kept bit for bit: tests/golden/step_bits.safetensors holds what those kernels wrote, and
+// tests/test_gpu_step_bits.py compares with it and restates each fp32 form on the host.
+//   STEP_VEC, every dtype:   x' = fma(c_z, z, fma(c_m, m1, fma(c_x, x, c_e * e))),   m0 = fma(d_x, x, d_e * e)
+//   STEP_SCALAR, fp32:       x' = fma(c_z, z, fma(c_m, m1, fma(c_e, e, c_x * x))),   m0 = d_x * x + d_e * e
+//   STEP_SCALAR, 16-bit:     x' = ((c_x * x + c_e * e) + c_m * m1) + c_z * z,        m0 = d_x * x + d_e * e
+//   STEP_DDIM, fp32:         x' = fma(c_x, x, c_e * e)      (v_mul_f32 c_e e; v_fmac_f32 c_x x)
+//   STEP_DDIM, 16-bit:       x' = c_x * x + c_e * e         (v_pk_mul_f32 (c_x, c_e) (x, e); v_add_f32)
+// STEP_DDIM has no m1 / z terms and no m0: it performs the two-column update's operations and no others.
+template <int DT, int FORM>
 __device__ __forceinline__ void sampler_update(float c_x, float c_e, float c_m, float c_z, float d_x, float d_e, float x, float e, float m1, float zz,
                                                float& xn, float& m0) {
 #pragma clang fp contract(off)
-    if constexpr (V == 8) {
+    if constexpr (FORM == STEP_DDIM) {
+        if constexpr (DT == APAD_F32) xn = fmaf(c_x, x, c_e * e);
+        else xn = c_x * x + c_e * e;
+        m0 = 0.f;  // not stored
+    } else if constexpr (FORM == STEP_VEC) {
         xn = fmaf(c_z, zz, fmaf(c_m, m1, fmaf(c_x, x, c_e * e)));
         m0 = fmaf(d_x, x, d_e * e);
     } else if constexpr (DT == APAD_F32) {
@@ -184,21 +145,32 @@ __device__ __forceinline__ float edit_blend(float m, float g, float kx, float kz
     return fmaf(m, g, (1.0f - m) * edit_known(kx, kz, x0, z0));
 }
 
-// cfg_sampler_kernel's step followed by the edit blend (scheduler.py ``keep`` table, row s = (kx, kz)): with g the sampler's update,
+// The denoise step's last kernel, behind all three entry points: the guided noise, formed in the model dtype as the reference does,
+//   eps = (elem)fma(g, e_c - e_u, e_u)   (pipeline_audioldm2.py:1020-1025; one fp32 fma, one rounding to the model dtype),
+// (f16 only, and the one fold still the compiler's: the scalar forms round the exact fma to f16 once, v_fma_mixlo_f16, the 16-byte form rounds
+// it to fp32 first, v_cvt_pk_f16_f32 -- as before the merge, and pinned by the recorded bits)
+// then a sampler whose update is linear in (x, eps, m1, z) -- row r = coef + 6 * step (scheduler.py SAMPLER_COLS),
+//   x' = r0 x + r1 eps + r2 m1 + r3 z[step],   m0 = r4 x + r5 eps -> hist (the next step's m1),   roundings as in sampler_update;
+// DPM-Solver++ 2M: r3 = 0;  DDIM eta > 0: r2 = 0, no hist.  m1 / z are not read on a step whose coefficient is 0 (wave-uniform) -- then the
+// edit blend (scheduler.py ``keep`` table, row s = (kx, kz)): with g the sampler's update,
 //   known = fma(kx, x0, kz * z0)   -- the source at the noise level the step lands on ((1, 0) on the last step: the bits of x0)
 //   x'    = fma(m, g, (1 - m) * known),  m = mask[pixel] in [0, 1]  -- m = 1 leaves the bits of g, m = 0 those of known
-// mask fp32 [mask_batch][n / C], element j of a clip belongs to pixel j / C (NHWC, channel fastest).  V = 8 requires C == 8: one vector is one
-// pixel and takes one mask value.  The data prediction m0 is formed from the pre-blend x and eps, as in cfg_sampler_kernel.  A null mask is
-// m = 1 everywhere (the plain sampler step).
-template <int DT, int V>
-__global__ __launch_bounds__(256) void cfg_edit_kernel(const uint8_t* eps2, float* latents, uint8_t* unet_in, float* eps_out, float* hist,
+// mask fp32 [mask_batch][n / C], element j of a clip belongs to pixel j / C (NHWC, channel fastest).  STEP_VEC requires C == 8: one vector is
+// one pixel and takes one mask value.  The data prediction m0 is formed from the pre-blend x and eps.  A null mask is m = 1 everywhere: the
+// plain sampler step (apad_cfg_sampler_step).  STEP_DDIM (apad_cfg_ddim_step, deterministic DDIM) reads row coef + 2 * step = (c_x, c_e) of a
+// table whose length the entry point is not told (no clamp), and has neither hist, noise nor mask.
+template <int DT, int FORM>
+__global__ __launch_bounds__(256) void cfg_step_kernel(const uint8_t* eps2, float* latents, uint8_t* unet_in, float* eps_out, float* hist,
                                                        const float* noise, const float* coef, const float* keep, const float* x0, const float* z0,
                                                        const float* mask, int mask_per_clip, int C, int64_t n, const int32_t* step_ptr, int n_steps,
                                                        float gs, int64_t total) {
+    constexpr int V = FORM == STEP_VEC ? 8 : 1;
+    constexpr bool ddim = FORM == STEP_DDIM;
+    if constexpr (ddim) hist = nullptr, noise = nullptr, mask = nullptr;
     int step = step_ptr ? *step_ptr : 0;
-    step = step < 0 ? 0 : (step >= n_steps ? n_steps - 1 : step);  // the tables and the noise buffer have n_steps rows
-    const float* r = coef + 6 * step;
-    const float c_x = r[0], c_e = r[1], c_m = r[2], c_z = r[3], d_x = r[4], d_e = r[5];
+    if constexpr (!ddim) step = step < 0 ? 0 : (step >= n_steps ? n_steps - 1 : step);  // the tables and the noise buffer have n_steps rows
+    const float* r = coef + (ddim ? 2 : 6) * step;
+    const float c_x = r[0], c_e = r[1], c_m = ddim ? 0.f : r[2], c_z = ddim ? 0.f : r[3], d_x = ddim ? 0.f : r[4], d_e = ddim ? 0.f : r[5];
     const float kx = mask ? keep[2 * step] : 0.f, kz = mask ? keep[2 * step + 1] : 0.f;
     const bool use_m1 = hist && c_m != 0.f, use_z = noise && c_z != 0.f;
     const float* z = noise + (use_z ? (int64_t)step * total : 0);
@@ -216,7 +188,7 @@ __global__ __launch_bounds__(256) void cfg_edit_kernel(const uint8_t* eps2, floa
         for (int j = 0; j < V; ++j) {
             e[j] = (float)(typename ET<DT>::elem)fmaf(gs, ec[j] - eu[j], eu[j]);
             float xn;
-            sampler_update<DT, V>(c_x, c_e, c_m, c_z, d_x, d_e, x[j], e[j], m1[j], zz[j], xn, m0[j]);
+            sampler_update<DT, FORM>(c_x, c_e, c_m, c_z, d_x, d_e, x[j], e[j], m1[j], zz[j], xn, m0[j]);
             x[j] = xn;
         }
         if (mask) {
@@ -384,12 +356,7 @@ extern "C" int apad_timestep_embedding(const float* t, void* out, int32_t n, int
     const int total = n * (dim / 2);
     dim3 grid((total + 255) / 256);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == APAD_F32)
-        hipLaunchKernelGGL((timestep_kernel<APAD_F32>), grid, dim3(256), 0, s, t, (uint8_t*)out, n, dim, flip_sin_to_cos, freq_shift);
-    else if (dtype == APAD_BF16)
-        hipLaunchKernelGGL((timestep_kernel<APAD_BF16>), grid, dim3(256), 0, s, t, (uint8_t*)out, n, dim, flip_sin_to_cos, freq_shift);
-    else
-        hipLaunchKernelGGL((timestep_kernel<APAD_F16>), grid, dim3(256), 0, s, t, (uint8_t*)out, n, dim, flip_sin_to_cos, freq_shift);
+    LAUNCH_DT(timestep_kernel, grid, t, (uint8_t*)out, n, dim, flip_sin_to_cos, freq_shift);
     return apad_check_launch("apad_timestep_embedding");
 }
 
@@ -403,30 +370,11 @@ extern "C" int apad_cfg_ddim_step(const void* eps2, float* latents, void* unet_i
     int64_t blocks = (total + 255) / 256;
     if (blocks > 2048) blocks = 2048;
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == APAD_F32)
-        hipLaunchKernelGGL((cfg_ddim_kernel<APAD_F32>), dim3((unsigned)blocks), dim3(256), 0, s, (const uint8_t*)eps2, latents,
-                           (uint8_t*)unet_in, eps_out, coef, step_ptr, guidance_scale, total);
-    else if (dtype == APAD_BF16)
-        hipLaunchKernelGGL((cfg_ddim_kernel<APAD_BF16>), dim3((unsigned)blocks), dim3(256), 0, s, (const uint8_t*)eps2, latents,
-                           (uint8_t*)unet_in, eps_out, coef, step_ptr, guidance_scale, total);
-    else
-        hipLaunchKernelGGL((cfg_ddim_kernel<APAD_F16>), dim3((unsigned)blocks), dim3(256), 0, s, (const uint8_t*)eps2, latents,
-                           (uint8_t*)unet_in, eps_out, coef, step_ptr, guidance_scale, total);
+    // the scalar launch only: the 16-byte form rounds differently (sampler_update)
+    LAUNCH_DT_F(cfg_step_kernel, STEP_DDIM, dim3((unsigned)blocks), (const uint8_t*)eps2, latents, (uint8_t*)unet_in, eps_out, nullptr, nullptr, coef,
+                nullptr, nullptr, nullptr, nullptr, 0, 1, n, step_ptr, 0, guidance_scale, total);
     return apad_check_launch("apad_cfg_ddim_step");
 }
-
-namespace {
-template <int DT>
-void launch_cfg_sampler(bool vec, unsigned blocks, hipStream_t s, const void* eps2, float* latents, void* unet_in, float* eps_out, float* history,
-                        const float* noise, const float* coef, const int32_t* step_ptr, int32_t n_steps, float gs, int64_t total) {
-    if (vec)
-        hipLaunchKernelGGL((cfg_sampler_kernel<DT, 8>), dim3(blocks), dim3(256), 0, s, (const uint8_t*)eps2, latents, (uint8_t*)unet_in, eps_out,
-                           history, noise, coef, step_ptr, n_steps, gs, total);
-    else
-        hipLaunchKernelGGL((cfg_sampler_kernel<DT, 1>), dim3(blocks), dim3(256), 0, s, (const uint8_t*)eps2, latents, (uint8_t*)unet_in, eps_out,
-                           history, noise, coef, step_ptr, n_steps, gs, total);
-}
-}  // namespace
 
 extern "C" int apad_cfg_sampler_step(const void* eps2, float* latents, void* unet_in, float* eps_out, float* history, const float* noise,
                                      const float* coef, const int32_t* step_ptr, int32_t n_steps, float guidance_scale, int32_t B, int64_t n,
@@ -441,38 +389,11 @@ extern "C" int apad_cfg_sampler_step(const void* eps2, float* latents, void* une
     int64_t blocks = ((vec ? total / 8 : total) + 255) / 256;
     if (blocks > 2048) blocks = 2048;
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == APAD_F32)
-        launch_cfg_sampler<APAD_F32>(vec, (unsigned)blocks, s, eps2, latents, unet_in, eps_out, history, noise, coef, step_ptr, n_steps, guidance_scale, total);
-    else if (dtype == APAD_BF16)
-        launch_cfg_sampler<APAD_BF16>(vec, (unsigned)blocks, s, eps2, latents, unet_in, eps_out, history, noise, coef, step_ptr, n_steps, guidance_scale, total);
-    else
-        launch_cfg_sampler<APAD_F16>(vec, (unsigned)blocks, s, eps2, latents, unet_in, eps_out, history, noise, coef, step_ptr, n_steps, guidance_scale, total);
+    // the edit step's kernel with a null mask: the plain sampler step
+    LAUNCH_DT_V(cfg_step_kernel, vec, dim3((unsigned)blocks), (const uint8_t*)eps2, latents, (uint8_t*)unet_in, eps_out, history, noise, coef, nullptr,
+                nullptr, nullptr, nullptr, 0, 1, n, step_ptr, n_steps, guidance_scale, total);
     return apad_check_launch("apad_cfg_sampler_step");
 }
-
-namespace {
-template <int DT>
-void launch_cfg_edit(bool vec, unsigned blocks, hipStream_t s, const void* eps2, float* latents, void* unet_in, float* eps_out, float* history,
-                     const float* noise, const float* coef, const float* keep, const float* x0, const float* z0, const float* mask, int per_clip, int C,
-                     int64_t n, const int32_t* step_ptr, int32_t n_steps, float gs, int64_t total) {
-    if (vec)
-        hipLaunchKernelGGL((cfg_edit_kernel<DT, 8>), dim3(blocks), dim3(256), 0, s, (const uint8_t*)eps2, latents, (uint8_t*)unet_in, eps_out, history,
-                           noise, coef, keep, x0, z0, mask, per_clip, C, n, step_ptr, n_steps, gs, total);
-    else
-        hipLaunchKernelGGL((cfg_edit_kernel<DT, 1>), dim3(blocks), dim3(256), 0, s, (const uint8_t*)eps2, latents, (uint8_t*)unet_in, eps_out, history,
-                           noise, coef, keep, x0, z0, mask, per_clip, C, n, step_ptr, n_steps, gs, total);
-}
-template <int DT>
-void launch_edit_start(bool vec, unsigned blocks, hipStream_t s, const void* moments, const float* post_noise, const float* z0, float* x0, float* latents,
-                       void* unet_in, float a, float sg, float scale, int64_t total, int Lc) {
-    if (vec)
-        hipLaunchKernelGGL((edit_start_kernel<DT, 8>), dim3(blocks), dim3(256), 0, s, (const uint8_t*)moments, post_noise, z0, x0, latents,
-                           (uint8_t*)unet_in, a, sg, scale, total, Lc);
-    else
-        hipLaunchKernelGGL((edit_start_kernel<DT, 1>), dim3(blocks), dim3(256), 0, s, (const uint8_t*)moments, post_noise, z0, x0, latents,
-                           (uint8_t*)unet_in, a, sg, scale, total, Lc);
-}
-}  // namespace
 
 extern "C" int apad_cfg_edit_step(const void* eps2, float* latents, void* unet_in, float* eps_out, float* history, const float* noise,
                                   const float* coef, const float* keep, const float* x0, const float* z0, const float* mask, int32_t mask_batch,
@@ -496,20 +417,13 @@ extern "C" int apad_cfg_edit_step(const void* eps2, float* latents, void* unet_i
     hipStream_t s = (hipStream_t)stream;
     const int per_clip = mask_batch == B && B > 1;
     const int Cc = mask ? C : 1;
-    if (dtype == APAD_F32)
-        launch_cfg_edit<APAD_F32>(vec, (unsigned)blocks, s, eps2, latents, unet_in, eps_out, history, noise, coef, keep, x0, z0, mask, per_clip, Cc, n,
-                                  step_ptr, n_steps, guidance_scale, total);
-    else if (dtype == APAD_BF16)
-        launch_cfg_edit<APAD_BF16>(vec, (unsigned)blocks, s, eps2, latents, unet_in, eps_out, history, noise, coef, keep, x0, z0, mask, per_clip, Cc, n,
-                                   step_ptr, n_steps, guidance_scale, total);
-    else
-        launch_cfg_edit<APAD_F16>(vec, (unsigned)blocks, s, eps2, latents, unet_in, eps_out, history, noise, coef, keep, x0, z0, mask, per_clip, Cc, n,
-                                  step_ptr, n_steps, guidance_scale, total);
+    LAUNCH_DT_V(cfg_step_kernel, vec, dim3((unsigned)blocks), (const uint8_t*)eps2, latents, (uint8_t*)unet_in, eps_out, history, noise, coef, keep, x0,
+                z0, mask, per_clip, Cc, n, step_ptr, n_steps, guidance_scale, total);
     return apad_check_launch("apad_cfg_edit_step");
 }
 
 extern "C" int apad_edit_start(const void* moments, const float* post_noise, const float* z0, float* x0_out, float* latents, void* unet_in, float a,
-                               float s, float scale, int64_t rows, int32_t Lc, int32_t dtype, void* stream) {
+                               float sg, float scale, int64_t rows, int32_t Lc, int32_t dtype, void* stream) {
     APAD_CHECK(z0 && x0_out && latents && unet_in, "apad_edit_start: null operand");
     APAD_CHECK(!moments || post_noise, "apad_edit_start: moments need post_noise (null operand)");
     APAD_CHECK(dtype == APAD_BF16 || dtype == APAD_F16 || dtype == APAD_F32, "apad_edit_start: dtype %d not supported", dtype);
@@ -519,10 +433,9 @@ extern "C" int apad_edit_start(const void* moments, const float* post_noise, con
     const bool vec = Lc == 8 && bases % 16 == 0;
     int64_t blocks = ((vec ? total / 8 : total) + 255) / 256;
     if (blocks > 2048) blocks = 2048;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == APAD_F32) launch_edit_start<APAD_F32>(vec, (unsigned)blocks, st, moments, post_noise, z0, x0_out, latents, unet_in, a, s, scale, total, Lc);
-    else if (dtype == APAD_BF16) launch_edit_start<APAD_BF16>(vec, (unsigned)blocks, st, moments, post_noise, z0, x0_out, latents, unet_in, a, s, scale, total, Lc);
-    else launch_edit_start<APAD_F16>(vec, (unsigned)blocks, st, moments, post_noise, z0, x0_out, latents, unet_in, a, s, scale, total, Lc);
+    hipStream_t s = (hipStream_t)stream;
+    LAUNCH_DT_V(edit_start_kernel, vec, dim3((unsigned)blocks), (const uint8_t*)moments, post_noise, z0, x0_out, latents, (uint8_t*)unet_in, a, sg, scale,
+                total, Lc);
     return apad_check_launch("apad_edit_start");
 }
 
@@ -533,9 +446,7 @@ extern "C" int apad_mix3(const void* a, const void* b, const void* c, void* out,
     if (blocks > 8192) blocks = 8192;
     hipStream_t s = (hipStream_t)stream;
     const uint8_t *pa = (const uint8_t*)a, *pb = (const uint8_t*)b, *pc = (const uint8_t*)c;
-    if (dtype == APAD_F32) hipLaunchKernelGGL((mix3_kernel<APAD_F32>), dim3((unsigned)blocks), dim3(256), 0, s, pa, pb, pc, (uint8_t*)out, n, scale);
-    else if (dtype == APAD_BF16) hipLaunchKernelGGL((mix3_kernel<APAD_BF16>), dim3((unsigned)blocks), dim3(256), 0, s, pa, pb, pc, (uint8_t*)out, n, scale);
-    else hipLaunchKernelGGL((mix3_kernel<APAD_F16>), dim3((unsigned)blocks), dim3(256), 0, s, pa, pb, pc, (uint8_t*)out, n, scale);
+    LAUNCH_DT(mix3_kernel, dim3((unsigned)blocks), pa, pb, pc, (uint8_t*)out, n, scale);
     return apad_check_launch("apad_mix3");
 }
 
@@ -547,9 +458,7 @@ extern "C" int apad_softmax_rows(const void* x, const float* bias, void* out, in
     const dim3 grid((unsigned)((M + 3) / 4));
     hipStream_t s = (hipStream_t)stream;
     const uint8_t* px = (const uint8_t*)x;
-    if (dtype == APAD_F32) hipLaunchKernelGGL((softmax_rows_kernel<APAD_F32>), grid, dim3(256), 0, s, px, bias, (uint8_t*)out, M, N, ldx, ldb, ldo, scale);
-    else if (dtype == APAD_BF16) hipLaunchKernelGGL((softmax_rows_kernel<APAD_BF16>), grid, dim3(256), 0, s, px, bias, (uint8_t*)out, M, N, ldx, ldb, ldo, scale);
-    else hipLaunchKernelGGL((softmax_rows_kernel<APAD_F16>), grid, dim3(256), 0, s, px, bias, (uint8_t*)out, M, N, ldx, ldb, ldo, scale);
+    LAUNCH_DT(softmax_rows_kernel, grid, px, bias, (uint8_t*)out, M, N, ldx, ldb, ldo, scale);
     return apad_check_launch("apad_softmax_rows");
 }
 
@@ -560,9 +469,7 @@ extern "C" int apad_rmsnorm(const void* x, const void* gamma, void* out, int64_t
     const dim3 grid((unsigned)((M + 3) / 4));
     hipStream_t s = (hipStream_t)stream;
     const uint8_t *px = (const uint8_t*)x, *pg = (const uint8_t*)gamma;
-    if (dtype == APAD_F32) hipLaunchKernelGGL((rmsnorm_kernel<APAD_F32>), grid, dim3(256), 0, s, px, pg, (uint8_t*)out, M, C, ldx, ldo, eps, mode);
-    else if (dtype == APAD_BF16) hipLaunchKernelGGL((rmsnorm_kernel<APAD_BF16>), grid, dim3(256), 0, s, px, pg, (uint8_t*)out, M, C, ldx, ldo, eps, mode);
-    else hipLaunchKernelGGL((rmsnorm_kernel<APAD_F16>), grid, dim3(256), 0, s, px, pg, (uint8_t*)out, M, C, ldx, ldo, eps, mode);
+    LAUNCH_DT(rmsnorm_kernel, grid, px, pg, (uint8_t*)out, M, C, ldx, ldo, eps, mode);
     return apad_check_launch("apad_rmsnorm");
 }
 
@@ -572,9 +479,7 @@ extern "C" int apad_gather_rows(const void* table, const int64_t* ids, void* out
     const dim3 grid((unsigned)((n + 3) / 4));
     hipStream_t s = (hipStream_t)stream;
     const uint8_t* pt = (const uint8_t*)table;
-    if (dtype == APAD_F32) hipLaunchKernelGGL((gather_rows_kernel<APAD_F32>), grid, dim3(256), 0, s, pt, ids, (uint8_t*)out, n, rows, C);
-    else if (dtype == APAD_BF16) hipLaunchKernelGGL((gather_rows_kernel<APAD_BF16>), grid, dim3(256), 0, s, pt, ids, (uint8_t*)out, n, rows, C);
-    else hipLaunchKernelGGL((gather_rows_kernel<APAD_F16>), grid, dim3(256), 0, s, pt, ids, (uint8_t*)out, n, rows, C);
+    LAUNCH_DT(gather_rows_kernel, grid, pt, ids, (uint8_t*)out, n, rows, C);
     return apad_check_launch("apad_gather_rows");
 }
 
@@ -586,9 +491,7 @@ extern "C" int apad_gaussian_sample(const void* moments, const void* noise, void
     if (blocks > 8192) blocks = 8192;
     hipStream_t s = (hipStream_t)stream;
     const uint8_t *pm = (const uint8_t*)moments, *pn = (const uint8_t*)noise;
-    if (dtype == APAD_F32) hipLaunchKernelGGL((gaussian_sample_kernel<APAD_F32>), dim3((unsigned)blocks), dim3(256), 0, s, pm, pn, (uint8_t*)out, rows, latent, scale);
-    else if (dtype == APAD_BF16) hipLaunchKernelGGL((gaussian_sample_kernel<APAD_BF16>), dim3((unsigned)blocks), dim3(256), 0, s, pm, pn, (uint8_t*)out, rows, latent, scale);
-    else hipLaunchKernelGGL((gaussian_sample_kernel<APAD_F16>), dim3((unsigned)blocks), dim3(256), 0, s, pm, pn, (uint8_t*)out, rows, latent, scale);
+    LAUNCH_DT(gaussian_sample_kernel, dim3((unsigned)blocks), pm, pn, (uint8_t*)out, rows, latent, scale);
     return apad_check_launch("apad_gaussian_sample");
 }
 

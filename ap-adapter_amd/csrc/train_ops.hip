@@ -356,12 +356,6 @@ constexpr int REDUCE_BLOCKS = 1024;
 }  // namespace
 
 #define TRAIN_DT_CHECK(name) APAD_CHECK(dtype == APAD_BF16 || dtype == APAD_F16 || dtype == APAD_F32, name ": dtype %d not supported", dtype)
-#define LAUNCH_DT(kern, grid, ...)                                                              \
-    do {                                                                                        \
-        if (dtype == APAD_BF16) hipLaunchKernelGGL((kern<APAD_BF16>), grid, dim3(256), 0, s, __VA_ARGS__); \
-        else if (dtype == APAD_F32) hipLaunchKernelGGL((kern<APAD_F32>), grid, dim3(256), 0, s, __VA_ARGS__); \
-        else hipLaunchKernelGGL((kern<APAD_F16>), grid, dim3(256), 0, s, __VA_ARGS__);          \
-    } while (0)
 
 extern "C" int apad_layernorm_bwd_add(const void* x, const void* gamma, const void* dy, const void* dres, void* dx, int64_t M, int32_t C,
                                       float eps, int32_t dtype, void* stream) {

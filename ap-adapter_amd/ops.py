@@ -1112,21 +1112,29 @@ def cfg_ddim_step(eps2, latents, unet_in, coef, step_ptr, guidance_scale, eps_ou
                                        _stream()), "apad_cfg_ddim_step")
 
 
-def cfg_sampler_step(eps2, latents, unet_in, coef, step_ptr, guidance_scale, eps_out=None, history=None, noise=None):
-    """cfg_ddim_step for a sampler with a six-column table (scheduler.SAMPLER_COLS): coef fp32 [steps, 6]; history fp32 like latents
-    (read as m1, overwritten with this step's data prediction); noise fp32 [steps, B, n...] (row *step_ptr is added, scaled)."""
-    _req(latents, "cfg_sampler_step.latents", torch.float32)
-    _req(coef, "cfg_sampler_step.coef", torch.float32)
+def _step_operands(fn, eps2, latents, unet_in, coef, eps_out, history, noise, x0=None, z0=None, keep=None):
+    """the table, dtype and numel checks of cfg_sampler_step / cfg_edit_step (``fn`` prefixes every message).  Returns (steps, B, n)."""
+    _req(latents, fn + ".latents", torch.float32)
+    _req(coef, fn + ".coef", torch.float32)
     if coef.dim() != 2 or coef.shape[1] != 6 or not coef.is_contiguous():
-        raise RuntimeError(f"cfg_sampler_step.coef: expected a contiguous [steps, 6] table, got {tuple(coef.shape)}")
+        raise RuntimeError(f"{fn}.coef: expected a contiguous [steps, 6] table, got {tuple(coef.shape)}")
     steps = coef.shape[0]
     B = latents.shape[0]
     n = latents.numel() // B
     if eps2.dtype != unet_in.dtype or eps2.numel() != 2 * latents.numel() or unet_in.numel() != latents.numel():
-        raise RuntimeError("cfg_sampler_step: eps2 [2B, n] and unet_in [B, n] must share the model dtype and match latents [B, n]")
-    for t, name, numel in ((eps_out, "eps_out", latents.numel()), (history, "history", latents.numel()), (noise, "noise", steps * latents.numel())):
-        if t is not None and (_req(t, "cfg_sampler_step." + name, torch.float32).numel() != numel or not t.is_contiguous()):
-            raise RuntimeError(f"cfg_sampler_step.{name}: expected {numel} contiguous fp32 values, got {tuple(t.shape)}")
+        raise RuntimeError(f"{fn}: eps2 [2B, n] and unet_in [B, n] must share the model dtype and match latents [B, n]")
+    numel = latents.numel()
+    for t, name, want in ((eps_out, "eps_out", numel), (history, "history", numel), (noise, "noise", steps * numel), (x0, "x0", numel),
+                          (z0, "z0", numel), (keep, "keep", 2 * steps)):
+        if t is not None and (_req(t, f"{fn}.{name}", torch.float32).numel() != want or not t.is_contiguous()):
+            raise RuntimeError(f"{fn}.{name}: expected {want} contiguous fp32 values, got {tuple(t.shape)}")
+    return steps, B, n
+
+
+def cfg_sampler_step(eps2, latents, unet_in, coef, step_ptr, guidance_scale, eps_out=None, history=None, noise=None):
+    """cfg_ddim_step for a sampler with a six-column table (scheduler.SAMPLER_COLS): coef fp32 [steps, 6]; history fp32 like latents
+    (read as m1, overwritten with this step's data prediction); noise fp32 [steps, B, n...] (row *step_ptr is added, scaled)."""
+    steps, B, n = _step_operands("cfg_sampler_step", eps2, latents, unet_in, coef, eps_out, history, noise)
     L.check(L.lib().apad_cfg_sampler_step(eps2.data_ptr(), latents.data_ptr(), unet_in.data_ptr(), _ptr(eps_out), _ptr(history), _ptr(noise),
                                           coef.data_ptr(), _ptr(step_ptr), steps, float(guidance_scale), B, n, _DT[eps2.dtype], _stream()),
             "apad_cfg_sampler_step")
@@ -1136,19 +1144,7 @@ def cfg_edit_step(eps2, latents, unet_in, coef, keep, step_ptr, guidance_scale, 
     """cfg_sampler_step followed by the edit blend: keep fp32 [steps, 2] (scheduler ``SamplerPlan.keep``), x0 / z0 fp32 like latents (the
     source latents and the noise that built the start), mask fp32 [1 or B, n / channels] with 1 = regenerate and 0 = keep;
     latents [B, n...] are NHWC with ``channels`` fastest.  mask = None is cfg_sampler_step."""
-    _req(latents, "cfg_edit_step.latents", torch.float32)
-    _req(coef, "cfg_edit_step.coef", torch.float32)
-    if coef.dim() != 2 or coef.shape[1] != 6 or not coef.is_contiguous():
-        raise RuntimeError(f"cfg_edit_step.coef: expected a contiguous [steps, 6] table, got {tuple(coef.shape)}")
-    steps = coef.shape[0]
-    B = latents.shape[0]
-    n = latents.numel() // B
-    if eps2.dtype != unet_in.dtype or eps2.numel() != 2 * latents.numel() or unet_in.numel() != latents.numel():
-        raise RuntimeError("cfg_edit_step: eps2 [2B, n] and unet_in [B, n] must share the model dtype and match latents [B, n]")
-    for t, name, numel in ((eps_out, "eps_out", latents.numel()), (history, "history", latents.numel()), (noise, "noise", steps * latents.numel()),
-                           (x0, "x0", latents.numel()), (z0, "z0", latents.numel()), (keep, "keep", 2 * steps)):
-        if t is not None and (_req(t, "cfg_edit_step." + name, torch.float32).numel() != numel or not t.is_contiguous()):
-            raise RuntimeError(f"cfg_edit_step.{name}: expected {numel} contiguous fp32 values, got {tuple(t.shape)}")
+    steps, B, n = _step_operands("cfg_edit_step", eps2, latents, unet_in, coef, eps_out, history, noise, x0, z0, keep)
     mask_batch = 0
     if mask is not None:
         _req(mask, "cfg_edit_step.mask", torch.float32)

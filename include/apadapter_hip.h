@@ -22,13 +22,15 @@
  *                       (pipeline/modeling_audioldm2.py:865-867)
  *   apad_audiomae_pool  AudioMAEConditionCTPoolRand.pool (audio_encoder/AudioMAE.py:148-182)
  *   apad_timestep_embedding  diffusers Timesteps (pipeline/modeling_audioldm2.py:317, :761)
- *   apad_cfg_ddim_step / apad_step_advance  CFG combine + DDIMScheduler.step
- *                       (pipeline/pipeline_audioldm2.py:1020-1025)
- *   apad_cfg_sampler_step  CFG combine + the step of any other scheduler the pipeline is built with (:158, :1025):
- *                       DDIMScheduler.step with eta > 0, DPMSolverMultistepScheduler.step (DPM-Solver++ 2M)
- *   apad_edit_start / apad_cfg_edit_step  editing from a source clip (no working counterpart in the reference; diffusers' img2img /
- *                       inpaint conventions): posterior draw + add_noise at the start timestep, and apad_cfg_sampler_step's step
- *                       followed by the re-imposition of the kept region
+ *   apad_cfg_ddim_step / apad_cfg_sampler_step / apad_cfg_edit_step  three entry points onto ONE kernel (cfg_step_kernel,
+ *                       csrc/elementwise.hip): CFG combine + scheduler step + fp32 master latents + model-dtype copy
+ *                       (pipeline/pipeline_audioldm2.py:1020-1025).  _ddim_: DDIMScheduler.step, eta = 0, two-column table;
+ *                       _sampler_: any other scheduler the pipeline is built with (:158, :1025) -- DDIMScheduler.step with eta > 0,
+ *                       DPMSolverMultistepScheduler.step (DPM-Solver++ 2M); _edit_: that step followed by the re-imposition of the kept
+ *                       region.  Each entry point's rounding form is written out beside the kernel (sampler_update, edit_blend)
+ *   apad_step_advance   the loop counter of the captured step
+ *   apad_edit_start     editing from a source clip (no working counterpart in the reference; diffusers' img2img / inpaint
+ *                       conventions): posterior draw + add_noise at the start timestep
  */
 #ifndef APADAPTER_HIP_H
 #define APADAPTER_HIP_H
@@ -464,7 +466,8 @@ int apad_timestep_embedding(const float* t, void* out, int32_t n, int32_t dim, i
 
 /* eps2 [2B][n] (dtype, unconditional half first); latents [B][n] fp32 updated in place;
    unet_in [B][n] (dtype) receives the new latents; eps_out (optional, fp32 [B][n]) the guided noise.
-   coef [steps][2] fp32: x_prev = coef[s][0]*x + coef[s][1]*eps, s = *step_ptr. */
+   coef [steps][2] fp32: x_prev = coef[s][0]*x + coef[s][1]*eps, s = *step_ptr.  The step kernel's STEP_DDIM form: scalar accesses only,
+   roundings as this entry point always had them (fp32: fma(c0, x, c1 * eps); 16-bit: c0 * x + c1 * eps, every operation rounded). */
 int apad_cfg_ddim_step(const void* eps2, float* latents, void* unet_in, float* eps_out, const float* coef,
                        const int32_t* step_ptr, float guidance_scale, int32_t B, int64_t n, int32_t dtype,
                        void* stream);
@@ -474,7 +477,9 @@ int apad_step_advance(int32_t* step_ptr, void* stream);
      x' = r[0] x + r[1] eps + r[2] m1 + r[3] z[s] ,   m0 = r[4] x + r[5] eps
    latents / unet_in / eps_out as above; history (optional, fp32 [B][n]): read as m1 -- only when r[2] != 0 -- and overwritten with
    m0, the data prediction the next step reads (DPM-Solver++ 2M); noise (optional, fp32 [n_steps][B][n]): z[s], read only when
-   r[3] != 0 (DDIM eta > 0).  A null history / noise contributes 0.  One launch, no host involvement: hipGraph-capturable. */
+   r[3] != 0 (DDIM eta > 0).  A null history / noise contributes 0.  One launch, no host involvement: hipGraph-capturable.
+   16-byte accesses when every base is 16-byte aligned and 8 | B * n, a scalar form otherwise; the two forms fuse their multiply-adds
+   differently, each as sampler_update (csrc/elementwise.hip) spells it.  This is apad_cfg_edit_step's kernel with a null mask. */
 int apad_cfg_sampler_step(const void* eps2, float* latents, void* unet_in, float* eps_out, float* history, const float* noise,
                           const float* coef, const int32_t* step_ptr, int32_t n_steps, float guidance_scale, int32_t B, int64_t n,
                           int32_t dtype, void* stream);
@@ -485,7 +490,8 @@ int apad_cfg_sampler_step(const void* eps2, float* latents, void* unet_in, float
    x0 / z0 fp32 [B][n]: the source latents and the noise that built the start (apad_edit_start).  mask fp32 [mask_batch][n / C],
    mask_batch 1 (shared) or B; element j of a clip belongs to pixel j / C (NHWC, channel fastest).  m0 -> history is formed from the
    pre-blend x and eps.  16-byte accesses under apad_cfg_sampler_step's rule plus C == 8 (one vector = one pixel), a scalar form
-   otherwise.  A null mask makes this apad_cfg_sampler_step (keep / x0 / z0 unread).  One launch, hipGraph-capturable. */
+   otherwise.  A null mask makes this apad_cfg_sampler_step (keep / x0 / z0 unread): the same kernel, the same bits.  One launch,
+   hipGraph-capturable. */
 int apad_cfg_edit_step(const void* eps2, float* latents, void* unet_in, float* eps_out, float* history, const float* noise,
                        const float* coef, const float* keep, const float* x0, const float* z0, const float* mask, int32_t mask_batch,
                        int32_t C, const int32_t* step_ptr, int32_t n_steps, float guidance_scale, int32_t B, int64_t n, int32_t dtype,

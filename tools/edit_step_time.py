@@ -1,5 +1,5 @@
-"""Time apad_cfg_edit_step against apad_cfg_sampler_step at the bench geometry (B = 32 clips of 4000 latent pixels x 8 channels, bf16),
-both in ONE process, alternating, and write the medians to profiles/edit_step.json.
+"""Time apad_cfg_edit_step against apad_cfg_sampler_step, and apad_cfg_ddim_step on its two-column table, at the bench geometry (B = 32
+clips of 4000 latent pixels x 8 channels, bf16), all in ONE process, alternating, and write the medians to profiles/edit_step.json.
 
     python tools/edit_step_time.py [--out profiles/edit_step.json] [--rounds 15] [--launches 200]
 
@@ -22,8 +22,9 @@ B, NPIX, C, STEPS = 32, 4000, 8, 200
 def bytes_per_element(kernel):
     """what the algorithm moves per latent element, bf16 model dtype, DPM-Solver++ 2M interior step (history read and written):
     eps2 2 x 2 read, latents 4 read + 4 written, unet_in 2 written, history 4 read + 4 written = 22; the edit step adds x0 and z0
-    (4 + 4 read) and one mask value per 8 elements (0.5)"""
-    return 22.0 if kernel == "sampler" else 30.5
+    (4 + 4 read) and one mask value per 8 elements (0.5);
+    the deterministic DDIM entry reads and writes no history: 14"""
+    return {"sampler": 22.0, "edit": 30.5, "cfg_ddim": 14.0}[kernel]
 
 
 def child(args):
@@ -48,6 +49,8 @@ def child(args):
         x0, z0 = R(B, n).to(dev), R(B, n).to(dev)
         mask = (torch.rand(B, NPIX, generator=g) > 0.5).float().to(dev)
         ptr = torch.full((1,), STEPS // 2, dtype=torch.int32, device=dev)  # an interior (second-order) row
+        kernels = ("sampler", "edit") + (("cfg_ddim",) if name == "ddim" else ())
+        coef2 = sched.coef_table().to(dev) if name == "ddim" else None  # apad_cfg_ddim_step's two-column table
 
         def run(kernel, launches):
             lat.copy_(lat0)
@@ -56,7 +59,9 @@ def child(args):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
             for _ in range(launches):
-                if kernel == "sampler":
+                if kernel == "cfg_ddim":
+                    ops.cfg_ddim_step(eps2, lat, unet_in, coef2, ptr, 7.5)
+                elif kernel == "sampler":
                     ops.cfg_sampler_step(eps2, lat, unet_in, coef, ptr, 7.5, None, hist)
                 else:
                     ops.cfg_edit_step(eps2, lat, unet_in, coef, keep, ptr, 7.5, x0, z0, mask, C, None, hist)
@@ -64,20 +69,21 @@ def child(args):
             torch.cuda.synchronize()
             return e0.elapsed_time(e1) * 1e3 / launches  # us per launch
 
-        for kernel in ("sampler", "edit"):  # warm-up: code objects loaded, buffers touched
+        for kernel in kernels:  # warm-up: code objects loaded, buffers touched
             run(kernel, 20)
-        times = {"sampler": [], "edit": []}
-        for _ in range(args.rounds):  # alternate the two within every round
-            for kernel in ("sampler", "edit"):
+        times = {kernel: [] for kernel in kernels}
+        for _ in range(args.rounds):  # alternate the kernels within every round
+            for kernel in kernels:
                 times[kernel].append(run(kernel, args.launches))
         results[name] = {}
         for kernel, ts in times.items():
             med = statistics.median(ts)
+            no_hist = 8.0 if hist is None and kernel != "cfg_ddim" else 0.0
             results[name][kernel] = {"median_us": round(med, 3), "min_us": round(min(ts), 3), "max_us": round(max(ts), 3),
-                                     "bytes_per_element_by_shape": bytes_per_element(kernel) if hist is not None else bytes_per_element(kernel) - 8.0,
-                                     "GB_per_s_at_median": round((bytes_per_element(kernel) - (0.0 if hist is not None else 8.0)) * B * n / med / 1e3, 1)}
+                                     "bytes_per_element_by_shape": bytes_per_element(kernel) - no_hist,
+                                     "GB_per_s_at_median": round((bytes_per_element(kernel) - no_hist) * B * n / med / 1e3, 1)}
         results[name]["edit_minus_sampler_us"] = round(results[name]["edit"]["median_us"] - results[name]["sampler"]["median_us"], 3)
-    out = {"what": "apad_cfg_edit_step vs apad_cfg_sampler_step, back-to-back launches timed with device events; medians over rounds, the two "
+    out = {"what": "apad_cfg_edit_step vs apad_cfg_sampler_step (and apad_cfg_ddim_step under \"ddim\"), back-to-back launches timed with device events; medians over rounds, the "
                    "kernels alternated within each round; the working set (tens of MB) stays cache-resident across launches, so the rates are "
                    "not HBM rates",
            "not_measured": ["end-to-end edit time", "audio quality (no real weights)"],
