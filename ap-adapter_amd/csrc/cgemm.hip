@@ -19,6 +19,7 @@
 //     (MI355X_MICROARCH.md, "Two waves per SIMD")
 #include <type_traits>
 #include "gfx950_prims.h"
+#include "gemm_shared.h"
 
 namespace {
 
@@ -104,20 +105,7 @@ __global__ __launch_bounds__(512) void cgemm_kernel(CgP p) {
 
     // XCD-aware tile order (speed only): all N-tiles of one M-tile share blockIdx % 8, i.e. one XCD's L2 fetches an A panel once
     int mt, nt;
-    {
-        const int nN = p.n_tiles, nM = p.m_tiles;
-        const int b = blockIdx.x;
-        const int full = (nM / 8) * 8 * nN;
-        if (b < full) {
-            const int g = b / (8 * nN), rem = b - g * 8 * nN;
-            nt = rem >> 3;
-            mt = g * 8 + (rem & 7);
-        } else {
-            const int rem = b - full, tail = nM - (nM / 8) * 8;
-            nt = rem / tail;
-            mt = (nM / 8) * 8 + rem - nt * tail;
-        }
-    }
+    xcd_tile_order(blockIdx.x, p.m_tiles, p.n_tiles, mt, nt);
     const int m0 = mt * CBM, n0 = nt * BN;
 
     // ---- DMA sources.  One instruction of a wave fills one 1 KB block = 8 tile rows x 128 bytes; lane -> (row r = lane / 8,
@@ -403,20 +391,7 @@ __global__ __launch_bounds__(256) void cconv_small_kernel(CgP p) {
     const int wm = wave >> 1, wn = wave & 1;
     const int half = lane >> 5, l31 = lane & 31;
     int mt, nt;
-    {
-        const int nN = p.n_tiles, nM = p.m_tiles;
-        const int b = blockIdx.x;
-        const int full = (nM / 8) * 8 * nN;
-        if (b < full) {
-            const int g = b / (8 * nN), rem = b - g * 8 * nN;
-            nt = rem >> 3;
-            mt = g * 8 + (rem & 7);
-        } else {
-            const int rem = b - full, tail = nM - (nM / 8) * 8;
-            nt = rem / tail;
-            mt = (nM / 8) * 8 + rem - nt * tail;
-        }
-    }
+    xcd_tile_order(blockIdx.x, p.m_tiles, p.n_tiles, mt, nt);
     const int m0 = mt * SBM, n0 = nt * SBN;
     const __amdgpu_buffer_rsrc_t ra = buf_rsrc(p.a, p.a_bytes), rw = buf_rsrc(p.w, p.w_bytes);
     // DMA sources: wave w fills blocks 2w, 2w + 1 (8 rows each) of the A tile and of the W tile

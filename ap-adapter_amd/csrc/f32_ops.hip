@@ -18,7 +18,7 @@
 // 32x32x16 MFMAs replace eight 32x32x2_f32 per 16 k.  Activations are split in registers on their way into LDS (an LDS-DMA
 // copy cannot split); weights arrive as the two bf16 planes of apad_f32_split_weight.
 #include <math.h>
-#include "common.h"
+#include "gemm_shared.h"
 #include "f32_ops.h"
 
 namespace {
@@ -32,7 +32,6 @@ __device__ __forceinline__ float silu_p(float x) { return x / (1.0f + expf(-x));
 __device__ __forceinline__ float gelu_p(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
 // "gelu_new" of GPT-2 / T5's gated-gelu (transformers NewGELUActivation)
 __device__ __forceinline__ float gelu_tanh_p(float x) { return 0.5f * x * (1.0f + tanhf(0.7978845608028654f * (x + 0.044715f * x * x * x))); }
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 int64_t g_f32x3_launches = 0;  // (tests assert the route with it; not synchronised: a diagnostic)
 
@@ -94,12 +93,10 @@ struct G32P {
     const float* rg;
     const int32_t* step_ptr;
     int64_t M, N, K, lda, ldw, ldo, ldr, ld_rg, rows_per_group;
-    int32_t Hin, Win, Cin, Hout, Wout, stride, Hup, Wup, src_batch_mod, res_mod;
+    AGeom g;  // (gemm_shared.h: the A-operand geometry, its row decode and gather offsets)
+    int32_t res_mod;
     int32_t heads, head_dim, L, Lpad;
     int32_t epi, outmode, n_tiles;
-    int32_t taps, dilation, pad, transposed, pre_act;  // APAD_A_CONV1D
-    float pre_slope;
-    int32_t lead;  // conv3x3: zero rows / columns before the first source row / column (1, or 0 with conv_asym_pad)
     int64_t wplane;  // APAD_F32_BF16X3: bf16 elements from the hi plane of w to its lo plane
 };
 
@@ -109,49 +106,18 @@ __device__ __forceinline__ int lds32(int row, int chunk) { return row * BKF + ((
 // fragment reads (32 rows at one chunk) are then conflict-free in each of ds_read_b128's 16-lane groups
 __device__ __forceinline__ int ldsx(int row, int c16) { return row * BKF + ((c16 ^ ((row >> 2) & 3)) << 3); }
 
-struct Row32 {
-    int64_t base;  // PLAIN: element offset of the row; CONV / PATCH: source batch index
-    int oy, ox;
-    bool valid;
-};
-
-template <int AMODE> __device__ __forceinline__ f4 load_a32(const G32P& p, const Row32& r, int k) {
+template <int AMODE> __device__ __forceinline__ f4 load_a32(const G32P& p, const ARow& r, int k) {
     const f4 z = {0.f, 0.f, 0.f, 0.f};
     if (!r.valid || k >= p.K) return z;
-    if (AMODE == APAD_A_PLAIN) {
-        return *reinterpret_cast<const f4*>(p.a + r.base + k);
-    } else if (AMODE == APAD_A_CONV3X3) {
-        const int tap = k / p.Cin, c = k - tap * p.Cin;
-        const int ky = tap / 3, kx = tap - ky * 3;
-        int iy = r.oy * p.stride + ky - p.lead, ix = r.ox * p.stride + kx - p.lead;
-        const int H = p.Hup > 0 ? p.Hup : p.Hin, W = p.Hup > 0 ? p.Wup : p.Win;
-        if (iy < 0 || iy >= H || ix < 0 || ix >= W) return z;
-        if (p.Hup > 0) {  // nearest-neighbour source index, floor(dst * in / out)
-            iy = (int)(((int64_t)iy * p.Hin) / p.Hup);
-            ix = (int)(((int64_t)ix * p.Win) / p.Wup);
-        }
-        return *reinterpret_cast<const f4*>(p.a + ((r.base * p.Hin + iy) * p.Win + ix) * p.Cin + c);
-    } else if (AMODE == APAD_A_CONV1D) {  // channels-last [B][Hin][Cin]; r.base = b, r.oy = t; k = (tap, c)
-        const int tap = k / p.Cin, c = k - tap * p.Cin;
-        int ti;
-        if (p.transposed) {
-            const int num = r.oy + p.pad - tap;
-            ti = num / p.stride;
-            if (num < 0 || ti * p.stride != num) return z;
-        } else {
-            ti = r.oy + tap * p.dilation - p.pad;
-        }
-        if (ti < 0 || ti >= p.Hin) return z;
-        f4 v = *reinterpret_cast<const f4*>(p.a + ((int64_t)r.base * p.Hin + ti) * p.Cin + c);
-        if (p.pre_act) {
+    if (AMODE == APAD_A_PLAIN) return *reinterpret_cast<const f4*>(p.a + r.base + k);
+    const int64_t off = a_src_offset<AMODE>(p.g, r, k);
+    if (off == A_ZERO) return z;
+    f4 v = *reinterpret_cast<const f4*>(p.a + off);
+    if (AMODE == APAD_A_CONV1D && p.g.pre_act) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * p.pre_slope;
-        }
-        return v;
-    } else {  // PATCH16: mel [B][Hin][Win]; k = py * 16 + px
-        const int py = k >> 4, px = k & 15;
-        return *reinterpret_cast<const f4*>(p.a + (r.base * p.Hin + r.oy * 16 + py) * p.Win + r.ox * 16 + px);
+        for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * p.g.pre_slope;
     }
+    return v;
 }
 
 template <int AMODE, bool X3> __device__ __forceinline__ void gemm_f32_body(const G32P& p) {
@@ -173,7 +139,7 @@ template <int AMODE, bool X3> __device__ __forceinline__ void gemm_f32_body(cons
         return n0 + nl < p.N;
     };
     const int chunk = tid & 7;
-    Row32 ra[2];
+    ARow ra[2];
     int64_t wb[2];
     bool wv[2];
 #pragma unroll
@@ -184,27 +150,8 @@ template <int AMODE, bool X3> __device__ __forceinline__ void gemm_f32_body(cons
         ra[i].oy = ra[i].ox = 0;
         ra[i].base = 0;
         if (ra[i].valid) {
-            if (AMODE == APAD_A_PLAIN) {
-                ra[i].base = m * p.lda;
-            } else if (AMODE == APAD_A_CONV3X3) {
-                const int64_t hw = (int64_t)p.Hout * p.Wout;
-                const int64_t b = m / hw;
-                const int rem = (int)(m - b * hw);
-                ra[i].oy = rem / p.Wout;
-                ra[i].ox = rem - ra[i].oy * p.Wout;
-                ra[i].base = p.src_batch_mod > 0 ? b % p.src_batch_mod : b;
-            } else if (AMODE == APAD_A_CONV1D) {
-                const int64_t b = m / p.Hout;
-                ra[i].oy = (int)(m - b * p.Hout);
-                ra[i].base = b;
-            } else {
-                const int wp = p.Win >> 4, hp = p.Hin >> 4;
-                const int64_t b = m / (hp * wp);
-                const int rem = (int)(m - b * hp * wp);
-                ra[i].oy = rem / wp;
-                ra[i].ox = rem - ra[i].oy * wp;
-                ra[i].base = b;
-            }
+            if (AMODE == APAD_A_PLAIN) ra[i].base = m * p.lda;
+            else decode_row<AMODE>(p.g, m, ra[i]);
         }
         wv[i] = wvalid(rl);
         wb[i] = wv[i] ? wrow(rl) * p.ldw : 0;
@@ -836,13 +783,27 @@ extern "C" int apad_f32_split_weight(const void* w, void* out, int64_t N, int64_
 extern "C" int64_t apad_f32x3_launch_count(void) { return g_f32x3_launches; }
 
 int apad_f32_gemm(const apad_gemm_desc* d, hipStream_t s) {
-    APAD_CHECK(d->a && d->w && d->out, "apad_gemm(f32): null operand");
-    APAD_CHECK(d->M > 0 && d->N > 0 && d->K > 0, "apad_gemm(f32): empty problem M=%lld N=%lld K=%lld", (long long)d->M, (long long)d->N,
-               (long long)d->K);
-    APAD_CHECK(d->K % 4 == 0 && d->ldw % 4 == 0, "apad_gemm(f32): K and ldw must be multiples of 4 (K=%lld ldw=%lld)", (long long)d->K,
-               (long long)d->ldw);
+    const bool geglu = d->epilogue == APAD_EPI_GEGLU || d->epilogue == APAD_EPI_GEGLU_TANH;
+    if (gemm_desc_check(d, 4, "apad_gemm(f32)", geglu, false) != 0) return -1;
     const bool x3 = d->dtype == APAD_F32_BF16X3;  // w: the split planes of apad_f32_split_weight, ldw in bf16 elements
-    APAD_CHECK(al16(d->a) && al16(d->w) && al16(d->out) && al16(d->residual), "apad_gemm(f32): pointers must be 16-byte aligned");
+    // what this path alone checks: its epilogue range and the epilogue / output combinations of each A mode
+    APAD_CHECK(d->epilogue >= APAD_EPI_NONE && d->epilogue <= APAD_EPI_GEGLU_TANH, "apad_gemm(f32): unknown epilogue %d", d->epilogue);
+    if (d->a_mode == APAD_A_CONV3X3) {
+        APAD_CHECK(d->epilogue == APAD_EPI_NONE && d->out_mode == APAD_OUT_ROWMAJOR,
+                   "apad_gemm(f32): conv3x3 supports epilogue NONE / row-major output only");
+    } else if (d->a_mode == APAD_A_PATCH16) {
+        APAD_CHECK(d->epilogue == APAD_EPI_NONE && d->out_mode == APAD_OUT_ROWMAJOR,
+                   "apad_gemm(f32): patch16 supports epilogue NONE / row-major output only");
+    } else if (d->a_mode == APAD_A_CONV1D) {
+        APAD_CHECK((d->epilogue == APAD_EPI_NONE || d->epilogue == APAD_EPI_TANH) && d->out_mode == APAD_OUT_ROWMAJOR,
+                   "apad_gemm(f32): conv1d supports epilogue NONE / TANH and row-major output only");
+    } else if (d->a_mode != APAD_A_PLAIN) {
+        apad_set_error("apad_gemm(f32): unknown a_mode %d", d->a_mode);
+        return -1;
+    }
+    if (d->out_mode == APAD_OUT_QKV)
+        APAD_CHECK(d->epilogue == APAD_EPI_NONE && d->a_mode == APAD_A_PLAIN, "apad_gemm(f32): APAD_OUT_QKV supports plain A / epilogue NONE only");
+    if (d->out_mode == APAD_OUT_VT) APAD_CHECK(d->epilogue == APAD_EPI_NONE, "apad_gemm(f32): APAD_OUT_VT supports epilogue NONE only");
     G32P p;
     p.a = (const float*)d->a; p.w = (const float*)d->w; p.out = (float*)d->out; p.out2 = (float*)d->out2; p.out3 = (float*)d->out3;
     p.bias = (const float*)d->bias; p.residual = (const float*)d->residual; p.rg = (const float*)d->rowgroup_bias;
@@ -850,62 +811,11 @@ int apad_f32_gemm(const apad_gemm_desc* d, hipStream_t s) {
     p.M = d->M; p.N = d->N; p.K = d->K;
     p.lda = d->lda; p.ldw = d->ldw; p.ldo = d->ldo; p.ldr = d->ldr; p.ld_rg = d->ld_rg;
     p.rows_per_group = d->rows_per_group > 0 ? d->rows_per_group : 1;
-    p.Hin = d->Hin; p.Win = d->Win; p.Cin = d->Cin; p.Hout = d->Hout; p.Wout = d->Wout;
-    p.stride = d->stride; p.Hup = d->Hup; p.Wup = d->Wup; p.src_batch_mod = d->src_batch_mod; p.res_mod = d->residual_row_mod;
+    p.g = a_geom(d);
+    p.res_mod = d->residual_row_mod;
     p.heads = d->heads; p.head_dim = d->head_dim; p.L = d->L; p.Lpad = d->Lpad;
     p.epi = d->epilogue; p.outmode = d->out_mode;
-    APAD_CHECK(d->epilogue >= APAD_EPI_NONE && d->epilogue <= APAD_EPI_GEGLU_TANH, "apad_gemm(f32): unknown epilogue %d", d->epilogue);
-    p.taps = d->taps; p.dilation = d->dilation; p.pad = d->pad; p.transposed = d->transposed; p.pre_act = d->a_pre_act;
-    p.pre_slope = d->a_pre_slope;
-    p.lead = d->conv_asym_pad ? 0 : 1;
-    if (d->a_mode == APAD_A_PLAIN) {
-        APAD_CHECK(d->lda % 4 == 0, "apad_gemm(f32): lda must be a multiple of 4");
-    } else if (d->a_mode == APAD_A_CONV3X3) {
-        APAD_CHECK(d->epilogue == APAD_EPI_NONE && d->out_mode == APAD_OUT_ROWMAJOR,
-                   "apad_gemm(f32): conv3x3 supports epilogue NONE / row-major output only");
-        APAD_CHECK(d->Cin > 0 && d->Cin % 4 == 0 && d->K == 9LL * d->Cin, "apad_gemm(f32): conv3x3 needs Cin%%4==0 and K==9*Cin");
-        APAD_CHECK(d->stride == 1 || d->stride == 2, "apad_gemm(f32): conv stride must be 1 or 2");
-        APAD_CHECK(d->Hin > 0 && d->Win > 0 && d->Hout > 0 && d->Wout > 0 && d->M % ((int64_t)d->Hout * d->Wout) == 0,
-                   "apad_gemm(f32): conv geometry inconsistent with M");
-        APAD_CHECK((d->Hup > 0) == (d->Wup > 0), "apad_gemm(f32): Hup/Wup must both be set or both 0");
-    } else if (d->a_mode == APAD_A_PATCH16) {
-        APAD_CHECK(d->epilogue == APAD_EPI_NONE && d->out_mode == APAD_OUT_ROWMAJOR,
-                   "apad_gemm(f32): patch16 supports epilogue NONE / row-major output only");
-        APAD_CHECK(d->K == 256 && d->Hin % 16 == 0 && d->Win % 16 == 0, "apad_gemm(f32): patch16 needs K==256 and H,W %% 16 == 0");
-        APAD_CHECK(d->M % ((int64_t)(d->Hin / 16) * (d->Win / 16)) == 0, "apad_gemm(f32): patch16 M inconsistent");
-    } else if (d->a_mode == APAD_A_CONV1D) {
-        APAD_CHECK((d->epilogue == APAD_EPI_NONE || d->epilogue == APAD_EPI_TANH) && d->out_mode == APAD_OUT_ROWMAJOR,
-                   "apad_gemm(f32): conv1d supports epilogue NONE / TANH and row-major output only");
-        APAD_CHECK(d->Cin > 0 && d->Cin % 4 == 0 && d->taps > 0 && d->K == (int64_t)d->taps * d->Cin, "apad_gemm(f32): conv1d needs Cin%%4==0 and K==taps*Cin");
-        APAD_CHECK(d->Hin > 0 && d->Hout > 0 && d->M % d->Hout == 0 && d->pad >= 0, "apad_gemm(f32): conv1d geometry inconsistent with M");
-        APAD_CHECK(d->transposed ? d->stride >= 1 : d->dilation >= 1, "apad_gemm(f32): conv1d needs dilation >= 1 (stride >= 1 when transposed)");
-    } else {
-        apad_set_error("apad_gemm(f32): unknown a_mode %d", d->a_mode);
-        return -1;
-    }
-    if (d->out_mode == APAD_OUT_ROWMAJOR) {
-        APAD_CHECK(d->N % 4 == 0 && d->ldo % 4 == 0, "apad_gemm(f32): N and ldo must be multiples of 4");
-        if (d->residual) APAD_CHECK(d->ldr % 4 == 0, "apad_gemm(f32): ldr must be a multiple of 4");
-        if (d->epilogue == APAD_EPI_GEGLU || d->epilogue == APAD_EPI_GEGLU_TANH) APAD_CHECK(d->N % 32 == 0, "apad_gemm(f32): GEGLU needs N %% 32 == 0");
-    } else if (d->out_mode == APAD_OUT_QKV) {
-        APAD_CHECK(d->epilogue == APAD_EPI_NONE && d->a_mode == APAD_A_PLAIN, "apad_gemm(f32): APAD_OUT_QKV supports plain A / epilogue NONE only");
-        APAD_CHECK(d->out2 && d->out3 && al16(d->out2) && al16(d->out3), "apad_gemm(f32): APAD_OUT_QKV needs 16-byte aligned out2 / out3");
-        APAD_CHECK(d->heads > 0 && d->head_dim > 0 && d->L > 0 && d->Lpad >= d->L && d->N == 3LL * d->heads * d->head_dim &&
-                       d->M % d->L == 0 && (d->N / 3) % 64 == 0 && d->ldo % 4 == 0,
-                   "apad_gemm(f32): fused q|k|v geometry inconsistent (needs C %% 64 == 0)");
-        APAD_CHECK(!d->residual, "apad_gemm(f32): fused q|k|v takes no residual");
-    } else if (d->out_mode == APAD_OUT_VT) {
-        APAD_CHECK(d->epilogue == APAD_EPI_NONE, "apad_gemm(f32): APAD_OUT_VT supports epilogue NONE only");
-        APAD_CHECK(d->heads > 0 && d->head_dim > 0 && d->L > 0 && d->Lpad >= d->L && d->N == (int64_t)d->heads * d->head_dim &&
-                       d->M % d->L == 0,
-                   "apad_gemm(f32): V^T output geometry inconsistent");
-        APAD_CHECK(!d->residual, "apad_gemm(f32): V^T output takes no residual");
-    } else {
-        apad_set_error("apad_gemm(f32): unknown out_mode %d", d->out_mode);
-        return -1;
-    }
-    if (d->rowgroup_bias) APAD_CHECK(d->ld_rg > 0, "apad_gemm(f32): rowgroup_bias needs ld_rg");
-    const int bn_out = (d->epilogue == APAD_EPI_GEGLU || d->epilogue == APAD_EPI_GEGLU_TANH) ? TB / 2 : TB;
+    const int bn_out = geglu ? TB / 2 : TB;
     p.n_tiles = (int)((d->N + bn_out - 1) / bn_out);
     const int64_t m_tiles = (d->M + TB - 1) / TB;
     dim3 grid((unsigned)(p.n_tiles * m_tiles));

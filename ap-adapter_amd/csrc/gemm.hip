@@ -12,6 +12,7 @@
 // Epilogue: accumulators -> LDS tile -> full-row 16 B stores (residual read with the same coalescing).
 #include <type_traits>
 #include "gfx950_prims.h"
+#include "gemm_shared.h"
 #include "f32_ops.h"
 
 namespace {
@@ -37,38 +38,7 @@ template <int TM, int NS = 1, int KG = 1> struct Tile {
     static constexpr int NLD = TM / 32;             // staging vectors per thread per operand
 };
 
-struct GemmP {
-    const uint8_t* a;
-    const uint8_t* w;
-    uint8_t* out;
-    uint8_t* out2;
-    uint8_t* out3;
-    uint8_t* out4;  // APAD_OUT_QKV: optional row-major v
-    const uint8_t* bias;
-    const uint8_t* residual;
-    const uint8_t* rg;
-    const int32_t* step_ptr;
-    int64_t M, N, K, lda, ldw, ldo, ldr, ld_rg, rows_per_group;
-    int32_t Hin, Win, Cin, Hout, Wout, stride, Hup, Wup, src_batch_mod, res_mod;
-    int32_t heads, head_dim, L, Lpad;
-    int32_t wrows;  // rows of w (N, or 2N for GEGLU)
-    int32_t m_tiles, n_tiles;
-    int32_t taps, dilation, pad, transposed, pre_act;  // APAD_A_CONV1D
-    float pre_slope;
-    int32_t lead;  // conv3x3: zero rows / columns before the first source row / column (1, or 0 with conv_asym_pad)
-    // LayerNorm folded into the contraction (apad_gemm_desc::rowstat_in): a = RAW rows, w = gamma-scaled weights,
-    // out = rstd_m * (acc - mean_m * ln_cs[n]) + ln_bb[n]; the row statistics are summed from the producing kernel's partials
-    float* rs_out;        // [M][rs_out_tiles][2]: per 64-column block (sum, sum of squares) of the stored output row
-    const float* rs_in;   // [M][rs_in_tiles][2]
-    const float* ln_cs;   // [w rows]
-    const float* ln_bb;   // [w rows]
-    int32_t rs_in_tiles, rs_out_tiles;
-    float ln_eps;
-    // two-source plain A (apad_gemm_desc::a2): columns >= ksplit of row m come from a2[(m % a2_mod) * lda2 + k - ksplit]
-    const uint8_t* a2;
-    int64_t lda2;
-    int32_t ksplit, a_mod, a2_mod;
-};
+// (GemmP, the A-operand geometry / decode / gather, the tile order and the epilogue: gemm_shared.h)
 
 // byte offset of 16-byte chunk `chunk` (0..7) of tile row `row` (128-byte rows)
 __device__ __forceinline__ int lds_off(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
@@ -78,14 +48,8 @@ __device__ __forceinline__ int lds_off(int row, int chunk) { return row * 128 + 
 // divisions, and each row keeps a precomputed element offset (the gather was 25 % of the conv kernel's wave cycles in VALU)
 #define APAD_A_CONV3X3_FAST 3
 
-template <int AMODE> struct RowInfo {
-    int64_t base;  // PLAIN: element offset of the row; CONV/PATCH: source batch index
-    int oy, ox;
-    bool valid;
-};
-
 template <int DT, int AMODE>
-__device__ __forceinline__ uint4 load_a(const GemmP& p, const RowInfo<AMODE>& r, int k) {
+__device__ __forceinline__ uint4 load_a(const GemmP& p, const ARow& r, int k) {
     uint4 z = make_uint4(0, 0, 0, 0);
     if (!r.valid || k >= p.K) return z;
     if (AMODE == APAD_A_PLAIN) {
@@ -94,47 +58,24 @@ __device__ __forceinline__ uint4 load_a(const GemmP& p, const RowInfo<AMODE>& r,
             return *reinterpret_cast<const uint4*>(p.a2 + (m2 * p.lda2 + (k - p.ksplit)) * 2);
         }
         return *reinterpret_cast<const uint4*>(p.a + (r.base + k) * 2);
-    } else if (AMODE == APAD_A_CONV3X3) {
-        int tap = k / p.Cin;
-        int c = k - tap * p.Cin;
-        int ky = tap / 3, kx = tap - ky * 3;
-        int iy = r.oy * p.stride + ky - p.lead, ix = r.ox * p.stride + kx - p.lead;
-        int H = p.Hup > 0 ? p.Hup : p.Hin, W = p.Hup > 0 ? p.Wup : p.Win;
-        if (iy < 0 || iy >= H || ix < 0 || ix >= W) return z;
-        if (p.Hup > 0) {  // nearest-neighbour source index, floor(dst * in / out)
-            iy = (int)(((int64_t)iy * p.Hin) / p.Hup);
-            ix = (int)(((int64_t)ix * p.Win) / p.Wup);
-        }
-        int64_t off = ((r.base * p.Hin + iy) * p.Win + ix) * p.Cin + c;
-        return *reinterpret_cast<const uint4*>(p.a + off * 2);
-    } else if (AMODE == APAD_A_CONV1D) {  // channels-last [B][Hin][Cin]; r.base = b, r.oy = t; k = (tap, c)
-        const int tap = k / p.Cin, c = k - tap * p.Cin;
-        int ti;
-        if (p.transposed) {
-            const int num = r.oy + p.pad - tap;
-            ti = num / p.stride;
-            if (num < 0 || ti * p.stride != num) return z;
-        } else {
-            ti = r.oy + tap * p.dilation - p.pad;
-        }
-        if (ti < 0 || ti >= p.Hin) return z;
-        uint4 v = *reinterpret_cast<const uint4*>(p.a + (((int64_t)r.base * p.Hin + ti) * p.Cin + c) * 2);
-        if (p.pre_act) {  // the vocoder's pre-activation, applied while staging
-            float f[8];
-            unpack8<DT>(v, f);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) f[e] = f[e] > 0.f ? f[e] : f[e] * p.pre_slope;
-            v = pack8<DT>(f);
-        }
-        return v;
-    } else {  // PATCH16: fp32 mel [B][Hin][Win]; k = py*16 + px
-        int py = k >> 4, px = k & 15;
-        int64_t off = (r.base * p.Hin + r.oy * 16 + py) * p.Win + r.ox * 16 + px;
+    }
+    const int64_t off = a_src_offset<AMODE>(p.g, r, k);
+    if (off == A_ZERO) return z;
+    if (AMODE == APAD_A_PATCH16) {  // fp32 mel, converted while staging
         const float4* src = reinterpret_cast<const float4*>(p.a + off * 4);
         float4 f0 = src[0], f1 = src[1];
         float f[8] = {f0.x, f0.y, f0.z, f0.w, f1.x, f1.y, f1.z, f1.w};
         return pack8<DT>(f);
     }
+    uint4 v = *reinterpret_cast<const uint4*>(p.a + off * 2);
+    if (AMODE == APAD_A_CONV1D && p.g.pre_act) {  // the vocoder's pre-activation, applied while staging
+        float f[8];
+        unpack8<DT>(v, f);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) f[e] = f[e] > 0.f ? f[e] : f[e] * p.g.pre_slope;
+        v = pack8<DT>(f);
+    }
+    return v;
 }
 
 template <int DT, int AMODE, int EPI, int OUTMODE, int TM, int NS = 1, int KG = 1>
@@ -151,57 +92,18 @@ __global__ __launch_bounds__(256 * KG) void gemm_kernel(GemmP p) {
     const int wm = wave >> 1, wn = wave & 1;
     const int half = lane >> 5, l31 = lane & 31;
     constexpr int BN_OUT = (EPI == APAD_EPI_GEGLU) ? BN / 2 : BN;
-    constexpr int GH = BN / 2;  // GEGLU: first half of the tile columns = value rows, second half = gate rows
-    // XCD-aware tile order: workgroup id b runs on XCD b % 8 (observed dispatch order, speed only).  Tiles are
-    // numbered so that all N-tiles of one M-tile share b % 8, i.e. one XCD's L2 fetches each A row-panel once.
     int mt, nt;
-    {
-        const int nN = p.n_tiles, nM = p.m_tiles;
-        const int b = blockIdx.x;
-        const int full = (nM / 8) * 8 * nN;  // blocks covered by complete groups of 8 M-tiles
-        if (b < full) {
-            const int grp = b / (8 * nN), rem = b - grp * 8 * nN;
-            nt = rem >> 3;
-            mt = grp * 8 + (rem & 7);
-        } else {
-            const int rem = b - full, tail = nM - (nM / 8) * 8;  // < 8 leftover M-tiles
-            nt = rem / tail;
-            mt = (nM / 8) * 8 + rem - nt * tail;
-        }
-    }
-    const int64_t m0 = (int64_t)mt * BM;
-    const int64_t n0 = (int64_t)nt * BN_OUT;
+    xcd_tile_order(blockIdx.x, p.m_tiles, p.n_tiles, mt, nt);
+    // (readfirstlane: the map's divisions run on the vector unit, and the 64-bit tile origin would ride in four VGPRs through the k-loop
+    //  for the epilogue -- with the epilogue in gemm_shared.h that put the conv1d form at 82 registers, one occupancy step down)
+    const int64_t m0 = (int64_t)__builtin_amdgcn_readfirstlane(mt) * BM;
+    const int64_t n0 = (int64_t)__builtin_amdgcn_readfirstlane(nt) * BN_OUT;
 
-    // W row feeding local tile column nl
-    auto wrow = [&](int nl) -> int64_t {
-        if (EPI == APAD_EPI_GEGLU) return nl < GH ? n0 + nl : p.N + n0 + (nl - GH);
-        return n0 + nl;
-    };
-    auto wrow_valid = [&](int nl) -> bool {
-        if (EPI == APAD_EPI_GEGLU) return (nl < GH ? n0 + nl : n0 + nl - GH) < p.N;
-        return n0 + nl < p.N;
-    };
-
-    // LayerNorm-by-algebra: mean / rstd of this tile's rows, summed in a fixed order from the producer's 64-column partials
     __shared__ float rstat[TM][2];
-    if (p.rs_in != nullptr && threadIdx.x < BM) {
-        const int64_t m = m0 + threadIdx.x;
-        float s1 = 0.f, s2 = 0.f;
-        if (m < p.M) {
-            const float* src = p.rs_in + m * p.rs_in_tiles * 2;
-            for (int t_ = 0; t_ < p.rs_in_tiles; ++t_) {
-                s1 += src[2 * t_];
-                s2 += src[2 * t_ + 1];
-            }
-        }
-        const float mean = s1 / (float)p.K;
-        const float var = fmaxf(s2 / (float)p.K - mean * mean, 0.f);
-        rstat[threadIdx.x][0] = mean;
-        rstat[threadIdx.x][1] = rsqrtf(var + p.ln_eps);
-    }
+    ln_row_stats<BM>(p.rs_in, p.rs_in_tiles, p.K, p.ln_eps, m0, p.M, rstat);
     // per-thread staging assignment: rows (tid>>3) + 32*i, 16-byte chunk tid&7
     const int chunk = tid & 7;
-    RowInfo<AMODE> ra[NLD];
+    ARow ra[NLD];
     int64_t wb[NLD];
     bool wv[NLD];
 #pragma unroll
@@ -215,37 +117,17 @@ __global__ __launch_bounds__(256 * KG) void gemm_kernel(GemmP p) {
             if (AMODE == APAD_A_PLAIN) {
                 ra[i].base = (p.a_mod > 0 ? m % p.a_mod : m) * p.lda;
                 ra[i].oy = (int)m;
-            } else if (AMODE == APAD_A_CONV3X3) {
-                int64_t hw = (int64_t)p.Hout * p.Wout;
-                int64_t b = m / hw;
-                int rem = (int)(m - b * hw);
-                ra[i].oy = rem / p.Wout;
-                ra[i].ox = rem - ra[i].oy * p.Wout;
-                ra[i].base = p.src_batch_mod > 0 ? b % p.src_batch_mod : b;
-            } else if (AMODE == APAD_A_CONV1D) {
-                const int64_t b = m / p.Hout;
-                ra[i].oy = (int)(m - b * p.Hout);
-                ra[i].base = b;
             } else if (AMODE == APAD_A_CONV3X3_FAST) {
-                int64_t hw = (int64_t)p.Hout * p.Wout;
-                int64_t b = m / hw;
-                int rem = (int)(m - b * hw);
-                const int oy = rem / p.Wout, ox = rem - oy * p.Wout;
-                ra[i].oy = oy * p.stride - p.lead;  // source row / column of filter tap (0, 0)
-                ra[i].ox = ox * p.stride - p.lead;
-                const int64_t sb = p.src_batch_mod > 0 ? b % p.src_batch_mod : b;
-                ra[i].base = ((sb * p.Hin + ra[i].oy) * p.Win + ra[i].ox) * p.Cin;  // element offset of that tap, channel 0
+                decode_row<APAD_A_CONV3X3>(p.g, m, ra[i]);
+                ra[i].oy = ra[i].oy * p.g.stride - p.g.lead;  // source row / column of filter tap (0, 0)
+                ra[i].ox = ra[i].ox * p.g.stride - p.g.lead;
+                ra[i].base = ((ra[i].base * p.g.Hin + ra[i].oy) * p.g.Win + ra[i].ox) * p.g.Cin;  // element offset of that tap, channel 0
             } else {
-                int wp = p.Win >> 4, hp = p.Hin >> 4;
-                int64_t b = m / (hp * wp);
-                int rem = (int)(m - b * hp * wp);
-                ra[i].oy = rem / wp;
-                ra[i].ox = rem - ra[i].oy * wp;
-                ra[i].base = b;
+                decode_row<AMODE>(p.g, m, ra[i]);
             }
         }
-        wv[i] = wrow_valid(rl);
-        wb[i] = wv[i] ? wrow(rl) * p.ldw : 0;
+        wv[i] = w_row_valid<EPI, BN>(p.N, n0, rl);
+        wb[i] = wv[i] ? w_row<EPI, BN>(p.N, n0, rl) * p.ldw : 0;
     }
 
     f32x16 acc[MI][MI];
@@ -270,15 +152,15 @@ __global__ __launch_bounds__(256 * KG) void gemm_kernel(GemmP p) {
         if (AMODE == APAD_A_CONV3X3_FAST) {
             fky = ftap / 3;
             fkx = ftap - fky * 3;
-            fkoff = ((int64_t)fky * p.Win + fkx) * p.Cin + fc0 + chunk * 8;
+            fkoff = ((int64_t)fky * p.g.Win + fkx) * p.g.Cin + fc0 + chunk * 8;
             fc0 += BK;
-            if (fc0 >= p.Cin) { fc0 = 0; ++ftap; }
+            if (fc0 >= p.g.Cin) { fc0 = 0; ++ftap; }
         }
 #pragma unroll
         for (int i = 0; i < NLD; ++i) {
             if (AMODE == APAD_A_CONV3X3_FAST) {
                 const int iy = ra[i].oy + fky, ix = ra[i].ox + fkx;
-                const bool ok = ra[i].valid && (unsigned)iy < (unsigned)p.Hin && (unsigned)ix < (unsigned)p.Win;
+                const bool ok = ra[i].valid && (unsigned)iy < (unsigned)p.g.Hin && (unsigned)ix < (unsigned)p.g.Win;
                 const u32x4 z0 = {0u, 0u, 0u, 0u};
                 gA[i] = ok ? *reinterpret_cast<const u32x4*>(p.a + (ra[i].base + fkoff) * 2) : z0;
             } else
@@ -318,7 +200,7 @@ __global__ __launch_bounds__(256 * KG) void gemm_kernel(GemmP p) {
         if constexpr (AMODE == APAD_A_CONV3X3_FAST) {
             for (int i = 0; i < n; ++i) {
                 fc0 += BK;
-                if (fc0 >= p.Cin) { fc0 = 0; ++ftap; }
+                if (fc0 >= p.g.Cin) { fc0 = 0; ++ftap; }
             }
         }
     };
@@ -414,7 +296,7 @@ __global__ __launch_bounds__(256 * KG) void gemm_kernel(GemmP p) {
 
     }
 
-    // ---- epilogue: acc (+bias, +rowgroup bias, activation) -> LDS tile ----
+    // ---- epilogue (gemm_shared.h): acc (+bias, +rowgroup bias, activation) -> LDS tile -> global ----
     typename E::elem* ct = reinterpret_cast<typename E::elem*>(smem);
     int64_t step = p.step_ptr ? (int64_t)*p.step_ptr : 0;
     const bool one_group = p.rows_per_group >= p.M;  // table mode: every row reads row `step` (no 64-bit divisions)
@@ -422,127 +304,12 @@ __global__ __launch_bounds__(256 * KG) void gemm_kernel(GemmP p) {
 #pragma unroll
     for (int j = 0; j < MI; ++j) {
         const int nl = wn * WT + j * 32 + l31;
-        const bool nvalid = wrow_valid(nl);
-        const int64_t wr = nvalid ? wrow(nl) : 0;
-        const float bv = (p.bias && nvalid) ? ld_elem<DT>(p.bias, wr) : 0.f;
-        const float rg0 = (p.rg && one_group && nvalid) ? ld_elem<DT>(p.rg, step * p.ld_rg + wr) : 0.f;
-        const bool lnf = p.rs_in != nullptr;
-        const float lcs = (lnf && nvalid) ? p.ln_cs[wr] : 0.f, lbb = (lnf && nvalid) ? p.ln_bb[wr] : 0.f;
+        const EpiCol c = epi_column<DT>(p, w_row_valid<EPI, BN>(p.N, n0, nl), w_row<EPI, BN>(p.N, n0, nl), step, one_group);
 #pragma unroll
-        for (int i = 0; i < MI; ++i) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int ml = wm * WT + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-                float v = acc[i][j][r] + bv + rg0;
-                if (lnf) v = rstat[ml][1] * (acc[i][j][r] - rstat[ml][0] * lcs) + lbb + rg0;
-                if (p.rg && !one_group) {
-                    int64_t m = m0 + ml;
-                    if (m < p.M && nvalid) v += ld_elem<DT>(p.rg, (m / p.rows_per_group + step) * p.ld_rg + wr);
-                }
-                if (EPI == APAD_EPI_SILU) v = silu_f(v);
-                if (EPI == APAD_EPI_GELU) v = gelu_erf_f(v);
-                if (EPI == APAD_EPI_TANH) v = tanhf(v);
-                ct[ml * C_LD + nl] = (typename E::elem)v;
-            }
-        }
+        for (int i = 0; i < MI; ++i) epi_acc_to_lds<DT, EPI, C_LD>(p, acc[i][j], ct, rstat, wm * WT + i * 32, nl, half, m0, c, step, one_group);
     }
     __syncthreads();
-
-    // fused q|k|v: the tile lies in exactly one third of the columns (C % tile == 0, checked on the host)
-    const int Cq = (int)(p.N / 3);
-    const int qseg = (OUTMODE == APAD_OUT_QKV) ? (int)(n0 / Cq) : 0;
-    if (OUTMODE == APAD_OUT_ROWMAJOR || (OUTMODE == APAD_OUT_QKV && qseg < 2)) {
-        uint8_t* const obase = (OUTMODE == APAD_OUT_QKV && qseg == 1) ? p.out2 : p.out;
-        const int64_t ncol0 = (OUTMODE == APAD_OUT_QKV) ? (int64_t)qseg * Cq : 0;
-        constexpr int VPR = BN_OUT / 8;  // 16-byte vectors per output row
-        if (p.rs_out != nullptr && VPR >= 8 && OUTMODE == APAD_OUT_ROWMAJOR) {
-            // the same store loop, plus the row statistics of what is stored: 8 consecutive lanes own 64 consecutive columns of one
-            // row (BM * VPR is a multiple of the thread count, so a group is never split and every lane takes part in the shuffles)
-            for (int idx = threadIdx.x; idx < BM * VPR; idx += NT) {
-                const int rl = idx / VPR, vc = idx - rl * VPR;
-                const int64_t m = m0 + rl, n = n0 + vc * 8;
-                const bool ok = m < p.M && n < p.N;
-                float f[8];
-                unpack8<DT>(*reinterpret_cast<const uint4*>(&ct[rl * C_LD + vc * 8]), f);
-                if (p.residual && ok) {
-                    float rr[8];
-                    const int64_t rm = p.res_mod > 0 ? m % p.res_mod : m;
-                    unpack8<DT>(*reinterpret_cast<const uint4*>(p.residual + (rm * p.ldr + n) * 2), rr);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) f[e] = (float)(typename E::elem)f[e] + rr[e];
-                }
-                const uint4 pk = pack8<DT>(f);
-                float s1 = 0.f, s2 = 0.f;
-                if (ok) {
-                    *reinterpret_cast<uint4*>(obase + (m * p.ldo + (n - ncol0)) * 2) = pk;
-                    float g[8];
-                    unpack8<DT>(pk, g);  // statistics of the ROUNDED values: what the consumer will read
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                        s1 += g[e];
-                        s2 = __builtin_fmaf(g[e], g[e], s2);
-                    }
-                }
-#pragma unroll
-                for (int o_ = 1; o_ < 8; o_ <<= 1) {
-                    s1 += __shfl_xor(s1, o_);
-                    s2 += __shfl_xor(s2, o_);
-                }
-                if (ok && (vc & 7) == 0) {
-                    float* dst = p.rs_out + (m * p.rs_out_tiles + (n >> 6)) * 2;
-                    dst[0] = s1;
-                    dst[1] = s2;
-                }
-            }
-        } else
-        for (int idx = threadIdx.x; idx < BM * VPR; idx += NT) {
-            const int rl = idx / VPR, vc = idx - rl * VPR;
-            const int64_t m = m0 + rl, n = n0 + vc * 8;
-            if (m >= p.M || n >= p.N) continue;
-            float f[8];
-            unpack8<DT>(*reinterpret_cast<const uint4*>(&ct[rl * C_LD + vc * 8]), f);
-            if (EPI == APAD_EPI_GEGLU) {
-                float g[8];
-                unpack8<DT>(*reinterpret_cast<const uint4*>(&ct[rl * C_LD + GH + vc * 8]), g);
-#pragma unroll
-                for (int e = 0; e < 8; e += 2) {
-                    const apad_f32x2 ge = gelu_erf_2((apad_f32x2){g[e], g[e + 1]});
-                    f[e] *= ge[0];
-                    f[e + 1] *= ge[1];
-                }
-            }
-            if (p.residual) {
-                float rr[8];
-                const int64_t rm = p.res_mod > 0 ? m % p.res_mod : m;
-                unpack8<DT>(*reinterpret_cast<const uint4*>(p.residual + (rm * p.ldr + n) * 2), rr);
-                // the un-fused reference rounds the linear output to the storage type before the add
-#pragma unroll
-                for (int e = 0; e < 8; ++e) f[e] = (float)(typename E::elem)f[e] + rr[e];
-            }
-            *reinterpret_cast<uint4*>(obase + (m * p.ldo + (n - ncol0)) * 2) = pack8<DT>(f);
-        }
-    } else {  // APAD_OUT_VT (or the v third of APAD_OUT_QKV): consecutive lanes -> consecutive tokens of one (head, dd) row
-        typename E::elem* o = reinterpret_cast<typename E::elem*>(OUTMODE == APAD_OUT_QKV ? p.out3 : p.out);
-        const int64_t nsub = (OUTMODE == APAD_OUT_QKV) ? 2 * (int64_t)Cq : 0;
-        if (OUTMODE == APAD_OUT_QKV && p.out4 != nullptr) {  // v row-major as well (the training step keeps both forms)
-            for (int idx = threadIdx.x; idx < BM * (BN / 8); idx += NT) {
-                const int rl = idx / (BN / 8), vc = idx - rl * (BN / 8);
-                const int64_t m = m0 + rl, n = n0 + vc * 8;
-                if (m < p.M && n < p.N) *reinterpret_cast<uint4*>(p.out4 + (m * p.ldo + (n - nsub)) * 2) = *reinterpret_cast<const uint4*>(&ct[rl * C_LD + vc * 8]);
-            }
-        }
-        for (int idx = threadIdx.x; idx < BM * BN; idx += NT) {
-            const int nl = idx / BM, rl = idx % BM;
-            const int64_t m = m0 + rl;
-            int64_t n = n0 + nl;
-            if (m >= p.M || n >= p.N) continue;
-            n -= nsub;
-            const int64_t b = m / p.L;
-            const int l = (int)(m - b * p.L);
-            const int h = (int)(n / p.head_dim), dd = (int)(n - (int64_t)h * p.head_dim);
-            o[((b * p.heads + h) * p.head_dim + dd) * p.Lpad + l] = ct[rl * C_LD + nl];
-        }
-    }
+    epi_store<DT, EPI, OUTMODE, BM, BN, NT>(p, ct, m0, n0);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -570,43 +337,11 @@ __global__ __launch_bounds__(256) void gemm_ring_kernel(GemmP p, uint32_t a_byte
     const int wm = wave >> 1, wn = wave & 1;
     const int half = lane >> 5, l31 = lane & 31;
     constexpr int BN_OUT = (EPI == APAD_EPI_GEGLU) ? BN / 2 : BN;
-    constexpr int GH = BN / 2;
     int mt, nt;
-    {
-        const int nN = p.n_tiles, nM = p.m_tiles;
-        const int b = blockIdx.x;
-        const int full = (nM / 8) * 8 * nN;
-        if (b < full) {
-            const int grp = b / (8 * nN), rem = b - grp * 8 * nN;
-            nt = rem >> 3;
-            mt = grp * 8 + (rem & 7);
-        } else {
-            const int rem = b - full, tail = nM - (nM / 8) * 8;
-            nt = rem / tail;
-            mt = (nM / 8) * 8 + rem - nt * tail;
-        }
-    }
+    xcd_tile_order(blockIdx.x, p.m_tiles, p.n_tiles, mt, nt);
     const int64_t m0 = (int64_t)mt * BM;
     const int64_t n0 = (int64_t)nt * BN_OUT;
-    auto wrow = [&](int nl) -> int64_t {
-        if (EPI == APAD_EPI_GEGLU) return nl < GH ? n0 + nl : p.N + n0 + (nl - GH);
-        return n0 + nl;
-    };
-    if (p.rs_in != nullptr && tid < BM) {
-        const int64_t m = m0 + tid;
-        float s1 = 0.f, s2 = 0.f;
-        if (m < p.M) {
-            const float* src = p.rs_in + m * p.rs_in_tiles * 2;
-            for (int t_ = 0; t_ < p.rs_in_tiles; ++t_) {
-                s1 += src[2 * t_];
-                s2 += src[2 * t_ + 1];
-            }
-        }
-        const float mean = s1 / (float)p.K;
-        const float var = fmaxf(s2 / (float)p.K - mean * mean, 0.f);
-        rstat[tid][0] = mean;
-        rstat[tid][1] = rsqrtf(var + p.ln_eps);
-    }
+    ln_row_stats<BM>(p.rs_in, p.rs_in_tiles, p.K, p.ln_eps, m0, p.M, rstat);
     // ---- DMA sources: wave w fills blocks 2w, 2w + 1 (8 rows each) of the A tile and of the W tile; lane -> (row, LDS slot), the
     //      slot holds source chunk slot ^ ((row >> 1) & 7) = lds_off's swizzle ----
     const __amdgpu_buffer_rsrc_t rw = buf_rsrc(p.w, w_bytes);
@@ -619,7 +354,7 @@ __global__ __launch_bounds__(256) void gemm_ring_kernel(GemmP p, uint32_t a_byte
         const bool valid = m < p.M;
         aoff[i] = valid ? (uint32_t)((p.a_mod > 0 ? m % p.a_mod : m) * p.lda * 2 + c * 16) : R_OOB;
         aoff2[i] = (valid && p.a2 != nullptr) ? (uint32_t)((p.a2_mod > 0 ? m % p.a2_mod : m) * p.lda2 * 2 + c * 16) : R_OOB;
-        boff[i] = (uint32_t)(wrow(R) * p.ldw * 2 + c * 16);
+        boff[i] = (uint32_t)(w_row<EPI, BN>(p.N, n0, R) * p.ldw * 2 + c * 16);
     }
     const int nk = (int)(p.K / BK);
     auto request = [&](int kt, int stage) {
@@ -689,123 +424,17 @@ __global__ __launch_bounds__(256) void gemm_ring_kernel(GemmP p, uint32_t a_byte
     }
     __syncthreads();  // the stages are dead (rstat lives behind them)
 
-    // ---- epilogue: the tiled kernel's (gemm_kernel), one MFMA tile per wave ----
+    // ---- epilogue: the tiled kernel's (gemm_shared.h), one MFMA tile per wave; the envelope has whole N tiles ----
     typename E::elem* ct = reinterpret_cast<typename E::elem*>(smem);
     const int64_t step = p.step_ptr ? (int64_t)*p.step_ptr : 0;
     const bool one_group = p.rows_per_group >= p.M;
     {
         const int nl = wn * WT + l31;
-        const int64_t wr = wrow(nl);
-        const float bv = p.bias ? ld_elem<DT>(p.bias, wr) : 0.f;
-        const float rg0 = (p.rg && one_group) ? ld_elem<DT>(p.rg, step * p.ld_rg + wr) : 0.f;
-        const bool lnf = p.rs_in != nullptr;
-        const float lcs = lnf ? p.ln_cs[wr] : 0.f, lbb = lnf ? p.ln_bb[wr] : 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int ml = wm * WT + (r & 3) + 8 * (r >> 2) + 4 * half;
-            float v = acc[r] + bv + rg0;
-            if (lnf) v = rstat[ml][1] * (acc[r] - rstat[ml][0] * lcs) + lbb + rg0;
-            if (p.rg && !one_group) {
-                const int64_t m = m0 + ml;
-                if (m < p.M) v += ld_elem<DT>(p.rg, (m / p.rows_per_group + step) * p.ld_rg + wr);
-            }
-            if (EPI == APAD_EPI_SILU) v = silu_f(v);
-            if (EPI == APAD_EPI_GELU) v = gelu_erf_f(v);
-            ct[ml * C_LD + nl] = (typename E::elem)v;
-        }
+        const EpiCol c = epi_column<DT>(p, true, w_row<EPI, BN>(p.N, n0, nl), step, one_group);
+        epi_acc_to_lds<DT, EPI, C_LD>(p, acc, ct, rstat, wm * WT, nl, half, m0, c, step, one_group);
     }
     __syncthreads();
-    const int Cq = (int)(p.N / 3);
-    const int qseg = (OUTMODE == APAD_OUT_QKV) ? (int)(n0 / Cq) : 0;
-    if (OUTMODE == APAD_OUT_ROWMAJOR || (OUTMODE == APAD_OUT_QKV && qseg < 2)) {
-        uint8_t* const obase = (OUTMODE == APAD_OUT_QKV && qseg == 1) ? p.out2 : p.out;
-        const int64_t ncol0 = (OUTMODE == APAD_OUT_QKV) ? (int64_t)qseg * Cq : 0;
-        constexpr int VPR = BN_OUT / 8;
-        if (p.rs_out != nullptr && VPR >= 8 && OUTMODE == APAD_OUT_ROWMAJOR) {
-            for (int idx = tid; idx < BM * VPR; idx += 256) {
-                const int rl = idx / VPR, vc = idx - rl * VPR;
-                const int64_t m = m0 + rl, n = n0 + vc * 8;
-                const bool ok = m < p.M && n < p.N;
-                float f[8];
-                unpack8<DT>(*reinterpret_cast<const uint4*>(&ct[rl * C_LD + vc * 8]), f);
-                if (p.residual && ok) {
-                    float rr[8];
-                    const int64_t rm = p.res_mod > 0 ? m % p.res_mod : m;
-                    unpack8<DT>(*reinterpret_cast<const uint4*>(p.residual + (rm * p.ldr + n) * 2), rr);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) f[e] = (float)(typename E::elem)f[e] + rr[e];
-                }
-                const uint4 pk = pack8<DT>(f);
-                float s1 = 0.f, s2 = 0.f;
-                if (ok) {
-                    *reinterpret_cast<uint4*>(obase + (m * p.ldo + (n - ncol0)) * 2) = pk;
-                    float g[8];
-                    unpack8<DT>(pk, g);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                        s1 += g[e];
-                        s2 = __builtin_fmaf(g[e], g[e], s2);
-                    }
-                }
-#pragma unroll
-                for (int o_ = 1; o_ < 8; o_ <<= 1) {
-                    s1 += __shfl_xor(s1, o_);
-                    s2 += __shfl_xor(s2, o_);
-                }
-                if (ok && (vc & 7) == 0) {
-                    float* dst = p.rs_out + (m * p.rs_out_tiles + (n >> 6)) * 2;
-                    dst[0] = s1;
-                    dst[1] = s2;
-                }
-            }
-        } else
-        for (int idx = tid; idx < BM * VPR; idx += 256) {
-            const int rl = idx / VPR, vc = idx - rl * VPR;
-            const int64_t m = m0 + rl, n = n0 + vc * 8;
-            if (m >= p.M || n >= p.N) continue;
-            float f[8];
-            unpack8<DT>(*reinterpret_cast<const uint4*>(&ct[rl * C_LD + vc * 8]), f);
-            if (EPI == APAD_EPI_GEGLU) {
-                float g[8];
-                unpack8<DT>(*reinterpret_cast<const uint4*>(&ct[rl * C_LD + GH + vc * 8]), g);
-#pragma unroll
-                for (int e = 0; e < 8; e += 2) {
-                    const apad_f32x2 ge = gelu_erf_2((apad_f32x2){g[e], g[e + 1]});
-                    f[e] *= ge[0];
-                    f[e + 1] *= ge[1];
-                }
-            }
-            if (p.residual) {
-                float rr[8];
-                const int64_t rm = p.res_mod > 0 ? m % p.res_mod : m;
-                unpack8<DT>(*reinterpret_cast<const uint4*>(p.residual + (rm * p.ldr + n) * 2), rr);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) f[e] = (float)(typename E::elem)f[e] + rr[e];
-            }
-            *reinterpret_cast<uint4*>(obase + (m * p.ldo + (n - ncol0)) * 2) = pack8<DT>(f);
-        }
-    } else {
-        typename E::elem* o = reinterpret_cast<typename E::elem*>(OUTMODE == APAD_OUT_QKV ? p.out3 : p.out);
-        const int64_t nsub = (OUTMODE == APAD_OUT_QKV) ? 2 * (int64_t)Cq : 0;
-        if (OUTMODE == APAD_OUT_QKV && p.out4 != nullptr) {
-            for (int idx = tid; idx < BM * (BN / 8); idx += 256) {
-                const int rl = idx / (BN / 8), vc = idx - rl * (BN / 8);
-                const int64_t m = m0 + rl, n = n0 + vc * 8;
-                if (m < p.M && n < p.N) *reinterpret_cast<uint4*>(p.out4 + (m * p.ldo + (n - nsub)) * 2) = *reinterpret_cast<const uint4*>(&ct[rl * C_LD + vc * 8]);
-            }
-        }
-        for (int idx = tid; idx < BM * BN; idx += 256) {
-            const int nl = idx / BM, rl = idx % BM;
-            const int64_t m = m0 + rl;
-            int64_t n = n0 + nl;
-            if (m >= p.M || n >= p.N) continue;
-            n -= nsub;
-            const int64_t b = m / p.L;
-            const int l = (int)(m - b * p.L);
-            const int h = (int)(n / p.head_dim), dd = (int)(n - (int64_t)h * p.head_dim);
-            o[((b * p.heads + h) * p.head_dim + dd) * p.Lpad + l] = ct[rl * C_LD + nl];
-        }
-    }
+    epi_store<DT, EPI, OUTMODE, BM, BN, 256>(p, ct, m0, n0);
 }
 
 // the ring kernel's envelope: plain A, K % 64 == 0, all weight rows of the tiles in range, operands below 2 GB; returns 1 when it
@@ -933,8 +562,6 @@ template <int DT> int dispatch_amode(const GemmP& p, const apad_gemm_desc* d, hi
     return -1;
 }
 
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace
 
 extern "C" int apad_set_gemm_ring(int32_t mode) {
@@ -947,12 +574,7 @@ extern "C" int apad_gemm(const apad_gemm_desc* d, void* stream) {
     APAD_CHECK(d != nullptr, "apad_gemm: null descriptor");
     if (d->dtype == APAD_F32 || d->dtype == APAD_F32_BF16X3) return apad_f32_gemm(d, (hipStream_t)stream);  // fp32 precision modes (f32_ops.hip)
     APAD_CHECK(d->dtype == APAD_BF16 || d->dtype == APAD_F16, "apad_gemm: dtype %d not supported (bf16/f16/f32)", d->dtype);
-    APAD_CHECK(d->a && d->w && d->out, "apad_gemm: null operand");
-    APAD_CHECK(d->M > 0 && d->N > 0 && d->K > 0, "apad_gemm: empty problem M=%lld N=%lld K=%lld", (long long)d->M,
-               (long long)d->N, (long long)d->K);
-    APAD_CHECK(d->K % 8 == 0 && d->ldw % 8 == 0, "apad_gemm: K and ldw must be multiples of 8 (K=%lld ldw=%lld)",
-               (long long)d->K, (long long)d->ldw);
-    APAD_CHECK(al16(d->a) && al16(d->w) && al16(d->out) && al16(d->residual), "apad_gemm: pointers must be 16-byte aligned");
+    if (gemm_desc_check(d, 8, "apad_gemm", d->epilogue == APAD_EPI_GEGLU, true) != 0) return -1;
     GemmP p;
     p.a = (const uint8_t*)d->a;
     p.w = (const uint8_t*)d->w;
@@ -967,50 +589,10 @@ extern "C" int apad_gemm(const apad_gemm_desc* d, void* stream) {
     p.M = d->M; p.N = d->N; p.K = d->K;
     p.lda = d->lda; p.ldw = d->ldw; p.ldo = d->ldo; p.ldr = d->ldr; p.ld_rg = d->ld_rg;
     p.rows_per_group = d->rows_per_group > 0 ? d->rows_per_group : 1;
-    p.Hin = d->Hin; p.Win = d->Win; p.Cin = d->Cin; p.Hout = d->Hout; p.Wout = d->Wout;
-    p.stride = d->stride; p.Hup = d->Hup; p.Wup = d->Wup; p.src_batch_mod = d->src_batch_mod; p.res_mod = d->residual_row_mod;
+    p.g = a_geom(d);
+    p.res_mod = d->residual_row_mod;
     p.heads = d->heads; p.head_dim = d->head_dim; p.L = d->L; p.Lpad = d->Lpad;
     p.wrows = (int32_t)(d->epilogue == APAD_EPI_GEGLU ? 2 * d->N : d->N);
-    if (d->a_mode == APAD_A_PLAIN) {
-        APAD_CHECK(d->lda % 8 == 0, "apad_gemm: lda must be a multiple of 8");
-    } else if (d->a_mode == APAD_A_CONV3X3) {
-        APAD_CHECK(d->Cin > 0 && d->Cin % 8 == 0 && d->K == 9LL * d->Cin, "apad_gemm: conv3x3 needs Cin%%8==0 and K==9*Cin");
-        APAD_CHECK(d->stride == 1 || d->stride == 2, "apad_gemm: conv stride must be 1 or 2");
-        APAD_CHECK(d->Hin > 0 && d->Win > 0 && d->Hout > 0 && d->Wout > 0 && d->M % ((int64_t)d->Hout * d->Wout) == 0,
-                   "apad_gemm: conv geometry inconsistent with M");
-        APAD_CHECK((d->Hup > 0) == (d->Wup > 0), "apad_gemm: Hup/Wup must both be set or both 0");
-    } else if (d->a_mode == APAD_A_PATCH16) {
-        APAD_CHECK(d->K == 256 && d->Hin % 16 == 0 && d->Win % 16 == 0, "apad_gemm: patch16 needs K==256 and H,W %% 16 == 0");
-        APAD_CHECK(d->M % ((int64_t)(d->Hin / 16) * (d->Win / 16)) == 0, "apad_gemm: patch16 M inconsistent");
-    } else if (d->a_mode == APAD_A_CONV1D) {
-        APAD_CHECK(d->Cin > 0 && d->Cin % 8 == 0 && d->taps > 0 && d->K == (int64_t)d->taps * d->Cin, "apad_gemm: conv1d needs Cin%%8==0 and K==taps*Cin");
-        APAD_CHECK(d->Hin > 0 && d->Hout > 0 && d->M % d->Hout == 0 && d->pad >= 0, "apad_gemm: conv1d geometry inconsistent with M");
-        APAD_CHECK(d->transposed ? d->stride >= 1 : d->dilation >= 1, "apad_gemm: conv1d needs dilation >= 1 (stride >= 1 when transposed)");
-    }
-    p.taps = d->taps; p.dilation = d->dilation; p.pad = d->pad; p.transposed = d->transposed; p.pre_act = d->a_pre_act;
-    p.pre_slope = d->a_pre_slope;
-    p.lead = d->conv_asym_pad ? 0 : 1;
-    if (d->out_mode == APAD_OUT_ROWMAJOR) {
-        APAD_CHECK(d->N % 8 == 0 && d->ldo % 8 == 0, "apad_gemm: N and ldo must be multiples of 8");
-        if (d->residual) APAD_CHECK(d->ldr % 8 == 0, "apad_gemm: ldr must be a multiple of 8");
-        if (d->epilogue == APAD_EPI_GEGLU) APAD_CHECK(d->N % 64 == 0, "apad_gemm: GEGLU needs N %% 64 == 0");
-    } else if (d->out_mode == APAD_OUT_QKV) {
-        APAD_CHECK(d->out2 && d->out3 && al16(d->out2) && al16(d->out3), "apad_gemm: APAD_OUT_QKV needs 16-byte aligned out2 / out3");
-        APAD_CHECK(al16(d->out4), "apad_gemm: out4 must be 16-byte aligned");
-        APAD_CHECK(d->heads > 0 && d->head_dim > 0 && d->L > 0 && d->Lpad >= d->L && d->N == 3LL * d->heads * d->head_dim &&
-                       d->M % d->L == 0 && (d->N / 3) % 128 == 0 && d->ldo % 8 == 0,
-                   "apad_gemm: fused q|k|v geometry inconsistent (needs C %% 128 == 0)");
-        APAD_CHECK(!d->residual, "apad_gemm: fused q|k|v takes no residual");
-    } else if (d->out_mode == APAD_OUT_VT) {
-        APAD_CHECK(d->heads > 0 && d->head_dim > 0 && d->L > 0 && d->Lpad >= d->L && d->N == (int64_t)d->heads * d->head_dim &&
-                       d->M % d->L == 0,
-                   "apad_gemm: V^T output geometry inconsistent");
-        APAD_CHECK(!d->residual, "apad_gemm: V^T output takes no residual");
-    } else {
-        apad_set_error("apad_gemm: unknown out_mode %d", d->out_mode);
-        return -1;
-    }
-    if (d->rowgroup_bias) APAD_CHECK(d->ld_rg > 0, "apad_gemm: rowgroup_bias needs ld_rg");
     p.a2 = (const uint8_t*)d->a2; p.lda2 = d->lda2; p.ksplit = d->k_split; p.a_mod = d->a_row_mod; p.a2_mod = d->a2_row_mod;
     if (d->a2 != nullptr)
         APAD_CHECK(d->a_mode == APAD_A_PLAIN && d->k_split > 0 && d->k_split % 64 == 0 && d->k_split < d->K && d->lda2 % 8 == 0 && al16(d->a2) &&

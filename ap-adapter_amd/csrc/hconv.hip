@@ -25,6 +25,7 @@
 #include <type_traits>
 #include <utility>
 #include "gfx950_prims.h"
+#include "gemm_shared.h"
 
 namespace {
 
@@ -106,19 +107,7 @@ __global__ __launch_bounds__(T::NT) void hconv_kernel(HcP p) {
         c_end = (kslice + 1) * p.nchunks / p.ksplit;
         // XCD-aware tile order (speed only): all N-tiles of one M-tile share tl % 8 -- one XCD's L2 serves their common halo
         int mt, nt;
-        {
-            const int nN = p.n_tiles, nM = p.m_tiles;
-            const int full = (nM / 8) * 8 * nN;
-            if (tl < full) {
-                const int g = tl / (8 * nN), rem = tl - g * 8 * nN;
-                nt = rem >> 3;
-                mt = g * 8 + (rem & 7);
-            } else {
-                const int rem = tl - full, tail = nM - (nM / 8) * 8;
-                nt = rem / tail;
-                mt = (nM / 8) * 8 + rem - nt * tail;
-            }
-        }
+        xcd_tile_order(tl, p.m_tiles, p.n_tiles, mt, nt);
         m0 = mt * BM;
         n0 = nt * BN;
         const int g0 = mt * R;  // the tile's first global row (sample * H + y)
