@@ -179,6 +179,9 @@ SYMBOLS = {
     "apad_wav_stats": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp]),
     "apad_stft_logmel": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp]),
     "apad_adamw_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _vp]),
+    # CLAP audio tower (score_waveforms)
+    "apad_window_attention": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "apad_clap_mel2img": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _f32, _vp, _i32, _i32, _i32, _i32, _vp]),
 }
 
 _lock = threading.Lock()

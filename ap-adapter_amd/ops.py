@@ -973,6 +973,48 @@ def embedding(table, ids):
     return out
 
 
+def gather_rows(table, ids):
+    """out[i] = table[ids[i]] for a [rows, C] activation matrix and an int64 GPU index (apad_gather_rows; an id outside [0, rows)
+    writes zeros) -- the patch-merging interleave of the CLAP audio tower"""
+    return embedding(table, ids)
+
+
+def window_attention(qkv, bias, B, H, W, heads, shift, out=None):
+    """Shifted-window attention of one Swin block (apad_window_attention): qkv fp32 [B * H * W, 3 * heads * 24] in raster order (the
+    fused q | k | v projection), bias fp32 [heads, 64, 64] -> [B * H * W, heads * 24] in raster order.  Always the exact-f32 kernel:
+    the fp32 matmul precision setting does not reach it."""
+    _req(qkv, "window_attention.qkv", torch.float32)
+    _req(bias, "window_attention.bias", torch.float32)
+    C3 = qkv.shape[-1]
+    if C3 % (3 * heads) != 0:
+        raise ValueError(f"window_attention: qkv width {C3} is not 3 * heads ({heads}) * head size")
+    if not (qkv.is_contiguous() and bias.is_contiguous()) or qkv.numel() != B * H * W * C3 or tuple(bias.shape) != (heads, 64, 64):
+        raise ValueError(f"window_attention: qkv {tuple(qkv.shape)} / bias {tuple(bias.shape)} do not match B={B} H={H} W={W} heads={heads}")
+    if out is None:
+        out = torch.empty(B * H * W, C3 // 3, dtype=torch.float32, device=qkv.device)
+    L.check(L.lib().apad_window_attention(qkv.data_ptr(), bias.data_ptr(), out.data_ptr(), B, H, W, heads, C3 // (3 * heads), 8, int(shift),
+                                          L.F32, _stream()), "apad_window_attention")
+    return out
+
+
+def clap_mel2img(x, bn_weight, bn_bias, bn_mean, bn_var, bn_eps, spec_size):
+    """input_features fp32 [B, 1, T, F] -> the patch matrix [B * (spec_size / 4)^2, 16] of the CLAP audio tower (apad_clap_mel2img):
+    BatchNorm (eval) per mel bin, bicubic time stretch, reshape_mel2img, 4 x 4 patch gather"""
+    _req(x, "clap_mel2img.x", torch.float32)
+    if x.dim() != 4 or x.shape[1] != 1 or not x.is_contiguous():
+        raise ValueError(f"clap_mel2img: input_features {tuple(x.shape)}: expected contiguous [B, 1, T, F]")
+    B, _, T, F = x.shape
+    for n, t in (("weight", bn_weight), ("bias", bn_bias), ("running_mean", bn_mean), ("running_var", bn_var)):
+        if tuple(_req(t, f"clap_mel2img.{n}", torch.float32).shape) != (F,):
+            raise ValueError(f"clap_mel2img: batch_norm {n} {tuple(t.shape)} does not match {F} mel bins")
+    if spec_size % 4 or spec_size % F or T > spec_size * (spec_size // F):
+        raise ValueError("the wav size should be less than or equal to the swin input size")  # (the module's message)
+    out = torch.empty(B * (spec_size // 4) ** 2, 16, dtype=torch.float32, device=x.device)
+    L.check(L.lib().apad_clap_mel2img(x.data_ptr(), bn_weight.data_ptr(), bn_bias.data_ptr(), bn_mean.data_ptr(), bn_var.data_ptr(),
+                                      float(bn_eps), out.data_ptr(), B, T, F, spec_size, _stream()), "apad_clap_mel2img")
+    return out
+
+
 def gaussian_sample(moments, noise, scale=1.0):
     """moments [rows, 2L] = (mean | logvar), noise [rows, L] -> (mean + exp(0.5 * clamp(logvar, -30, 20)) * noise) * scale"""
     _req(moments, "gaussian_sample.moments")

@@ -19,6 +19,7 @@ conventions, PARITY UNPINNED): the VAE posterior draw, ``add_noise`` to the star
 (``apad_edit_start``), the run visits ``timesteps[k:]``, and with a mask the captured step's update kernel is ``apad_cfg_edit_step``, which
 re-imposes the kept region at every step's noise level.  A call without a source takes none of this.
 """
+import math
 from dataclasses import dataclass
 from typing import Optional, Union
 
@@ -55,12 +56,16 @@ class AudioLDM2Pipeline:
     latent_row_seconds = 0.04      # one latent row = vae_scale_factor mel frames of vocoder_upsample_factor seconds
 
     def __init__(self, unet, scheduler: Optional[Union[DDIMScheduler, DPMSolverMultistepScheduler]] = None, audiomae=None, vocoder=None, vae=None, prompt_encoder=None,
-                 tokenizer=None, tokenizer_2=None):
+                 tokenizer=None, tokenizer_2=None, audio_tower=None, feature_extractor=None):
         self.unet = unet
         self.vocoder = vocoder  # vocoder.SpeechT5HifiGan (HIP) -- mel -> waveform
         self.vae = vae          # vae.AutoencoderKL (HIP) -- latents -> mel
         self.prompt_encoder = prompt_encoder  # text_encoders.PromptEncoder (HIP): CLAP text + T5 + projection + GPT-2
         self.tokenizer, self.tokenizer_2 = tokenizer, tokenizer_2  # the caller's CLAP (RoBERTa) / T5 tokenizers (host-side, vocab files)
+        self.audio_tower = audio_tower  # clap_audio.ClapAudioModelWithProjection (HIP): ranks num_waveforms_per_prompt candidates
+        self.feature_extractor = feature_extractor  # the caller's transformers ClapFeatureExtractor (host-side, like the tokenizers)
+        self.logit_scale_t = math.log(1.0 / 0.07)  # ClapModel.logit_scale_t (logit_scale_init_value); set it from a checkpoint's value
+        self.last_logits_per_text = None
         self.scheduler = scheduler or DDIMScheduler()
         self.audiomae = audiomae
         self._uncond_cache = {}
@@ -78,6 +83,37 @@ class AudioLDM2Pipeline:
         if mel_spectrogram.dim() == 4:
             mel_spectrogram = mel_spectrogram.squeeze(1)
         return self.vocoder(mel_spectrogram).cpu().float()
+
+    def score_waveforms(self, text, audio, num_waveforms_per_prompt, device, dtype):
+        """pipeline_audioldm2.py:592-614, same name and arguments: the candidates [n, samples] (CPU) re-ordered so that each prompt's
+        ``num_waveforms_per_prompt`` best matches by CLAP text-audio similarity come first, best first -- chosen among ALL candidates
+        of the batch, as the reference does.  Resampling to the feature extractor's rate runs on ``apad_resample_fir`` (torchaudio's
+        polyphase kernel; the reference calls librosa.resample: parity unpinned), the features come from the caller's
+        ``feature_extractor`` on the host, the audio tower and the CLAP text tower run in fp32 (``dtype`` is accepted for the
+        reference's signature)."""
+        if self.audio_tower is None or self.feature_extractor is None:
+            raise NotImplementedError("score_waveforms needs audio_tower=ap_adapter_amd.ClapAudioModelWithProjection(...) and "
+                                      "feature_extractor= (transformers' ClapFeatureExtractor)")
+        if self.prompt_encoder is None or self.tokenizer is None:
+            raise NotImplementedError("score_waveforms needs prompt_encoder= (its CLAP text tower) and tokenizer=")
+        from .clap_audio import rank_waveforms
+        from .frontend import resample
+        text = [text] if isinstance(text, str) else list(text)
+        inputs = self.tokenizer(text, return_tensors="pt", padding=True)
+        sr = int(self.feature_extractor.sampling_rate)
+        wav = resample(torch.as_tensor(audio).to(device, torch.float32), int(self.vocoder.config.sampling_rate), sr)
+        feats = self.feature_extractor(list(wav.cpu().numpy()), return_tensors="pt", sampling_rate=sr).input_features
+        audio_embeds = self.audio_tower.get_audio_features(torch.as_tensor(feats).to(device, torch.float32))
+        text_embeds = self.prompt_encoder.text_encoder.get_text_features(inputs.input_ids.to(device), attention_mask=inputs.attention_mask.to(device))
+        P, n, D = text_embeds.shape[0], audio_embeds.shape[0], text_embeds.shape[1]
+        n4 = ops.round_up(n, 4)  # (the GEMM's vector width: zero rows pad the candidates, their columns are dropped)
+        cand = audio_embeds.new_zeros(n4, D)
+        cand[:n] = audio_embeds
+        dots = torch.empty(P, n4, dtype=torch.float32, device=text_embeds.device)
+        ops.gemm(text_embeds, cand, M=P, N=n4, K=D, lda=D, out=dots, ldo=n4, exact=True)
+        logits = ops.mix3(dots, torch.zeros_like(dots), torch.zeros_like(dots), math.exp(self.logit_scale_t))
+        self.last_logits_per_text = logits[:, :n]
+        return rank_waveforms(self.last_logits_per_text, torch.as_tensor(audio), num_waveforms_per_prompt)
 
     def _encode_text(self, texts, t5_max_length=None):
         """tokenise as encode_prompt does (:381-392 positive, :485-496 negative) and run the HIP prompt encoder on one CFG half"""
@@ -515,11 +551,14 @@ class AudioLDM2Pipeline:
         if output_type != "latent" and (self.vae is None or self.vocoder is None):
             raise NotImplementedError("waveform output needs latents -> mel (vae=ap_adapter_amd.AutoencoderKL) and mel -> waveform "
                                       "(vocoder=ap_adapter_amd.SpeechT5HifiGan); or use output_type='latent'")
-        if num_waveforms_per_prompt > 1 and prompt is not None and output_type != "latent":
-            # pipeline_audioldm2.py:1048-1056 re-orders the candidates by CLAP text-audio similarity (score_waveforms); the CLAP audio
-            # tower is outside this path, and returning them un-ranked would silently differ from the reference
-            raise NotImplementedError("num_waveforms_per_prompt > 1 with text prompts needs the CLAP audio tower for score_waveforms "
-                                      "(not on this path); use output_type='latent' or rank the waveforms yourself")
+        ranking = num_waveforms_per_prompt > 1 and prompt is not None and output_type != "latent"
+        if ranking and (self.audio_tower is None or self.feature_extractor is None):
+            # pipeline_audioldm2.py:1047-1054 re-orders the candidates by CLAP text-audio similarity (score_waveforms); returning them
+            # un-ranked would silently differ from the reference
+            raise NotImplementedError("num_waveforms_per_prompt > 1 with text prompts needs the CLAP audio tower for score_waveforms: build "
+                                      "the pipeline with audio_tower=ap_adapter_amd.ClapAudioModelWithProjection(...) and "
+                                      "feature_extractor= (transformers' ClapFeatureExtractor); or use output_type='latent' or rank the "
+                                      "waveforms yourself")
         if prompt is None:
             for n, v in (("prompt_embeds", prompt_embeds), ("negative_prompt_embeds", negative_prompt_embeds),
                          ("generated_prompt_embeds", generated_prompt_embeds),
@@ -568,6 +607,8 @@ class AudioLDM2Pipeline:
             mel = self.vae.decode(out / scaling)
             mel = getattr(mel, "sample", mel)
             out = self.mel_spectrogram_to_waveform(mel)[:, : int(audio_length_in_s * 16000)]
+            if ranking:  # :1047-1054
+                out = self.score_waveforms(text=prompt, audio=out, num_waveforms_per_prompt=num_waveforms_per_prompt, device=dev, dtype=pe.dtype)
             if output_type == "np":
                 out = out.numpy()
         if not return_dict:

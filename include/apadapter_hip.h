@@ -648,6 +648,27 @@ int apad_stft_logmel(const float* x, const int64_t* offsets, const int64_t* offs
                      const float* window, const float* twiddle, const float* mel, const int32_t* mel_range, float* out,
                      int32_t batch, int64_t segment, int32_t target_frames, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * CLAP audio tower (HTSAT; transformers ClapAudioModelWithProjection) for score_waveforms
+ * (pipeline_audioldm2.py:592-614).  fp32, additive to ABI 12.
+ * ------------------------------------------------------------------------------------------------------------- */
+/* Shifted-window attention of one Swin block in one launch.  qkv [B][H][W][3 * heads * head_dim] = the fused q | k | v
+   projection of the tokens in raster order; bias fp32 [heads][64][64] = relative_position_bias_table[relative_position_index]
+   as (head, query, key); out [B][H][W][heads * head_dim] in raster order.  The cyclic shift, the window partition and their
+   inverses are index arithmetic inside the kernel; with shift > 0 a score gets -100 where the two tokens' shift regions
+   differ (ClapAudioLayer.get_attn_mask).  Scores q.k / sqrt(head_dim) + bias (+ mask), softmax over the window's 64 keys,
+   out = P.V, all on the exact-f32 matrix instruction whatever the fp32 matmul precision setting.
+   Envelope: dtype APAD_F32, window 8, head_dim 24, H and W multiples of 8, shift 0 or 4; anything else returns -1. */
+int apad_window_attention(const void* qkv, const float* bias, void* out, int32_t B, int32_t H, int32_t W, int32_t heads,
+                          int32_t head_dim, int32_t window, int32_t shift, int32_t dtype, void* stream);
+/* x fp32 [B][1][T][F] (ClapFeatureExtractor's input_features) -> out fp32 [B * (S/4)^2][16], the patch matrix of the 4 x 4 /
+   stride-4 patch convolution (row = patch in raster order, column = ky * 4 + kx), S = spec_size: BatchNorm2d over the mel
+   bins in eval form (weight, bias, running mean / variance [F], eps), the bicubic align_corners=True stretch of the time axis
+   to S * S / F frames when T is shorter (A = -0.75, border taps clamped), the fold of ClapAudioEncoder.reshape_mel2img and
+   the patch gather.  -1 when T exceeds S * S / F, S % 4 != 0 or S % F != 0. */
+int apad_clap_mel2img(const float* x, const float* bn_weight, const float* bn_bias, const float* bn_mean, const float* bn_var,
+                      float bn_eps, float* out, int32_t B, int32_t T, int32_t F, int32_t spec_size, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
