@@ -9,7 +9,7 @@ import pytest
 import torch
 
 import clap_audio_models as M
-from util import rel_err
+from util import nan_fill_free, rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -33,15 +33,18 @@ def test_window_attention_vs_torch(dev, B, H, W, heads, shift):
     if shift > 0:  # the mask matters on these inputs: without it the oracle moves by far more than the tolerance
         assert rel_err(M.ref_window_attention(qkv, bias, heads, shift, masked=False), ref) > 1000 * M.TOL
         assert rel_err(M.ref_window_attention(qkv, bias, heads, 0), ref) > 1000 * M.TOL
-    out = ops.window_attention(qkv.view(-1, 3 * C).to(dev), bias.to(dev), B, H, W, heads, shift)
-    assert out.shape == (B * H * W, C)
+    qd, bd = qkv.view(-1, 3 * C).to(dev), bias.to(dev)
+    nan_fill_free(dev)
+    out = ops.window_attention(qd, bd, B, H, W, heads, shift)
+    assert out.shape == (B * H * W, C) and torch.isfinite(out).all()
     err = rel_err(out.view(B, H, W, C), ref)
     print(f"window_attention B={B} {H}x{W} heads={heads} shift={shift}: rel_err {err:.3e}")
     assert err < M.TOL
     # the fp32 matmul precision setting does not reach this entry point: same bits under "high"
     ops.set_float32_matmul_precision("high")
     try:
-        again = ops.window_attention(qkv.view(-1, 3 * C).to(dev), bias.to(dev), B, H, W, heads, shift)
+        nan_fill_free(dev)
+        again = ops.window_attention(qd, bd, B, H, W, heads, shift)
     finally:
         ops.set_float32_matmul_precision("highest")
     assert torch.equal(again, out)
@@ -75,8 +78,10 @@ def test_clap_mel2img_vs_torch(dev, T, Fb, S):
     w, b, mean, var = 1 + 0.1 * R(Fb, seed=1), 0.2 * R(Fb, seed=2), 0.3 * R(Fb, seed=3), 0.5 + torch.rand(Fb, generator=torch.Generator().manual_seed(4))
     ref = M.ref_mel2img(x, w, b, mean, var, 1e-5, S)
     D = lambda t: t.to(dev)
-    out = ops.clap_mel2img(D(x), D(w), D(b), D(mean), D(var), 1e-5, S)
-    assert out.shape == ref.shape == (2 * (S // 4) ** 2, 16)
+    args = D(x), D(w), D(b), D(mean), D(var)
+    nan_fill_free(dev)
+    out = ops.clap_mel2img(*args, 1e-5, S)
+    assert out.shape == ref.shape == (2 * (S // 4) ** 2, 16) and torch.isfinite(out).all()
     err = rel_err(out, ref)
     print(f"clap_mel2img T={T} F={Fb}: rel_err {err:.3e}")
     assert err < M.TOL

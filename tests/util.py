@@ -102,8 +102,14 @@ NAN_WORD = 0x7FFF7FFF
 def nan_fill_free(dev):
     """Fill every free block of torch's caching allocator on ``dev`` with NaN (NAN_WORD).  Outputs and scratch buffers the next
     launches allocate come from these blocks, so an element, pad column or scratch entry a kernel fails to write reads as NaN
-    instead of as stale data of an earlier test.  (Only memory the allocator holds and no live tensor uses is written.)"""
+    instead of as stale data of an earlier test.  (Only memory the allocator holds and no live tensor uses is written.)
+
+    Unreachable reference cycles are collected first: the snapshot below builds thousands of Python objects, which can start a
+    collection of its own, and a tensor that one frees AFTER the snapshot was taken leaves a block of stale data that is neither
+    live nor filled -- the next small torch.empty then returns it."""
     import ctypes
+    import gc
+    gc.collect()
     torch.cuda.synchronize(dev)
     lib = _hip_runtime()
     stream = torch.cuda.current_stream(dev).cuda_stream
@@ -112,8 +118,82 @@ def nan_fill_free(dev):
             continue
         addr = seg["address"]
         for blk in seg["blocks"]:
-            if blk["state"] == "inactive" and blk["size"] >= 4:
+            # (after the synchronize no kernel uses a freed block any more, whether or not the allocator has retired its events yet)
+            if blk["state"] != "active_allocated" and blk["size"] >= 4:
                 rc = lib.hipMemsetD32Async(ctypes.c_void_p(addr), NAN_WORD, blk["size"] // 4, ctypes.c_void_p(stream))
                 assert rc == 0, f"hipMemsetD32Async: error {rc}"
             addr += blk["size"]
     torch.cuda.synchronize(dev)
+
+
+def _nan_bits(dtype):
+    """(integer view dtype, the NAN_WORD pattern at that width) of a storage dtype"""
+    size = torch.empty((), dtype=dtype).element_size()
+    if size == 2:
+        return torch.int16, NAN_WORD & 0xFFFF
+    if size == 4:
+        return torch.int32, NAN_WORD
+    raise TypeError(f"no NaN fill pattern for {dtype}")
+
+
+def nan_buffer(n, dtype, device):
+    """a flat [n] tensor of ``dtype`` whose every element is the NAN_WORD pattern"""
+    idt, word = _nan_bits(dtype)
+    return torch.full((n,), word, dtype=idt, device=device).view(dtype)
+
+
+# the largest row tile of any kernel in csrc/ (cgemm.hip CBM = 256, hconv.hip BM = 256): a whole-tile over-run of any launch
+# lands inside a guard of this many rows
+GUARD_ROWS = 256
+
+
+def guarded(rows, cols, dtype, device, ld=None, guard_rows=GUARD_ROWS):
+    """(view, check): ONE flat allocation [guard_rows | rows | guard_rows] x ld (ld >= cols) whose every byte is the NAN_WORD
+    pattern, the [rows, cols] strided view of its middle, and a check() to call after the launches that write the view.  check()
+    asserts that both guards and the pad columns cols..ld are bit-identical to the fill and that every interior element is finite;
+    its message names the first offending (row, column) in the view's coordinates (front guard: negative rows, back guard: rows
+    >= ``rows``, pad: columns >= ``cols``) and says whether it is a stray write or a missing write."""
+    ld = cols if ld is None else ld
+    assert ld >= cols > 0 and rows > 0 and guard_rows >= 0
+    idt, word = _nan_bits(dtype)
+    buf = nan_buffer((rows + 2 * guard_rows) * ld, dtype, device)
+    view = buf[guard_rows * ld:(guard_rows + rows) * ld].view(rows, ld)[:, :cols]
+
+    def first(mask):
+        i = int(mask.reshape(-1).to(torch.uint8).argmax())
+        return i // mask.shape[1], i % mask.shape[1]
+
+    def check(what=""):
+        bits = buf.view(idt).view(rows + 2 * guard_rows, ld).cpu()
+        vals = buf.view(rows + 2 * guard_rows, ld).cpu()
+        tag = f"{what}: " if what else ""
+        regions = (("front guard", bits[:guard_rows], -guard_rows, 0), ("back guard", bits[guard_rows + rows:], rows, 0),
+                   ("pad columns", bits[guard_rows:guard_rows + rows, cols:], 0, cols))
+        for name, reg, r0, c0 in regions:
+            bad = reg != word
+            if bool(bad.any()):
+                r, c = first(bad)
+                raise AssertionError(f"{tag}stray write in the {name} at (row {r + r0}, column {c + c0}) of a [{rows}, {cols}] result "
+                                     f"(ld {ld}): {int(bad.sum())} element(s) changed")
+        inner = vals[guard_rows:guard_rows + rows, :cols]
+        bad = ~torch.isfinite(inner.float())
+        if bool(bad.any()):
+            r, c = first(bad)
+            unwritten = int(bits[guard_rows + r, c]) == word
+            kind = "missing write (still the fill pattern)" if unwritten else f"non-finite value written ({float(inner[r, c])})"
+            raise AssertionError(f"{tag}{kind} at (row {r}, column {c}) of a [{rows}, {cols}] result (ld {ld}): "
+                                 f"{int(bad.sum())} non-finite element(s)")
+
+    return view, check
+
+
+def poisoned_input(t, ld, tail_rows=GUARD_ROWS):
+    """the dense 2-D operand ``t`` embedded in a [rows + tail_rows, ld] buffer whose pad columns and rows after the last are NaN
+    (NAN_WORD); returns the [rows, cols] strided view.  A kernel that lets bytes outside its operand reach the result (a K tail
+    masked by multiplication, a row past M) gives NaN."""
+    rows, cols = t.shape
+    assert ld >= cols
+    buf = nan_buffer((rows + tail_rows) * ld, t.dtype, t.device).view(rows + tail_rows, ld)
+    view = buf[:rows, :cols]
+    view.copy_(t)
+    return view
