@@ -11,6 +11,7 @@ from .vae import AutoencoderKL, VaeConfig  # noqa: F401
 from .text_encoders import (PromptEncoder, ClapTextModelWithProjection, T5EncoderModel, GPT2Model,  # noqa: F401
                             AudioLDM2ProjectionModel)
 from .clap_audio import ClapAudioConfig, ClapAudioModelWithProjection  # noqa: F401
+from .clap_features import ClapFeatureExtractor  # noqa: F401
 from .wiring import install_ap_adapter, build_processors, ip_layer_names, adapter_state_dict, save_adapter, load_adapter  # noqa: F401
 from . import ops, distributed, autograd, config, sharded  # noqa: F401
 from .config import get_config  # noqa: F401

@@ -182,6 +182,8 @@ SYMBOLS = {
     # CLAP audio tower (score_waveforms)
     "apad_window_attention": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "apad_clap_mel2img": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _f32, _vp, _i32, _i32, _i32, _i32, _vp]),
+    # CLAP log-mel front-end (ClapFeatureExtractor)
+    "apad_clap_logmel": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _vp]),
 }
 
 _lock = threading.Lock()

@@ -13,6 +13,11 @@
 //                       normalisation, folded into one affine map)
 //   apad_stft_logmel    1024-point periodic-Hann STFT (hop 160, reflect-padded by 512) -> |X| -> 64 Slaney mel filters ->
 //                       log(max(., 1e-5)), the first `target_frames` frames of each clip
+//
+// CLAP front-end (score_waveforms; transformers ClapFeatureExtractor with truncation="rand_trunc"):
+//   apad_clap_logmel    resample (the polyphase sum of apad_resample_fir, on the fly) -> crop / repeatpad / repeat / pad to
+//                       max_length -> 1024-point periodic-Hann STFT (run-time hop, reflect-padded by 512) -> |X|^2 -> Slaney
+//                       mel filters -> 10 log10(max(., 1e-10)), one launch for a ragged batch
 #include "common.h"
 
 namespace {
@@ -282,4 +287,157 @@ extern "C" int apad_stft_logmel(const float* x, const int64_t* offsets, const in
     hipLaunchKernelGGL(stft_logmel_kernel, dim3((unsigned)target_frames, (unsigned)batch), dim3(256), 0, (hipStream_t)stream, x, offsets,
                        stats, window, twiddle, mel, mel_range, out, segment, (int)target_frames);
     return apad_check_launch("apad_stft_logmel");
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// CLAP log-mel front-end
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+
+constexpr int CLAP_SRC_CAP = 4096;  // floats of LDS for a frame's source window (two segments when a repeat seam cuts it)
+enum { CLAP_REPEATPAD = 0, CLAP_REPEAT = 1, CLAP_PAD = 2 };
+
+// One output sample of the polyphase resampler, resample_kernel's arithmetic on a staged window: the same taps, acc = 0 then
+// acc = fmaf(kp[j], v, acc) in tap order, v = 0 outside the clip (the staging wrote those zeros).  resample_kernel keeps its
+// own copy of the loop: routing it through this function flips a branch in its device code.
+__device__ __forceinline__ float polyphase_sum(const float* kp, int kw, const float* v) {
+    float acc = 0.f;
+    for (int j = 0; j < kw; ++j) acc = fmaf(kp[j], v[j], acc);
+    return acc;
+}
+
+// grid (frames, B), 256 threads: frame f of clip b.  The clip of n source samples is r[0 .. n48) after resampling (n48 =
+// ceil(n * newf / orig), r[q] = the polyphase sum resample_kernel computes; never stored).  The max_length samples the STFT
+// frames are v[i] = r[shift + i mod n48] for i < limit, else 0, with (shift, limit) = (starts[b], max_length) for a clip longer
+// than max_length, else shift = 0 and limit = max_length (repeat), n48 (pad) or (max_length / n48) n48 (repeatpad).  Frame f
+// reads v reflect-padded by 512 (edge sample not repeated) from f * hop - 512.
+// The frame's indices i cover one range [imin, imax]; modulo n48 that is one range of q or two (a seam), each staged into LDS
+// as the source samples its taps reach, zeros outside [0, n).
+__global__ __launch_bounds__(256) void clap_logmel_kernel(const float* x, const int64_t* offsets, const int64_t* starts, const float* kern,
+                                                          int orig, int newf, int width, const float* window,
+                                                          const float* twiddle /* [512][2] */, const float* mel /* [n_mels][513] */,
+                                                          const int32_t* mel_range /* [n_mels][2] */, float* out, int64_t max_length,
+                                                          int hop, int n_mels, int mode) {
+    __shared__ float re[SNFFT], im[SNFFT], src[CLAP_SRC_CAP];
+    const int f = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const int64_t o0 = offsets[b], n = offsets[b + 1] - o0;
+    const float* xc = x + o0;
+    const int64_t n48 = (n * newf + orig - 1) / orig;
+    const bool longer = n48 > max_length;
+    const int64_t shift = longer ? starts[b] : 0;
+    const int64_t limit = (longer || mode == CLAP_REPEAT) ? max_length : mode == CLAP_PAD ? n48 : (max_length / n48) * n48;
+    const int kw = 2 * width + orig;
+    const int64_t first = (int64_t)f * hop - SPAD;
+    // the range of i the frame reads, after both reflections and the cut at `limit`
+    int64_t imin = first < 0 ? 0 : first, imax = first + SNFFT - 1;
+    if (first < 0 && -first > imax) imax = -first;
+    if (imax >= max_length) {
+        const int64_t refl = 2 * (max_length - 1) - imax;
+        if (refl < imin) imin = refl;
+        imax = max_length - 1;
+    }
+    if (imax >= limit) imax = limit - 1;
+    // its image under q = shift + i mod n48: segment A = [qa0, qa1], segment B = [qb0, qb1] (empty: q1 < q0)
+    int64_t qa0 = 0, qa1 = -1, qb0 = 0, qb1 = -1;
+    if (imin <= imax) {
+        if (imax - imin + 1 >= n48) {
+            qa1 = n48 - 1;
+        } else {
+            qa0 = imin % n48;
+            qa1 = imax % n48;
+            if (qa0 > qa1) {
+                qb1 = qa1;
+                qa1 = n48 - 1;
+            }
+        }
+        qa0 += shift; qa1 += shift; qb0 += shift; qb1 += shift;
+    }
+    // source samples the segments' taps reach: [sa0, sa0 + la) and [sb0, sb0 + lb)
+    const int64_t sa0 = (qa0 / newf) * orig - width, sb0 = (qb0 / newf) * orig - width;
+    int la = qa1 >= qa0 ? (int)((qa1 / newf - qa0 / newf) * orig) + kw : 0;
+    int lb = qb1 >= qb0 ? (int)((qb1 / newf - qb0 / newf) * orig) + kw : 0;
+    if (la > CLAP_SRC_CAP) la = CLAP_SRC_CAP;  // (the host checked la + lb <= CLAP_SRC_CAP for every frame)
+    if (lb > CLAP_SRC_CAP - la) lb = CLAP_SRC_CAP - la;
+    for (int t = tid; t < la + lb; t += 256) {
+        const int64_t s = t < la ? sa0 + t : sb0 + (t - la);
+        src[t] = (s >= 0 && s < n) ? xc[s] : 0.f;
+    }
+    __syncthreads();
+    for (int j = tid; j < SNFFT; j += 256) {
+        int64_t i = first + j;
+        if (i < 0) i = -i;                                   // left reflection: i in [1, 512], max_length > 512
+        if (i >= max_length) i = 2 * (max_length - 1) - i;   // right reflection
+        float v = 0.f;
+        if (i < limit) {
+            const int64_t q = shift + i % n48;
+            const bool in_a = q >= qa0 && q <= qa1;
+            const int64_t blk = q / newf;
+            const int phase = (int)(q - blk * newf);
+            const int at = (int)(blk * orig - width - (in_a ? sa0 : sb0)) + (in_a ? 0 : la);
+            if (at >= 0 && at + kw <= la + lb)  // (always: the segments cover the frame)
+                v = kern ? polyphase_sum(kern + (int64_t)phase * kw, kw, src + at) : src[at];
+        }
+        const int r = (int)(__brev((unsigned)j) >> 22);  // 10-bit reversal
+        re[r] = v * window[j];
+        im[r] = 0.f;
+    }
+    __syncthreads();
+    fft_radix2<10, 256>(re, im, twiddle, tid);
+    // power of bins 0..512 into re[] (every read before any write)
+    const float p0 = re[tid] * re[tid] + im[tid] * im[tid];
+    const float p1 = re[tid + 256] * re[tid + 256] + im[tid + 256] * im[tid + 256];
+    const float p2 = tid == 0 ? re[512] * re[512] + im[512] * im[512] : 0.f;
+    __syncthreads();
+    re[tid] = p0;
+    re[tid + 256] = p1;
+    if (tid == 0) re[512] = p2;
+    __syncthreads();
+    // 4 lanes per mel filter over its non-zero bins [lo, hi), combined in a fixed order
+    const int filt = tid >> 2, lane = tid & 3;
+    const bool live = filt < n_mels;
+    const int lo = live ? mel_range[2 * filt] : 0, hi = live ? mel_range[2 * filt + 1] : 0;
+    const float* w = mel + (int64_t)filt * SBIN;
+    float e = 0.f;
+    for (int k = lo + lane; k < hi; k += 4) e = fmaf(w[k], re[k], e);
+    e += __shfl_xor(e, 1, 64);
+    e += __shfl_xor(e, 2, 64);
+    // power_to_db: 10 log10(max(e, 1e-10)); the floor itself is -100 exactly
+    if (live && lane == 0)
+        out[((int64_t)b * gridDim.x + f) * n_mels + filt] = e <= 1e-10f ? -100.f : 10.f * log10f(e);
+}
+
+}  // namespace
+
+extern "C" int apad_clap_logmel(const float* x, const int64_t* offsets, const int64_t* offsets_host, const int64_t* starts,
+                                const int64_t* starts_host, const float* kernel, int32_t orig, int32_t newf, int32_t width,
+                                const float* window, const float* twiddle, const float* mel, const int32_t* mel_range, float* out,
+                                int32_t batch, int64_t max_length, int32_t hop, int32_t n_mels, int32_t padding, void* stream) {
+    APAD_CHECK(x && offsets && offsets_host && starts && starts_host && window && twiddle && mel && mel_range && out && batch > 0,
+               "apad_clap_logmel: bad operands");
+    APAD_CHECK(orig >= 1 && newf >= 1 && width >= 0, "apad_clap_logmel: resampling ratio %d : %d (width %d) out of range", orig, newf, width);
+    APAD_CHECK(kernel || (orig == 1 && newf == 1 && width == 0), "apad_clap_logmel: a null kernel table means orig = new = 1, width = 0");
+    APAD_CHECK(max_length > SPAD, "apad_clap_logmel: max_length %lld must exceed the 512-sample reflect pad", (long long)max_length);
+    APAD_CHECK(n_mels >= 1 && n_mels <= SMEL, "apad_clap_logmel: n_mels %d outside [1, 64]", n_mels);
+    APAD_CHECK(hop >= 1, "apad_clap_logmel: hop %d must be at least 1", hop);
+    APAD_CHECK(batch <= 65535, "apad_clap_logmel: batch %d exceeds 65535", batch);
+    APAD_CHECK(padding == CLAP_REPEATPAD || padding == CLAP_REPEAT || padding == CLAP_PAD, "apad_clap_logmel: padding mode %d unknown", padding);
+    const int64_t frames = max_length / hop + 1;
+    APAD_CHECK(frames <= 0x7fffffffLL, "apad_clap_logmel: %lld frames exceed the grid", (long long)frames);
+    // a frame's source window: at most 1024 resampled samples in two segments, each with the taps' reach
+    const int64_t need = ((int64_t)(SNFFT - 1) / newf + 2) * orig + 2 * (2 * (int64_t)width + orig);
+    APAD_CHECK(need <= CLAP_SRC_CAP, "apad_clap_logmel: ratio %d : %d needs %lld staged samples per frame (limit %d)", orig, newf,
+               (long long)need, CLAP_SRC_CAP);
+    APAD_CHECK(offsets_host[0] == 0, "apad_clap_logmel: offsets[0] must be 0");
+    for (int i = 0; i < batch; ++i) {
+        const int64_t n = offsets_host[i + 1] - offsets_host[i];
+        APAD_CHECK(n > 0, "apad_clap_logmel: clip %d is empty", i);
+        const int64_t n48 = (n * newf + orig - 1) / orig;
+        if (n48 > max_length)
+            APAD_CHECK(starts_host[i] >= 0 && starts_host[i] <= n48 - max_length, "apad_clap_logmel: clip %d: crop start %lld outside [0, %lld]",
+                       i, (long long)starts_host[i], (long long)(n48 - max_length));
+    }
+    hipLaunchKernelGGL(clap_logmel_kernel, dim3((unsigned)frames, (unsigned)batch), dim3(256), 0, (hipStream_t)stream, x, offsets, starts,
+                       kernel, (int)orig, (int)newf, (int)width, window, twiddle, mel, mel_range, out, max_length, (int)hop, (int)n_mels,
+                       (int)padding);
+    return apad_check_launch("apad_clap_logmel");
 }

@@ -63,7 +63,8 @@ class AudioLDM2Pipeline:
         self.prompt_encoder = prompt_encoder  # text_encoders.PromptEncoder (HIP): CLAP text + T5 + projection + GPT-2
         self.tokenizer, self.tokenizer_2 = tokenizer, tokenizer_2  # the caller's CLAP (RoBERTa) / T5 tokenizers (host-side, vocab files)
         self.audio_tower = audio_tower  # clap_audio.ClapAudioModelWithProjection (HIP): ranks num_waveforms_per_prompt candidates
-        self.feature_extractor = feature_extractor  # the caller's transformers ClapFeatureExtractor (host-side, like the tokenizers)
+        # clap_features.ClapFeatureExtractor (HIP: resampling and features in one launch) or the caller's transformers one (host-side)
+        self.feature_extractor = feature_extractor
         self.logit_scale_t = math.log(1.0 / 0.07)  # ClapModel.logit_scale_t (logit_scale_init_value); set it from a checkpoint's value
         self.last_logits_per_text = None
         self.scheduler = scheduler or DDIMScheduler()
@@ -84,26 +85,34 @@ class AudioLDM2Pipeline:
             mel_spectrogram = mel_spectrogram.squeeze(1)
         return self.vocoder(mel_spectrogram).cpu().float()
 
-    def score_waveforms(self, text, audio, num_waveforms_per_prompt, device, dtype):
+    def score_waveforms(self, text, audio, num_waveforms_per_prompt, device, dtype, audio_device=None):
         """pipeline_audioldm2.py:592-614, same name and arguments: the candidates [n, samples] (CPU) re-ordered so that each prompt's
         ``num_waveforms_per_prompt`` best matches by CLAP text-audio similarity come first, best first -- chosen among ALL candidates
-        of the batch, as the reference does.  Resampling to the feature extractor's rate runs on ``apad_resample_fir`` (torchaudio's
-        polyphase kernel; the reference calls librosa.resample: parity unpinned), the features come from the caller's
-        ``feature_extractor`` on the host, the audio tower and the CLAP text tower run in fp32 (``dtype`` is accepted for the
-        reference's signature)."""
+        of the batch, as the reference does.  The resampler to the feature extractor's rate is torchaudio's polyphase kernel (the
+        reference calls librosa.resample: that difference stays).  With ``feature_extractor=ap_adapter_amd.ClapFeatureExtractor`` the
+        candidates go to the device once (``audio_device``: the copy that is already there) and one ``apad_clap_logmel`` launch
+        resamples them and makes the features the tower reads; with any other extractor object they are resampled by
+        ``apad_resample_fir`` and the features come from that object on the host.  The audio tower and the CLAP text tower run in
+        fp32 (``dtype`` is accepted for the reference's signature)."""
         if self.audio_tower is None or self.feature_extractor is None:
             raise NotImplementedError("score_waveforms needs audio_tower=ap_adapter_amd.ClapAudioModelWithProjection(...) and "
                                       "feature_extractor= (transformers' ClapFeatureExtractor)")
         if self.prompt_encoder is None or self.tokenizer is None:
             raise NotImplementedError("score_waveforms needs prompt_encoder= (its CLAP text tower) and tokenizer=")
         from .clap_audio import rank_waveforms
-        from .frontend import resample
+        from .clap_features import ClapFeatureExtractor
+        from . import frontend
         text = [text] if isinstance(text, str) else list(text)
         inputs = self.tokenizer(text, return_tensors="pt", padding=True)
         sr = int(self.feature_extractor.sampling_rate)
-        wav = resample(torch.as_tensor(audio).to(device, torch.float32), int(self.vocoder.config.sampling_rate), sr)
-        feats = self.feature_extractor(list(wav.cpu().numpy()), return_tensors="pt", sampling_rate=sr).input_features
-        audio_embeds = self.audio_tower.get_audio_features(torch.as_tensor(feats).to(device, torch.float32))
+        if isinstance(self.feature_extractor, ClapFeatureExtractor):
+            wav = (torch.as_tensor(audio) if audio_device is None else audio_device).to(device, torch.float32).contiguous()
+            feats = self.feature_extractor(wav, sampling_rate=sr, source_sampling_rate=int(self.vocoder.config.sampling_rate)).input_features
+        else:
+            wav = frontend.resample(torch.as_tensor(audio).to(device, torch.float32), int(self.vocoder.config.sampling_rate), sr)
+            feats = self.feature_extractor(list(wav.cpu().numpy()), return_tensors="pt", sampling_rate=sr).input_features
+            feats = torch.as_tensor(feats).to(device, torch.float32)
+        audio_embeds = self.audio_tower.get_audio_features(feats)
         text_embeds = self.prompt_encoder.text_encoder.get_text_features(inputs.input_ids.to(device), attention_mask=inputs.attention_mask.to(device))
         P, n, D = text_embeds.shape[0], audio_embeds.shape[0], text_embeds.shape[1]
         n4 = ops.round_up(n, 4)  # (the GEMM's vector width: zero rows pad the candidates, their columns are dropped)
@@ -606,9 +615,16 @@ class AudioLDM2Pipeline:
             scaling = getattr(getattr(self.vae, "config", None), "scaling_factor", 1.0)
             mel = self.vae.decode(out / scaling)
             mel = getattr(mel, "sample", mel)
-            out = self.mel_spectrogram_to_waveform(mel)[:, : int(audio_length_in_s * 16000)]
-            if ranking:  # :1047-1054
-                out = self.score_waveforms(text=prompt, audio=out, num_waveforms_per_prompt=num_waveforms_per_prompt, device=dev, dtype=pe.dtype)
+            from .clap_features import ClapFeatureExtractor
+            if ranking and isinstance(self.feature_extractor, ClapFeatureExtractor):  # :1047-1054, scored from the device copy
+                wav = self.vocoder(mel.squeeze(1) if mel.dim() == 4 else mel)[:, : int(audio_length_in_s * 16000)]
+                out = self.score_waveforms(text=prompt, audio=wav.cpu().float(), num_waveforms_per_prompt=num_waveforms_per_prompt, device=dev,
+                                           dtype=pe.dtype, audio_device=wav)
+            else:
+                out = self.mel_spectrogram_to_waveform(mel)[:, : int(audio_length_in_s * 16000)]
+                if ranking:  # :1047-1054
+                    out = self.score_waveforms(text=prompt, audio=out, num_waveforms_per_prompt=num_waveforms_per_prompt, device=dev,
+                                               dtype=pe.dtype)
             if output_type == "np":
                 out = out.numpy()
         if not return_dict:

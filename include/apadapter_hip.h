@@ -669,6 +669,28 @@ int apad_window_attention(const void* qkv, const float* bias, void* out, int32_t
 int apad_clap_mel2img(const float* x, const float* bn_weight, const float* bn_bias, const float* bn_mean, const float* bn_var,
                       float bn_eps, float* out, int32_t B, int32_t T, int32_t F, int32_t spec_size, void* stream);
 
+/* CLAP log-mel front-end (transformers ClapFeatureExtractor, truncation="rand_trunc"), additive to ABI 12: one launch from a
+   ragged batch of fp32 clips at the SOURCE rate to out fp32 [batch][1][frames][n_mels], frames = max_length / hop + 1, the layout
+   apad_clap_mel2img reads.  x / offsets / offsets_host as for apad_stft_logmel (every clip non-empty).  Clip b of n samples is
+   r[0 .. n48) at the target rate, n48 = ceil(n * newf / orig), r = apad_resample_fir's polyphase sum over `kernel`
+   [newf][2 * width + orig] (same taps, same order, zeros outside the clip), computed per frame and never stored; kernel = NULL
+   with orig = newf = 1, width = 0 means the clips are already at the target rate.  The max_length samples that are framed:
+     n48 >  max_length   v[i] = r[starts[b] + i]  (starts int64 [batch] in device memory, starts_host the same on the host, each
+                         within [0, n48 - max_length]; entries of shorter clips are not read)
+     padding 0 repeatpad v[i] = r[i mod n48] for i < (max_length / n48) n48, else 0
+     padding 1 repeat    v[i] = r[i mod n48]
+     padding 2 pad       v[i] = r[i] for i < n48, else 0
+   then the 1024-point periodic-Hann STFT of v reflect-padded by 512 (frame f starts at f * hop), power re^2 + im^2 of bins
+   0..512, mel [n_mels][513] (mel_range [n_mels][2] = each filter's non-zero bins [lo, hi)) and 10 log10(max(., 1e-10)); a
+   frame of zeros gives -100 exactly.  window [1024], twiddle [512][2] = (cos, -sin)(2 pi k / 1024).  A clip's rows do not
+   depend on the batch around it; no host synchronisation (hipGraph-capturable).
+   -1 when max_length <= 512, n_mels outside [1, 64], hop < 1, batch > 65535, a clip is empty, a crop start is out of range, or
+   the ratio's per-frame source window exceeds the kernel's LDS budget. */
+int apad_clap_logmel(const float* x, const int64_t* offsets, const int64_t* offsets_host, const int64_t* starts,
+                     const int64_t* starts_host, const float* kernel, int32_t orig, int32_t newf, int32_t width,
+                     const float* window, const float* twiddle, const float* mel, const int32_t* mel_range, float* out,
+                     int32_t batch, int64_t max_length, int32_t hop, int32_t n_mels, int32_t padding, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,12 @@
     sample), reported per window as measured, and EXTRAPOLATED linearly to the 64 windows x candidates of the launch it replaces -- the
     file says which number is which.  The chain here omits the shift mask and the window gather, so it is a lower bound of that route.
 
+  * the feature extractor in front of the tower, for 3 and for 96 candidates of 10.24 s at 16 kHz: the INSTALLED transformers
+    ClapFeatureExtractor (truncation="rand_trunc") on this host's CPU, on audio already resampled to 48 kHz (wall clock, one run
+    for 96 candidates; the resampling, the download and the upload of the features around it are not in the figure), beside
+    ap_adapter_amd.ClapFeatureExtractor on the device from the 16 kHz samples (resampling inside the launch; device events, and
+    the wall clock of the whole call with its host side).  A measurement on one host, not a pass / fail.
+
 Times are medians of ``--repeats`` timed runs after ``--warmup`` runs of the same shapes, device events around work ending in a
 synchronise.  Audio quality and ranking quality are not measured (no real weights).
 
@@ -83,6 +89,39 @@ def family_split(ops, fn):
     return {k: {"launches": v["launches"], "ms": round(v["ms"], 4)} for k, v in sorted(out.items())}
 
 
+def extractor_leg(A, dev, warmup, repeats):
+    """the host extractor against the device one, per candidate count"""
+    import time
+    from transformers.models.clap.feature_extraction_clap import ClapFeatureExtractor as Installed
+    from ap_adapter_amd import frontend
+    host, ours = Installed(truncation="rand_trunc"), A.ClapFeatureExtractor(truncation="rand_trunc")
+    n16 = int(10.24 * 16000)
+    leg = {"clip": "10.24 s: 163840 samples at 16 kHz, 491520 at 48 kHz, cropped to 480000; output [n, 1, 1001, 64]",
+           "host": "transformers.ClapFeatureExtractor(truncation='rand_trunc') on 48 kHz numpy audio, wall clock",
+           "device": "ap_adapter_amd.ClapFeatureExtractor on the 16 kHz device tensor (source_sampling_rate=16000), one apad_clap_logmel launch"}
+    for n in (3, 96):
+        wav = (0.1 * torch.randn(n, n16, generator=torch.Generator().manual_seed(n))).to(dev)
+        run = lambda: ours(wav, sampling_rate=48000, source_sampling_rate=16000)
+        med, best = timed(run, warmup, repeats)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        run()
+        torch.cuda.synchronize()
+        wall = time.perf_counter() - t0
+        wav48 = list(frontend.resample(wav, 16000, 48000).cpu().numpy())
+        host_runs = 3 if n <= 3 else 1
+        secs = []
+        for _ in range(host_runs):
+            t0 = time.perf_counter()
+            host(wav48, sampling_rate=48000, return_tensors="pt")
+            secs.append(time.perf_counter() - t0)
+        leg[str(n)] = {"candidates": n, "device_ms_median": round(med, 3), "device_ms_min": round(best, 3), "device_call_wall_ms": round(1e3 * wall, 3),
+                       "host_s": round(statistics.median(secs), 3), "host_runs": host_runs,
+                       "host_over_device": round(1e3 * statistics.median(secs) / med, 1)}
+    leg["host_torch_threads"] = torch.get_num_threads()
+    return leg
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join("profiles", "clap_rank.json"))
@@ -144,7 +183,8 @@ def main():
     ops.window_attention(strip, bias, 1, 8, 64, heads, 0, out=ref)
     back = ref.view(8, 8, 8, C).permute(1, 0, 2, 3).reshape(8 * 64, C)
     res["chain"]["max_abs_diff_vs_kernel"] = float((back - o).abs().max())
-    res["not_measured"] = "audio quality and ranking quality (no real weights); the feature extractor (host side, the caller's component)"
+    res["feature_extractor"] = extractor_leg(A, dev, args.warmup, args.repeats)
+    res["not_measured"] = "audio quality and ranking quality (no real weights)"
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(res, f, indent=1)
