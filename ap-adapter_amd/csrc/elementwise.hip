@@ -1,6 +1,6 @@
 // Small HBM-bound kernels of the path: AudioMAE token pooling, sinusoidal timestep embedding, fused
-// classifier-free-guidance + sampler update (one kernel behind apad_cfg_ddim_step / apad_cfg_sampler_step / apad_cfg_edit_step) and the edit
-// run's start, device-side step counter.
+// classifier-free-guidance + sampler update (one kernel behind apad_cfg_ddim_step / apad_cfg_sampler_step / apad_cfg_edit_step), its three-branch
+// twin (apad_cfg_dual_step) and the edit run's start, device-side step counter.
 #include "common.h"
 #include "f32_ops.h"
 
@@ -187,6 +187,64 @@ __global__ __launch_bounds__(256) void cfg_step_kernel(const uint8_t* eps2, floa
 #pragma unroll
         for (int j = 0; j < V; ++j) {
             e[j] = (float)(typename ET<DT>::elem)fmaf(gs, ec[j] - eu[j], eu[j]);
+            float xn;
+            sampler_update<DT, FORM>(c_x, c_e, c_m, c_z, d_x, d_e, x[j], e[j], m1[j], zz[j], xn, m0[j]);
+            x[j] = xn;
+        }
+        if (mask) {
+            const int64_t pix = V == 8 ? (i >> 3) : i / C;  // over the whole batch: clip * npix + pixel
+            const float m = mask[mask_per_clip ? pix : pix % npix];
+            float a[V], b[V];
+            ld_f32v<V>(x0, i, a);
+            ld_f32v<V>(z0, i, b);
+#pragma unroll
+            for (int j = 0; j < V; ++j) x[j] = edit_blend(m, x[j], kx, kz, a[j], b[j]);
+        }
+        st_f32v<V>(latents, i, x);
+        st_elemv<DT, V>(unet_in, i, x);
+        if (hist) st_f32v<V>(hist, i, m0);
+        if (eps_out) st_f32v<V>(eps_out, i, e);
+    }
+}
+
+// The three-branch step (apad_cfg_dual_step): eps3 = [e_0 ; e_A ; e_AT] (no condition / audio prompt / audio prompt + text), the guided noise
+//   eps = (elem)fma(s_T, e_AT - e_A, fma(s_A, e_A - e_0, e_0)),   (s_A, s_T) = guidance[2 * step]   (InstructPix2Pix's two scales)
+// -- each difference and each fma rounded to fp32, one rounding to the model dtype -- then cfg_step_kernel's sampler update and edit blend, by the
+// same sampler_update / edit_blend, always on the six-column table.  A kernel of its own: cfg_step_kernel's instantiations keep their device code.
+// The f16 rounding is pinned here (the fp32 fma first, in every form): the guidance values are arbitrary floats, and folding the store's rounding
+// into the fma would move a rounding tie by a whole f16 ulp against the written formula.
+template <int DT, int FORM>
+__global__ __launch_bounds__(256) void cfg_dual_step_kernel(const uint8_t* eps3, float* latents, uint8_t* unet_in, float* eps_out, float* hist,
+                                                            const float* noise, const float* coef, const float* guidance, const float* keep,
+                                                            const float* x0, const float* z0, const float* mask, int mask_per_clip, int C, int64_t n,
+                                                            const int32_t* step_ptr, int n_steps, int64_t total) {
+#pragma clang fp contract(off)
+    static_assert(FORM == STEP_VEC || FORM == STEP_SCALAR, "the two-column table has no three-branch form");
+    constexpr int V = FORM == STEP_VEC ? 8 : 1;
+    int step = step_ptr ? *step_ptr : 0;
+    step = step < 0 ? 0 : (step >= n_steps ? n_steps - 1 : step);  // the three tables and the noise buffer have n_steps rows
+    const float* r = coef + 6 * step;
+    const float c_x = r[0], c_e = r[1], c_m = r[2], c_z = r[3], d_x = r[4], d_e = r[5];
+    const float s_a = guidance[2 * step], s_t = guidance[2 * step + 1];
+    const float kx = mask ? keep[2 * step] : 0.f, kz = mask ? keep[2 * step + 1] : 0.f;
+    const bool use_m1 = hist && c_m != 0.f, use_z = noise && c_z != 0.f;
+    const float* z = noise + (use_z ? (int64_t)step * total : 0);
+    const int64_t npix = n / C;  // pixels per clip
+    for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * V; i < total; i += (int64_t)gridDim.x * 256 * V) {
+        float e0[V], ea[V], eat[V], x[V], m1[V], zz[V], e[V], m0[V];
+        ld_elemv<DT, V>(eps3, i, e0);
+        ld_elemv<DT, V>(eps3, total + i, ea);
+        ld_elemv<DT, V>(eps3, 2 * total + i, eat);
+        ld_f32v<V>(latents, i, x);
+#pragma unroll
+        for (int j = 0; j < V; ++j) m1[j] = zz[j] = 0.f;
+        if (use_m1) ld_f32v<V>(hist, i, m1);
+        if (use_z) ld_f32v<V>(z, i, zz);
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            float g = fmaf(s_t, eat[j] - ea[j], fmaf(s_a, ea[j] - e0[j], e0[j]));
+            if constexpr (DT == APAD_F16) asm volatile("" : "+v"(g));  // (the fp32 value exists before the f16 rounding: see above)
+            e[j] = (float)(typename ET<DT>::elem)g;
             float xn;
             sampler_update<DT, FORM>(c_x, c_e, c_m, c_z, d_x, d_e, x[j], e[j], m1[j], zz[j], xn, m0[j]);
             x[j] = xn;
@@ -420,6 +478,34 @@ extern "C" int apad_cfg_edit_step(const void* eps2, float* latents, void* unet_i
     LAUNCH_DT_V(cfg_step_kernel, vec, dim3((unsigned)blocks), (const uint8_t*)eps2, latents, (uint8_t*)unet_in, eps_out, history, noise, coef, keep, x0,
                 z0, mask, per_clip, Cc, n, step_ptr, n_steps, guidance_scale, total);
     return apad_check_launch("apad_cfg_edit_step");
+}
+
+extern "C" int apad_cfg_dual_step(const void* eps3, float* latents, void* unet_in, float* eps_out, float* history, const float* noise,
+                                  const float* coef, const float* guidance, const float* keep, const float* x0, const float* z0, const float* mask,
+                                  int32_t mask_batch, int32_t C, const int32_t* step_ptr, int32_t n_steps, int32_t B, int64_t n, int32_t dtype,
+                                  void* stream) {
+    APAD_CHECK(eps3 && latents && unet_in && coef, "apad_cfg_dual_step: null operand");
+    APAD_CHECK(guidance, "apad_cfg_dual_step: null guidance table");
+    APAD_CHECK(dtype == APAD_BF16 || dtype == APAD_F16 || dtype == APAD_F32, "apad_cfg_dual_step: dtype %d not supported", dtype);
+    APAD_CHECK(B > 0 && n > 0 && n_steps > 0, "apad_cfg_dual_step: empty problem");
+    if (mask) {
+        APAD_CHECK(keep && x0 && z0, "apad_cfg_dual_step: a mask needs the keep table, x0 and z0 (null operand)");
+        APAD_CHECK(mask_batch == 1 || mask_batch == B, "apad_cfg_dual_step: mask_batch %d must be 1 or B = %d", mask_batch, B);
+        APAD_CHECK(C > 0 && n % C == 0, "apad_cfg_dual_step: n = %lld is not a multiple of C = %d", (long long)n, C);
+    }
+    const int64_t total = (int64_t)B * n;
+    // apad_cfg_edit_step's rule (every base 16-byte aligned, 8 | total, C == 8 with a mask): then the second and third branch are aligned too
+    const uintptr_t bases = (uintptr_t)eps3 | (uintptr_t)latents | (uintptr_t)unet_in | (uintptr_t)eps_out | (uintptr_t)history | (uintptr_t)noise |
+                            (uintptr_t)x0 | (uintptr_t)z0;
+    const bool vec = total % 8 == 0 && bases % 16 == 0 && (!mask || C == 8);
+    int64_t blocks = ((vec ? total / 8 : total) + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    hipStream_t s = (hipStream_t)stream;
+    const int per_clip = mask_batch == B && B > 1;
+    const int Cc = mask ? C : 1;
+    LAUNCH_DT_V(cfg_dual_step_kernel, vec, dim3((unsigned)blocks), (const uint8_t*)eps3, latents, (uint8_t*)unet_in, eps_out, history, noise, coef,
+                guidance, keep, x0, z0, mask, per_clip, Cc, n, step_ptr, n_steps, total);
+    return apad_check_launch("apad_cfg_dual_step");
 }
 
 extern "C" int apad_edit_start(const void* moments, const float* post_noise, const float* z0, float* x0_out, float* latents, void* unet_in, float a,

@@ -1201,6 +1201,35 @@ def cfg_edit_step(eps2, latents, unet_in, coef, keep, step_ptr, guidance_scale, 
                                        float(guidance_scale), B, n, _DT[eps2.dtype], _stream()), "apad_cfg_edit_step")
 
 
+def cfg_dual_step(eps3, latents, unet_in, coef, guidance, step_ptr, eps_out=None, history=None, noise=None, keep=None, x0=None, z0=None, mask=None,
+                  channels=8):
+    """the three-branch step: eps3 [3B, n...] = [no condition ; audio prompt ; audio prompt + text], guidance fp32 [steps, 2] = (s_A, s_T) per
+    step, read on the device at row *step_ptr: eps = fma(s_T, e_AT - e_A, fma(s_A, e_A - e_0, e_0)), then cfg_edit_step's sampler update and
+    (with ``mask``) edit blend.  coef is always the six-column table.  mask = None is the plain sampler step."""
+    fn = "cfg_dual_step"
+    _req(latents, fn + ".latents", torch.float32)
+    if eps3.numel() != 3 * latents.numel() or (eps3.dim() > 1 and eps3.shape[0] != 3 * latents.shape[0]):
+        raise RuntimeError(f"{fn}: eps3 must hold three branches [3B, n] of latents [B, n] = {tuple(latents.shape)}, got {tuple(eps3.shape)}")
+    steps, B, n = _step_operands(fn, eps3[: 2 * latents.shape[0]], latents, unet_in, coef, eps_out, history, noise, x0, z0, keep)
+    _req(guidance, fn + ".guidance", torch.float32)
+    if guidance.dim() != 2 or tuple(guidance.shape) != (steps, 2) or not guidance.is_contiguous():
+        raise RuntimeError(f"{fn}.guidance: expected a contiguous fp32 [{steps}, 2] table of (s_A, s_T), got {tuple(guidance.shape)}")
+    if not eps3.is_contiguous():
+        raise RuntimeError(f"{fn}: eps3 must be contiguous")
+    mask_batch = 0
+    if mask is not None:
+        _req(mask, fn + ".mask", torch.float32)
+        channels = int(channels)
+        # (n % channels != 0 and a mask batch other than 1 or B are the entry point's own checks)
+        if mask.dim() != 2 or not mask.is_contiguous() or (channels > 0 and n % channels == 0 and mask.shape[1] != n // channels):
+            raise RuntimeError(f"{fn}.mask: expected a contiguous [1 or B, n / channels] table with n = {n}, channels = {channels}, "
+                               f"got {tuple(mask.shape)}")
+        mask_batch = mask.shape[0]
+    L.check(L.lib().apad_cfg_dual_step(eps3.data_ptr(), latents.data_ptr(), unet_in.data_ptr(), _ptr(eps_out), _ptr(history), _ptr(noise),
+                                       coef.data_ptr(), guidance.data_ptr(), _ptr(keep), _ptr(x0), _ptr(z0), _ptr(mask), mask_batch, int(channels),
+                                       _ptr(step_ptr), steps, B, n, _DT[eps3.dtype], _stream()), "apad_cfg_dual_step")
+
+
 def edit_start(z0, x0, latents, unet_in, a, s, moments=None, post_noise=None, scale=1.0):
     """the start of an edit run, written into the loop's buffers: with ``moments`` [rows, 2L] = (mean | logvar) in unet_in's dtype and
     ``post_noise`` fp32 [rows, L], x0 <- (mean + exp(0.5 clamp(logvar, -30, 20)) post_noise) * scale; without, x0 holds the source latents

@@ -26,7 +26,7 @@ from typing import Optional, Union
 import torch
 
 from . import ops
-from .scheduler import DDIMScheduler, DPMSolverMultistepScheduler, edit_start_index
+from .scheduler import DDIMScheduler, DPMSolverMultistepScheduler, edit_start_index, guidance_table
 
 
 @dataclass
@@ -222,12 +222,17 @@ class AudioLDM2Pipeline:
         return tokens, self._uncond_cache[key]
 
     @staticmethod
-    def assemble_condition(generated_prompt_embeds, audio_tokens, uncond_audio_tokens, dtype):
-        """:934-956 -- text tokens first, audio after; unconditional half first; cast to the UNet dtype."""
+    def assemble_condition(generated_prompt_embeds, audio_tokens, uncond_audio_tokens, dtype, branches=2):
+        """:934-956 -- text tokens first, audio after; unconditional half first; cast to the UNet dtype.  ``branches=3`` (separate audio and
+        text guidance; ``generated_prompt_embeds`` is still [negative; positive]): [neg | zero-mel audio ; neg | audio ; pos | audio]."""
+        if branches not in (2, 3):
+            raise ValueError(f"branches={branches!r}: 2 (unconditional, conditional) or 3 (no condition, audio, audio + text)")
         num = generated_prompt_embeds.shape[0] // 2
         a = audio_tokens.to(dtype).repeat(num, 1, 1)
         u = uncond_audio_tokens.to(dtype).repeat(num, 1, 1)
         neg, pos = generated_prompt_embeds.to(dtype).chunk(2)
+        if branches == 3:
+            return torch.cat([torch.cat([neg, u], dim=1), torch.cat([neg, a], dim=1), torch.cat([pos, a], dim=1)], dim=0).contiguous()
         return torch.cat([torch.cat([neg, u], dim=1), torch.cat([pos, a], dim=1)], dim=0).contiguous()
 
     # ---- editing from a source clip ----
@@ -376,7 +381,7 @@ class AudioLDM2Pipeline:
     @torch.no_grad()
     def denoise(self, latents_nchw, generated_prompt_embeds, prompt_embeds, attention_mask, num_inference_steps,
                 guidance_scale, use_graph=True, callback=None, callback_steps=1, keep_noise_pred=False, eta=0.0, generator=None, *,
-                source=None, start=0):
+                source=None, start=0, audio_guidance_scale=None):
         """CFG + scheduler loop (:983-1031).  With ``use_graph`` the step is captured ONCE per (batch, token counts, steps, guidance,
         weights, sampler) and kept: later calls copy their latents / conditions into the graph's static buffers, refresh the hoisted
         K/V in place and replay -- no warm-up step, no re-capture (a sharded job runs many batches through one pipeline).
@@ -387,8 +392,17 @@ class AudioLDM2Pipeline:
         ``source`` (an ``EditSource``, or the fp32 (x0, z0, mask) triple, each [B, C, H, W] / mask [1 or B, 1, H, W] or None) makes this
         an edit run entering the timestep grid at index ``start``: ``latents_nchw`` is then unused (pass None) -- the run starts from
         ``add_noise(x0, z0, timesteps[start])`` -- it visits ``timesteps[start:]``, and with a mask every step re-imposes the kept
-        region.  x0 / z0 / mask live with the captured step as static buffers, refilled in place on a cache hit."""
+        region.  x0 / z0 / mask live with the captured step as static buffers, refilled in place on a cache hit.
+
+        ``audio_guidance_scale`` (not None) selects the three-branch step with separate audio and text guidance: the three condition tensors
+        then carry 3B rows, [no condition ; audio prompt ; audio prompt + text] (``assemble_condition(branches=3)``), the UNet runs at
+        ``batch_repeat=3`` and every sampler / edit combination goes through ``apad_cfg_dual_step`` with
+        eps = e_0 + s_A (e_A - e_0) + s_T (e_AT - e_A), s_A = ``audio_guidance_scale`` and s_T = ``guidance_scale``; each is a float or a
+        sequence of ``num_inference_steps`` floats (``scheduler.guidance_table``), any value >= 0.  The scales are a device table the step reads
+        at its counter, a static buffer refilled on a cache hit like the noise: the graph key carries no guidance value, and a sweep over
+        scales replays one captured graph."""
         unet = self.unet
+        dual = audio_guidance_scale is not None
         dtype = unet.conv_in.weight.dtype
         src = None
         if source is not None:
@@ -402,23 +416,26 @@ class AudioLDM2Pipeline:
         else:
             dev = latents_nchw.device
             B, Cc, H, W = latents_nchw.shape
-        if not guidance_scale > 1.0:
+        if not dual and not guidance_scale > 1.0:
             raise NotImplementedError("the audio-conditioned path requires classifier-free guidance (:941 chunk(2))")
         sched = self.scheduler
         sched.set_timesteps(num_inference_steps)
         if src is None:
-            plan, n_run, emask_shape = sched.sampler_plan(eta), num_inference_steps, None
+            plan, n_run, emask_shape = (sched.sampler_plan(eta, dual=True) if dual else sched.sampler_plan(eta)), num_inference_steps, None
         else:
-            plan = sched.sampler_plan(eta, start=start, masked=src.mask is not None)
+            plan = (sched.sampler_plan(eta, start=start, masked=src.mask is not None, dual=True) if dual
+                    else sched.sampler_plan(eta, start=start, masked=src.mask is not None))
             n_run = num_inference_steps - plan.start
             noise_a, noise_s = sched.add_noise_coefs(plan.start)
             emask_shape = None if src.mask is None else (src.mask.shape[0], H * W)
             if emask_shape is not None and (tuple(src.mask.shape[1:]) != (1, H, W) or emask_shape[0] not in (1, B)):
                 raise ValueError(f"source mask {tuple(src.mask.shape)}: expected [1 or {B}, 1, {H}, {W}]")
+        # (s_A, s_T) of the steps this run visits; checked here, on the host, before any device work
+        gtab = guidance_table(audio_guidance_scale, guidance_scale, num_inference_steps, plan.start) if dual else None
         graphed = use_graph and callback is None
         key = (B, Cc, H, W, tuple(generated_prompt_embeds.shape), tuple(prompt_embeds.shape),
                None if attention_mask is None else (tuple(attention_mask.shape), attention_mask.dtype), num_inference_steps,
-               float(guidance_scale), dtype, bool(keep_noise_pred), str(dev),
+               "dual" if dual else float(guidance_scale), dtype, bool(keep_noise_pred), str(dev),
                ops.get_float32_matmul_precision() if dtype == torch.float32 else None,  # (a step captured in one precision never replays in the other)
                plan.key)  # (... nor one captured for another sampler / eta: the table and the update kernel are baked in)
         if src is not None:  # an edit run: start index and masked flag are in plan.key; the mask's batch form selects the kernel's indexing
@@ -442,6 +459,8 @@ class AudioLDM2Pipeline:
             if attention_mask is not None:
                 e["mask"].copy_(attention_mask)
             e["step_ptr"].zero_()
+            if dual:
+                e["guidance"].copy_(gtab)
             if e["hist"] is not None:
                 e["hist"].zero_()
             if e["noise"] is not None:
@@ -466,6 +485,7 @@ class AudioLDM2Pipeline:
                 e["emask"] = None if emask_shape is None else torch.empty(emask_shape, dtype=torch.float32, device=dev)
                 e["keep"] = None if plan.keep is None else plan.keep.to(dev)
                 self._fill_edit_buffers(e, src, noise_a, noise_s)
+            e["guidance"] = gtab.to(dev) if dual else None
             e["eps_out"] = torch.empty_like(e["lat"]) if keep_noise_pred else None
             e["hist"] = torch.zeros_like(e["lat"]) if plan.needs_history else None
             e["noise"] = self.prepare_step_noise(B, Cc, H, W, n_run, generator, device=dev) if plan.needs_noise else None
@@ -482,6 +502,14 @@ class AudioLDM2Pipeline:
             #  -- same-box A/B 37.35 vs 37.49 ms with two half-batch streams -- and this is the configuration bench.py measures;
             #  ``unet.low_res_streams`` remains an opt-in attribute)
 
+            def dual_step():  # three sample-forwards per clip; the condition-free prefix still runs once
+                eps3 = unet.forward_nhwc(unet_in, H, W, None, gen, pe, None, mask, batch_repeat=3)
+                if masked:
+                    ops.cfg_dual_step(eps3, lat, unet_in, coef, e["guidance"], step_ptr, eps_out, hist, noise, e["keep"], e["x0"], e["z0"], e["emask"], Cc)
+                else:
+                    ops.cfg_dual_step(eps3, lat, unet_in, coef, e["guidance"], step_ptr, eps_out, hist, noise)
+                ops.step_advance(step_ptr)
+
             def step():
                 eps2 = unet.forward_nhwc(unet_in, H, W, None, gen, pe, None, mask, batch_repeat=2)
                 if masked:
@@ -491,6 +519,9 @@ class AudioLDM2Pipeline:
                 else:
                     ops.cfg_sampler_step(eps2, lat, unet_in, coef, step_ptr, guidance_scale, eps_out, hist, noise)
                 ops.step_advance(step_ptr)
+
+            if dual:
+                step = dual_step
 
             def reset():  # back to step 0 of this call (after the warm-up step and after the capture)
                 lat.copy_(lat0)
@@ -547,7 +578,8 @@ class AudioLDM2Pipeline:
                  negative_prompt_embeds=None, generated_prompt_embeds=None, negative_generated_prompt_embeds=None,
                  attention_mask=None, negative_attention_mask=None, max_new_tokens=None, return_dict=True,
                  callback=None, callback_steps=1, cross_attention_kwargs=None, output_type="np", mel=None,
-                 use_graph=True, source_audio=None, source_mel=None, source_latents=None, strength=1.0, edit_mask=None, edit_region=None):
+                 use_graph=True, source_audio=None, source_mel=None, source_latents=None, strength=1.0, edit_mask=None, edit_region=None,
+                 audio_guidance_scale=None):
         """Same keyword surface and defaults as the reference (pipeline_audioldm2.py:748-775, ``output_type="np"`` included): a
         pipeline built with ``vae=`` and ``vocoder=`` returns waveforms by default; ``output_type="latent"`` is the exit for a pipeline
         that holds the denoise path only.
@@ -556,7 +588,19 @@ class AudioLDM2Pipeline:
         ``source_mel`` (the 64-bin log-mel [b, 1, height, 64]) or ``source_latents`` ([b, C, height / 4, 16], scaled) is encoded, noised
         to the interior timestep that ``strength`` in (0, 1] selects (diffusers' img2img convention: the last int(N * strength) steps
         run) and denoised from there.  ``edit_mask`` (broadcastable to [B, 1, height / 4, 16]; 1 = regenerate, 0 = keep) or
-        ``edit_region`` = (start_s, end_s) restricts the change: the rest of the returned latents is the source's, bit for bit."""
+        ``edit_region`` = (start_s, end_s) restricts the change: the rest of the returned latents is the source's, bit for bit.
+
+        Beyond the reference -- separate audio and text guidance: ``audio_guidance_scale`` (needs ``mel=`` or ``audio_file=``) runs three
+        branches per clip, (negative text, zero-mel tokens), (negative text, audio prompt) and (positive text, audio prompt), and guides
+        by eps_0 + audio_guidance_scale (eps_A - eps_0) + guidance_scale (eps_AT - eps_A) (InstructPix2Pix's two scales; the adapter's
+        training drops each condition independently, which is what makes this valid).  Either scale may be a float >= 0 or a sequence of
+        ``num_inference_steps`` floats; changing them does not re-capture the step.  Editing, both samplers, ``eta``,
+        ``num_waveforms_per_prompt`` and ranking work as without it."""
+        dual = audio_guidance_scale is not None
+        if dual:
+            if mel is None and audio_file is None:
+                raise ValueError("audio_guidance_scale needs an audio condition (mel= or audio_file=): without one there is no audio branch to "
+                                 "guide toward")
         if output_type != "latent" and (self.vae is None or self.vocoder is None):
             raise NotImplementedError("waveform output needs latents -> mel (vae=ap_adapter_amd.AutoencoderKL) and mel -> waveform "
                                       "(vocoder=ap_adapter_amd.SpeechT5HifiGan); or use output_type='latent'")
@@ -587,6 +631,8 @@ class AudioLDM2Pipeline:
         edit_k, edit_mask = self.check_edit_arguments(batch_size * num_waveforms_per_prompt, height, num_inference_steps, audio_length_in_s, latents,
                                                       source_audio, source_mel, source_latents, strength, edit_mask, edit_region)
         editing = source_audio is not None or source_mel is not None or source_latents is not None
+        if dual:  # the scales of the steps this call runs, checked before any device work (a ValueError names ``audio`` or ``text``)
+            guidance_table(audio_guidance_scale, guidance_scale, num_inference_steps, edit_k)
         if audio_file is not None and mel is None:
             from .frontend import load_mel  # "next" row f-2
             mel = load_mel(audio_file)
@@ -599,18 +645,23 @@ class AudioLDM2Pipeline:
                                         negative_attention_mask=negative_attention_mask, max_new_tokens=max_new_tokens)
         if mel is not None:
             tokens, uncond = self.encode_audio(mel.to(dev), time_pooling, freq_pooling)
-            ge = self.assemble_condition(ge, tokens, uncond, dtype)
+            ge = self.assemble_condition(ge, tokens, uncond, dtype, branches=3 if dual else 2)
+        if dual:  # T5 states and mask of the three branches: [negative; negative; positive]
+            half = pe.shape[0] // 2
+            pe, am = torch.cat([pe[:half], pe]), torch.cat([am[:half], am])
         # prepare_extra_step_kwargs (:617-632): eta reaches a scheduler whose step takes it (DDIM) and is ignored by the others
         if editing:
             src = self.prepare_edit_source(batch_size * num_waveforms_per_prompt, height, dev, generator, source_audio, source_mel, source_latents,
                                            edit_mask)
             out = self.denoise(None, ge, pe, am, num_inference_steps, guidance_scale, use_graph=use_graph, callback=callback,
-                               callback_steps=callback_steps, eta=eta, generator=generator, source=src, start=edit_k)
+                               callback_steps=callback_steps, eta=eta, generator=generator, source=src, start=edit_k,
+                               audio_guidance_scale=audio_guidance_scale)
         else:
             lat = self.prepare_latents(batch_size * num_waveforms_per_prompt, self.unet.config.in_channels, height, dtype,
                                        dev, generator, latents)
             out = self.denoise(lat, ge, pe, am, num_inference_steps, guidance_scale, use_graph=use_graph, callback=callback,
-                               callback_steps=callback_steps, eta=eta, generator=generator)
+                               callback_steps=callback_steps, eta=eta, generator=generator,
+                               audio_guidance_scale=audio_guidance_scale)
         if output_type != "latent":  # :1036-1044
             scaling = getattr(getattr(self.vae, "config", None), "scaling_factor", 1.0)
             mel = self.vae.decode(out / scaling)

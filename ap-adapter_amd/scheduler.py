@@ -10,7 +10,8 @@ conventions.  The reference pipeline accepts any ``KarrasDiffusionSchedulers`` m
 
 The per-step update itself runs on the device from a coefficient table (``apad_cfg_ddim_step`` for deterministic DDIM,
 ``apad_cfg_sampler_step`` for everything else, ``apad_cfg_edit_step`` with a region mask: three entry points onto one kernel, whose
-rounding form per entry point is written out in csrc/elementwise.hip's ``sampler_update``), which removes the reference's per-step
+rounding form per entry point is written out in csrc/elementwise.hip's ``sampler_update``; ``apad_cfg_dual_step`` for the three-branch step
+with separate audio and text guidance, ``sampler_plan(dual=True)`` + ``guidance_table``), which removes the reference's per-step
 host<->device sync inside ``scheduler.step``.  Every update here is LINEAR in (x, eps, previous data prediction m1, fresh noise z), so one row of six
 coefficients per step describes it (``SAMPLER_COLS``); ``sampler_plan`` tells the loop which kernel, table and per-sampler buffers
 a call needs.
@@ -57,6 +58,31 @@ def edit_start_index(num_inference_steps, strength):
     if run == 0:
         raise ValueError(f"strength={strength!r} leaves no step to run at num_inference_steps={n} (int(N * strength) == 0)")
     return n - run
+
+
+def guidance_table(audio, text, num_inference_steps, start=0):
+    """fp32 [N - start, 2], row i = (s_A, s_T) of step ``start + i``: the table apad_cfg_dual_step reads at ``*step_ptr``.  ``audio`` / ``text``:
+    a float (every step) or a sequence of exactly N floats over the FULL grid -- a per-step guidance schedule -- of which rows ``start:`` are
+    kept, like the coefficient table of an edit run.  Every value must be finite and >= 0 (rows before ``start`` are not used and not
+    checked); a ValueError names the argument."""
+    n, start = int(num_inference_steps), int(start)
+    if not 0 <= start < n:
+        raise ValueError(f"start={start!r} must lie in [0, {n})")
+    cols = []
+    for name, v in (("audio", audio), ("text", text)):
+        if isinstance(v, torch.Tensor):
+            v = v.detach().cpu().tolist()
+        try:
+            vals = [float(v)] * n if not hasattr(v, "__len__") else [float(x) for x in v]
+        except (TypeError, ValueError):
+            raise ValueError(f"{name}={v!r}: expected a float or a sequence of {n} floats") from None
+        if len(vals) != n:
+            raise ValueError(f"{name} holds {len(vals)} values; a per-step sequence needs exactly num_inference_steps = {n}")
+        vals = vals[start:]
+        if not all(math.isfinite(x) and x >= 0.0 for x in vals):
+            raise ValueError(f"{name}={v!r}: every guidance value must be finite and >= 0")
+        cols.append(vals)
+    return torch.tensor(cols, dtype=torch.float64).t().float().contiguous()
 
 
 class _EditSchedule:
@@ -152,16 +178,19 @@ class DDIMScheduler(_EditSchedule):
             rows.append([float(c_x), float(c_e), 0.0, float(std), 0.0, 0.0])
         return torch.tensor(rows, dtype=torch.float64)
 
-    def sampler_plan(self, eta=0.0, start=0, masked=False):
+    def sampler_plan(self, eta=0.0, start=0, masked=False, dual=False):
         """eta = 0 keeps the two-column table and apad_cfg_ddim_step; eta > 0 needs one fresh noise tensor per step.  ``start`` > 0: rows
         ``start:`` of the FULL table (the previous timestep stays t - num_train_timesteps // N).  ``masked``: always the six-column
-        table, plus ``keep``."""
+        table, plus ``keep``.  ``dual`` (the three-branch step, apad_cfg_dual_step): always the six-column table, ``sampler_rows(0.0)`` at
+        eta = 0, and "dual" in ``key``."""
         eta = float(eta)
         start, masked = self._check_start(start), bool(masked)
         key = ("DDIMScheduler", self.order, "leading", self.num_train_timesteps, self.steps_offset, self._betas, eta)
         if start or masked:
             key += (start, masked)
-        if eta == 0.0 and not masked:
+        if dual:
+            key += ("dual",)
+        if eta == 0.0 and not masked and not dual:
             return SamplerPlan(self.coef_table()[start:].contiguous(), True, False, False, key, None, start)
         return SamplerPlan(self.sampler_rows(eta)[start:].float().contiguous(), False, False, eta != 0.0, key,
                            self.keep_table(start) if masked else None, start)
@@ -240,13 +269,16 @@ class DPMSolverMultistepScheduler(_EditSchedule):
             rows.append([A + E * (1.0 + k) * d_x, E * (1.0 + k) * d_e, -E * k, 0.0, d_x, d_e])
         return torch.tensor(rows, dtype=torch.float64)
 
-    def sampler_plan(self, eta=0.0, start=0, masked=False):
+    def sampler_plan(self, eta=0.0, start=0, masked=False, dual=False):
         """``eta`` is ignored, as the reference's ``prepare_extra_step_kwargs`` drops it for a scheduler whose ``step`` has none.
-        ``start`` / ``masked``: see ``sampler_rows`` and ``DDIMScheduler.sampler_plan``."""
+        ``start`` / ``masked`` / ``dual``: see ``sampler_rows`` and ``DDIMScheduler.sampler_plan`` (the table is six-column already; ``dual``
+        only marks ``key``)."""
         start, masked = self._check_start(start), bool(masked)
         key = ("DPMSolverMultistepScheduler", self.solver_order, self.timestep_spacing, self.lower_order_final, self.num_train_timesteps,
                self.steps_offset, self._betas)
         if start or masked:
             key += (start, masked)
+        if dual:
+            key += ("dual",)
         return SamplerPlan(self.sampler_rows(start=start).float(), False, self.solver_order > 1, False, key,
                            self.keep_table(start) if masked else None, start)

@@ -49,13 +49,17 @@ def clip_latents(index, shape, seed=0):
 
 
 def run_sharded(clips, cfg, encode_audio, denoise, batch, rank=0, world=1, latent_shape=(8, 250, 16), seed=0, device="cpu",
-                text_embeddings=synthetic_text_embeddings, pass_clips=False):
+                text_embeddings=synthetic_text_embeddings, pass_clips=False, branches=2):
     """Denoise this rank's share of ``clips`` in batches of ``batch``; returns {clip index: latents} for the local clips.
 
     encode_audio(path, time_pooling, freq_pooling) -> (tokens [La, 768], uncond tokens [La, 768])   (front-end + AudioMAE)
     denoise(latents [b, ...], gen [2b, 8 + La, 768], t5 [2b, L, 1024], mask [2b, L], guidance_scale) -> latents [b, ...]
     Condition layout per batch (pipeline_audioldm2.py:934-956): unconditional half first; text tokens first, audio after.
-    ``pass_clips``: denoise also receives ``clips=`` -- the batch's clip records, padding included (an edit job looks up each clip's source)."""
+    ``pass_clips``: denoise also receives ``clips=`` -- the batch's clip records, padding included (an edit job looks up each clip's source).
+    ``branches=3`` (separate audio and text guidance, ``pipeline.denoise(audio_guidance_scale=)``): gen / t5 / mask carry 3b rows,
+    [negative text | zero-mel tokens ; negative text | audio tokens ; positive text | audio tokens]."""
+    if branches not in (2, 3):
+        raise ValueError(f"branches={branches!r}: 2 or 3")
     mine = [clips[i] for i in shard_clips(len(clips), rank, world)]
     out = {}
     audio_cache = {}
@@ -77,6 +81,10 @@ def run_sharded(clips, cfg, encode_audio, denoise, batch, rank=0, world=1, laten
         gen = torch.cat([torch.cat([dv(neg), dv(unc).to(dv(neg).dtype)], 1), torch.cat([dv(pos), dv(aud).to(dv(pos).dtype)], 1)], 0)
         t5 = torch.cat([dv(t5n), dv(t5p)], 0)
         mask = torch.cat([dv(mn), dv(mp)], 0)
+        if branches == 3:
+            b = len(chunk_p)
+            gen = torch.cat([gen[:b], torch.cat([dv(neg), dv(aud).to(dv(neg).dtype)], 1), gen[b:]], 0)
+            t5, mask = torch.cat([t5[:b], t5], 0), torch.cat([mask[:b], mask], 0)
         res = denoise(dv(lat), gen, t5, mask, cfg["guidance_scale"], **({"clips": chunk_p} if pass_clips else {}))
         for j, c in enumerate(chunk):
             out[c["index"]] = res[j].detach()

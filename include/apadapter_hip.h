@@ -28,6 +28,9 @@
  *                       _sampler_: any other scheduler the pipeline is built with (:158, :1025) -- DDIMScheduler.step with eta > 0,
  *                       DPMSolverMultistepScheduler.step (DPM-Solver++ 2M); _edit_: that step followed by the re-imposition of the kept
  *                       region.  Each entry point's rounding form is written out beside the kernel (sampler_update, edit_blend)
+ *   apad_cfg_dual_step  the same step on THREE branches with separate audio and text guidance scales read from a device table (no
+ *                       counterpart in the reference: InstructPix2Pix's two-scale guidance); its own kernel, the same
+ *                       sampler_update / edit_blend
  *   apad_step_advance   the loop counter of the captured step
  *   apad_edit_start     editing from a source clip (no working counterpart in the reference; diffusers' img2img / inpaint
  *                       conventions): posterior draw + add_noise at the start timestep
@@ -495,6 +498,19 @@ int apad_cfg_sampler_step(const void* eps2, float* latents, void* unet_in, float
 int apad_cfg_edit_step(const void* eps2, float* latents, void* unet_in, float* eps_out, float* history, const float* noise,
                        const float* coef, const float* keep, const float* x0, const float* z0, const float* mask, int32_t mask_batch,
                        int32_t C, const int32_t* step_ptr, int32_t n_steps, float guidance_scale, int32_t B, int64_t n, int32_t dtype,
+                       void* stream);
+/* Three branches per clip instead of two: eps3 [3B][n] (dtype) = [e_0 ; e_A ; e_AT] -- negative text + zero-mel audio tokens, negative text +
+   prompt audio tokens, positive text + prompt audio tokens -- and TWO guidance scales, read from device memory: guidance [n_steps][2] fp32,
+   row s = *step_ptr (clamped like coef) = (s_A, s_T):
+     eps = (dtype) fma(s_T, e_AT - e_A, fma(s_A, e_A - e_0, e_0))     (operands widened to fp32, each difference and each fma rounded to
+   fp32, one rounding to `dtype`; InstructPix2Pix's two-scale guidance).  With e_A == e_0 or e_AT == e_A this is the two-branch
+   expression exactly.  Everything after it is apad_cfg_edit_step: the same sampler update on the six-column coef table (deterministic DDIM
+   too: sampler_rows(0.0)), the same history / noise rules, and -- with a mask -- the same edit blend, operand rules, checks and 16-byte /
+   scalar forms (8 | B * n, every base 16-byte aligned, C == 8 with a mask).  A null mask is the plain sampler step.  Because the scales are
+   a table, a sweep over guidance values or a per-step guidance schedule replays one captured graph.  One launch, hipGraph-capturable. */
+int apad_cfg_dual_step(const void* eps3, float* latents, void* unet_in, float* eps_out, float* history, const float* noise,
+                       const float* coef, const float* guidance, const float* keep, const float* x0, const float* z0, const float* mask,
+                       int32_t mask_batch, int32_t C, const int32_t* step_ptr, int32_t n_steps, int32_t B, int64_t n, int32_t dtype,
                        void* stream);
 /* The buffers an edit run starts from, in the loop's layout ([rows = B * h * w][Lc], NHWC), in one pass:
      x0_out  = (mean + exp(0.5 * clamp(logvar, -30, 20)) * post_noise) * scale   fp32; moments [rows][2 * Lc] = (mean | logvar) in `dtype`

@@ -114,6 +114,8 @@ def main():
                                                         "(default: the audio prompt itself)")
     ap.add_argument("--strength", type=float, default=None, help="edit: in (0, 1], the share of the schedule that is run from the noised source")
     ap.add_argument("--edit-region", default=None, metavar="A:B", help="edit: regenerate seconds A..B only, keep the rest of the source")
+    ap.add_argument("--audio-guidance", type=float, default=None, metavar="S", help="separate audio and text guidance: three branches per clip, "
+                    "eps_0 + S (eps_A - eps_0) + guidance_scale (eps_AT - eps_A); without it the job is the two-branch one")
     ap.add_argument("--gpus", type=int, default=1, help="N > 1 without a launcher: this script starts its N ranks itself (one per GPU)")
     args = ap.parse_args()
 
@@ -158,18 +160,21 @@ def main():
                 moments[src] = pipe.vae.encode(mel[None]).latent_dist._m.reshape(H * 16, 16)
             return moments[src]
 
+    dual = {} if args.audio_guidance is None else {"audio_guidance_scale": args.audio_guidance}
+
     def denoise(lat, gen, t5, mask, gs, clips=None):
         if not editing:
-            return pipe.denoise(lat, gen, t5, mask, args.steps, gs)
+            return pipe.denoise(lat, gen, t5, mask, args.steps, gs, **dual)
         # z0 = the clip's seeded latents (what a generation run would start from); the posterior draw is seeded by the clip index too
         post = torch.stack([torch.randn(8, H, 16, generator=torch.Generator().manual_seed(7919 * c["index"] + 1)) for c in clips])
         src = A.EditSource(z0=lat, moments=torch.cat([source_moments(c["audio"]) for c in clips]), post_noise=post,
                            scale=pipe.vae.config.scaling_factor, mask=region_mask)
-        return pipe.denoise(None, gen, t5, mask, args.steps, gs, source=src, start=start)
+        return pipe.denoise(None, gen, t5, mask, args.steps, gs, source=src, start=start, **dual)
 
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    local_out = S.run_sharded(clips, cfg, encode_audio, denoise, args.batch, rank, world, latent_shape=(8, H, 16), device=dev, pass_clips=True)
+    local_out = S.run_sharded(clips, cfg, encode_audio, denoise, args.batch, rank, world, latent_shape=(8, H, 16), device=dev, pass_clips=True,
+                              **({"branches": 3} if dual else {}))
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     n_wavs = 0
@@ -190,7 +195,7 @@ def main():
         print(json.dumps({"task": args.task, "clips": len(clips), "world": world, "batch": args.batch, "steps": args.steps,
                           "sampler": args.sampler, "strength": args.strength, "edit_region": args.edit_region, "La": A.config.audio_tokens(cfg), "seconds_rank0": round(dt, 2), "clips_per_s": round(len(clips) / dt, 4),
                           "graph_captures": pipe.graph_captures, "graph_hits": pipe.graph_hits, "finite": finite,
-                          "wavs_written_rank0": n_wavs}))
+                          "wavs_written_rank0": n_wavs, **({"audio_guidance": args.audio_guidance} if dual else {})}))
         if args.out:
             torch.save({"latents": torch.stack([x.cpu() for x in allc]), "clips": clips}, args.out)
     if world > 1:
