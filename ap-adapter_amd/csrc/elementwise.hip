@@ -1,6 +1,6 @@
 // Small HBM-bound kernels of the path: AudioMAE token pooling, sinusoidal timestep embedding, fused
-// classifier-free-guidance + sampler update (one kernel behind apad_cfg_ddim_step / apad_cfg_sampler_step / apad_cfg_edit_step), its three-branch
-// twin (apad_cfg_dual_step) and the edit run's start, device-side step counter.
+// classifier-free-guidance + sampler update (one kernel of two or three guidance branches and one host launch path behind apad_cfg_ddim_step /
+// apad_cfg_sampler_step / apad_cfg_edit_step / apad_cfg_dual_step), the edit run's start, device-side step counter.
 #include "common.h"
 #include "f32_ops.h"
 
@@ -103,7 +103,6 @@ template <int DT, int V> __device__ __forceinline__ void st_elemv(uint8_t* p, in
 
 // The forms of the step kernel: the 16-byte form (8 elements per access), the scalar form, and apad_cfg_ddim_step's (scalar, two-column table)
 enum { STEP_DDIM = 0, STEP_SCALAR = 1, STEP_VEC = 8 };
-static_assert(STEP_VEC == 8 && STEP_SCALAR == 1, "LAUNCH_DT_V passes 8 / 1 as the form");
 
 // The sampler's update, linear in (x, eps, m1, z), with every rounding spelled out: contraction is off and each fused multiply-add is written
 // as one.  The forms are the ones hipcc once chose for three separately compiled kernels, read off their gfx950 code (v_fma / v_fmac = fused,
@@ -145,10 +144,28 @@ __device__ __forceinline__ float edit_blend(float m, float g, float kx, float kz
     return fmaf(m, g, (1.0f - m) * edit_known(kx, kz, x0, z0));
 }
 
-// The denoise step's last kernel, behind all three entry points: the guided noise, formed in the model dtype as the reference does,
-//   eps = (elem)fma(g, e_c - e_u, e_u)   (pipeline_audioldm2.py:1020-1025; one fp32 fma, one rounding to the model dtype),
+// The guided noise, formed in the model dtype as the reference does, one device function per branch count.
+// Two branches (eps = [e_u ; e_c], one scale, a kernel argument):
+//   eps = (elem)fma(g, e_c - e_u, e_u)   (pipeline_audioldm2.py:1020-1025; one fp32 fma, one rounding to the model dtype)
 // (f16 only, and the one fold still the compiler's: the scalar forms round the exact fma to f16 once, v_fma_mixlo_f16, the 16-byte form rounds
-// it to fp32 first, v_cvt_pk_f16_f32 -- as before the merge, and pinned by the recorded bits)
+// it to fp32 first, v_cvt_pk_f16_f32 -- as before the kernels were merged, and pinned by the recorded bits)
+template <int DT> __device__ __forceinline__ float guided_noise(float gs, float, const float (&e)[2]) {
+    return (float)(typename ET<DT>::elem)fmaf(gs, e[1] - e[0], e[0]);
+}
+// Three branches (eps = [e_0 ; e_A ; e_AT]: no condition / audio prompt / audio prompt + text; InstructPix2Pix's two scales):
+//   eps = (elem)fma(s_T, e_AT - e_A, fma(s_A, e_A - e_0, e_0))
+// -- each difference and each fma rounded to fp32, one rounding to the model dtype.  The f16 rounding is pinned here (the fp32 fma first, in
+// every form): the guidance values are arbitrary floats, and folding the store's rounding into the fma would move a rounding tie by a whole f16
+// ulp against the written formula.
+template <int DT> __device__ __forceinline__ float guided_noise(float s_a, float s_t, const float (&e)[3]) {
+#pragma clang fp contract(off)
+    float g = fmaf(s_t, e[2] - e[1], fmaf(s_a, e[1] - e[0], e[0]));
+    if constexpr (DT == APAD_F16) asm volatile("" : "+v"(g));  // (the fp32 value exists before the f16 rounding: see above)
+    return (float)(typename ET<DT>::elem)g;
+}
+
+// The denoise step's last kernel, behind all four entry points: the guided noise of NB = 2 or 3 branches (guided_noise; NB = 2 guides by the
+// argument gs, NB = 3 by (s_A, s_T) = guidance[2 * step], apad_cfg_dual_step),
 // then a sampler whose update is linear in (x, eps, m1, z) -- row r = coef + 6 * step (scheduler.py SAMPLER_COLS),
 //   x' = r0 x + r1 eps + r2 m1 + r3 z[step],   m0 = r4 x + r5 eps -> hist (the next step's m1),   roundings as in sampler_update;
 // DPM-Solver++ 2M: r3 = 0;  DDIM eta > 0: r2 = 0, no hist.  m1 / z are not read on a step whose coefficient is 0 (wave-uniform) -- then the
@@ -159,11 +176,12 @@ __device__ __forceinline__ float edit_blend(float m, float g, float kx, float kz
 // one pixel and takes one mask value.  The data prediction m0 is formed from the pre-blend x and eps.  A null mask is m = 1 everywhere: the
 // plain sampler step (apad_cfg_sampler_step).  STEP_DDIM (apad_cfg_ddim_step, deterministic DDIM) reads row coef + 2 * step = (c_x, c_e) of a
 // table whose length the entry point is not told (no clamp), and has neither hist, noise nor mask.
-template <int DT, int FORM>
-__global__ __launch_bounds__(256) void cfg_step_kernel(const uint8_t* eps2, float* latents, uint8_t* unet_in, float* eps_out, float* hist,
+template <int DT, int FORM, int NB>
+__global__ __launch_bounds__(256) void cfg_step_kernel(const uint8_t* eps, float* latents, uint8_t* unet_in, float* eps_out, float* hist,
                                                        const float* noise, const float* coef, const float* keep, const float* x0, const float* z0,
                                                        const float* mask, int mask_per_clip, int C, int64_t n, const int32_t* step_ptr, int n_steps,
-                                                       float gs, int64_t total) {
+                                                       float gs, int64_t total, const float* guidance) {
+    static_assert(NB == 2 || (NB == 3 && FORM != STEP_DDIM), "the two-column table has no three-branch form");
     constexpr int V = FORM == STEP_VEC ? 8 : 1;
     constexpr bool ddim = FORM == STEP_DDIM;
     if constexpr (ddim) hist = nullptr, noise = nullptr, mask = nullptr;
@@ -171,14 +189,15 @@ __global__ __launch_bounds__(256) void cfg_step_kernel(const uint8_t* eps2, floa
     if constexpr (!ddim) step = step < 0 ? 0 : (step >= n_steps ? n_steps - 1 : step);  // the tables and the noise buffer have n_steps rows
     const float* r = coef + (ddim ? 2 : 6) * step;
     const float c_x = r[0], c_e = r[1], c_m = ddim ? 0.f : r[2], c_z = ddim ? 0.f : r[3], d_x = ddim ? 0.f : r[4], d_e = ddim ? 0.f : r[5];
+    const float s_a = NB == 3 ? guidance[2 * step] : gs, s_t = NB == 3 ? guidance[2 * step + 1] : 0.f;
     const float kx = mask ? keep[2 * step] : 0.f, kz = mask ? keep[2 * step + 1] : 0.f;
     const bool use_m1 = hist && c_m != 0.f, use_z = noise && c_z != 0.f;
     const float* z = noise + (use_z ? (int64_t)step * total : 0);
     const int64_t npix = n / C;  // pixels per clip
     for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * V; i < total; i += (int64_t)gridDim.x * 256 * V) {
-        float eu[V], ec[V], x[V], m1[V], zz[V], e[V], m0[V];
-        ld_elemv<DT, V>(eps2, i, eu);
-        ld_elemv<DT, V>(eps2, total + i, ec);
+        float eb[NB][V], x[V], m1[V], zz[V], e[V], m0[V];
+#pragma unroll
+        for (int b = 0; b < NB; ++b) ld_elemv<DT, V>(eps, b * total + i, eb[b]);
         ld_f32v<V>(latents, i, x);
 #pragma unroll
         for (int j = 0; j < V; ++j) m1[j] = zz[j] = 0.f;
@@ -186,65 +205,10 @@ __global__ __launch_bounds__(256) void cfg_step_kernel(const uint8_t* eps2, floa
         if (use_z) ld_f32v<V>(z, i, zz);
 #pragma unroll
         for (int j = 0; j < V; ++j) {
-            e[j] = (float)(typename ET<DT>::elem)fmaf(gs, ec[j] - eu[j], eu[j]);
-            float xn;
-            sampler_update<DT, FORM>(c_x, c_e, c_m, c_z, d_x, d_e, x[j], e[j], m1[j], zz[j], xn, m0[j]);
-            x[j] = xn;
-        }
-        if (mask) {
-            const int64_t pix = V == 8 ? (i >> 3) : i / C;  // over the whole batch: clip * npix + pixel
-            const float m = mask[mask_per_clip ? pix : pix % npix];
-            float a[V], b[V];
-            ld_f32v<V>(x0, i, a);
-            ld_f32v<V>(z0, i, b);
+            float ej[NB];
 #pragma unroll
-            for (int j = 0; j < V; ++j) x[j] = edit_blend(m, x[j], kx, kz, a[j], b[j]);
-        }
-        st_f32v<V>(latents, i, x);
-        st_elemv<DT, V>(unet_in, i, x);
-        if (hist) st_f32v<V>(hist, i, m0);
-        if (eps_out) st_f32v<V>(eps_out, i, e);
-    }
-}
-
-// The three-branch step (apad_cfg_dual_step): eps3 = [e_0 ; e_A ; e_AT] (no condition / audio prompt / audio prompt + text), the guided noise
-//   eps = (elem)fma(s_T, e_AT - e_A, fma(s_A, e_A - e_0, e_0)),   (s_A, s_T) = guidance[2 * step]   (InstructPix2Pix's two scales)
-// -- each difference and each fma rounded to fp32, one rounding to the model dtype -- then cfg_step_kernel's sampler update and edit blend, by the
-// same sampler_update / edit_blend, always on the six-column table.  A kernel of its own: cfg_step_kernel's instantiations keep their device code.
-// The f16 rounding is pinned here (the fp32 fma first, in every form): the guidance values are arbitrary floats, and folding the store's rounding
-// into the fma would move a rounding tie by a whole f16 ulp against the written formula.
-template <int DT, int FORM>
-__global__ __launch_bounds__(256) void cfg_dual_step_kernel(const uint8_t* eps3, float* latents, uint8_t* unet_in, float* eps_out, float* hist,
-                                                            const float* noise, const float* coef, const float* guidance, const float* keep,
-                                                            const float* x0, const float* z0, const float* mask, int mask_per_clip, int C, int64_t n,
-                                                            const int32_t* step_ptr, int n_steps, int64_t total) {
-#pragma clang fp contract(off)
-    static_assert(FORM == STEP_VEC || FORM == STEP_SCALAR, "the two-column table has no three-branch form");
-    constexpr int V = FORM == STEP_VEC ? 8 : 1;
-    int step = step_ptr ? *step_ptr : 0;
-    step = step < 0 ? 0 : (step >= n_steps ? n_steps - 1 : step);  // the three tables and the noise buffer have n_steps rows
-    const float* r = coef + 6 * step;
-    const float c_x = r[0], c_e = r[1], c_m = r[2], c_z = r[3], d_x = r[4], d_e = r[5];
-    const float s_a = guidance[2 * step], s_t = guidance[2 * step + 1];
-    const float kx = mask ? keep[2 * step] : 0.f, kz = mask ? keep[2 * step + 1] : 0.f;
-    const bool use_m1 = hist && c_m != 0.f, use_z = noise && c_z != 0.f;
-    const float* z = noise + (use_z ? (int64_t)step * total : 0);
-    const int64_t npix = n / C;  // pixels per clip
-    for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * V; i < total; i += (int64_t)gridDim.x * 256 * V) {
-        float e0[V], ea[V], eat[V], x[V], m1[V], zz[V], e[V], m0[V];
-        ld_elemv<DT, V>(eps3, i, e0);
-        ld_elemv<DT, V>(eps3, total + i, ea);
-        ld_elemv<DT, V>(eps3, 2 * total + i, eat);
-        ld_f32v<V>(latents, i, x);
-#pragma unroll
-        for (int j = 0; j < V; ++j) m1[j] = zz[j] = 0.f;
-        if (use_m1) ld_f32v<V>(hist, i, m1);
-        if (use_z) ld_f32v<V>(z, i, zz);
-#pragma unroll
-        for (int j = 0; j < V; ++j) {
-            float g = fmaf(s_t, eat[j] - ea[j], fmaf(s_a, ea[j] - e0[j], e0[j]));
-            if constexpr (DT == APAD_F16) asm volatile("" : "+v"(g));  // (the fp32 value exists before the f16 rounding: see above)
-            e[j] = (float)(typename ET<DT>::elem)g;
+            for (int b = 0; b < NB; ++b) ej[b] = eb[b][j];
+            e[j] = guided_noise<DT>(s_a, s_t, ej);
             float xn;
             sampler_update<DT, FORM>(c_x, c_e, c_m, c_z, d_x, d_e, x[j], e[j], m1[j], zz[j], xn, m0[j]);
             x[j] = xn;
@@ -418,94 +382,104 @@ extern "C" int apad_timestep_embedding(const float* t, void* out, int32_t n, int
     return apad_check_launch("apad_timestep_embedding");
 }
 
+namespace {
+
+// what a step entry point hands to step_launch: its own arguments, null / 0 where it has none
+struct StepOperands {
+    const void* eps;  // [branches * B][n] in the model dtype
+    float* latents;
+    void* unet_in;
+    float *eps_out, *history;
+    const float *noise, *coef, *guidance, *keep, *x0, *z0, *mask;
+    int mask_batch, C;
+    const int32_t* step_ptr;
+    int n_steps;
+    float gs;
+    int B;
+    int64_t n;
+    int dtype;
+    void* stream;
+    int branches;  // 2, or 3: the guidance table instead of gs
+    bool ddim;     // apad_cfg_ddim_step: two-column table of a length it is not told, scalar form only
+};
+
+using step_kernel_t = decltype(&cfg_step_kernel<APAD_BF16, STEP_VEC, 2>);
+template <int DT> step_kernel_t step_kernel(int form, int branches) {
+    if (branches == 3) return form == STEP_VEC ? cfg_step_kernel<DT, STEP_VEC, 3> : cfg_step_kernel<DT, STEP_SCALAR, 3>;
+    return form == STEP_VEC ? cfg_step_kernel<DT, STEP_VEC, 2> : form == STEP_SCALAR ? cfg_step_kernel<DT, STEP_SCALAR, 2> : cfg_step_kernel<DT, STEP_DDIM, 2>;
+}
+
+// Every check, the choice of form, the grid and the launch of the four step entry points; ``fn`` prefixes the messages.
+int step_launch(const char* fn, const StepOperands& a) {
+    APAD_CHECK(a.eps && a.latents && a.unet_in && a.coef, "%s: null operand", fn);
+    APAD_CHECK(a.branches == 2 || a.guidance, "%s: null guidance table", fn);
+    APAD_CHECK(a.dtype == APAD_BF16 || a.dtype == APAD_F16 || a.dtype == APAD_F32, "%s: dtype %d not supported", fn, a.dtype);
+    APAD_CHECK(a.B > 0 && a.n > 0 && (a.ddim || a.n_steps > 0), "%s: empty problem", fn);
+    if (a.mask) {
+        APAD_CHECK(a.keep && a.x0 && a.z0, "%s: a mask needs the keep table, x0 and z0 (null operand)", fn);
+        APAD_CHECK(a.mask_batch == 1 || a.mask_batch == a.B, "%s: mask_batch %d must be 1 or B = %d", fn, a.mask_batch, a.B);
+        APAD_CHECK(a.C > 0 && a.n % a.C == 0, "%s: n = %lld is not a multiple of C = %d", fn, (long long)a.n, a.C);
+    }
+    const int64_t total = (int64_t)a.B * a.n;
+    // 16-byte accesses need every non-null base 16-byte aligned and 8 | total (then every further branch and every noise row is aligned too), and
+    // with a mask C == 8, which makes one 8-element vector one pixel.  apad_cfg_ddim_step launches the scalar form only: the 16-byte form rounds
+    // differently (sampler_update)
+    const uintptr_t bases = (uintptr_t)a.eps | (uintptr_t)a.latents | (uintptr_t)a.unet_in | (uintptr_t)a.eps_out | (uintptr_t)a.history |
+                            (uintptr_t)a.noise | (uintptr_t)a.x0 | (uintptr_t)a.z0;
+    const bool vec = !a.ddim && total % 8 == 0 && bases % 16 == 0 && (!a.mask || a.C == 8);
+    int64_t blocks = ((vec ? total / 8 : total) + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    const int form = a.ddim ? STEP_DDIM : vec ? STEP_VEC : STEP_SCALAR;
+    const step_kernel_t kern = a.dtype == APAD_BF16  ? step_kernel<APAD_BF16>(form, a.branches)
+                               : a.dtype == APAD_F32 ? step_kernel<APAD_F32>(form, a.branches)
+                                                     : step_kernel<APAD_F16>(form, a.branches);
+    const int per_clip = a.mask_batch == a.B && a.B > 1;
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)a.stream, (const uint8_t*)a.eps, a.latents, (uint8_t*)a.unet_in, a.eps_out,
+                       a.history, a.noise, a.coef, a.keep, a.x0, a.z0, a.mask, per_clip, a.mask ? a.C : 1, a.n, a.step_ptr, a.n_steps, a.gs, total,
+                       a.guidance);
+    return apad_check_launch(fn);
+}
+
+}  // namespace
+
 extern "C" int apad_cfg_ddim_step(const void* eps2, float* latents, void* unet_in, float* eps_out, const float* coef,
                                   const int32_t* step_ptr, float guidance_scale, int32_t B, int64_t n, int32_t dtype,
                                   void* stream) {
-    APAD_CHECK(eps2 && latents && unet_in && coef, "apad_cfg_ddim_step: null operand");
-    APAD_CHECK(dtype == APAD_BF16 || dtype == APAD_F16 || dtype == APAD_F32, "apad_cfg_ddim_step: dtype %d not supported", dtype);
-    APAD_CHECK(B > 0 && n > 0, "apad_cfg_ddim_step: empty problem");
-    const int64_t total = (int64_t)B * n;
-    int64_t blocks = (total + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    hipStream_t s = (hipStream_t)stream;
-    // the scalar launch only: the 16-byte form rounds differently (sampler_update)
-    LAUNCH_DT_F(cfg_step_kernel, STEP_DDIM, dim3((unsigned)blocks), (const uint8_t*)eps2, latents, (uint8_t*)unet_in, eps_out, nullptr, nullptr, coef,
-                nullptr, nullptr, nullptr, nullptr, 0, 1, n, step_ptr, 0, guidance_scale, total);
-    return apad_check_launch("apad_cfg_ddim_step");
+    StepOperands a = {};
+    a.eps = eps2, a.latents = latents, a.unet_in = unet_in, a.eps_out = eps_out, a.coef = coef, a.step_ptr = step_ptr, a.gs = guidance_scale;
+    a.B = B, a.n = n, a.dtype = dtype, a.stream = stream, a.branches = 2, a.ddim = true;
+    return step_launch("apad_cfg_ddim_step", a);
 }
 
 extern "C" int apad_cfg_sampler_step(const void* eps2, float* latents, void* unet_in, float* eps_out, float* history, const float* noise,
                                      const float* coef, const int32_t* step_ptr, int32_t n_steps, float guidance_scale, int32_t B, int64_t n,
                                      int32_t dtype, void* stream) {
-    APAD_CHECK(eps2 && latents && unet_in && coef, "apad_cfg_sampler_step: null operand");
-    APAD_CHECK(dtype == APAD_BF16 || dtype == APAD_F16 || dtype == APAD_F32, "apad_cfg_sampler_step: dtype %d not supported", dtype);
-    APAD_CHECK(B > 0 && n > 0 && n_steps > 0, "apad_cfg_sampler_step: empty problem");
-    const int64_t total = (int64_t)B * n;
-    // 16-byte accesses need every base 16-byte aligned and 8 | total (then the second CFG half and every noise row are aligned too)
-    const uintptr_t bases = (uintptr_t)eps2 | (uintptr_t)latents | (uintptr_t)unet_in | (uintptr_t)eps_out | (uintptr_t)history | (uintptr_t)noise;
-    const bool vec = total % 8 == 0 && bases % 16 == 0;
-    int64_t blocks = ((vec ? total / 8 : total) + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    hipStream_t s = (hipStream_t)stream;
-    // the edit step's kernel with a null mask: the plain sampler step
-    LAUNCH_DT_V(cfg_step_kernel, vec, dim3((unsigned)blocks), (const uint8_t*)eps2, latents, (uint8_t*)unet_in, eps_out, history, noise, coef, nullptr,
-                nullptr, nullptr, nullptr, 0, 1, n, step_ptr, n_steps, guidance_scale, total);
-    return apad_check_launch("apad_cfg_sampler_step");
+    StepOperands a = {};
+    a.eps = eps2, a.latents = latents, a.unet_in = unet_in, a.eps_out = eps_out, a.history = history, a.noise = noise, a.coef = coef;
+    a.step_ptr = step_ptr, a.n_steps = n_steps, a.gs = guidance_scale, a.B = B, a.n = n, a.dtype = dtype, a.stream = stream, a.branches = 2;
+    return step_launch("apad_cfg_sampler_step", a);
 }
 
 extern "C" int apad_cfg_edit_step(const void* eps2, float* latents, void* unet_in, float* eps_out, float* history, const float* noise,
                                   const float* coef, const float* keep, const float* x0, const float* z0, const float* mask, int32_t mask_batch,
                                   int32_t C, const int32_t* step_ptr, int32_t n_steps, float guidance_scale, int32_t B, int64_t n, int32_t dtype,
                                   void* stream) {
-    APAD_CHECK(eps2 && latents && unet_in && coef, "apad_cfg_edit_step: null operand");
-    APAD_CHECK(dtype == APAD_BF16 || dtype == APAD_F16 || dtype == APAD_F32, "apad_cfg_edit_step: dtype %d not supported", dtype);
-    APAD_CHECK(B > 0 && n > 0 && n_steps > 0, "apad_cfg_edit_step: empty problem");
-    if (mask) {
-        APAD_CHECK(keep && x0 && z0, "apad_cfg_edit_step: a mask needs the keep table, x0 and z0 (null operand)");
-        APAD_CHECK(mask_batch == 1 || mask_batch == B, "apad_cfg_edit_step: mask_batch %d must be 1 or B = %d", mask_batch, B);
-        APAD_CHECK(C > 0 && n % C == 0, "apad_cfg_edit_step: n = %lld is not a multiple of C = %d", (long long)n, C);
-    }
-    const int64_t total = (int64_t)B * n;
-    // cfg_sampler_step's rule (every base 16-byte aligned, 8 | total) plus C == 8, which makes one 8-element vector one pixel
-    const uintptr_t bases = (uintptr_t)eps2 | (uintptr_t)latents | (uintptr_t)unet_in | (uintptr_t)eps_out | (uintptr_t)history | (uintptr_t)noise |
-                            (uintptr_t)x0 | (uintptr_t)z0;
-    const bool vec = total % 8 == 0 && bases % 16 == 0 && (!mask || C == 8);
-    int64_t blocks = ((vec ? total / 8 : total) + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    hipStream_t s = (hipStream_t)stream;
-    const int per_clip = mask_batch == B && B > 1;
-    const int Cc = mask ? C : 1;
-    LAUNCH_DT_V(cfg_step_kernel, vec, dim3((unsigned)blocks), (const uint8_t*)eps2, latents, (uint8_t*)unet_in, eps_out, history, noise, coef, keep, x0,
-                z0, mask, per_clip, Cc, n, step_ptr, n_steps, guidance_scale, total);
-    return apad_check_launch("apad_cfg_edit_step");
+    StepOperands a = {};
+    a.eps = eps2, a.latents = latents, a.unet_in = unet_in, a.eps_out = eps_out, a.history = history, a.noise = noise, a.coef = coef;
+    a.keep = keep, a.x0 = x0, a.z0 = z0, a.mask = mask, a.mask_batch = mask_batch, a.C = C;
+    a.step_ptr = step_ptr, a.n_steps = n_steps, a.gs = guidance_scale, a.B = B, a.n = n, a.dtype = dtype, a.stream = stream, a.branches = 2;
+    return step_launch("apad_cfg_edit_step", a);
 }
 
 extern "C" int apad_cfg_dual_step(const void* eps3, float* latents, void* unet_in, float* eps_out, float* history, const float* noise,
                                   const float* coef, const float* guidance, const float* keep, const float* x0, const float* z0, const float* mask,
                                   int32_t mask_batch, int32_t C, const int32_t* step_ptr, int32_t n_steps, int32_t B, int64_t n, int32_t dtype,
                                   void* stream) {
-    APAD_CHECK(eps3 && latents && unet_in && coef, "apad_cfg_dual_step: null operand");
-    APAD_CHECK(guidance, "apad_cfg_dual_step: null guidance table");
-    APAD_CHECK(dtype == APAD_BF16 || dtype == APAD_F16 || dtype == APAD_F32, "apad_cfg_dual_step: dtype %d not supported", dtype);
-    APAD_CHECK(B > 0 && n > 0 && n_steps > 0, "apad_cfg_dual_step: empty problem");
-    if (mask) {
-        APAD_CHECK(keep && x0 && z0, "apad_cfg_dual_step: a mask needs the keep table, x0 and z0 (null operand)");
-        APAD_CHECK(mask_batch == 1 || mask_batch == B, "apad_cfg_dual_step: mask_batch %d must be 1 or B = %d", mask_batch, B);
-        APAD_CHECK(C > 0 && n % C == 0, "apad_cfg_dual_step: n = %lld is not a multiple of C = %d", (long long)n, C);
-    }
-    const int64_t total = (int64_t)B * n;
-    // apad_cfg_edit_step's rule (every base 16-byte aligned, 8 | total, C == 8 with a mask): then the second and third branch are aligned too
-    const uintptr_t bases = (uintptr_t)eps3 | (uintptr_t)latents | (uintptr_t)unet_in | (uintptr_t)eps_out | (uintptr_t)history | (uintptr_t)noise |
-                            (uintptr_t)x0 | (uintptr_t)z0;
-    const bool vec = total % 8 == 0 && bases % 16 == 0 && (!mask || C == 8);
-    int64_t blocks = ((vec ? total / 8 : total) + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    hipStream_t s = (hipStream_t)stream;
-    const int per_clip = mask_batch == B && B > 1;
-    const int Cc = mask ? C : 1;
-    LAUNCH_DT_V(cfg_dual_step_kernel, vec, dim3((unsigned)blocks), (const uint8_t*)eps3, latents, (uint8_t*)unet_in, eps_out, history, noise, coef,
-                guidance, keep, x0, z0, mask, per_clip, Cc, n, step_ptr, n_steps, total);
-    return apad_check_launch("apad_cfg_dual_step");
+    StepOperands a = {};
+    a.eps = eps3, a.latents = latents, a.unet_in = unet_in, a.eps_out = eps_out, a.history = history, a.noise = noise, a.coef = coef;
+    a.guidance = guidance, a.keep = keep, a.x0 = x0, a.z0 = z0, a.mask = mask, a.mask_batch = mask_batch, a.C = C;
+    a.step_ptr = step_ptr, a.n_steps = n_steps, a.B = B, a.n = n, a.dtype = dtype, a.stream = stream, a.branches = 3;
+    return step_launch("apad_cfg_dual_step", a);
 }
 
 extern "C" int apad_edit_start(const void* moments, const float* post_noise, const float* z0, float* x0_out, float* latents, void* unet_in, float a,

@@ -1154,68 +1154,26 @@ def cfg_ddim_step(eps2, latents, unet_in, coef, step_ptr, guidance_scale, eps_ou
                                        _stream()), "apad_cfg_ddim_step")
 
 
-def _step_operands(fn, eps2, latents, unet_in, coef, eps_out, history, noise, x0=None, z0=None, keep=None):
-    """the table, dtype and numel checks of cfg_sampler_step / cfg_edit_step (``fn`` prefixes every message).  Returns (steps, B, n)."""
+def _cfg_step(fn, branches, eps, latents, unet_in, coef, step_ptr, eps_out, history, noise, keep=None, x0=None, z0=None, mask=None, channels=8):
+    """the checks behind cfg_sampler_step / cfg_edit_step / cfg_dual_step (``fn`` prefixes every message): the six-column table, ``branches``
+    (2 or 3) branches of eps in unet_in's dtype, the fp32 buffers' sizes and the mask's shape.  Returns the entry points' common arguments:
+    (eps .. coef), (keep .. channels), (step_ptr, steps), (B, n, dtype, stream)."""
     _req(latents, fn + ".latents", torch.float32)
+    if branches == 3 and (eps.numel() != 3 * latents.numel() or (eps.dim() > 1 and eps.shape[0] != 3 * latents.shape[0])):
+        raise RuntimeError(f"{fn}: eps3 must hold three branches [3B, n] of latents [B, n] = {tuple(latents.shape)}, got {tuple(eps.shape)}")
     _req(coef, fn + ".coef", torch.float32)
     if coef.dim() != 2 or coef.shape[1] != 6 or not coef.is_contiguous():
         raise RuntimeError(f"{fn}.coef: expected a contiguous [steps, 6] table, got {tuple(coef.shape)}")
     steps = coef.shape[0]
     B = latents.shape[0]
     n = latents.numel() // B
-    if eps2.dtype != unet_in.dtype or eps2.numel() != 2 * latents.numel() or unet_in.numel() != latents.numel():
-        raise RuntimeError(f"{fn}: eps2 [2B, n] and unet_in [B, n] must share the model dtype and match latents [B, n]")
+    if eps.dtype != unet_in.dtype or eps.numel() != branches * latents.numel() or unet_in.numel() != latents.numel():
+        raise RuntimeError(f"{fn}: eps{branches} [{branches}B, n] and unet_in [B, n] must share the model dtype and match latents [B, n]")
     numel = latents.numel()
     for t, name, want in ((eps_out, "eps_out", numel), (history, "history", numel), (noise, "noise", steps * numel), (x0, "x0", numel),
                           (z0, "z0", numel), (keep, "keep", 2 * steps)):
         if t is not None and (_req(t, f"{fn}.{name}", torch.float32).numel() != want or not t.is_contiguous()):
             raise RuntimeError(f"{fn}.{name}: expected {want} contiguous fp32 values, got {tuple(t.shape)}")
-    return steps, B, n
-
-
-def cfg_sampler_step(eps2, latents, unet_in, coef, step_ptr, guidance_scale, eps_out=None, history=None, noise=None):
-    """cfg_ddim_step for a sampler with a six-column table (scheduler.SAMPLER_COLS): coef fp32 [steps, 6]; history fp32 like latents
-    (read as m1, overwritten with this step's data prediction); noise fp32 [steps, B, n...] (row *step_ptr is added, scaled)."""
-    steps, B, n = _step_operands("cfg_sampler_step", eps2, latents, unet_in, coef, eps_out, history, noise)
-    L.check(L.lib().apad_cfg_sampler_step(eps2.data_ptr(), latents.data_ptr(), unet_in.data_ptr(), _ptr(eps_out), _ptr(history), _ptr(noise),
-                                          coef.data_ptr(), _ptr(step_ptr), steps, float(guidance_scale), B, n, _DT[eps2.dtype], _stream()),
-            "apad_cfg_sampler_step")
-
-
-def cfg_edit_step(eps2, latents, unet_in, coef, keep, step_ptr, guidance_scale, x0, z0, mask, channels=8, eps_out=None, history=None, noise=None):
-    """cfg_sampler_step followed by the edit blend: keep fp32 [steps, 2] (scheduler ``SamplerPlan.keep``), x0 / z0 fp32 like latents (the
-    source latents and the noise that built the start), mask fp32 [1 or B, n / channels] with 1 = regenerate and 0 = keep;
-    latents [B, n...] are NHWC with ``channels`` fastest.  mask = None is cfg_sampler_step."""
-    steps, B, n = _step_operands("cfg_edit_step", eps2, latents, unet_in, coef, eps_out, history, noise, x0, z0, keep)
-    mask_batch = 0
-    if mask is not None:
-        _req(mask, "cfg_edit_step.mask", torch.float32)
-        channels = int(channels)
-        # (n % channels != 0 and a mask batch other than 1 or B are the entry point's own checks)
-        if mask.dim() != 2 or not mask.is_contiguous() or (channels > 0 and n % channels == 0 and mask.shape[1] != n // channels):
-            raise RuntimeError(f"cfg_edit_step.mask: expected a contiguous [1 or B, n / channels] table with n = {n}, channels = {channels}, "
-                               f"got {tuple(mask.shape)}")
-        mask_batch = mask.shape[0]  # 1 or B: the entry point checks it
-    L.check(L.lib().apad_cfg_edit_step(eps2.data_ptr(), latents.data_ptr(), unet_in.data_ptr(), _ptr(eps_out), _ptr(history), _ptr(noise),
-                                       coef.data_ptr(), _ptr(keep), _ptr(x0), _ptr(z0), _ptr(mask), mask_batch, int(channels), _ptr(step_ptr), steps,
-                                       float(guidance_scale), B, n, _DT[eps2.dtype], _stream()), "apad_cfg_edit_step")
-
-
-def cfg_dual_step(eps3, latents, unet_in, coef, guidance, step_ptr, eps_out=None, history=None, noise=None, keep=None, x0=None, z0=None, mask=None,
-                  channels=8):
-    """the three-branch step: eps3 [3B, n...] = [no condition ; audio prompt ; audio prompt + text], guidance fp32 [steps, 2] = (s_A, s_T) per
-    step, read on the device at row *step_ptr: eps = fma(s_T, e_AT - e_A, fma(s_A, e_A - e_0, e_0)), then cfg_edit_step's sampler update and
-    (with ``mask``) edit blend.  coef is always the six-column table.  mask = None is the plain sampler step."""
-    fn = "cfg_dual_step"
-    _req(latents, fn + ".latents", torch.float32)
-    if eps3.numel() != 3 * latents.numel() or (eps3.dim() > 1 and eps3.shape[0] != 3 * latents.shape[0]):
-        raise RuntimeError(f"{fn}: eps3 must hold three branches [3B, n] of latents [B, n] = {tuple(latents.shape)}, got {tuple(eps3.shape)}")
-    steps, B, n = _step_operands(fn, eps3[: 2 * latents.shape[0]], latents, unet_in, coef, eps_out, history, noise, x0, z0, keep)
-    _req(guidance, fn + ".guidance", torch.float32)
-    if guidance.dim() != 2 or tuple(guidance.shape) != (steps, 2) or not guidance.is_contiguous():
-        raise RuntimeError(f"{fn}.guidance: expected a contiguous fp32 [{steps}, 2] table of (s_A, s_T), got {tuple(guidance.shape)}")
-    if not eps3.is_contiguous():
-        raise RuntimeError(f"{fn}: eps3 must be contiguous")
     mask_batch = 0
     if mask is not None:
         _req(mask, fn + ".mask", torch.float32)
@@ -1224,10 +1182,39 @@ def cfg_dual_step(eps3, latents, unet_in, coef, guidance, step_ptr, eps_out=None
         if mask.dim() != 2 or not mask.is_contiguous() or (channels > 0 and n % channels == 0 and mask.shape[1] != n // channels):
             raise RuntimeError(f"{fn}.mask: expected a contiguous [1 or B, n / channels] table with n = {n}, channels = {channels}, "
                                f"got {tuple(mask.shape)}")
-        mask_batch = mask.shape[0]
-    L.check(L.lib().apad_cfg_dual_step(eps3.data_ptr(), latents.data_ptr(), unet_in.data_ptr(), _ptr(eps_out), _ptr(history), _ptr(noise),
-                                       coef.data_ptr(), guidance.data_ptr(), _ptr(keep), _ptr(x0), _ptr(z0), _ptr(mask), mask_batch, int(channels),
-                                       _ptr(step_ptr), steps, B, n, _DT[eps3.dtype], _stream()), "apad_cfg_dual_step")
+        mask_batch = mask.shape[0]  # 1 or B: the entry point checks it
+    return ((eps.data_ptr(), latents.data_ptr(), unet_in.data_ptr(), _ptr(eps_out), _ptr(history), _ptr(noise), coef.data_ptr()),
+            (_ptr(keep), _ptr(x0), _ptr(z0), _ptr(mask), mask_batch, int(channels)), (_ptr(step_ptr), steps), (B, n, _DT[eps.dtype], _stream()))
+
+
+def cfg_sampler_step(eps2, latents, unet_in, coef, step_ptr, guidance_scale, eps_out=None, history=None, noise=None):
+    """cfg_ddim_step for a sampler with a six-column table (scheduler.SAMPLER_COLS): coef fp32 [steps, 6]; history fp32 like latents
+    (read as m1, overwritten with this step's data prediction); noise fp32 [steps, B, n...] (row *step_ptr is added, scaled)."""
+    bufs, _, step, geom = _cfg_step("cfg_sampler_step", 2, eps2, latents, unet_in, coef, step_ptr, eps_out, history, noise)
+    L.check(L.lib().apad_cfg_sampler_step(*bufs, *step, float(guidance_scale), *geom), "apad_cfg_sampler_step")
+
+
+def cfg_edit_step(eps2, latents, unet_in, coef, keep, step_ptr, guidance_scale, x0, z0, mask, channels=8, eps_out=None, history=None, noise=None):
+    """cfg_sampler_step followed by the edit blend: keep fp32 [steps, 2] (scheduler ``SamplerPlan.keep``), x0 / z0 fp32 like latents (the
+    source latents and the noise that built the start), mask fp32 [1 or B, n / channels] with 1 = regenerate and 0 = keep;
+    latents [B, n...] are NHWC with ``channels`` fastest.  mask = None is cfg_sampler_step."""
+    bufs, edit, step, geom = _cfg_step("cfg_edit_step", 2, eps2, latents, unet_in, coef, step_ptr, eps_out, history, noise, keep, x0, z0, mask, channels)
+    L.check(L.lib().apad_cfg_edit_step(*bufs, *edit, *step, float(guidance_scale), *geom), "apad_cfg_edit_step")
+
+
+def cfg_dual_step(eps3, latents, unet_in, coef, guidance, step_ptr, eps_out=None, history=None, noise=None, keep=None, x0=None, z0=None, mask=None,
+                  channels=8):
+    """the three-branch step: eps3 [3B, n...] = [no condition ; audio prompt ; audio prompt + text], guidance fp32 [steps, 2] = (s_A, s_T) per
+    step, read on the device at row *step_ptr: eps = fma(s_T, e_AT - e_A, fma(s_A, e_A - e_0, e_0)), then cfg_edit_step's sampler update and
+    (with ``mask``) edit blend.  coef is always the six-column table.  mask = None is the plain sampler step."""
+    fn = "cfg_dual_step"
+    bufs, edit, step, geom = _cfg_step(fn, 3, eps3, latents, unet_in, coef, step_ptr, eps_out, history, noise, keep, x0, z0, mask, channels)
+    _req(guidance, fn + ".guidance", torch.float32)
+    if guidance.dim() != 2 or tuple(guidance.shape) != (step[1], 2) or not guidance.is_contiguous():
+        raise RuntimeError(f"{fn}.guidance: expected a contiguous fp32 [{step[1]}, 2] table of (s_A, s_T), got {tuple(guidance.shape)}")
+    if not eps3.is_contiguous():
+        raise RuntimeError(f"{fn}: eps3 must be contiguous")
+    L.check(L.lib().apad_cfg_dual_step(*bufs, guidance.data_ptr(), *edit, *step, *geom), "apad_cfg_dual_step")
 
 
 def edit_start(z0, x0, latents, unet_in, a, s, moments=None, post_noise=None, scale=1.0):

@@ -357,6 +357,27 @@ class AudioLDM2Pipeline:
         if e["emask"] is not None:
             e["emask"].copy_(src.mask.to(lat.device, torch.float32).reshape(e["emask"].shape))
 
+    def _fill_step_buffers(self, e, H, W, latents_nchw, src, start_coefs, conditions, gtab, generator):
+        """What one run writes into a step's static buffers before its first step, on a cache hit and after the capture path has allocated
+        them: the start (``latents_nchw``, or the noised source of an edit run with its x0 / z0 / mask), the conditions
+        (generated_prompt_embeds, prompt_embeds, attention_mask), the step counter, the guidance table, the zeroed history and the per-step
+        noise -- the only draws from ``generator`` here, after the edit source's (``prepare_edit_source``)."""
+        lat = e["lat"]
+        B, _, C = lat.shape
+        if src is None:
+            lat.copy_(latents_nchw.float().permute(0, 2, 3, 1).reshape(lat.shape))  # fp32 master, NHWC
+            e["unet_in"].copy_(lat)
+        else:
+            self._fill_edit_buffers(e, src, *start_coefs)
+        for name, t in zip(("gen", "pe", "mask", "guidance"), (*conditions, gtab)):
+            if e[name] is not None:
+                e[name].copy_(t)
+        e["step_ptr"].zero_()
+        if e["hist"] is not None:
+            e["hist"].zero_()
+        if e["noise"] is not None:
+            self.prepare_step_noise(B, C, H, W, e["noise"].shape[0], generator, out=e["noise"])
+
     # ---- the loop ----
     MAX_CACHED_GRAPHS = 4  # each holds its activation pool (GBs at batch 32): least-recently-used entries are dropped
 
@@ -421,17 +442,18 @@ class AudioLDM2Pipeline:
         sched = self.scheduler
         sched.set_timesteps(num_inference_steps)
         if src is None:
-            plan, n_run, emask_shape = (sched.sampler_plan(eta, dual=True) if dual else sched.sampler_plan(eta)), num_inference_steps, None
+            plan, n_run, emask_shape, start_coefs = (sched.sampler_plan(eta, dual=True) if dual else sched.sampler_plan(eta)), num_inference_steps, None, None
         else:
             plan = (sched.sampler_plan(eta, start=start, masked=src.mask is not None, dual=True) if dual
                     else sched.sampler_plan(eta, start=start, masked=src.mask is not None))
             n_run = num_inference_steps - plan.start
-            noise_a, noise_s = sched.add_noise_coefs(plan.start)
+            start_coefs = sched.add_noise_coefs(plan.start)
             emask_shape = None if src.mask is None else (src.mask.shape[0], H * W)
             if emask_shape is not None and (tuple(src.mask.shape[1:]) != (1, H, W) or emask_shape[0] not in (1, B)):
                 raise ValueError(f"source mask {tuple(src.mask.shape)}: expected [1 or {B}, 1, {H}, {W}]")
         # (s_A, s_T) of the steps this run visits; checked here, on the host, before any device work
         gtab = guidance_table(audio_guidance_scale, guidance_scale, num_inference_steps, plan.start) if dual else None
+        conditions = (generated_prompt_embeds, prompt_embeds, attention_mask)
         graphed = use_graph and callback is None
         key = (B, Cc, H, W, tuple(generated_prompt_embeds.shape), tuple(prompt_embeds.shape),
                None if attention_mask is None else (tuple(attention_mask.shape), attention_mask.dtype), num_inference_steps,
@@ -449,22 +471,7 @@ class AudioLDM2Pipeline:
                 e = None
         if e is not None:
             self._graphs[key] = self._graphs.pop(key)  # most recently used last
-            if src is None:
-                e["lat"].copy_(latents_nchw.float().permute(0, 2, 3, 1).reshape(B, H * W, Cc))
-                e["unet_in"].copy_(e["lat"])
-            else:
-                self._fill_edit_buffers(e, src, noise_a, noise_s)
-            e["gen"].copy_(generated_prompt_embeds)
-            e["pe"].copy_(prompt_embeds)
-            if attention_mask is not None:
-                e["mask"].copy_(attention_mask)
-            e["step_ptr"].zero_()
-            if dual:
-                e["guidance"].copy_(gtab)
-            if e["hist"] is not None:
-                e["hist"].zero_()
-            if e["noise"] is not None:
-                self.prepare_step_noise(B, Cc, H, W, n_run, generator, out=e["noise"])
+            self._fill_step_buffers(e, H, W, latents_nchw, src, start_coefs, conditions, gtab, generator)
             unet.set_kv_cache(True, clear=False)
             try:
                 unet.refresh_kv_cache()  # hoisted K/V of the new conditions, recomputed into the buffers the graph reads
@@ -474,21 +481,19 @@ class AudioLDM2Pipeline:
                 e["graph"].replay()
             self.graph_hits += 1
         else:
-            e = {"lat": (latents_nchw.float().permute(0, 2, 3, 1).reshape(B, H * W, Cc).contiguous() if src is None  # fp32 master, NHWC
-                         else torch.empty(B, H * W, Cc, dtype=torch.float32, device=dev)),
-                 "gen": generated_prompt_embeds.to(dtype).contiguous().clone(), "pe": prompt_embeds.to(dtype).contiguous().clone(),
-                 "mask": None if attention_mask is None else attention_mask.clone(),
-                 "coef": plan.table.to(dev), "step_ptr": torch.zeros(1, dtype=torch.int32, device=dev)}
-            e["unet_in"] = e["lat"].to(dtype).clone() if dtype == torch.float32 else e["lat"].to(dtype)
+            f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+            e = {"lat": f32(B, H * W, Cc), "unet_in": torch.empty(B, H * W, Cc, dtype=dtype, device=dev),
+                 "gen": torch.empty(generated_prompt_embeds.shape, dtype=dtype, device=generated_prompt_embeds.device),
+                 "pe": torch.empty(prompt_embeds.shape, dtype=dtype, device=prompt_embeds.device),
+                 "mask": None if attention_mask is None else torch.empty_like(attention_mask),
+                 "coef": plan.table.to(dev), "step_ptr": torch.empty(1, dtype=torch.int32, device=dev),
+                 "guidance": f32(n_run, 2) if dual else None, "eps_out": f32(B, H * W, Cc) if keep_noise_pred else None,
+                 "hist": f32(B, H * W, Cc) if plan.needs_history else None, "noise": f32(n_run, B, H * W, Cc) if plan.needs_noise else None}
             if src is not None:
-                e["x0"], e["z0"] = torch.empty_like(e["lat"]), torch.empty_like(e["lat"])
-                e["emask"] = None if emask_shape is None else torch.empty(emask_shape, dtype=torch.float32, device=dev)
+                e["x0"], e["z0"] = f32(B, H * W, Cc), f32(B, H * W, Cc)
+                e["emask"] = None if emask_shape is None else f32(*emask_shape)
                 e["keep"] = None if plan.keep is None else plan.keep.to(dev)
-                self._fill_edit_buffers(e, src, noise_a, noise_s)
-            e["guidance"] = gtab.to(dev) if dual else None
-            e["eps_out"] = torch.empty_like(e["lat"]) if keep_noise_pred else None
-            e["hist"] = torch.zeros_like(e["lat"]) if plan.needs_history else None
-            e["noise"] = self.prepare_step_noise(B, Cc, H, W, n_run, generator, device=dev) if plan.needs_noise else None
+            self._fill_step_buffers(e, H, W, latents_nchw, src, start_coefs, conditions, gtab, generator)
             lat, unet_in, gen, pe, mask, coef, step_ptr, eps_out = (e[k] for k in ("lat", "unet_in", "gen", "pe", "mask", "coef", "step_ptr", "eps_out"))
             hist, noise = e["hist"], e["noise"]
             from . import processors as P_
@@ -502,26 +507,20 @@ class AudioLDM2Pipeline:
             #  -- same-box A/B 37.35 vs 37.49 ms with two half-batch streams -- and this is the configuration bench.py measures;
             #  ``unet.low_res_streams`` remains an opt-in attribute)
 
-            def dual_step():  # three sample-forwards per clip; the condition-free prefix still runs once
-                eps3 = unet.forward_nhwc(unet_in, H, W, None, gen, pe, None, mask, batch_repeat=3)
-                if masked:
-                    ops.cfg_dual_step(eps3, lat, unet_in, coef, e["guidance"], step_ptr, eps_out, hist, noise, e["keep"], e["x0"], e["z0"], e["emask"], Cc)
-                else:
-                    ops.cfg_dual_step(eps3, lat, unet_in, coef, e["guidance"], step_ptr, eps_out, hist, noise)
-                ops.step_advance(step_ptr)
+            # the update op of this run and its arguments, bound once (ops.* is looked up when the step runs)
+            edit = (e["keep"], e["x0"], e["z0"], e["emask"], Cc) if masked else ()
+            if dual:  # three sample-forwards per clip; the condition-free prefix still runs once
+                update = lambda eps: ops.cfg_dual_step(eps, lat, unet_in, coef, e["guidance"], step_ptr, eps_out, hist, noise, *edit)
+            elif masked:
+                update = lambda eps: ops.cfg_edit_step(eps, lat, unet_in, coef, edit[0], step_ptr, guidance_scale, *edit[1:], eps_out, hist, noise)
+            elif plan.legacy:
+                update = lambda eps: ops.cfg_ddim_step(eps, lat, unet_in, coef, step_ptr, guidance_scale, eps_out)
+            else:
+                update = lambda eps: ops.cfg_sampler_step(eps, lat, unet_in, coef, step_ptr, guidance_scale, eps_out, hist, noise)
 
             def step():
-                eps2 = unet.forward_nhwc(unet_in, H, W, None, gen, pe, None, mask, batch_repeat=2)
-                if masked:
-                    ops.cfg_edit_step(eps2, lat, unet_in, coef, e["keep"], step_ptr, guidance_scale, e["x0"], e["z0"], e["emask"], Cc, eps_out, hist, noise)
-                elif plan.legacy:
-                    ops.cfg_ddim_step(eps2, lat, unet_in, coef, step_ptr, guidance_scale, eps_out)
-                else:
-                    ops.cfg_sampler_step(eps2, lat, unet_in, coef, step_ptr, guidance_scale, eps_out, hist, noise)
+                update(unet.forward_nhwc(unet_in, H, W, None, gen, pe, None, mask, batch_repeat=3 if dual else 2))
                 ops.step_advance(step_ptr)
-
-            if dual:
-                step = dual_step
 
             def reset():  # back to step 0 of this call (after the warm-up step and after the capture)
                 lat.copy_(lat0)

@@ -9,9 +9,9 @@
 conventions.  The reference pipeline accepts any ``KarrasDiffusionSchedulers`` member (:158); this is the second one here.
 
 The per-step update itself runs on the device from a coefficient table (``apad_cfg_ddim_step`` for deterministic DDIM,
-``apad_cfg_sampler_step`` for everything else, ``apad_cfg_edit_step`` with a region mask: three entry points onto one kernel, whose
-rounding form per entry point is written out in csrc/elementwise.hip's ``sampler_update``; ``apad_cfg_dual_step`` for the three-branch step
-with separate audio and text guidance, ``sampler_plan(dual=True)`` + ``guidance_table``), which removes the reference's per-step
+``apad_cfg_sampler_step`` for everything else, ``apad_cfg_edit_step`` with a region mask: ``apad_cfg_dual_step`` for the three-branch step
+with separate audio and text guidance, ``sampler_plan(dual=True)`` + ``guidance_table``: four entry points onto one kernel, whose rounding
+form per entry point is written out in csrc/elementwise.hip's ``guided_noise`` and ``sampler_update``), which removes the reference's per-step
 host<->device sync inside ``scheduler.step``.  Every update here is LINEAR in (x, eps, previous data prediction m1, fresh noise z), so one row of six
 coefficients per step describes it (``SAMPLER_COLS``); ``sampler_plan`` tells the loop which kernel, table and per-sampler buffers
 a call needs.

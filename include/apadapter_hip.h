@@ -29,8 +29,8 @@
  *                       DPMSolverMultistepScheduler.step (DPM-Solver++ 2M); _edit_: that step followed by the re-imposition of the kept
  *                       region.  Each entry point's rounding form is written out beside the kernel (sampler_update, edit_blend)
  *   apad_cfg_dual_step  the same step on THREE branches with separate audio and text guidance scales read from a device table (no
- *                       counterpart in the reference: InstructPix2Pix's two-scale guidance); its own kernel, the same
- *                       sampler_update / edit_blend
+ *                       counterpart in the reference: InstructPix2Pix's two-scale guidance): the fourth entry point onto
+ *                       cfg_step_kernel, its three-branch instantiations (guided_noise), the same sampler_update / edit_blend
  *   apad_step_advance   the loop counter of the captured step
  *   apad_edit_start     editing from a source clip (no working counterpart in the reference; diffusers' img2img / inpaint
  *                       conventions): posterior draw + add_noise at the start timestep
