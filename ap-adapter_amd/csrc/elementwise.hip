@@ -1,6 +1,7 @@
 // Small HBM-bound kernels of the path: AudioMAE token pooling, sinusoidal timestep embedding, fused
 // classifier-free-guidance + sampler update (one kernel of two or three guidance branches and one host launch path behind apad_cfg_ddim_step /
-// apad_cfg_sampler_step / apad_cfg_edit_step / apad_cfg_dual_step), the edit run's start, device-side step counter.
+// apad_cfg_sampler_step / apad_cfg_edit_step / apad_cfg_dual_step), the noise-extracting step of DDPM inversion beside it (apad_cfg_invert_step),
+// the edit run's start, device-side step counter.
 #include "common.h"
 #include "f32_ops.h"
 
@@ -264,6 +265,85 @@ __global__ __launch_bounds__(256) void edit_start_kernel(const uint8_t* moments,
     }
 }
 
+// z = (x' - mu) / std: one fp32 subtraction and one IEEE fp32 division (correctly rounded, v_div_scale / v_div_fmas / v_div_fixup), nothing
+// fused into either.  std == 0 (a deterministic row: the step adds no noise, so there is none to extract) gives z = 0, never inf or NaN.
+__device__ __forceinline__ float invert_noise(float xn, float mu, float sd) {
+#pragma clang fp contract(off)
+    const float d = xn - mu;
+    return sd != 0.f ? d / sd : 0.f;
+}
+
+// The guided noise as cfg_step_kernel<DT, FORM, NB> forms it, so that the inversion and the sampler step that consumes its z see the same eps
+// bits: guided_noise, except for the one fold that function leaves to the compiler (f16, two branches).  The step kernel's 16-byte form
+// rounds the fma to fp32 and then to f16 (v_cvt_pk_f16_f32), its scalar form rounds the exact fma once (v_fma_mixlo_f16); here the compiler
+// chooses the single rounding in both forms, so the 16-byte form is pinned to the step kernel's two roundings.
+template <int DT, int FORM> __device__ __forceinline__ float invert_guided_noise(float gs, float, const float (&e)[2]) {
+    if constexpr (DT == APAD_F16 && FORM == STEP_VEC) {
+        float g = fmaf(gs, e[1] - e[0], e[0]);
+        asm volatile("" : "+v"(g));
+        return (float)(typename ET<DT>::elem)g;
+    } else {
+        return guided_noise<DT>(gs, 0.f, e);
+    }
+}
+template <int DT, int FORM> __device__ __forceinline__ float invert_guided_noise(float s_a, float s_t, const float (&e)[3]) {
+    return guided_noise<DT>(s_a, s_t, e);
+}
+
+// Edit-friendly DDPM inversion (Huberman-Spiegelglas et al. 2024), the step that EXTRACTS a stochastic sampler's noise instead of
+// consuming it -- cfg_step_kernel's layout, grid, step clamp, guided noise and forms (STEP_VEC / STEP_SCALAR), at the end of the same captured
+// UNet step.  With row r = coef + 6 * step = (c_x, c_e, -, std, -, -), (kx, kz) = keep[2 * step] and n~ = noise[step] (an independent draw):
+//   eps = guided_noise<DT>(branches at x)                            the source condition's guided noise, as the sampler forms it
+//                                                                     (invert_guided_noise)
+//   mu  = sampler_update<DT, FORM>'s c_x x + c_e eps                 (c_m = c_z = 0, m1 = z = 0: the same operations in the same order, so
+//                                                                     STEP_VEC: fma(c_x, x, c_e * e);  STEP_SCALAR fp32: fma(c_e, e, c_x * x);
+//                                                                     STEP_SCALAR 16-bit: c_x * x + c_e * e -- the added zeros change no bit
+//                                                                     of a nonzero mu)
+//   x'  = edit_known(kx, kz, x0, n~) = fma(kx, x0, kz * n~)          the source at the noise level the step lands on; (1, 0) on the last row:
+//                                                                     the bits of x0
+//   z   = (x' - mu) / std   (invert_noise)                           -> written over n~, row ``step`` of the noise table
+//   latents = x',  unet_in = (model dtype) x'
+// so that the sampler's own step from x with the same eps and noise = z gives fma(std, z, mu) = x' up to the roundings of z.  x is only read to
+// form mu: the trajectory x_(i) is independent of the UNet, the z_i are not.
+template <int DT, int FORM, int NB>
+__global__ __launch_bounds__(256) void cfg_invert_step_kernel(const uint8_t* eps, float* latents, uint8_t* unet_in, float* eps_out, float* noise,
+                                                              const float* coef, const float* keep, const float* x0, const int32_t* step_ptr,
+                                                              int n_steps, float gs, int64_t total, const float* guidance) {
+    static_assert(FORM == STEP_VEC || FORM == STEP_SCALAR, "the two-column table has no noise column to invert into");
+    constexpr int V = FORM == STEP_VEC ? 8 : 1;
+    int step = step_ptr ? *step_ptr : 0;
+    step = step < 0 ? 0 : (step >= n_steps ? n_steps - 1 : step);  // the tables and the noise buffer have n_steps rows
+    const float* r = coef + 6 * step;
+    const float c_x = r[0], c_e = r[1], sd = r[3];
+    const float s_a = NB == 3 ? guidance[2 * step] : gs, s_t = NB == 3 ? guidance[2 * step + 1] : 0.f;
+    const float kx = keep[2 * step], kz = keep[2 * step + 1];
+    float* z = noise + (int64_t)step * total;
+    for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * V; i < total; i += (int64_t)gridDim.x * 256 * V) {
+        float eb[NB][V], x[V], a[V], zz[V], e[V];
+#pragma unroll
+        for (int b = 0; b < NB; ++b) ld_elemv<DT, V>(eps, b * total + i, eb[b]);
+        ld_f32v<V>(latents, i, x);
+        ld_f32v<V>(x0, i, a);
+        ld_f32v<V>(z, i, zz);
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            float ej[NB];
+#pragma unroll
+            for (int b = 0; b < NB; ++b) ej[b] = eb[b][j];
+            e[j] = invert_guided_noise<DT, FORM>(s_a, s_t, ej);
+            float mu, m0;
+            sampler_update<DT, FORM>(c_x, c_e, 0.f, 0.f, 0.f, 0.f, x[j], e[j], 0.f, 0.f, mu, m0);
+            x[j] = edit_known(kx, kz, a[j], zz[j]);
+            asm volatile("" : "+v"(x[j]));  // unet_in is the rounded copy of the fp32 master (see edit_start_kernel)
+            zz[j] = invert_noise(x[j], mu, sd);
+        }
+        st_f32v<V>(latents, i, x);
+        st_elemv<DT, V>(unet_in, i, x);
+        st_f32v<V>(z, i, zz);
+        if (eps_out) st_f32v<V>(eps_out, i, e);
+    }
+}
+
 __global__ void step_advance_kernel(int32_t* p) { *p = *p + 1; }
 
 template <int DT> __global__ __launch_bounds__(256) void mix3_kernel(const uint8_t* a, const uint8_t* b, const uint8_t* c, uint8_t* out, int64_t n,
@@ -480,6 +560,37 @@ extern "C" int apad_cfg_dual_step(const void* eps3, float* latents, void* unet_i
     a.guidance = guidance, a.keep = keep, a.x0 = x0, a.z0 = z0, a.mask = mask, a.mask_batch = mask_batch, a.C = C;
     a.step_ptr = step_ptr, a.n_steps = n_steps, a.B = B, a.n = n, a.dtype = dtype, a.stream = stream, a.branches = 3;
     return step_launch("apad_cfg_dual_step", a);
+}
+
+namespace {
+using invert_kernel_t = decltype(&cfg_invert_step_kernel<APAD_BF16, STEP_VEC, 2>);
+template <int DT> invert_kernel_t invert_kernel(bool vec, int branches) {
+    if (branches == 3) return vec ? cfg_invert_step_kernel<DT, STEP_VEC, 3> : cfg_invert_step_kernel<DT, STEP_SCALAR, 3>;
+    return vec ? cfg_invert_step_kernel<DT, STEP_VEC, 2> : cfg_invert_step_kernel<DT, STEP_SCALAR, 2>;
+}
+}  // namespace
+
+extern "C" int apad_cfg_invert_step(const void* eps, float* latents, void* unet_in, float* eps_out, float* noise, const float* coef,
+                                    const float* guidance, const float* keep, const float* x0, const int32_t* step_ptr, int32_t n_steps,
+                                    float guidance_scale, int32_t branches, int32_t B, int64_t n, int32_t dtype, void* stream) {
+    const char* fn = "apad_cfg_invert_step";
+    APAD_CHECK(eps && latents && unet_in && noise && coef && keep && x0, "%s: null operand", fn);
+    APAD_CHECK(branches == 2 || branches == 3, "%s: branches = %d must be 2 or 3", fn, branches);
+    APAD_CHECK(branches == 2 || guidance, "%s: null guidance table", fn);
+    APAD_CHECK(dtype == APAD_BF16 || dtype == APAD_F16 || dtype == APAD_F32, "%s: dtype %d not supported", fn, dtype);
+    APAD_CHECK(B > 0 && n > 0 && n_steps > 0, "%s: empty problem", fn);
+    const int64_t total = (int64_t)B * n;
+    // the step kernel's rule (step_launch): 16-byte accesses need every non-null base 16-byte aligned and 8 | total
+    const uintptr_t bases = (uintptr_t)eps | (uintptr_t)latents | (uintptr_t)unet_in | (uintptr_t)eps_out | (uintptr_t)noise | (uintptr_t)x0;
+    const bool vec = total % 8 == 0 && bases % 16 == 0;
+    int64_t blocks = ((vec ? total / 8 : total) + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    const invert_kernel_t kern = dtype == APAD_BF16  ? invert_kernel<APAD_BF16>(vec, branches)
+                                 : dtype == APAD_F32 ? invert_kernel<APAD_F32>(vec, branches)
+                                                     : invert_kernel<APAD_F16>(vec, branches);
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)eps, latents, (uint8_t*)unet_in, eps_out, noise, coef,
+                       keep, x0, step_ptr, n_steps, branches == 3 ? 0.f : guidance_scale, total, guidance);
+    return apad_check_launch(fn);
 }
 
 extern "C" int apad_edit_start(const void* moments, const float* post_noise, const float* z0, float* x0_out, float* latents, void* unet_in, float a,

@@ -1217,6 +1217,41 @@ def cfg_dual_step(eps3, latents, unet_in, coef, guidance, step_ptr, eps_out=None
     L.check(L.lib().apad_cfg_dual_step(*bufs, guidance.data_ptr(), *edit, *step, *geom), "apad_cfg_dual_step")
 
 
+def cfg_invert_step(eps, latents, unet_in, coef, keep, x0, noise, step_ptr, guidance_scale=None, guidance=None, eps_out=None):
+    """the edit-friendly DDPM inversion step: eps [2B, n...] guided by ``guidance_scale`` (two branches), or [3B, n...] guided by ``guidance``
+    fp32 [steps, 2] = (s_A, s_T) per step (three branches, cfg_dual_step's); coef fp32 [steps, 6] with std in column 3 (DDIM eta > 0), keep
+    fp32 [steps, 2], x0 fp32 like latents, noise fp32 [steps, B, n...]: row *step_ptr holds an independent Gaussian draw on entry and the
+    extracted z = (x' - mu) / std on return, with x' = fma(kx, x0, kz * draw) -> latents / unet_in and mu = c_x x + c_e eps as
+    cfg_sampler_step rounds it.  Exactly one of ``guidance_scale`` / ``guidance`` is given."""
+    fn = "cfg_invert_step"
+    if (guidance is None) == (guidance_scale is None):
+        raise RuntimeError(f"{fn}: pass guidance_scale (two branches) or the guidance table (three branches), not both or neither")
+    branches = 2 if guidance is None else 3
+    if branches == 2 and (eps.dim() > 1 and latents.dim() > 0 and eps.shape[0] != 2 * latents.shape[0]):
+        raise RuntimeError(f"{fn}: eps2 must hold two branches [2B, n] of latents [B, n] = {tuple(latents.shape)}, got {tuple(eps.shape)}")
+    for t, name in ((keep, "keep"), (x0, "x0"), (noise, "noise")):
+        if t is None:
+            raise RuntimeError(f"{fn}.{name}: required")
+    for t, name in ((eps, "eps"), (unet_in, "unet_in")):
+        if not _req(t, f"{fn}.{name}").is_contiguous():
+            raise RuntimeError(f"{fn}.{name}: must be contiguous")
+    if not latents.is_contiguous():
+        raise RuntimeError(f"{fn}.latents: must be contiguous")
+    bufs, edit, step, geom = _cfg_step(fn, branches, eps, latents, unet_in, coef, step_ptr, eps_out, None, noise, keep, x0)
+    if noise.shape[0] != step[1] or keep.shape[0] != step[1]:
+        raise RuntimeError(f"{fn}: noise {tuple(noise.shape)}, coef {tuple(coef.shape)} and keep {tuple(keep.shape)} must have one row per step")
+    if guidance is not None:
+        _req(guidance, fn + ".guidance", torch.float32)
+        if tuple(guidance.shape) != (step[1], 2) or not guidance.is_contiguous():
+            raise RuntimeError(f"{fn}.guidance: expected a contiguous fp32 [{step[1]}, 2] table of (s_A, s_T), got {tuple(guidance.shape)}")
+    for t in (eps, unet_in, coef, keep, x0, noise, step_ptr, guidance, eps_out):
+        if t is not None and t.device != latents.device:
+            raise RuntimeError(f"{fn}: every operand must live on latents' device {latents.device}, got {t.device}")
+    eps_p, lat_p, unet_p, eps_out_p, _, noise_p, coef_p = bufs
+    L.check(L.lib().apad_cfg_invert_step(eps_p, lat_p, unet_p, eps_out_p, noise_p, coef_p, _ptr(guidance), edit[0], edit[1], *step,
+                                         0.0 if guidance_scale is None else float(guidance_scale), branches, *geom), "apad_cfg_invert_step")
+
+
 def edit_start(z0, x0, latents, unet_in, a, s, moments=None, post_noise=None, scale=1.0):
     """the start of an edit run, written into the loop's buffers: with ``moments`` [rows, 2L] = (mean | logvar) in unet_in's dtype and
     ``post_noise`` fp32 [rows, L], x0 <- (mean + exp(0.5 clamp(logvar, -30, 20)) post_noise) * scale; without, x0 holds the source latents

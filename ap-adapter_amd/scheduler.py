@@ -19,6 +19,9 @@ a call needs.
 An edit run (a source clip noised to an interior timestep, optionally with a region mask; ``edit_start_index``, ``_EditSchedule``,
 ``sampler_plan(start=, masked=)``) enters the same grid at index k and uses rows ``k:`` of the same tables.
 
+Edit-friendly DDPM inversion (``DDIMScheduler.inversion_plan``, ``apad_cfg_invert_step``; Huberman-Spiegelglas et al. 2024) reads the
+same ``eta`` > 0 rows and the same ``keep`` table on the same slice: it extracts the noise those rows would consume.
+
 PARITY UNPINNED: the ``eta`` arithmetic and the multistep solver are restated from the published formulas (diffusers is not
 vendored and not installable offline); ``tests/sampler_oracle.py`` restates them a second time, independently, in float64."""
 import math
@@ -195,6 +198,20 @@ class DDIMScheduler(_EditSchedule):
         return SamplerPlan(self.sampler_rows(eta)[start:].float().contiguous(), False, False, eta != 0.0, key,
                            self.keep_table(start) if masked else None, start)
 
+    def inversion_plan(self, eta, start=0, dual=False):
+        """what edit-friendly DDPM inversion (apad_cfg_invert_step; Huberman-Spiegelglas et al. 2024) asks of the loop: rows
+        ``start:`` of ``sampler_rows(eta)`` -- the table the edit phase's sampler step reads, whose std column the inversion divides by --
+        ``keep_table(start)`` (the noise level each step lands on), one noise row per step, and "invert" in ``key``.  ``eta`` must be > 0:
+        a deterministic step has no noise to invert into."""
+        eta = float(eta)
+        if not eta > 0.0:
+            raise ValueError(f"eta={eta!r}: DDPM inversion extracts the per-step noise of a stochastic sampler and needs eta > 0 (pass eta=1.0)")
+        start = self._check_start(start)
+        key = ("DDIMScheduler", self.order, "leading", self.num_train_timesteps, self.steps_offset, self._betas, eta, start, "invert")
+        if dual:
+            key += ("dual",)
+        return SamplerPlan(self.sampler_rows(eta)[start:].float().contiguous(), False, False, True, key, self.keep_table(start), start)
+
 
 class DPMSolverMultistepScheduler(_EditSchedule):
     """DPM-Solver++ multistep (2M), epsilon prediction, data-prediction form, midpoint -- diffusers' class name, constructor keywords
@@ -282,3 +299,8 @@ class DPMSolverMultistepScheduler(_EditSchedule):
             key += ("dual",)
         return SamplerPlan(self.sampler_rows(start=start).float(), False, self.solver_order > 1, False, key,
                            self.keep_table(start) if masked else None, start)
+
+    def inversion_plan(self, eta=0.0, start=0, dual=False):
+        """not available: the multistep solver is deterministic -- it has no per-step noise to invert into (``DDIMScheduler.inversion_plan``)"""
+        raise ValueError("scheduler: DDPM inversion needs DDIMScheduler with eta > 0; DPMSolverMultistepScheduler has no per-step noise to "
+                         "invert into")

@@ -31,6 +31,8 @@
  *   apad_cfg_dual_step  the same step on THREE branches with separate audio and text guidance scales read from a device table (no
  *                       counterpart in the reference: InstructPix2Pix's two-scale guidance): the fourth entry point onto
  *                       cfg_step_kernel, its three-branch instantiations (guided_noise), the same sampler_update / edit_blend
+ *   apad_cfg_invert_step  edit-friendly DDPM inversion (no counterpart in the reference): the step that extracts the per-step
+ *                       noise of DDIM eta > 0 under the source condition (cfg_invert_step_kernel, beside cfg_step_kernel)
  *   apad_step_advance   the loop counter of the captured step
  *   apad_edit_start     editing from a source clip (no working counterpart in the reference; diffusers' img2img / inpaint
  *                       conventions): posterior draw + add_noise at the start timestep
@@ -512,6 +514,23 @@ int apad_cfg_dual_step(const void* eps3, float* latents, void* unet_in, float* e
                        const float* coef, const float* guidance, const float* keep, const float* x0, const float* z0, const float* mask,
                        int32_t mask_batch, int32_t C, const int32_t* step_ptr, int32_t n_steps, int32_t B, int64_t n, int32_t dtype,
                        void* stream);
+/* Edit-friendly DDPM inversion (Huberman-Spiegelglas et al. 2024; Manor & Michaeli 2024; no counterpart in the reference): the
+   step that EXTRACTS the noise of a stochastic sampler instead of consuming it, at the end of the same captured UNet step.  eps [branches * B][n]
+   (dtype) as apad_cfg_sampler_step (branches 2, guided by guidance_scale; guidance may be null) or apad_cfg_dual_step (branches 3, guided by
+   guidance [n_steps][2], required).  With s = *step_ptr clamped to [0, n_steps), r = coef + 6 * s (the six-column table of DDIM eta > 0:
+   r[3] = std), (kx, kz) = keep [n_steps][2] row s, x0 fp32 [B][n] the source latents and noise fp32 [n_steps][B][n] holding independent
+   Gaussian draws on entry:
+     mu      = r[0] x + r[1] eps              rounded exactly as apad_cfg_sampler_step rounds these two terms in the same form and dtype
+     x'      = fma(kx, x0, kz * noise[s])     the source at the noise level the step lands on; the keep row (1, 0), the last, gives the bits of x0
+     noise[s] <- (x' - mu) / r[3]             one fp32 subtraction, one IEEE fp32 division; r[3] == 0 writes 0 (never inf / NaN)
+     latents <- x',  unet_in <- (dtype) x',  eps_out (optional) <- the guided noise
+   so apad_cfg_sampler_step / _edit_step / _dual_step from the same start with the same table, eps and this noise table reproduce every x' --
+   and end on x0 -- up to the roundings of noise[s]; under another condition they edit the clip and keep its structure.  16-byte accesses when
+   every non-null base is 16-byte aligned and 8 | B * n, a scalar form otherwise (the same rule, hence the same form, as the sampler step on
+   the same buffers).  One launch, no host involvement: hipGraph-capturable. */
+int apad_cfg_invert_step(const void* eps, float* latents, void* unet_in, float* eps_out, float* noise, const float* coef, const float* guidance,
+                         const float* keep, const float* x0, const int32_t* step_ptr, int32_t n_steps, float guidance_scale, int32_t branches,
+                         int32_t B, int64_t n, int32_t dtype, void* stream);
 /* The buffers an edit run starts from, in the loop's layout ([rows = B * h * w][Lc], NHWC), in one pass:
      x0_out  = (mean + exp(0.5 * clamp(logvar, -30, 20)) * post_noise) * scale   fp32; moments [rows][2 * Lc] = (mean | logvar) in `dtype`
                as apad_gaussian_sample reads them, post_noise fp32 [rows][Lc].  Null moments: x0_out already holds the source latents.

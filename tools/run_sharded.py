@@ -12,6 +12,11 @@ wav -- the file of the same name in DIR, by default the audio prompt itself -- e
 the interior timestep S selects, and only seconds A..B are regenerated.  Each clip's noise is seeded by its index, so a clip's result
 does not depend on the batch or rank it lands in.
     python tools/run_sharded.py --clips 64 --steps 50 --strength 0.6 --edit-region 4:7
+
+Edit-friendly DDPM inversion (--inversion ddpm, with --source-prompt TEXT and --source-guidance S; an edit run, DDIM only, eta = 1): each
+batch first extracts its sources' per-step noise maps under the source prompt (``pipeline.invert``), then runs the edit on those maps under
+the task's prompt.  The inversion's per-step draws are seeded by the batch's first clip, so here a clip's result does depend on its batch.
+    python tools/run_sharded.py --clips 64 --steps 50 --strength 0.6 --inversion ddpm --source-prompt "a recording of a piano"
 """
 import argparse
 import glob
@@ -116,8 +121,14 @@ def main():
     ap.add_argument("--edit-region", default=None, metavar="A:B", help="edit: regenerate seconds A..B only, keep the rest of the source")
     ap.add_argument("--audio-guidance", type=float, default=None, metavar="S", help="separate audio and text guidance: three branches per clip, "
                     "eps_0 + S (eps_A - eps_0) + guidance_scale (eps_AT - eps_A); without it the job is the two-branch one")
+    ap.add_argument("--inversion", choices=["ddpm"], default=None, help="edit from the source's own per-step noise (edit-friendly DDPM inversion) "
+                    "instead of fresh noise: one more pass of the run's UNet steps; needs --sampler ddim, runs at eta = 1")
+    ap.add_argument("--source-prompt", default="", metavar="TEXT", help="--inversion: the text describing the SOURCE clip (default: the empty prompt)")
+    ap.add_argument("--source-guidance", type=float, default=3.0, metavar="S", help="--inversion: the text guidance scale of the inversion pass")
     ap.add_argument("--gpus", type=int, default=1, help="N > 1 without a launcher: this script starts its N ranks itself (one per GPU)")
     args = ap.parse_args()
+    if args.inversion and args.sampler != "ddim":
+        ap.error("--inversion ddpm needs --sampler ddim: the multistep solver has no per-step noise to invert into")
 
     from ap_adapter_amd import distributed as D
     if args.gpus > 1 and not D.launched_by_torchrun():
@@ -142,7 +153,7 @@ def main():
         tok, unc = pipe.encode_audio(load_mel(path, device=dev), tp, fp)
         return tok[0], unc[0]
 
-    editing = args.strength is not None or args.edit_region is not None or args.source_dir is not None
+    editing = args.strength is not None or args.edit_region is not None or args.source_dir is not None or args.inversion is not None
     if editing:
         height = H * pipe.vae_scale_factor
         pipe.vae = build_decoder(dev, dtype, small=args.small)[0]
@@ -169,7 +180,16 @@ def main():
         post = torch.stack([torch.randn(8, H, 16, generator=torch.Generator().manual_seed(7919 * c["index"] + 1)) for c in clips])
         src = A.EditSource(z0=lat, moments=torch.cat([source_moments(c["audio"]) for c in clips]), post_noise=post,
                            scale=pipe.vae.config.scaling_factor, mask=region_mask)
-        return pipe.denoise(None, gen, t5, mask, args.steps, gs, source=src, start=start, **dual)
+        if args.inversion is None:
+            return pipe.denoise(None, gen, t5, mask, args.steps, gs, source=src, start=start, **dual)
+        # the source condition: the batch's own, with the positive branch's text (the last b rows; 8 generated tokens) replaced
+        b = lat.shape[0]
+        sg, st, sm = S.synthetic_text_embeddings(args.source_prompt, t5_len=t5.shape[1])
+        sgen, st5, smask = gen.clone(), t5.clone(), mask.clone()
+        sgen[-b:, :8], st5[-b:], smask[-b:] = sg.to(gen), st.to(t5), sm.to(mask)
+        inv = pipe.invert(src, sgen, st5, smask, args.steps, args.source_guidance, start=start, eta=1.0,
+                          generator=torch.Generator().manual_seed(104729 * clips[0]["index"] + 2), **dual)
+        return pipe.denoise(None, gen, t5, mask, args.steps, gs, source=inv, start=start, eta=1.0, **dual)
 
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -195,7 +215,9 @@ def main():
         print(json.dumps({"task": args.task, "clips": len(clips), "world": world, "batch": args.batch, "steps": args.steps,
                           "sampler": args.sampler, "strength": args.strength, "edit_region": args.edit_region, "La": A.config.audio_tokens(cfg), "seconds_rank0": round(dt, 2), "clips_per_s": round(len(clips) / dt, 4),
                           "graph_captures": pipe.graph_captures, "graph_hits": pipe.graph_hits, "finite": finite,
-                          "wavs_written_rank0": n_wavs, **({"audio_guidance": args.audio_guidance} if dual else {})}))
+                          "wavs_written_rank0": n_wavs, **({"audio_guidance": args.audio_guidance} if dual else {}),
+                          **({"inversion": args.inversion, "source_prompt": args.source_prompt, "source_guidance": args.source_guidance}
+                             if args.inversion else {})}))
         if args.out:
             torch.save({"latents": torch.stack([x.cpu() for x in allc]), "clips": clips}, args.out)
     if world > 1:
