@@ -186,6 +186,9 @@ SYMBOLS = {
     "apad_clap_mel2img": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _f32, _vp, _i32, _i32, _i32, _i32, _vp]),
     # CLAP log-mel front-end (ClapFeatureExtractor)
     "apad_clap_logmel": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _vp]),
+    # chroma features and chroma similarity (score_fidelity)
+    "apad_chroma": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
+    "apad_chroma_similarity": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
 }
 
 _lock = threading.Lock()

@@ -18,6 +18,11 @@
 //   apad_clap_logmel    resample (the polyphase sum of apad_resample_fir, on the fly) -> crop / repeatpad / repeat / pad to
 //                       max_length -> 1024-point periodic-Hann STFT (run-time hop, reflect-padded by 512) -> |X|^2 -> Slaney
 //                       mel filters -> 10 log10(max(., 1e-10)), one launch for a ragged batch
+//
+// Edit fidelity (score_fidelity; librosa.feature.chroma_stft at its defaults with the tuning fixed, restated: PARITY UNPINNED):
+//   apad_chroma              2048-point periodic-Hann STFT (hop 512, zero-padded by 1024) -> |X|^2 -> 12 chroma filters -> each frame
+//                            divided by its maximum, one launch for a ragged batch
+//   apad_chroma_similarity   mean over the frames of the cosine between a candidate's and its reference's chroma vectors
 #include "common.h"
 
 namespace {
@@ -440,4 +445,129 @@ extern "C" int apad_clap_logmel(const float* x, const int64_t* offsets, const in
                        kernel, (int)orig, (int)newf, (int)width, window, twiddle, mel, mel_range, out, max_length, (int)hop, (int)n_mels,
                        (int)padding);
     return apad_check_launch("apad_clap_logmel");
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Chroma features and chroma similarity (librosa.feature.chroma_stft at its defaults, tuning fixed by the host's filterbank)
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+
+constexpr int CNFFT = 2048, CHOP = 512, CPAD = CNFFT / 2, CBIN = CNFFT / 2 + 1, NCHROMA = 12;
+
+// grid (target_frames, B), 256 threads: frame f of clip b covers samples [512 f - 1024, 512 f + 1024) of the clip, zeros outside
+// it (center=True, pad_mode="constant"); a clip of n samples has 1 + n / 512 frames, later rows are 0.  Thread t owns bins t,
+// t + 256, t + 512, t + 768 (thread 0 also bin 1024): their powers never go back to LDS.  Each of the 12 filter sums goes lane (bins
+// in increasing order) -> wave (xor butterfly) -> workgroup (waves 0..3 in order): no atomics, nothing depends on the grid.
+__global__ __launch_bounds__(256) void chroma_kernel(const float* x, const int64_t* offsets, const float* window,
+                                                     const float* twiddle /* [1024][2] */, const float* fb /* [12][1025] */, float* out,
+                                                     int target) {
+    __shared__ float re[CNFFT], im[CNFFT], part[4][NCHROMA];
+    const int f = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    float* o = out + ((int64_t)b * target + f) * NCHROMA;
+    const int64_t o0 = offsets[b], n = offsets[b + 1] - o0;
+    if ((int64_t)f >= n / CHOP + 1) {
+        if (tid < NCHROMA) o[tid] = 0.f;
+        return;
+    }
+    const float* xc = x + o0;
+    const int64_t start = (int64_t)f * CHOP - CPAD;
+    for (int j = tid; j < CNFFT; j += 256) {
+        const int64_t i = start + j;
+        const float v = (i >= 0 && i < n) ? xc[i] : 0.f;
+        const int r = (int)(__brev((unsigned)j) >> 21);  // 11-bit reversal
+        re[r] = v * window[j];
+        im[r] = 0.f;
+    }
+    __syncthreads();
+    fft_radix2<11, 256>(re, im, twiddle, tid);
+    float acc[NCHROMA];
+#pragma unroll
+    for (int c = 0; c < NCHROMA; ++c) acc[c] = 0.f;
+#pragma unroll
+    for (int r = 0; r < 5; ++r) {
+        const int k = tid + r * 256;
+        if (k < CBIN) {  // r = 4: bin 1024, thread 0 only
+            const float p = re[k] * re[k] + im[k] * im[k];
+#pragma unroll
+            for (int c = 0; c < NCHROMA; ++c) acc[c] = fmaf(fb[c * CBIN + k], p, acc[c]);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < NCHROMA; ++c) acc[c] = wave_sum(acc[c]);
+    if ((tid & 63) == 0) {
+#pragma unroll
+        for (int c = 0; c < NCHROMA; ++c) part[tid >> 6][c] = acc[c];
+    }
+    __syncthreads();
+    if (tid < 64) {  // lanes 0..11 hold the classes; the maximum goes over the first 16 lanes (lanes 12..15 carry 0 <= every sum)
+        float v = tid < NCHROMA ? ((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid] : 0.f;
+        float m = fabsf(v);
+#pragma unroll
+        for (int s = 8; s > 0; s >>= 1) m = fmaxf(m, __shfl_xor(m, s, 64));
+        if (m < 1.1754944e-38f) m = 1.f;  // util.normalize: a frame below the smallest normal is left as it is (silence: exactly 0)
+        if (tid < NCHROMA) o[tid] = v / m;
+    }
+}
+
+// One workgroup per candidate i: cosine of a[i][f] and b[ref_index[i]][f] over the 12 classes for f < frames[i], each thread its
+// frames f = t, t + 256, ... in increasing order, then lane -> wave -> workgroup in a fixed order and one division by frames[i].
+__global__ __launch_bounds__(256) void chroma_similarity_kernel(const float* a, const float* b, const int32_t* ref_index,
+                                                                const int32_t* frames, float* out, float* per_frame, int T) {
+    __shared__ float sh[4];
+    const int i = blockIdx.x, tid = threadIdx.x;
+    const int nf = frames[i];
+    const float* ai = a + (int64_t)i * T * NCHROMA;
+    const float* bi = b + (int64_t)ref_index[i] * T * NCHROMA;
+    float sum = 0.f;
+    for (int f = tid; f < T; f += 256) {
+        float c = 0.f;
+        if (f < nf) {
+            float dot = 0.f, na = 0.f, nb = 0.f;
+#pragma unroll
+            for (int k = 0; k < NCHROMA; ++k) {
+                const float u = ai[(int64_t)f * NCHROMA + k], v = bi[(int64_t)f * NCHROMA + k];
+                dot = fmaf(u, v, dot);
+                na = fmaf(u, u, na);
+                nb = fmaf(v, v, nb);
+            }
+            c = dot / fmaxf(sqrtf(na) * sqrtf(nb), 1e-8f);
+            sum += c;
+        }
+        if (per_frame) per_frame[(int64_t)i * T + f] = c;
+    }
+    sum = block_sum(sum, sh);
+    if (tid == 0) out[i] = nf > 0 ? sum / (float)nf : 0.f;
+}
+
+}  // namespace
+
+extern "C" int apad_chroma(const float* x, const int64_t* offsets, const int64_t* offsets_host, const float* window, const float* twiddle,
+                           const float* fb, float* out, int32_t batch, int32_t target_frames, void* stream) {
+    APAD_CHECK(x && offsets && offsets_host && window && twiddle && fb && out && batch > 0 && target_frames > 0, "apad_chroma: bad operands");
+    APAD_CHECK(batch <= 65535, "apad_chroma: batch %d exceeds 65535", batch);
+    APAD_CHECK(offsets_host[0] == 0, "apad_chroma: offsets[0] must be 0");
+    for (int i = 0; i < batch; ++i) {
+        const int64_t n = offsets_host[i + 1] - offsets_host[i];
+        APAD_CHECK(n > 0, "apad_chroma: clip %d is empty", i);
+        APAD_CHECK(n / CHOP + 1 <= target_frames, "apad_chroma: clip %d has %lld frames, target_frames is %d", i, (long long)(n / CHOP + 1),
+                   target_frames);
+    }
+    hipLaunchKernelGGL(chroma_kernel, dim3((unsigned)target_frames, (unsigned)batch), dim3(256), 0, (hipStream_t)stream, x, offsets, window,
+                       twiddle, fb, out, (int)target_frames);
+    return apad_check_launch("apad_chroma");
+}
+
+extern "C" int apad_chroma_similarity(const float* a, const float* b, const int32_t* ref_index, const int32_t* ref_index_host,
+                                      const int32_t* frames, const int32_t* frames_host, float* out, float* per_frame, int32_t n, int32_t m,
+                                      int32_t T, void* stream) {
+    APAD_CHECK(a && b && ref_index && ref_index_host && frames && frames_host && out && n > 0 && m > 0 && T > 0,
+               "apad_chroma_similarity: bad operands");
+    for (int i = 0; i < n; ++i) {
+        APAD_CHECK(ref_index_host[i] >= 0 && ref_index_host[i] < m, "apad_chroma_similarity: ref_index[%d] = %d outside [0, %d)", i,
+                   ref_index_host[i], m);
+        APAD_CHECK(frames_host[i] >= 0 && frames_host[i] <= T, "apad_chroma_similarity: frames[%d] = %d outside [0, %d]", i, frames_host[i], T);
+    }
+    hipLaunchKernelGGL(chroma_similarity_kernel, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, a, b, ref_index, frames, out, per_frame,
+                       (int)T);
+    return apad_check_launch("apad_chroma_similarity");
 }

@@ -1015,6 +1015,56 @@ def clap_mel2img(x, bn_weight, bn_bias, bn_mean, bn_var, bn_eps, spec_size):
     return out
 
 
+def chroma(x, offsets, offsets_host, window, twiddle, fb, out):
+    """apad_chroma on pre-allocated buffers (hipGraph-capturable: no allocation, no read-back): x fp32 [sum n] = the 16 kHz clips packed
+    back to back, offsets int64 [B + 1] on the device and ``offsets_host`` the same on the host, window [2048], twiddle [1024, 2] and
+    fb [12, 1025] fp32 (``chroma.tables``), out fp32 [B, target_frames, 12]: each clip's chromagram, zero rows after its 1 + n // 512
+    frames."""
+    for t, name in ((x, "x"), (window, "window"), (twiddle, "twiddle"), (fb, "fb"), (out, "out")):
+        if not _req(t, "chroma." + name, torch.float32).is_contiguous():
+            raise RuntimeError(f"chroma.{name}: must be contiguous")
+    _req(offsets, "chroma.offsets", torch.int64)
+    if offsets_host.is_cuda or offsets_host.dtype != torch.int64 or not offsets_host.is_contiguous():
+        raise RuntimeError("chroma.offsets_host: expected a contiguous int64 host tensor")
+    B = offsets_host.numel() - 1
+    if offsets.numel() != B + 1 or out.dim() != 3 or out.shape[0] != B or out.shape[2] != 12:
+        raise RuntimeError(f"chroma: offsets {tuple(offsets.shape)} / out {tuple(out.shape)} do not describe {B} clips as [B + 1] / [B, frames, 12]")
+    if tuple(window.shape) != (2048,) or tuple(twiddle.shape) != (1024, 2) or tuple(fb.shape) != (12, 1025):
+        raise RuntimeError("chroma: expected window [2048], twiddle [1024, 2] and fb [12, 1025]")
+    if B and x.numel() < int(offsets_host[-1]):
+        raise RuntimeError(f"chroma.x: {x.numel()} samples, the offsets end at {int(offsets_host[-1])}")
+    L.check(L.lib().apad_chroma(x.data_ptr(), offsets.data_ptr(), offsets_host.data_ptr(), window.data_ptr(), twiddle.data_ptr(), fb.data_ptr(),
+                                out.data_ptr(), B, out.shape[1], _stream()), "apad_chroma")
+    return out
+
+
+def chroma_similarity(a, b, ref_index, ref_index_host, frames, frames_host, out=None, per_frame=None):
+    """apad_chroma_similarity: a fp32 [n, T, 12] (candidates), b fp32 [m, T, 12] (references), ref_index / frames int32 [n] on the device
+    with their host copies (validation only) -> out fp32 [n], the mean over the first frames[i] frames of the cosine between a[i] and
+    b[ref_index[i]]; ``per_frame`` fp32 [n, T] receives the cosines (0 past frames[i])."""
+    for t, name in ((a, "a"), (b, "b")):
+        if not _req(t, "chroma_similarity." + name, torch.float32).is_contiguous() or t.dim() != 3 or t.shape[2] != 12:
+            raise RuntimeError(f"chroma_similarity.{name}: expected a contiguous fp32 [clips, frames, 12] tensor, got {tuple(t.shape)}")
+    n, T = a.shape[0], a.shape[1]
+    if b.shape[1] != T:
+        raise RuntimeError(f"chroma_similarity: a has {T} frames per clip, b has {b.shape[1]}")
+    for d, h, name in ((ref_index, ref_index_host, "ref_index"), (frames, frames_host, "frames")):
+        if _req(d, "chroma_similarity." + name, torch.int32).numel() != n or not d.is_contiguous():
+            raise RuntimeError(f"chroma_similarity.{name}: expected {n} contiguous int32 values")
+        if h.is_cuda or h.dtype != torch.int32 or h.numel() != n or not h.is_contiguous():
+            raise RuntimeError(f"chroma_similarity.{name}_host: expected {n} contiguous int32 values on the host")
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device=a.device)
+    if _req(out, "chroma_similarity.out", torch.float32).numel() != n or not out.is_contiguous():
+        raise RuntimeError(f"chroma_similarity.out: expected {n} contiguous fp32 values")
+    if per_frame is not None and (tuple(_req(per_frame, "chroma_similarity.per_frame", torch.float32).shape) != (n, T) or not per_frame.is_contiguous()):
+        raise RuntimeError(f"chroma_similarity.per_frame: expected a contiguous fp32 [{n}, {T}] tensor")
+    L.check(L.lib().apad_chroma_similarity(a.data_ptr(), b.data_ptr(), ref_index.data_ptr(), ref_index_host.data_ptr(), frames.data_ptr(),
+                                           frames_host.data_ptr(), out.data_ptr(), _ptr(per_frame), n, b.shape[0], T, _stream()),
+            "apad_chroma_similarity")
+    return out
+
+
 def gaussian_sample(moments, noise, scale=1.0):
     """moments [rows, 2L] = (mean | logvar), noise [rows, L] -> (mean + exp(0.5 * clamp(logvar, -30, 20)) * noise) * scale"""
     _req(moments, "gaussian_sample.moments")

@@ -23,6 +23,12 @@ Edit-friendly DDPM inversion (``inversion="ddpm"``, ``invert``, ``InvertedSource
 PAPERS.md; PARITY UNPINNED): one more pass of the same captured loop under the SOURCE text, whose update kernel (``apad_cfg_invert_step``)
 extracts the per-step noise maps with which the stochastic sampler retraces the source; the edit run then reads those maps where it would
 have drawn noise.  A call without ``inversion=`` takes none of this.
+
+Ranking edits by fidelity (``rank_by="chroma"`` or ``{"clap": w_t, "chroma": w_f}``, ``fidelity_reference=``, ``score_fidelity``; chroma
+similarity is the AP-adapter paper's fidelity metric; PARITY UNPINNED, chroma.py): the source latents go through the same VAE
+and vocoder as the candidates, both sides become chromagrams (``apad_chroma``) and each prompt's own candidates are ordered by their
+similarity to that source (``apad_chroma_similarity``), all from the vocoder's device output.  A call without ``rank_by=`` takes none of
+this.
 """
 import math
 from dataclasses import dataclass
@@ -86,6 +92,7 @@ class AudioLDM2Pipeline:
         self.feature_extractor = feature_extractor
         self.logit_scale_t = math.log(1.0 / 0.07)  # ClapModel.logit_scale_t (logit_scale_init_value); set it from a checkpoint's value
         self.last_logits_per_text = None
+        self.last_chroma_similarity = None
         self.scheduler = scheduler or DDIMScheduler()
         self.audiomae = audiomae
         self._uncond_cache = {}
@@ -142,6 +149,69 @@ class AudioLDM2Pipeline:
         logits = ops.mix3(dots, torch.zeros_like(dots), torch.zeros_like(dots), math.exp(self.logit_scale_t))
         self.last_logits_per_text = logits[:, :n]
         return rank_waveforms(self.last_logits_per_text, torch.as_tensor(audio), num_waveforms_per_prompt)
+
+    def score_fidelity(self, audio, reference, ref_index=None):
+        """Chroma similarity of each candidate to its reference, fp32 [n] on the device (1 = the same pitch-class content in every
+        frame); also kept in ``last_chroma_similarity``.  ``audio`` [n, samples] and ``reference`` [m, samples] (or [samples]) are
+        waveforms at the vocoder's rate, scored where they are when they are on the device; candidate i is compared with reference
+        ``ref_index[i]`` (default i // (n / m): each reference serves a run of consecutive candidates)."""
+        from . import chroma
+        sr = int(self.vocoder.config.sampling_rate) if self.vocoder is not None else chroma.SR
+        self.last_chroma_similarity = chroma.chroma_similarity(audio, reference, sampling_rate=sr, ref_index=ref_index)
+        return self.last_chroma_similarity
+
+    def check_rank_arguments(self, rank_by, fidelity_reference, editing, prompt, batch):
+        """every argument check of ``rank_by=`` / ``fidelity_reference=``, on the host, before any device work.  Returns None (today's
+        path) or the weights (w_clap, w_chroma)."""
+        from .chroma import resolve_rank_by
+        weights = resolve_rank_by(rank_by)
+        if weights is None:
+            if fidelity_reference is not None:
+                raise ValueError("fidelity_reference is the reference of rank_by='chroma'; without a chroma rank_by it has no use")
+            return None
+        if not editing:
+            raise ValueError(f"rank_by={rank_by!r} measures fidelity to a source clip and needs one (source_audio=, source_mel= or source_latents=)")
+        if weights[0] != 0.0:  # what "clap" needs
+            if prompt is None:
+                raise ValueError(f"rank_by={rank_by!r}: the 'clap' weight scores the candidates against text prompts (prompt=)")
+            if self.audio_tower is None or self.feature_extractor is None or self.prompt_encoder is None or self.tokenizer is None:
+                raise NotImplementedError(f"rank_by={rank_by!r}: the 'clap' weight needs audio_tower=, feature_extractor=, prompt_encoder= and "
+                                          "tokenizer= (score_waveforms)")
+        if fidelity_reference is not None:
+            shp = tuple(fidelity_reference.shape)
+            if len(shp) not in (1, 2) or shp[-1] == 0 or (len(shp) == 2 and (shp[0] == 0 or batch % shp[0] != 0)):
+                raise ValueError(f"fidelity_reference {shp}: expected a 16 kHz waveform [samples] or [b, samples] with b dividing the batch of {batch}")
+        return weights
+
+    def _fidelity_reference(self, src, n_sources, samples):
+        """the source as the candidates' own chain renders it: its latents through the same VAE and vocoder, [n_sources, samples] on the device"""
+        if src.x0 is not None:
+            x0 = src.x0
+        else:  # the posterior draw the run started from (apad_edit_start takes the same one)
+            B, C, H, W = src.z0.shape
+            m = src.moments.contiguous()
+            noise = src.post_noise.to(m.device, m.dtype).permute(0, 2, 3, 1).reshape(B * H * W, C).contiguous()
+            x0 = ops.gaussian_sample(m, noise, src.scale).reshape(B, H, W, C).permute(0, 3, 1, 2)
+        # (prepare_edit_source repeated each source per candidate; fp32 like the latents the candidates are decoded from)
+        x0 = x0[:: x0.shape[0] // n_sources].to(self.unet.conv_in.weight.device, torch.float32).contiguous()
+        scaling = getattr(getattr(self.vae, "config", None), "scaling_factor", 1.0)
+        mel = self.vae.decode(x0 / scaling)
+        mel = getattr(mel, "sample", mel)
+        return self.vocoder(mel.squeeze(1) if mel.dim() == 4 else mel)[:, :samples]
+
+    def _rank_by_fidelity(self, weights, wav, reference, prompt, num_waveforms_per_prompt, device, dtype):
+        """candidates [B, samples] on the device -> the same waveforms on the host, each prompt's own group ordered by
+        w_clap cos_clap + w_chroma chroma, best first"""
+        from .chroma import group_order, mixed_scores
+        sim = self.score_fidelity(wav, reference.to(wav.device, torch.float32))
+        audio = wav.cpu().float()
+        logits = None
+        if weights[0] != 0.0:
+            self.score_waveforms(text=prompt, audio=audio, num_waveforms_per_prompt=num_waveforms_per_prompt, device=device, dtype=dtype,
+                                 audio_device=wav)
+            logits = self.last_logits_per_text
+        scores = mixed_scores(weights, sim, logits, math.exp(self.logit_scale_t), num_waveforms_per_prompt)
+        return torch.index_select(audio, 0, group_order(scores, num_waveforms_per_prompt))
 
     def _encode_text(self, texts, t5_max_length=None):
         """tokenise as encode_prompt does (:381-392 positive, :485-496 negative) and run the HIP prompt encoder on one CFG half"""
@@ -719,8 +789,8 @@ class AudioLDM2Pipeline:
                  attention_mask=None, negative_attention_mask=None, max_new_tokens=None, return_dict=True,
                  callback=None, callback_steps=1, cross_attention_kwargs=None, output_type="np", mel=None,
                  use_graph=True, source_audio=None, source_mel=None, source_latents=None, strength=1.0, edit_mask=None, edit_region=None,
-                 audio_guidance_scale=None, inversion=None, source_prompt=None, source_guidance_scale=3.0, source_prompt_embeds=None,
-                 source_generated_prompt_embeds=None, source_attention_mask=None):
+                 audio_guidance_scale=None, rank_by=None, fidelity_reference=None, inversion=None, source_prompt=None, source_guidance_scale=3.0,
+                 source_prompt_embeds=None, source_generated_prompt_embeds=None, source_attention_mask=None):
         """Same keyword surface and defaults as the reference (pipeline_audioldm2.py:748-775, ``output_type="np"`` included): a
         pipeline built with ``vae=`` and ``vocoder=`` returns waveforms by default; ``output_type="latent"`` is the exit for a pipeline
         that holds the denoise path only.
@@ -744,7 +814,15 @@ class AudioLDM2Pipeline:
         on the embeddings path (the negatives are the call's own) -- guided by ``source_guidance_scale``; the edit run then consumes those
         maps instead of fresh noise, under the call's own prompt and ``guidance_scale``.  The audio prompt (``mel=`` / ``audio_file=``)
         conditions both phases.  ``strength``, ``edit_mask`` / ``edit_region``, ``audio_guidance_scale``, ``num_waveforms_per_prompt`` and ranking
-        work as without it; the cost is one more pass of the run's UNet steps."""
+        work as without it; the cost is one more pass of the run's UNet steps.
+
+        Beyond the reference -- ``rank_by``: None or "clap" is the ranking above (CLAP text-audio similarity, text prompts only).  "chroma"
+        (needs a source clip; neither text prompts nor the audio tower, so it also ranks on the embeddings path) returns each prompt's own
+        ``num_waveforms_per_prompt`` candidates ordered by chroma similarity to that prompt's source, best first; {"clap": w_t, "chroma": w_f}
+        orders them by w_t cos_clap + w_f chroma (cos_clap = logits_per_text / logit_scale) and needs what both need.  The reference is the
+        source latents decoded by the same VAE and vocoder as the candidates (one more decode), or ``fidelity_reference``: a 16 kHz
+        waveform [samples] or [b, samples].  ``last_chroma_similarity`` keeps the scores in generation order; ``output_type="latent"``
+        exits before any scoring, as above."""
         dual = audio_guidance_scale is not None
         if dual:
             if mel is None and audio_file is None:
@@ -780,6 +858,9 @@ class AudioLDM2Pipeline:
         edit_k, edit_mask = self.check_edit_arguments(batch_size * num_waveforms_per_prompt, height, num_inference_steps, audio_length_in_s, latents,
                                                       source_audio, source_mel, source_latents, strength, edit_mask, edit_region)
         editing = source_audio is not None or source_mel is not None or source_latents is not None
+        rank_weights = None
+        if rank_by is not None or fidelity_reference is not None:
+            rank_weights = self.check_rank_arguments(rank_by, fidelity_reference, editing, prompt, batch_size * num_waveforms_per_prompt)
         if inversion is not None or source_prompt is not None or source_prompt_embeds is not None or source_generated_prompt_embeds is not None \
                 or source_attention_mask is not None:
             self.check_inversion_arguments(inversion, editing, eta, prompt, source_prompt, source_guidance_scale, source_prompt_embeds,
@@ -838,7 +919,17 @@ class AudioLDM2Pipeline:
             mel = self.vae.decode(out / scaling)
             mel = getattr(mel, "sample", mel)
             from .clap_features import ClapFeatureExtractor
-            if ranking and isinstance(self.feature_extractor, ClapFeatureExtractor):  # :1047-1054, scored from the device copy
+            if rank_weights is not None:  # each prompt's own candidates by fidelity to its source, scored from the device copy
+                samples = int(audio_length_in_s * 16000)
+                wav = self.vocoder(mel.squeeze(1) if mel.dim() == 4 else mel)[:, :samples].float().contiguous()
+                if fidelity_reference is None:
+                    n_sources = source_latents.shape[0] if source_latents is not None else \
+                        (1 if source_mel.dim() == 2 else source_mel.shape[0]) if source_mel is not None else \
+                        1 if isinstance(source_audio, str) else len(source_audio)
+                    fidelity_reference = self._fidelity_reference(src, n_sources, samples).float().contiguous()
+                out = self._rank_by_fidelity(rank_weights, wav, torch.as_tensor(fidelity_reference), prompt, num_waveforms_per_prompt, dev,
+                                             pe.dtype)
+            elif ranking and isinstance(self.feature_extractor, ClapFeatureExtractor):  # :1047-1054, scored from the device copy
                 wav = self.vocoder(mel.squeeze(1) if mel.dim() == 4 else mel)[:, : int(audio_length_in_s * 16000)]
                 out = self.score_waveforms(text=prompt, audio=wav.cpu().float(), num_waveforms_per_prompt=num_waveforms_per_prompt, device=dev,
                                            dtype=pe.dtype, audio_device=wav)

@@ -726,6 +726,29 @@ int apad_clap_logmel(const float* x, const int64_t* offsets, const int64_t* offs
                      const float* window, const float* twiddle, const float* mel, const int32_t* mel_range, float* out,
                      int32_t batch, int64_t max_length, int32_t hop, int32_t n_mels, int32_t padding, void* stream);
 
+/* Chroma features and chroma similarity (edit fidelity; librosa.feature.chroma_stft at its defaults -- n_fft 2048, hop 512,
+   periodic Hann, center=True with zero padding, power 2, L-infinity normalisation -- with the tuning fixed by the host's
+   filterbank; restated, PARITY UNPINNED), additive to ABI 12.
+   x / offsets / offsets_host as for apad_stft_logmel: a ragged batch of fp32 clips at 16 kHz (or whatever rate `fb` was built
+   for), every clip non-empty.  Frame f of a clip of n samples covers samples [512 f - 1024, 512 f + 1024), zeros outside the
+   clip; the clip has 1 + n / 512 frames.  out fp32 [batch][target_frames][12]: row f = fb . (re^2 + im^2 of bins 0..1024)
+   divided by its maximum over the 12 classes (by 1 when that maximum is below 1.1754944e-38: a silent frame is exactly 0, never
+   NaN); rows past a clip's last frame are 0.  window [2048] (periodic Hann), twiddle [1024][2] = (cos, -sin)(2 pi k / 2048),
+   fb [12][1025] row-major (class, bin; row 0 = C): lanes read consecutive bins of one class.  The 12 sums are reduced lane ->
+   wave -> workgroup in a fixed order (no atomics): a clip's rows do not depend on the batch around it.  No host
+   synchronisation (hipGraph-capturable).
+   -1 when a clip is empty, offsets[0] != 0, target_frames is smaller than some clip's frame count, or batch > 65535. */
+int apad_chroma(const float* x, const int64_t* offsets, const int64_t* offsets_host, const float* window, const float* twiddle,
+                const float* fb, float* out, int32_t batch, int32_t target_frames, void* stream);
+/* a fp32 [n][T][12] (candidates), b fp32 [m][T][12] (references), ref_index int32 [n] and frames int32 [n] in DEVICE memory,
+   ref_index_host / frames_host the same on the host (validation only).  out fp32 [n]: out[i] = mean over f < frames[i] of
+   dot(a[i][f], b[ref_index[i]][f]) / max(|a[i][f]| |b[ref_index[i]][f]|, 1e-8); frames[i] = 0 gives 0.  per_frame fp32
+   [n][T] (or NULL): the cosines, 0 for f >= frames[i].  One workgroup per candidate, a fixed reduction order, no atomics:
+   out[i] does not depend on the other candidates.  -1 when a ref_index is outside [0, m) or a frames[i] outside [0, T]. */
+int apad_chroma_similarity(const float* a, const float* b, const int32_t* ref_index, const int32_t* ref_index_host,
+                           const int32_t* frames, const int32_t* frames_host, float* out, float* per_frame, int32_t n, int32_t m,
+                           int32_t T, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,11 @@ Edit-friendly DDPM inversion (--inversion ddpm, with --source-prompt TEXT and --
 batch first extracts its sources' per-step noise maps under the source prompt (``pipeline.invert``), then runs the edit on those maps under
 the task's prompt.  The inversion's per-step draws are seeded by the batch's first clip, so here a clip's result does depend on its batch.
     python tools/run_sharded.py --clips 64 --steps 50 --strength 0.6 --inversion ddpm --source-prompt "a recording of a piano"
+
+Fidelity of the edits (--rank-by chroma, an edit run with --wav-dir): every written clip is scored by chroma similarity (``score_fidelity``)
+against its source as the same VAE and vocoder render it (the mean of the source's posterior, decoded), and each rank lists its clips best
+first in WAV_DIR/fidelity_rank<R>.json.
+    python tools/run_sharded.py --clips 64 --steps 50 --strength 0.6 --wav-dir out --rank-by chroma
 """
 import argparse
 import glob
@@ -125,10 +130,16 @@ def main():
                     "instead of fresh noise: one more pass of the run's UNet steps; needs --sampler ddim, runs at eta = 1")
     ap.add_argument("--source-prompt", default="", metavar="TEXT", help="--inversion: the text describing the SOURCE clip (default: the empty prompt)")
     ap.add_argument("--source-guidance", type=float, default=3.0, metavar="S", help="--inversion: the text guidance scale of the inversion pass")
+    ap.add_argument("--rank-by", choices=["chroma"], default=None, help="edit + --wav-dir: score every written clip by chroma similarity to its "
+                    "source and list each rank's clips best first in WAV_DIR/fidelity_rank<R>.json")
     ap.add_argument("--gpus", type=int, default=1, help="N > 1 without a launcher: this script starts its N ranks itself (one per GPU)")
     args = ap.parse_args()
     if args.inversion and args.sampler != "ddim":
         ap.error("--inversion ddpm needs --sampler ddim: the multistep solver has no per-step noise to invert into")
+    if args.rank_by and not (args.wav_dir and (args.strength is not None or args.edit_region is not None or args.source_dir is not None
+                                               or args.inversion is not None)):
+        ap.error("--rank-by chroma scores decoded edits against their sources: it needs an edit run (--strength / --edit-region / --source-dir / "
+                 "--inversion) and --wav-dir")
 
     from ap_adapter_amd import distributed as D
     if args.gpus > 1 and not D.launched_by_torchrun():
@@ -202,6 +213,15 @@ def main():
         os.makedirs(args.wav_dir, exist_ok=True)
         vae, voc = build_decoder(dev, dtype, small=args.small)
         pipe.vae, pipe.vocoder = vae, voc
+        scored, rendered = [], {}
+
+        def rendered_source(path):
+            """the source as this VAE and vocoder render it: the mean of its posterior, decoded"""
+            if path not in rendered:
+                mean = source_moments(path)[:, :8].reshape(1, H, 16, 8).permute(0, 3, 1, 2).contiguous()
+                rendered[path] = voc(vae.decode(mean.to(dev, dtype)).sample.squeeze(1))[:, : int(args.seconds * 16000)].float()
+            return rendered[path]
+
         for idx in sorted(local_out):
             mel = vae.decode(local_out[idx][None].to(dev, dtype) / vae.config.scaling_factor).sample
             wav = pipe.mel_spectrogram_to_waveform(mel)[0, : int(args.seconds * 16000)]
@@ -209,6 +229,14 @@ def main():
             name = f"{c['prompt']}_{idx}_ip{cfg['ap_scale']}_t{cfg['time_pooling']}_f{cfg['freq_pooling']}.wav".replace("/", "_")
             write_wav16(os.path.join(args.wav_dir, name), wav)
             n_wavs += 1
+            if args.rank_by:
+                scored.append({"file": name, "source": os.path.basename(c["audio"]),
+                               "chroma_similarity": round(float(pipe.score_fidelity(wav[None].to(dev), rendered_source(c["audio"]))[0]), 6)})
+        if args.rank_by:
+            scored.sort(key=lambda r: -r["chroma_similarity"])
+            with open(os.path.join(args.wav_dir, f"fidelity_rank{rank}.json"), "w") as f:
+                json.dump(scored, f, indent=1)
+                f.write("\n")
     allc = S.gather_clips(local_out, len(clips), rank, world)
     if rank == 0:
         finite = all(bool(torch.isfinite(x).all()) for x in allc)
@@ -217,7 +245,9 @@ def main():
                           "graph_captures": pipe.graph_captures, "graph_hits": pipe.graph_hits, "finite": finite,
                           "wavs_written_rank0": n_wavs, **({"audio_guidance": args.audio_guidance} if dual else {}),
                           **({"inversion": args.inversion, "source_prompt": args.source_prompt, "source_guidance": args.source_guidance}
-                             if args.inversion else {})}))
+                             if args.inversion else {}),
+                          **({"rank_by": args.rank_by, "chroma_similarity_mean_rank0": round(sum(r["chroma_similarity"] for r in scored) / max(len(scored), 1), 6)}
+                             if args.rank_by else {})}))
         if args.out:
             torch.save({"latents": torch.stack([x.cpu() for x in allc]), "clips": clips}, args.out)
     if world > 1:
