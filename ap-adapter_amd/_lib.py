@@ -149,6 +149,7 @@ SYMBOLS = {
     "apad_cfg_sampler_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _f32, _i32, _i64, _i32, _vp]),
     "apad_cfg_edit_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _f32, _i32, _i64, _i32, _vp]),
     "apad_cfg_dual_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i64, _i32, _vp]),
+    "apad_cfg_shaped_step": (C.c_int, [_vp] * 15 + [_i32, _i32, _vp, _i32, _f32, _i32, _i32, _i64, _i32, _vp]),
     "apad_cfg_invert_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _f32, _i32, _i32, _i64, _i32, _vp]),
     "apad_edit_start": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _i64, _i32, _i32, _vp]),
     "apad_mix3": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _f32, _i32, _vp]),

@@ -1,7 +1,8 @@
 // Small HBM-bound kernels of the path: AudioMAE token pooling, sinusoidal timestep embedding, fused
 // classifier-free-guidance + sampler update (one kernel of two or three guidance branches and one host launch path behind apad_cfg_ddim_step /
 // apad_cfg_sampler_step / apad_cfg_edit_step / apad_cfg_dual_step), the noise-extracting step of DDPM inversion beside it (apad_cfg_invert_step),
-// the edit run's start, device-side step counter.
+// the same step with guidance rescale / projected guidance, which sums over each clip (apad_cfg_shaped_step), the edit run's start, device-side
+// step counter.
 #include "common.h"
 #include "f32_ops.h"
 
@@ -222,6 +223,230 @@ __global__ __launch_bounds__(256) void cfg_step_kernel(const uint8_t* eps, float
             ld_f32v<V>(z0, i, b);
 #pragma unroll
             for (int j = 0; j < V; ++j) x[j] = edit_blend(m, x[j], kx, kz, a[j], b[j]);
+        }
+        st_f32v<V>(latents, i, x);
+        st_elemv<DT, V>(unet_in, i, x);
+        if (hist) st_f32v<V>(hist, i, m0);
+        if (eps_out) st_f32v<V>(eps_out, i, e);
+    }
+}
+
+// ---- shaped guidance: guidance rescale and adaptive projected guidance, the per-clip sums inside the step (apad_cfg_shaped_step) ----
+//
+// cfg_step_kernel with another guided-noise stage; everything after eps -- sampler_update, history, noise table, edit_blend, mask indexing,
+// eps_out -- is that kernel's, statement for statement.  The stage needs sums over a whole clip (n = h * w * C values), so ONE workgroup of 1024
+// threads owns a clip (gridDim.x = B) and walks it up to three times; a clip is at most a few hundred KB and stays in L2 between the passes.
+//
+// Per clip b and step s = *step_ptr clamped to [0, n_steps), operands widened to fp32, every sum over the clip's n elements.  Branches as in
+// guided_noise: NB = 2: e_0, c = e_1, one difference d_1 = c - e_0 with weight w_1 = gs;  NB = 3: e_0, e_A, c = e_AT, d_1 = e_A - e_0 (w_1 = s_A),
+// d_2 = e_AT - e_A (w_2 = s_T), the weights from the guidance table.  Row s of shape [n_steps][4] fp32 is (phi, eta, r, beta):
+//   1. momentum      beta != 0:  m_k <- fma(beta, m_k, d_k) -> momentum [NB - 1][B][n] fp32, and d_k := m_k.  beta == 0: neither read nor written.
+//   2. norm          r > 0:  t_k = min(1, r / ||d_k||_2), a zero norm gives 1;  otherwise t_k = 1.
+//   3. projection    p_k = <d_k, c> / <c, c>, a zero denominator gives 0;  q_k = (1 - eta) p_k (eta == 1: q_k = 0, nothing divided);
+//                    u_k = t_k * fma(-q_k, c, d_k)  -- orthogonal + eta * parallel = d - (1 - eta) * parallel (Sadat et al. 2024)
+//   4. guided noise  g = fma(w_2, u_2, fma(w_1, u_1, e_0))  (NB = 2: fma(w_1, u_1, e_0)) -- diffusers' non-original APG form, plain CFG at eta = 1
+//   5. rescale       phi > 0:  f = fma(phi, std(c) / std(g), 1 - phi), std(g) == 0 or n == 1 gives f = 1;  g <- f * g.  std is the unbiased one
+//                    (n - 1), from centred values: sqrt(sum (x - mean)^2 / (n - 1))  (Lin et al. 2024)
+//   6. eps = (dtype) g, the fp32 value rounded once, in every form and dtype (asm barrier for f16, as the three-branch guided_noise)
+// A factor that is off is not applied at all: q_k == 0 skips the fma, t_k == 1 and phi == 0 skip the multiplies.  So the row (0, 1, 0, 0) leaves
+// u_k the bits of d_k and g the very fma chain of guided_noise: the kernel then writes cfg_step_kernel's bits (except where that kernel leaves
+// the f16 rounding to the compiler: two branches, f16, scalar form), and a schedule may switch the stage on for part of a run.
+//
+// Passes, each thread visiting the same elements in each (thread t: vectors t, t + 1024, ...), so what pass 1 stores pass 3 re-reads itself:
+//   pass 1 (any of beta != 0, r > 0, eta != 1, phi > 0)   momentum update;  <d_k, c>, <d_k, d_k>, sum d_k, <c, c>, sum c, sum e_0.
+//          mean(g) follows from these: g is linear in the vectors once t_k, q_k are known.
+//   pass 2 (phi > 0 and n > 1)                            sum (g - mean g)^2, sum (c - mean c)^2
+//   pass 3                                                g, f, eps, then the step
+// Sums: each thread adds its elements in index order (fma for the products), a xor butterfly inside the wave (a + b == b + a: every lane holds the
+// same bits), the 16 wave sums through LDS, added in order 0 .. 15 by one thread per sum and read back by all.  The order depends on n and the form only, so a clip's
+// outputs are the same bits whatever B is and wherever the clip sits in the batch.  No atomics, no host reads.
+// stats (optional) [B][8] fp32 = (t_1, q_1, t_2, q_2, mean g, std g, std c, f) per clip; NB = 2: (t_2, q_2) = (1, 0); phi == 0: (0, 0, 0, 1) in
+// the last four (not computed).  STEP_VEC additionally needs 8 | n: a clip must start on a 16-byte boundary.
+constexpr int SHAPED_THREADS = 1024, SHAPED_WAVES = SHAPED_THREADS / 64;
+
+template <int NS> __device__ __forceinline__ void shaped_block_sum(float (&v)[NS], float (*part)[SHAPED_WAVES]) {
+#pragma unroll
+    for (int k = 0; k < NS; ++k) v[k] = wave_sum(v[k]);
+    __syncthreads();  // (the previous sum's partials have been read by everyone)
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < NS; ++k) part[k][threadIdx.x >> 6] = v[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < NS) {  // thread k adds sum k's wave partials in order 0 .. 15
+        float s = part[threadIdx.x][0];
+#pragma unroll
+        for (int w = 1; w < SHAPED_WAVES; ++w) s += part[threadIdx.x][w];
+        part[threadIdx.x][0] = s;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < NS; ++k) v[k] = part[k][0];
+}
+
+// e_0, c and the NB - 1 differences of elements i .. i + V of the batch; with ``m`` (a momentum row, after pass 1) the running averages instead
+template <int DT, int V, int NB>
+__device__ __forceinline__ void shaped_load(const uint8_t* eps, const float* m, int64_t total, int64_t i, float (&e0)[V], float (&c)[V],
+                                            float (&d)[NB - 1][V]) {
+    float eb[NB][V];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) ld_elemv<DT, V>(eps, b * total + i, eb[b]);
+#pragma unroll
+    for (int j = 0; j < V; ++j) e0[j] = eb[0][j], c[j] = eb[NB - 1][j];
+#pragma unroll
+    for (int k = 0; k < NB - 1; ++k) {
+        if (m) {
+            ld_f32v<V>(m, k * total + i, d[k]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < V; ++j) d[k][j] = eb[k + 1][j] - eb[k][j];
+        }
+    }
+}
+
+// steps 3 and 4 for one element: g before the rescale
+template <int K> __device__ __forceinline__ float shaped_guided(float e0, float c, const float (&d)[K], const float (&w)[K], const float (&t)[K],
+                                                                const float (&q)[K]) {
+#pragma clang fp contract(off)
+    float g = e0;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        float u = d[k];
+        if (q[k] != 0.f) u = fmaf(-q[k], c, u);
+        if (t[k] != 1.f) u = t[k] * u;
+        g = fmaf(w[k], u, g);
+    }
+    return g;
+}
+
+template <int DT, int FORM, int NB>
+__global__ __launch_bounds__(SHAPED_THREADS) void cfg_shaped_step_kernel(const uint8_t* eps, float* latents, uint8_t* unet_in, float* eps_out, float* hist,
+                                                                         const float* noise, const float* coef, const float* keep, const float* x0,
+                                                                         const float* z0, const float* mask, int mask_per_clip, int C, int64_t n,
+                                                                         const int32_t* step_ptr, int n_steps, float gs, int64_t total,
+                                                                         const float* guidance, const float* shape, float* momentum, float* stats) {
+#pragma clang fp contract(off)
+    static_assert(FORM == STEP_VEC || FORM == STEP_SCALAR, "the shaped step reads the six-column table");
+    constexpr int V = FORM == STEP_VEC ? 8 : 1, K = NB - 1, NS = 3 * K + 3;
+    __shared__ float part[NS][SHAPED_WAVES];
+    int step = step_ptr ? *step_ptr : 0;
+    step = step < 0 ? 0 : (step >= n_steps ? n_steps - 1 : step);
+    const float* r = coef + 6 * step;
+    const float c_x = r[0], c_e = r[1], c_m = r[2], c_z = r[3], d_x = r[4], d_e = r[5];
+    float w[K], t[K], q[K];
+    w[0] = NB == 3 ? guidance[2 * step] : gs;
+    if constexpr (NB == 3) w[1] = guidance[2 * step + 1];
+#pragma unroll
+    for (int k = 0; k < K; ++k) t[k] = 1.f, q[k] = 0.f;
+    const float phi = shape[4 * step], eta = shape[4 * step + 1], rr = shape[4 * step + 2], beta = momentum ? shape[4 * step + 3] : 0.f;
+    const float kx = mask ? keep[2 * step] : 0.f, kz = mask ? keep[2 * step + 1] : 0.f;
+    const bool use_m1 = hist && c_m != 0.f, use_z = noise && c_z != 0.f;
+    const float* z = noise + (use_z ? (int64_t)step * total : 0);
+    const int64_t npix = n / C;                  // pixels per clip
+    const int64_t base = (int64_t)blockIdx.x * n;  // this workgroup's clip
+    const int64_t first = (int64_t)threadIdx.x * V, stride = (int64_t)SHAPED_THREADS * V;
+    const float* mom = beta != 0.f ? momentum : nullptr;  // where passes 2 and 3 find d_k
+    float f = 1.f, mean_g = 0.f, mean_c = 0.f, std_g = 0.f, std_c = 0.f;
+
+    if (beta != 0.f || rr > 0.f || eta != 1.f || phi > 0.f) {  // pass 1
+        float s[NS];  // per k: <d_k, c>, <d_k, d_k>, sum d_k;  then <c, c>, sum c, sum e_0
+#pragma unroll
+        for (int k = 0; k < NS; ++k) s[k] = 0.f;
+        for (int64_t j = first; j < n; j += stride) {
+            const int64_t i = base + j;
+            float e0[V], c[V], d[K][V];
+            shaped_load<DT, V, NB>(eps, nullptr, total, i, e0, c, d);
+            if (mom) {
+#pragma unroll
+                for (int k = 0; k < K; ++k) {
+                    float m[V];
+                    ld_f32v<V>(momentum, k * total + i, m);
+#pragma unroll
+                    for (int l = 0; l < V; ++l) d[k][l] = fmaf(beta, m[l], d[k][l]);
+                    st_f32v<V>(momentum, k * total + i, d[k]);
+                }
+            }
+#pragma unroll
+            for (int l = 0; l < V; ++l) {
+#pragma unroll
+                for (int k = 0; k < K; ++k) {
+                    s[3 * k] = fmaf(d[k][l], c[l], s[3 * k]);
+                    s[3 * k + 1] = fmaf(d[k][l], d[k][l], s[3 * k + 1]);
+                    s[3 * k + 2] += d[k][l];
+                }
+                s[3 * K] = fmaf(c[l], c[l], s[3 * K]);
+                s[3 * K + 1] += c[l];
+                s[3 * K + 2] += e0[l];
+            }
+        }
+        shaped_block_sum<NS>(s, part);
+        float sum_g = s[3 * K + 2];
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const float nrm = sqrtf(s[3 * k + 1]);
+            if (rr > 0.f && nrm > rr) t[k] = rr / nrm;
+            if (eta != 1.f && s[3 * K] != 0.f) q[k] = (1.f - eta) * (s[3 * k] / s[3 * K]);
+            sum_g = fmaf(w[k] * t[k], fmaf(-q[k], s[3 * K + 1], s[3 * k + 2]), sum_g);
+        }
+        if (phi > 0.f) mean_g = sum_g / (float)n, mean_c = s[3 * K + 1] / (float)n;
+    }
+
+    if (phi > 0.f && n > 1) {  // pass 2
+        float s[2] = {0.f, 0.f};
+        for (int64_t j = first; j < n; j += stride) {
+            float e0[V], c[V], d[K][V];
+            shaped_load<DT, V, NB>(eps, mom, total, base + j, e0, c, d);
+#pragma unroll
+            for (int l = 0; l < V; ++l) {
+                float dl[K];
+#pragma unroll
+                for (int k = 0; k < K; ++k) dl[k] = d[k][l];
+                const float a = shaped_guided<K>(e0[l], c[l], dl, w, t, q) - mean_g, b = c[l] - mean_c;
+                s[0] = fmaf(a, a, s[0]);
+                s[1] = fmaf(b, b, s[1]);
+            }
+        }
+        shaped_block_sum<2>(s, part);
+        std_g = sqrtf(s[0] / (float)(n - 1)), std_c = sqrtf(s[1] / (float)(n - 1));
+        if (std_g != 0.f) f = fmaf(phi, std_c / std_g, 1.f - phi);
+    }
+    if (stats && threadIdx.x == 0) {
+        float* o = stats + 8 * (int64_t)blockIdx.x;
+        o[0] = t[0], o[1] = q[0], o[2] = t[K - 1], o[3] = q[K - 1];
+        if constexpr (NB == 2) o[2] = 1.f, o[3] = 0.f;
+        o[4] = mean_g, o[5] = std_g, o[6] = std_c, o[7] = f;
+    }
+
+    for (int64_t j = first; j < n; j += stride) {  // pass 3: cfg_step_kernel's body on the shaped noise
+        const int64_t i = base + j;
+        float e0[V], c[V], d[K][V], x[V], m1[V], zz[V], e[V], m0[V];
+        shaped_load<DT, V, NB>(eps, mom, total, i, e0, c, d);
+        ld_f32v<V>(latents, i, x);
+#pragma unroll
+        for (int l = 0; l < V; ++l) m1[l] = zz[l] = 0.f;
+        if (use_m1) ld_f32v<V>(hist, i, m1);
+        if (use_z) ld_f32v<V>(z, i, zz);
+#pragma unroll
+        for (int l = 0; l < V; ++l) {
+            float dl[K];
+#pragma unroll
+            for (int k = 0; k < K; ++k) dl[k] = d[k][l];
+            float g = shaped_guided<K>(e0[l], c[l], dl, w, t, q);
+            if (phi > 0.f) g = f * g;
+            if constexpr (DT == APAD_F16) asm volatile("" : "+v"(g));  // (the fp32 value exists before the f16 rounding)
+            e[l] = (float)(typename ET<DT>::elem)g;
+            float xn;
+            sampler_update<DT, FORM>(c_x, c_e, c_m, c_z, d_x, d_e, x[l], e[l], m1[l], zz[l], xn, m0[l]);
+            x[l] = xn;
+        }
+        if (mask) {
+            const int64_t pix = V == 8 ? (i >> 3) : i / C;  // over the whole batch: clip * npix + pixel
+            const float m = mask[mask_per_clip ? pix : pix % npix];
+            float a[V], b[V];
+            ld_f32v<V>(x0, i, a);
+            ld_f32v<V>(z0, i, b);
+#pragma unroll
+            for (int l = 0; l < V; ++l) x[l] = edit_blend(m, x[l], kx, kz, a[l], b[l]);
         }
         st_f32v<V>(latents, i, x);
         st_elemv<DT, V>(unet_in, i, x);
@@ -481,6 +706,9 @@ struct StepOperands {
     void* stream;
     int branches;  // 2, or 3: the guidance table instead of gs
     bool ddim;     // apad_cfg_ddim_step: two-column table of a length it is not told, scalar form only
+    // apad_cfg_shaped_step (cfg_shaped_step_kernel, one workgroup per clip): the (phi, eta, r, beta) table, and null or its optional buffers
+    const float* shape;
+    float *momentum, *stats;
 };
 
 using step_kernel_t = decltype(&cfg_step_kernel<APAD_BF16, STEP_VEC, 2>);
@@ -489,7 +717,13 @@ template <int DT> step_kernel_t step_kernel(int form, int branches) {
     return form == STEP_VEC ? cfg_step_kernel<DT, STEP_VEC, 2> : form == STEP_SCALAR ? cfg_step_kernel<DT, STEP_SCALAR, 2> : cfg_step_kernel<DT, STEP_DDIM, 2>;
 }
 
-// Every check, the choice of form, the grid and the launch of the four step entry points; ``fn`` prefixes the messages.
+using shaped_kernel_t = decltype(&cfg_shaped_step_kernel<APAD_BF16, STEP_VEC, 2>);
+template <int DT> shaped_kernel_t shaped_kernel(bool vec, int branches) {
+    if (branches == 3) return vec ? cfg_shaped_step_kernel<DT, STEP_VEC, 3> : cfg_shaped_step_kernel<DT, STEP_SCALAR, 3>;
+    return vec ? cfg_shaped_step_kernel<DT, STEP_VEC, 2> : cfg_shaped_step_kernel<DT, STEP_SCALAR, 2>;
+}
+
+// Every check, the choice of form, the grid and the launch of the step entry points; ``fn`` prefixes the messages.
 int step_launch(const char* fn, const StepOperands& a) {
     APAD_CHECK(a.eps && a.latents && a.unet_in && a.coef, "%s: null operand", fn);
     APAD_CHECK(a.branches == 2 || a.guidance, "%s: null guidance table", fn);
@@ -505,15 +739,25 @@ int step_launch(const char* fn, const StepOperands& a) {
     // with a mask C == 8, which makes one 8-element vector one pixel.  apad_cfg_ddim_step launches the scalar form only: the 16-byte form rounds
     // differently (sampler_update)
     const uintptr_t bases = (uintptr_t)a.eps | (uintptr_t)a.latents | (uintptr_t)a.unet_in | (uintptr_t)a.eps_out | (uintptr_t)a.history |
-                            (uintptr_t)a.noise | (uintptr_t)a.x0 | (uintptr_t)a.z0;
+                            (uintptr_t)a.noise | (uintptr_t)a.x0 | (uintptr_t)a.z0 | (uintptr_t)a.momentum;
     const bool vec = !a.ddim && total % 8 == 0 && bases % 16 == 0 && (!a.mask || a.C == 8);
+    const int per_clip = a.mask_batch == a.B && a.B > 1;
+    if (a.shape) {  // one workgroup per clip, which must then start on a 16-byte boundary for the 16-byte form: 8 | n
+        const bool svec = vec && a.n % 8 == 0;
+        const shaped_kernel_t kern = a.dtype == APAD_BF16  ? shaped_kernel<APAD_BF16>(svec, a.branches)
+                                     : a.dtype == APAD_F32 ? shaped_kernel<APAD_F32>(svec, a.branches)
+                                                           : shaped_kernel<APAD_F16>(svec, a.branches);
+        hipLaunchKernelGGL(kern, dim3((unsigned)a.B), dim3(SHAPED_THREADS), 0, (hipStream_t)a.stream, (const uint8_t*)a.eps, a.latents,
+                           (uint8_t*)a.unet_in, a.eps_out, a.history, a.noise, a.coef, a.keep, a.x0, a.z0, a.mask, per_clip, a.mask ? a.C : 1, a.n,
+                           a.step_ptr, a.n_steps, a.gs, total, a.guidance, a.shape, a.momentum, a.stats);
+        return apad_check_launch(fn);
+    }
     int64_t blocks = ((vec ? total / 8 : total) + 255) / 256;
     if (blocks > 2048) blocks = 2048;
     const int form = a.ddim ? STEP_DDIM : vec ? STEP_VEC : STEP_SCALAR;
     const step_kernel_t kern = a.dtype == APAD_BF16  ? step_kernel<APAD_BF16>(form, a.branches)
                                : a.dtype == APAD_F32 ? step_kernel<APAD_F32>(form, a.branches)
                                                      : step_kernel<APAD_F16>(form, a.branches);
-    const int per_clip = a.mask_batch == a.B && a.B > 1;
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)a.stream, (const uint8_t*)a.eps, a.latents, (uint8_t*)a.unet_in, a.eps_out,
                        a.history, a.noise, a.coef, a.keep, a.x0, a.z0, a.mask, per_clip, a.mask ? a.C : 1, a.n, a.step_ptr, a.n_steps, a.gs, total,
                        a.guidance);
@@ -560,6 +804,21 @@ extern "C" int apad_cfg_dual_step(const void* eps3, float* latents, void* unet_i
     a.guidance = guidance, a.keep = keep, a.x0 = x0, a.z0 = z0, a.mask = mask, a.mask_batch = mask_batch, a.C = C;
     a.step_ptr = step_ptr, a.n_steps = n_steps, a.B = B, a.n = n, a.dtype = dtype, a.stream = stream, a.branches = 3;
     return step_launch("apad_cfg_dual_step", a);
+}
+
+extern "C" int apad_cfg_shaped_step(const void* eps, float* latents, void* unet_in, float* eps_out, float* history, const float* noise,
+                                    const float* coef, const float* guidance, const float* shape, float* momentum, float* stats, const float* keep,
+                                    const float* x0, const float* z0, const float* mask, int32_t mask_batch, int32_t C, const int32_t* step_ptr,
+                                    int32_t n_steps, float guidance_scale, int32_t branches, int32_t B, int64_t n, int32_t dtype, void* stream) {
+    const char* fn = "apad_cfg_shaped_step";
+    APAD_CHECK(branches == 2 || branches == 3, "%s: branches = %d must be 2 or 3", fn, branches);
+    APAD_CHECK(shape, "%s: null shape table", fn);
+    StepOperands a = {};
+    a.eps = eps, a.latents = latents, a.unet_in = unet_in, a.eps_out = eps_out, a.history = history, a.noise = noise, a.coef = coef;
+    a.guidance = guidance, a.keep = keep, a.x0 = x0, a.z0 = z0, a.mask = mask, a.mask_batch = mask_batch, a.C = C;
+    a.step_ptr = step_ptr, a.n_steps = n_steps, a.gs = branches == 3 ? 0.f : guidance_scale, a.B = B, a.n = n, a.dtype = dtype, a.stream = stream;
+    a.branches = branches, a.shape = shape, a.momentum = momentum, a.stats = stats;
+    return step_launch(fn, a);
 }
 
 namespace {

@@ -1267,6 +1267,41 @@ def cfg_dual_step(eps3, latents, unet_in, coef, guidance, step_ptr, eps_out=None
     L.check(L.lib().apad_cfg_dual_step(*bufs, guidance.data_ptr(), *edit, *step, *geom), "apad_cfg_dual_step")
 
 
+def cfg_shaped_step(eps, latents, unet_in, coef, shape, step_ptr, guidance_scale=None, guidance=None, momentum=None, stats=None, eps_out=None,
+                    history=None, noise=None, keep=None, x0=None, z0=None, mask=None, channels=8):
+    """cfg_edit_step (eps [2B, n...], ``guidance_scale``) or cfg_dual_step (eps [3B, n...], ``guidance`` fp32 [steps, 2]) with guidance rescale and
+    adaptive projected guidance in the guided-noise stage (include/apadapter_hip.h, apad_cfg_shaped_step): shape fp32 [steps, 4] = (phi, eta, r,
+    beta) per step (``scheduler.shape_table``), read on the device at row *step_ptr; momentum fp32 [branches - 1, B, n...], carried from step to
+    step on the rows with beta != 0 (the caller zeroes it before a run); stats (optional) fp32 [B, 8] receives (t_1, q_1, t_2, q_2, mean g,
+    std g, std c, f) per clip.  Exactly one of ``guidance_scale`` / ``guidance`` is given.  What only the table's values decide is the check of
+    whoever builds the table on the host (the pipeline): a row with beta != 0 needs ``momentum`` (without it every beta reads as 0), and phi > 0
+    needs n >= 2 (n = 1 gives f = 1)."""
+    fn = "cfg_shaped_step"
+    if (guidance is None) == (guidance_scale is None):
+        raise RuntimeError(f"{fn}: pass guidance_scale (two branches) or the guidance table (three branches), not both or neither")
+    branches = 2 if guidance is None else 3
+    if branches == 2 and eps.dim() > 1 and eps.shape[0] != 2 * latents.shape[0]:
+        raise RuntimeError(f"{fn}: eps2 must hold two branches [2B, n] of latents [B, n] = {tuple(latents.shape)}, got {tuple(eps.shape)}")
+    bufs, edit, step, geom = _cfg_step(fn, branches, eps, latents, unet_in, coef, step_ptr, eps_out, history, noise, keep, x0, z0, mask, channels)
+    for t, name, want in ((guidance, "guidance", (step[1], 2)), (shape, "shape", (step[1], 4)), (stats, "stats", (geom[0], 8))):
+        if t is not None and (_req(t, f"{fn}.{name}", torch.float32).dim() != 2 or tuple(t.shape) != want or not t.is_contiguous()):
+            raise RuntimeError(f"{fn}.{name}: expected a contiguous fp32 {list(want)} table, got {tuple(t.shape)}")
+    if shape is None:
+        raise RuntimeError(f"{fn}.shape: required")
+    if momentum is not None and (_req(momentum, fn + ".momentum", torch.float32).numel() != (branches - 1) * latents.numel()
+                                 or not momentum.is_contiguous()):
+        raise RuntimeError(f"{fn}.momentum: expected {(branches - 1) * latents.numel()} contiguous fp32 values [{branches - 1}, B, n], got "
+                           f"{tuple(momentum.shape)}")
+    for t, name in ((eps, "eps"), (unet_in, "unet_in"), (latents, "latents")):
+        if not t.is_contiguous():
+            raise RuntimeError(f"{fn}.{name}: must be contiguous")
+    for t in (eps, unet_in, coef, shape, guidance, momentum, stats, step_ptr, eps_out, history, noise, keep, x0, z0, mask):
+        if t is not None and t.device != latents.device:
+            raise RuntimeError(f"{fn}: every operand must live on latents' device {latents.device}, got {t.device}")
+    L.check(L.lib().apad_cfg_shaped_step(*bufs, _ptr(guidance), shape.data_ptr(), _ptr(momentum), _ptr(stats), *edit, *step,
+                                         0.0 if guidance_scale is None else float(guidance_scale), branches, *geom), "apad_cfg_shaped_step")
+
+
 def cfg_invert_step(eps, latents, unet_in, coef, keep, x0, noise, step_ptr, guidance_scale=None, guidance=None, eps_out=None):
     """the edit-friendly DDPM inversion step: eps [2B, n...] guided by ``guidance_scale`` (two branches), or [3B, n...] guided by ``guidance``
     fp32 [steps, 2] = (s_A, s_T) per step (three branches, cfg_dual_step's); coef fp32 [steps, 6] with std in column 3 (DDIM eta > 0), keep

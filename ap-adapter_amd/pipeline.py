@@ -37,7 +37,7 @@ from typing import Optional, Union
 import torch
 
 from . import ops
-from .scheduler import DDIMScheduler, DPMSolverMultistepScheduler, edit_start_index, guidance_table
+from .scheduler import DDIMScheduler, DPMSolverMultistepScheduler, edit_start_index, guidance_table, shape_table
 
 
 @dataclass
@@ -101,6 +101,7 @@ class AudioLDM2Pipeline:
         self.graph_captures = 0
         self.graph_hits = 0
         self.last_noise_pred = None
+        self.last_guidance_stats = None  # fp32 [B, 8] of the most recent call with guidance_rescale= / apg_eta= (apad_cfg_shaped_step's stats)
 
     # ---- pieces ----
     def mel_spectrogram_to_waveform(self, mel_spectrogram):
@@ -450,6 +451,21 @@ class AudioLDM2Pipeline:
                 raise ValueError(f"source_guidance_scale={source_guidance_scale!r} must be a float > 1: the two-branch step needs classifier-free "
                                  "guidance (or pass audio_guidance_scale= for the three-branch step, where any value >= 0 holds)")
 
+    @staticmethod
+    def check_shaping_arguments(guidance_rescale, apg_eta, apg_norm_threshold, apg_momentum, num_inference_steps, start=0):
+        """the four keywords of guidance rescale and adaptive projected guidance, on the host, before any device work; each ValueError names the
+        offending argument.  Returns None when the stage is off (the defaults), else the fp32 [N - start, 4] table of ``scheduler.shape_table``
+        (``apg_eta=None`` with a rescale: eta = 1, no projection)."""
+        off = lambda v: not isinstance(v, torch.Tensor) and not hasattr(v, "__len__") and v is not None and float(v) == 0.0
+        if apg_eta is None:
+            for n, v in (("apg_norm_threshold", apg_norm_threshold), ("apg_momentum", apg_momentum)):
+                if not off(v):
+                    raise ValueError(f"{n}={v!r} belongs to adaptive projected guidance and needs apg_eta= (apg_eta=1.0 keeps plain guidance "
+                                     "and applies only the threshold / momentum)")
+            if off(guidance_rescale):
+                return None
+        return shape_table(guidance_rescale, 1.0 if apg_eta is None else apg_eta, apg_norm_threshold, apg_momentum, num_inference_steps, start)
+
     def prepare_edit_source(self, batch, height, device, generator, source_audio=None, source_mel=None, source_latents=None, mask=None):
         """The ``EditSource`` of a call.  Generator draw order, each on the generator's own device like ``prepare_latents``: the posterior
         noise [B, C, H, W] (skipped for ``source_latents``), then z0 [B, C, H, W]; a stochastic sampler's per-step noise follows in
@@ -496,12 +512,13 @@ class AudioLDM2Pipeline:
         if e["emask"] is not None:
             e["emask"].copy_(src.mask.to(lat.device, torch.float32).reshape(e["emask"].shape))
 
-    def _fill_step_buffers(self, e, H, W, latents_nchw, src, start_coefs, conditions, gtab, generator, step_noise=None):
+    def _fill_step_buffers(self, e, H, W, latents_nchw, src, start_coefs, conditions, gtab, generator, step_noise=None, stab=None):
         """What one run writes into a step's static buffers before its first step, on a cache hit and after the capture path has allocated
         them: the start (``latents_nchw``, or the noised source of an edit run with its x0 / z0 / mask), the conditions
         (generated_prompt_embeds, prompt_embeds, attention_mask), the step counter, the guidance table, the zeroed history and the per-step
         noise -- the only draws from ``generator`` here, after the edit source's (``prepare_edit_source``); ``step_noise`` (the ``z`` of an
-        ``InvertedSource``) is copied in its place, and nothing is drawn."""
+        ``InvertedSource``) is copied in its place, and nothing is drawn.  ``stab`` (a shaped run: guidance rescale / projected guidance) fills
+        the shape table, and the momentum of the guidance differences starts from zero."""
         lat = e["lat"]
         B, _, C = lat.shape
         if src is None:
@@ -515,6 +532,10 @@ class AudioLDM2Pipeline:
         e["step_ptr"].zero_()
         if e["hist"] is not None:
             e["hist"].zero_()
+        if stab is not None:
+            e["shape"].copy_(stab)
+            if e["momentum"] is not None:
+                e["momentum"].zero_()
         if step_noise is not None:
             self._copy_step_noise(e["noise"], step_noise)
         elif e["noise"] is not None:
@@ -549,7 +570,7 @@ class AudioLDM2Pipeline:
     @torch.no_grad()
     def denoise(self, latents_nchw, generated_prompt_embeds, prompt_embeds, attention_mask, num_inference_steps,
                 guidance_scale, use_graph=True, callback=None, callback_steps=1, keep_noise_pred=False, eta=0.0, generator=None, *,
-                source=None, start=0, audio_guidance_scale=None):
+                source=None, start=0, audio_guidance_scale=None, guidance_rescale=0.0, apg_eta=None, apg_norm_threshold=0.0, apg_momentum=0.0):
         """CFG + scheduler loop (:983-1031).  With ``use_graph`` the step is captured ONCE per (batch, token counts, steps, guidance,
         weights, sampler) and kept: later calls copy their latents / conditions into the graph's static buffers, refresh the hoisted
         K/V in place and replay -- no warm-up step, no re-capture (a sharded job runs many batches through one pipeline).
@@ -572,9 +593,22 @@ class AudioLDM2Pipeline:
 
         ``source`` an ``InvertedSource`` (from ``invert``): the edit phase of DDPM inversion.  The run is the edit run above with one
         difference -- its per-step noise buffer receives ``source.z`` instead of draws from ``generator`` -- and must be on the grid the
-        maps were extracted on: the same scheduler, ``num_inference_steps``, ``start`` and ``eta`` (a ValueError names the field)."""
+        maps were extracted on: the same scheduler, ``num_inference_steps``, ``start`` and ``eta`` (a ValueError names the field).
+
+        ``guidance_rescale`` (phi in [0, 1]; Lin et al. 2024) and ``apg_eta`` / ``apg_norm_threshold`` / ``apg_momentum`` (adaptive projected
+        guidance; Sadat et al. 2024; PARITY UNPINNED: no counterpart in the reference) shape the guided noise before the sampler
+        sees it -- the arithmetic is written out at ``apad_cfg_shaped_step`` (include/apadapter_hip.h); it acts on the noise prediction, as
+        diffusers' guider does, not on the denoised prediction of the APG paper.  Each is a float or a sequence of ``num_inference_steps``
+        floats (``scheduler.shape_table``); ``apg_eta=None`` is APG off, and the threshold and the momentum need it.  When any is active the
+        update kernel is ``apad_cfg_shaped_step`` on the six-column table, two or three branches, every sampler / edit / mask combination;
+        the values are a device table refilled on a cache hit, so a sweep or a per-step schedule replays one captured graph (the key only
+        says that the stage is on and whether it carries momentum).  ``keep_noise_pred`` then returns the shaped noise, and
+        ``last_guidance_stats`` the last step's per-clip scalars.  With an ``InvertedSource`` the knobs shape this edit pass only: ``invert``
+        has none, so inverting and denoising under one condition no longer retraces the source when a knob is on."""
+        stab = self.check_shaping_arguments(guidance_rescale, apg_eta, apg_norm_threshold, apg_momentum, num_inference_steps, start)
         e, (B, Cc, H, W) = self._run(latents_nchw, generated_prompt_embeds, prompt_embeds, attention_mask, num_inference_steps, guidance_scale,
-                                     use_graph, callback, callback_steps, keep_noise_pred, eta, generator, source, start, audio_guidance_scale)
+                                     use_graph, callback, callback_steps, keep_noise_pred, eta, generator, source, start, audio_guidance_scale,
+                                     stab=stab)
         eps_out = e["eps_out"]
         self.last_noise_pred = None if eps_out is None else eps_out.reshape(B, H, W, Cc).permute(0, 3, 1, 2).clone()
         return e["lat"].reshape(B, H, W, Cc).permute(0, 3, 1, 2).contiguous()
@@ -619,11 +653,13 @@ class AudioLDM2Pipeline:
                              f"{None if src.z is None else (tuple(src.z.shape), src.z.dtype)}")
 
     def _run(self, latents_nchw, generated_prompt_embeds, prompt_embeds, attention_mask, num_inference_steps, guidance_scale, use_graph, callback,
-             callback_steps, keep_noise_pred, eta, generator, source, start, audio_guidance_scale, invert=False):
+             callback_steps, keep_noise_pred, eta, generator, source, start, audio_guidance_scale, invert=False, stab=None):
         """the loop behind ``denoise`` and (``invert=True``: another plan, another update op, nothing else) ``invert``; returns the step's
-        buffers (on a cache hit: the cached entry) and (B, C, H, W)"""
+        buffers (on a cache hit: the cached entry) and (B, C, H, W).  ``stab`` (``check_shaping_arguments``; None = off): the shaped step."""
         unet = self.unet
         dual = audio_guidance_scale is not None
+        shaped = stab is not None
+        six = dual or shaped  # both read the six-column table, deterministic DDIM too (``sampler_rows(0.0)``)
         dtype = unet.conv_in.weight.dtype
         src = None
         if source is not None:
@@ -643,12 +679,12 @@ class AudioLDM2Pipeline:
         sched.set_timesteps(num_inference_steps)
         step_noise = None
         if src is None:
-            plan, n_run, emask_shape, start_coefs = (sched.sampler_plan(eta, dual=True) if dual else sched.sampler_plan(eta)), num_inference_steps, None, None
+            plan, n_run, emask_shape, start_coefs = (sched.sampler_plan(eta, dual=True) if six else sched.sampler_plan(eta)), num_inference_steps, None, None
         elif invert:  # the inversion's own plan; the source's mask belongs to the edit phase
             plan = sched.inversion_plan(eta, start=start, dual=dual)
             n_run, emask_shape, start_coefs = num_inference_steps - plan.start, None, sched.add_noise_coefs(plan.start)
         else:
-            plan = (sched.sampler_plan(eta, start=start, masked=src.mask is not None, dual=True) if dual
+            plan = (sched.sampler_plan(eta, start=start, masked=src.mask is not None, dual=True) if six
                     else sched.sampler_plan(eta, start=start, masked=src.mask is not None))
             n_run = num_inference_steps - plan.start
             start_coefs = sched.add_noise_coefs(plan.start)
@@ -661,6 +697,12 @@ class AudioLDM2Pipeline:
         # (s_A, s_T) of the steps this run visits; checked here, on the host, before any device work
         gtab = guidance_table(audio_guidance_scale, guidance_scale, num_inference_steps, plan.start) if dual else None
         conditions = (generated_prompt_embeds, prompt_embeds, attention_mask)
+        if shaped:  # what only the table's values decide is checked here, on the host copy
+            if tuple(stab.shape) != (n_run, 4):
+                raise ValueError(f"the shape table holds {tuple(stab.shape)}; this run's steps need {(n_run, 4)}")
+            carries = bool((stab[:, 3] != 0).any())
+            if bool((stab[:, 0] > 0).any()) and Cc * H * W < 2:
+                raise ValueError("guidance_rescale > 0 needs clips of at least two values: a standard deviation over one is undefined")
         graphed = use_graph and callback is None
         key = (B, Cc, H, W, tuple(generated_prompt_embeds.shape), tuple(prompt_embeds.shape),
                None if attention_mask is None else (tuple(attention_mask.shape), attention_mask.dtype), num_inference_steps,
@@ -669,6 +711,8 @@ class AudioLDM2Pipeline:
                plan.key)  # (... nor one captured for another sampler / eta: the table and the update kernel are baked in)
         if src is not None:  # an edit run: start index and masked flag are in plan.key; the mask's batch form selects the kernel's indexing
             key += (("edit", emask_shape),)
+        if shaped:  # the stage is on, with or without the momentum buffer; its values are a table, not part of the key
+            key += (("shaped", carries),)
         e = None
         if graphed:
             wsig = self._weights_signature()
@@ -678,7 +722,7 @@ class AudioLDM2Pipeline:
                 e = None
         if e is not None:
             self._graphs[key] = self._graphs.pop(key)  # most recently used last
-            self._fill_step_buffers(e, H, W, latents_nchw, src, start_coefs, conditions, gtab, generator, step_noise)
+            self._fill_step_buffers(e, H, W, latents_nchw, src, start_coefs, conditions, gtab, generator, step_noise, stab)
             unet.set_kv_cache(True, clear=False)
             try:
                 unet.refresh_kv_cache()  # hoisted K/V of the new conditions, recomputed into the buffers the graph reads
@@ -696,11 +740,14 @@ class AudioLDM2Pipeline:
                  "coef": plan.table.to(dev), "step_ptr": torch.empty(1, dtype=torch.int32, device=dev),
                  "guidance": f32(n_run, 2) if dual else None, "eps_out": f32(B, H * W, Cc) if keep_noise_pred else None,
                  "hist": f32(B, H * W, Cc) if plan.needs_history else None, "noise": f32(n_run, B, H * W, Cc) if plan.needs_noise else None}
+            if shaped:
+                e["shape"], e["stats"] = f32(n_run, 4), f32(B, 8)
+                e["momentum"] = f32(2 if dual else 1, B, H * W, Cc) if carries else None
             if src is not None:
                 e["x0"], e["z0"] = f32(B, H * W, Cc), f32(B, H * W, Cc)
                 e["emask"] = None if emask_shape is None else f32(*emask_shape)
                 e["keep"] = None if plan.keep is None else plan.keep.to(dev)
-            self._fill_step_buffers(e, H, W, latents_nchw, src, start_coefs, conditions, gtab, generator, step_noise)
+            self._fill_step_buffers(e, H, W, latents_nchw, src, start_coefs, conditions, gtab, generator, step_noise, stab)
             lat, unet_in, gen, pe, mask, coef, step_ptr, eps_out = (e[k] for k in ("lat", "unet_in", "gen", "pe", "mask", "coef", "step_ptr", "eps_out"))
             hist, noise = e["hist"], e["noise"]
             from . import processors as P_
@@ -716,7 +763,10 @@ class AudioLDM2Pipeline:
 
             # the update op of this run and its arguments, bound once (ops.* is looked up when the step runs)
             edit = (e["keep"], e["x0"], e["z0"], e["emask"], Cc) if masked else ()
-            if invert:  # extracts the step's noise instead of consuming it; two or three branches in one op
+            if shaped:  # guidance rescale / projected guidance: per-clip sums in the guided-noise stage; two or three branches, mask or none
+                update = lambda eps: ops.cfg_shaped_step(eps, lat, unet_in, coef, e["shape"], step_ptr, None if dual else guidance_scale, e["guidance"],
+                                                         e["momentum"], e["stats"], eps_out, hist, noise, *edit)
+            elif invert:  # extracts the step's noise instead of consuming it; two or three branches in one op
                 update = lambda eps: ops.cfg_invert_step(eps, lat, unet_in, coef, e["keep"], e["x0"], noise, step_ptr, None if dual else guidance_scale,
                                                          e["guidance"], eps_out)
             elif dual:  # three sample-forwards per clip; the condition-free prefix still runs once
@@ -738,6 +788,8 @@ class AudioLDM2Pipeline:
                 step_ptr.zero_()
                 if hist is not None:
                     hist.zero_()
+                if shaped and e["momentum"] is not None:
+                    e["momentum"].zero_()
                 if invert:  # the warm-up step wrote z_0 over the draw of row 0
                     noise[0].copy_(noise0)
 
@@ -779,6 +831,8 @@ class AudioLDM2Pipeline:
                 # cached graph keeps its hoisted buffers -- they are refreshed in place before each replay -- but a direct
                 # unet(...) / a training step on the same UNet never enters the cache, so nothing accumulates there)
                 unet.set_kv_cache(False, clear=False)
+        if shaped:
+            self.last_guidance_stats = e["stats"]
         return e, (B, Cc, H, W)
 
     @torch.no_grad()
@@ -789,8 +843,9 @@ class AudioLDM2Pipeline:
                  attention_mask=None, negative_attention_mask=None, max_new_tokens=None, return_dict=True,
                  callback=None, callback_steps=1, cross_attention_kwargs=None, output_type="np", mel=None,
                  use_graph=True, source_audio=None, source_mel=None, source_latents=None, strength=1.0, edit_mask=None, edit_region=None,
-                 audio_guidance_scale=None, rank_by=None, fidelity_reference=None, inversion=None, source_prompt=None, source_guidance_scale=3.0,
-                 source_prompt_embeds=None, source_generated_prompt_embeds=None, source_attention_mask=None):
+                 audio_guidance_scale=None, guidance_rescale=0.0, apg_eta=None, apg_norm_threshold=0.0, apg_momentum=0.0, rank_by=None,
+                 fidelity_reference=None, inversion=None, source_prompt=None, source_guidance_scale=3.0, source_prompt_embeds=None,
+                 source_generated_prompt_embeds=None, source_attention_mask=None):
         """Same keyword surface and defaults as the reference (pipeline_audioldm2.py:748-775, ``output_type="np"`` included): a
         pipeline built with ``vae=`` and ``vocoder=`` returns waveforms by default; ``output_type="latent"`` is the exit for a pipeline
         that holds the denoise path only.
@@ -815,6 +870,15 @@ class AudioLDM2Pipeline:
         maps instead of fresh noise, under the call's own prompt and ``guidance_scale``.  The audio prompt (``mel=`` / ``audio_file=``)
         conditions both phases.  ``strength``, ``edit_mask`` / ``edit_region``, ``audio_guidance_scale``, ``num_waveforms_per_prompt`` and ranking
         work as without it; the cost is one more pass of the run's UNet steps.
+
+        Beyond the reference -- shaped guidance (PARITY UNPINNED): ``guidance_rescale`` (phi in [0, 1], diffusers' keyword: pulls the
+        guided noise's per-clip standard deviation back towards the conditioned branch's) and adaptive projected guidance, ``apg_eta`` (None =
+        off; the weight of the guidance component parallel to the conditioned prediction, 1 = plain guidance, 0 = orthogonal part only) with
+        ``apg_norm_threshold`` (>= 0, 0 = off: clips the guidance difference's norm) and ``apg_momentum`` (|beta| < 1, APG uses negative values:
+        a running average of the differences over the steps).  Each is a float or a sequence of ``num_inference_steps`` floats; changing them
+        does not re-capture the step.  They act on the noise prediction, and work with both samplers, ``eta``, ``strength``, masks,
+        ``audio_guidance_scale``, ``num_waveforms_per_prompt`` and ranking.  With ``inversion="ddpm"`` they shape the EDIT pass only: the
+        inversion pass runs plain guidance, so a call whose source and edit conditions agree no longer retraces the source when a knob is on.
 
         Beyond the reference -- ``rank_by``: None or "clap" is the ranking above (CLAP text-audio similarity, text prompts only).  "chroma"
         (needs a source clip; neither text prompts nor the audio tower, so it also ranks on the embeddings path) returns each prompt's own
@@ -868,6 +932,8 @@ class AudioLDM2Pipeline:
                                            num_inference_steps, edit_k)
         if dual:  # the scales of the steps this call runs, checked before any device work (a ValueError names ``audio`` or ``text``)
             guidance_table(audio_guidance_scale, guidance_scale, num_inference_steps, edit_k)
+        self.check_shaping_arguments(guidance_rescale, apg_eta, apg_norm_threshold, apg_momentum, num_inference_steps, edit_k)
+        shaping = dict(guidance_rescale=guidance_rescale, apg_eta=apg_eta, apg_norm_threshold=apg_norm_threshold, apg_momentum=apg_momentum)
         if audio_file is not None and mel is None:
             from .frontend import load_mel  # "next" row f-2
             mel = load_mel(audio_file)
@@ -907,13 +973,13 @@ class AudioLDM2Pipeline:
                                   use_graph=use_graph, audio_guidance_scale=audio_guidance_scale)
             out = self.denoise(None, ge, pe, am, num_inference_steps, guidance_scale, use_graph=use_graph, callback=callback,
                                callback_steps=callback_steps, eta=eta, generator=generator, source=src, start=edit_k,
-                               audio_guidance_scale=audio_guidance_scale)
+                               audio_guidance_scale=audio_guidance_scale, **shaping)
         else:
             lat = self.prepare_latents(batch_size * num_waveforms_per_prompt, self.unet.config.in_channels, height, dtype,
                                        dev, generator, latents)
             out = self.denoise(lat, ge, pe, am, num_inference_steps, guidance_scale, use_graph=use_graph, callback=callback,
                                callback_steps=callback_steps, eta=eta, generator=generator,
-                               audio_guidance_scale=audio_guidance_scale)
+                               audio_guidance_scale=audio_guidance_scale, **shaping)
         if output_type != "latent":  # :1036-1044
             scaling = getattr(getattr(self.vae, "config", None), "scaling_factor", 1.0)
             mel = self.vae.decode(out / scaling)

@@ -22,6 +22,9 @@ An edit run (a source clip noised to an interior timestep, optionally with a reg
 Edit-friendly DDPM inversion (``DDIMScheduler.inversion_plan``, ``apad_cfg_invert_step``; Huberman-Spiegelglas et al. 2024) reads the
 same ``eta`` > 0 rows and the same ``keep`` table on the same slice: it extracts the noise those rows would consume.
 
+Guidance rescale and adaptive projected guidance (``shape_table``, ``apad_cfg_shaped_step``; Lin et al. 2024, Sadat et al. 2024) read the
+same six-column tables; their own per-step values (phi, eta, r, beta) are one more device table on the same slice.
+
 PARITY UNPINNED: the ``eta`` arithmetic and the multistep solver are restated from the published formulas (diffusers is not
 vendored and not installable offline); ``tests/sampler_oracle.py`` restates them a second time, independently, in float64."""
 import math
@@ -84,6 +87,37 @@ def guidance_table(audio, text, num_inference_steps, start=0):
         vals = vals[start:]
         if not all(math.isfinite(x) and x >= 0.0 for x in vals):
             raise ValueError(f"{name}={v!r}: every guidance value must be finite and >= 0")
+        cols.append(vals)
+    return torch.tensor(cols, dtype=torch.float64).t().float().contiguous()
+
+
+SHAPE_COLS = ("guidance_rescale", "apg_eta", "apg_norm_threshold", "apg_momentum")  # one row of shape_table: (phi, eta, r, beta)
+
+
+def shape_table(guidance_rescale, apg_eta, apg_norm_threshold, apg_momentum, num_inference_steps, start=0):
+    """fp32 [N - start, 4], row i = (phi, eta, r, beta) of step ``start + i``: the table apad_cfg_shaped_step reads at ``*step_ptr`` (guidance
+    rescale, Lin et al. 2024; adaptive projected guidance, Sadat et al. 2024: PAPERS.md).  Each argument is a float (every step) or a sequence
+    of exactly N floats over the FULL grid, of which rows ``start:`` are kept, like ``guidance_table``.  phi in [0, 1] (0 = no rescale), eta any
+    finite value (1 = no projection), r >= 0 (0 = no norm threshold), |beta| < 1 (0 = no momentum; APG uses negative values); a ValueError
+    names the argument.  The row (0, 1, 0, 0) is plain classifier-free guidance."""
+    n, start = int(num_inference_steps), int(start)
+    if not 0 <= start < n:
+        raise ValueError(f"start={start!r} must lie in [0, {n})")
+    ok = {"guidance_rescale": (lambda x: 0.0 <= x <= 1.0, "must lie in [0, 1]"), "apg_eta": (lambda x: True, "must be finite"),
+          "apg_norm_threshold": (lambda x: x >= 0.0, "must be >= 0"), "apg_momentum": (lambda x: abs(x) < 1.0, "must lie in (-1, 1)")}
+    cols = []
+    for name, v in zip(SHAPE_COLS, (guidance_rescale, apg_eta, apg_norm_threshold, apg_momentum)):
+        if isinstance(v, torch.Tensor):
+            v = v.detach().cpu().tolist()
+        try:
+            vals = [float(v)] * n if not hasattr(v, "__len__") else [float(x) for x in v]
+        except (TypeError, ValueError):
+            raise ValueError(f"{name}={v!r}: expected a float or a sequence of {n} floats") from None
+        if len(vals) != n:
+            raise ValueError(f"{name} holds {len(vals)} values; a per-step sequence needs exactly num_inference_steps = {n}")
+        vals = vals[start:]
+        if not all(math.isfinite(x) and ok[name][0](x) for x in vals):
+            raise ValueError(f"{name}={v!r}: every value {ok[name][1]}")
         cols.append(vals)
     return torch.tensor(cols, dtype=torch.float64).t().float().contiguous()
 

@@ -33,6 +33,9 @@
  *                       cfg_step_kernel, its three-branch instantiations (guided_noise), the same sampler_update / edit_blend
  *   apad_cfg_invert_step  edit-friendly DDPM inversion (no counterpart in the reference): the step that extracts the per-step
  *                       noise of DDIM eta > 0 under the source condition (cfg_invert_step_kernel, beside cfg_step_kernel)
+ *   apad_cfg_shaped_step  guidance rescale and adaptive projected guidance (no counterpart in the reference; diffusers' guidance_rescale /
+ *                       AdaptiveProjectedGuidance): the sampler / edit / dual step with per-clip sums in the guided-noise stage
+ *                       (cfg_shaped_step_kernel, one workgroup per clip, beside cfg_step_kernel)
  *   apad_step_advance   the loop counter of the captured step
  *   apad_edit_start     editing from a source clip (no working counterpart in the reference; diffusers' img2img / inpaint
  *                       conventions): posterior draw + add_noise at the start timestep
@@ -514,6 +517,31 @@ int apad_cfg_dual_step(const void* eps3, float* latents, void* unet_in, float* e
                        const float* coef, const float* guidance, const float* keep, const float* x0, const float* z0, const float* mask,
                        int32_t mask_batch, int32_t C, const int32_t* step_ptr, int32_t n_steps, int32_t B, int64_t n, int32_t dtype,
                        void* stream);
+/* Guidance rescale (Lin et al. 2024) and adaptive projected guidance (Sadat et al. 2024; both PAPERS.md; no counterpart in the reference) inside
+   the step: apad_cfg_sampler_step / _edit_step (branches 2: eps [2B][n], guided by guidance_scale, guidance may be null) or apad_cfg_dual_step
+   (branches 3: eps [3B][n], guided by guidance [n_steps][2], required) with another guided-noise stage, which needs sums over a whole clip.  With
+   c the fully conditioned branch (e_1 / e_AT), d_1 = c - e_0 weighted w_1 = guidance_scale (branches 2) or d_1 = e_A - e_0, d_2 = e_AT - e_A
+   weighted (w_1, w_2) = (s_A, s_T) (branches 3), and row s = *step_ptr (clamped to [0, n_steps)) of shape [n_steps][4] fp32 = (phi, eta, r, beta),
+   per clip, in fp32, every sum over the clip's n elements:
+     beta != 0:  m_k <- fma(beta, m_k, d_k) -> momentum [branches - 1][B][n] fp32, d_k := m_k     (beta == 0: momentum neither read nor written)
+     t_k = r > 0 ? min(1, r / ||d_k||_2) : 1                                                      (a zero norm gives 1)
+     q_k = (1 - eta) <d_k, c> / <c, c> ,   u_k = t_k * fma(-q_k, c, d_k)                           (a zero denominator gives q_k = 0)
+     g   = fma(w_2, u_2, fma(w_1, u_1, e_0))                                                      (branches 2: fma(w_1, u_1, e_0))
+     phi > 0:  g <- f g,  f = fma(phi, std(c) / std(g), 1 - phi)                                  (unbiased std from centred values; std(g) == 0
+                                                                                                   or n == 1 gives f = 1)
+     eps = (dtype) g
+   and from there the step of apad_cfg_edit_step / apad_cfg_dual_step exactly: sampler update, history, noise table, edit blend, mask, eps_out.
+   A factor that is off is skipped, not multiplied in: on a row (0, 1, 0, 0) the launch writes the bits of those entry points (except two-branch
+   f16 in the scalar form, where they leave one rounding to the compiler and this one rounds the fp32 g).  momentum may be null when no row has
+   beta != 0 (a null momentum reads every beta as 0).  stats (optional) [B][8] fp32 receives (t_1, q_1, t_2, q_2, mean g, std g, std c, f) per
+   clip -- (t_2, q_2) = (1, 0) for branches 2, and (0, 0, 0, 1) in the last four when phi == 0.  phi > 0 wants n >= 2 (the caller's check: the
+   table lives on the device; n == 1 gives f = 1).  One workgroup per clip and a summation order that depends on n and the form only: a clip's
+   outputs are the same bits whatever B is.  16-byte accesses under apad_cfg_edit_step's rule plus 8 | n and a 16-byte aligned momentum, a
+   scalar form otherwise.  One launch, no atomics, no host reads: hipGraph-capturable. */
+int apad_cfg_shaped_step(const void* eps, float* latents, void* unet_in, float* eps_out, float* history, const float* noise, const float* coef,
+                         const float* guidance, const float* shape, float* momentum, float* stats, const float* keep, const float* x0,
+                         const float* z0, const float* mask, int32_t mask_batch, int32_t C, const int32_t* step_ptr, int32_t n_steps,
+                         float guidance_scale, int32_t branches, int32_t B, int64_t n, int32_t dtype, void* stream);
 /* Edit-friendly DDPM inversion (Huberman-Spiegelglas et al. 2024; Manor & Michaeli 2024; no counterpart in the reference): the
    step that EXTRACTS the noise of a stochastic sampler instead of consuming it, at the end of the same captured UNet step.  eps [branches * B][n]
    (dtype) as apad_cfg_sampler_step (branches 2, guided by guidance_scale; guidance may be null) or apad_cfg_dual_step (branches 3, guided by

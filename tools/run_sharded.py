@@ -126,6 +126,13 @@ def main():
     ap.add_argument("--edit-region", default=None, metavar="A:B", help="edit: regenerate seconds A..B only, keep the rest of the source")
     ap.add_argument("--audio-guidance", type=float, default=None, metavar="S", help="separate audio and text guidance: three branches per clip, "
                     "eps_0 + S (eps_A - eps_0) + guidance_scale (eps_AT - eps_A); without it the job is the two-branch one")
+    ap.add_argument("--guidance-rescale", type=float, default=0.0, metavar="PHI", help="guidance rescale in [0, 1]: pulls the guided noise's "
+                    "per-clip standard deviation back towards the conditioned branch's (0 = off)")
+    ap.add_argument("--apg-eta", type=float, default=None, metavar="ETA", help="adaptive projected guidance: the weight of the guidance component "
+                    "parallel to the conditioned prediction (1 = plain guidance, 0 = orthogonal part only; default: APG off)")
+    ap.add_argument("--apg-norm-threshold", type=float, default=0.0, metavar="R", help="--apg-eta: clip the guidance difference's norm at R (0 = off)")
+    ap.add_argument("--apg-momentum", type=float, default=0.0, metavar="BETA", help="--apg-eta: running average of the guidance differences over the "
+                    "steps, |BETA| < 1 (APG uses negative values; 0 = off)")
     ap.add_argument("--inversion", choices=["ddpm"], default=None, help="edit from the source's own per-step noise (edit-friendly DDPM inversion) "
                     "instead of fresh noise: one more pass of the run's UNet steps; needs --sampler ddim, runs at eta = 1")
     ap.add_argument("--source-prompt", default="", metavar="TEXT", help="--inversion: the text describing the SOURCE clip (default: the empty prompt)")
@@ -183,16 +190,24 @@ def main():
             return moments[src]
 
     dual = {} if args.audio_guidance is None else {"audio_guidance_scale": args.audio_guidance}
+    # guidance rescale / projected guidance (the edit pass only under --inversion); checked once, before any clip is touched
+    shaping = dict(guidance_rescale=args.guidance_rescale, apg_eta=args.apg_eta, apg_norm_threshold=args.apg_norm_threshold,
+                   apg_momentum=args.apg_momentum)
+    try:
+        shaped = pipe.check_shaping_arguments(*shaping.values(), args.steps) is not None
+    except ValueError as err:
+        ap.error(str(err))
+    shaping = shaping if shaped else {}
 
     def denoise(lat, gen, t5, mask, gs, clips=None):
         if not editing:
-            return pipe.denoise(lat, gen, t5, mask, args.steps, gs, **dual)
+            return pipe.denoise(lat, gen, t5, mask, args.steps, gs, **dual, **shaping)
         # z0 = the clip's seeded latents (what a generation run would start from); the posterior draw is seeded by the clip index too
         post = torch.stack([torch.randn(8, H, 16, generator=torch.Generator().manual_seed(7919 * c["index"] + 1)) for c in clips])
         src = A.EditSource(z0=lat, moments=torch.cat([source_moments(c["audio"]) for c in clips]), post_noise=post,
                            scale=pipe.vae.config.scaling_factor, mask=region_mask)
         if args.inversion is None:
-            return pipe.denoise(None, gen, t5, mask, args.steps, gs, source=src, start=start, **dual)
+            return pipe.denoise(None, gen, t5, mask, args.steps, gs, source=src, start=start, **dual, **shaping)
         # the source condition: the batch's own, with the positive branch's text (the last b rows; 8 generated tokens) replaced
         b = lat.shape[0]
         sg, st, sm = S.synthetic_text_embeddings(args.source_prompt, t5_len=t5.shape[1])
@@ -200,7 +215,7 @@ def main():
         sgen[-b:, :8], st5[-b:], smask[-b:] = sg.to(gen), st.to(t5), sm.to(mask)
         inv = pipe.invert(src, sgen, st5, smask, args.steps, args.source_guidance, start=start, eta=1.0,
                           generator=torch.Generator().manual_seed(104729 * clips[0]["index"] + 2), **dual)
-        return pipe.denoise(None, gen, t5, mask, args.steps, gs, source=inv, start=start, eta=1.0, **dual)
+        return pipe.denoise(None, gen, t5, mask, args.steps, gs, source=inv, start=start, eta=1.0, **dual, **shaping)
 
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -243,7 +258,7 @@ def main():
         print(json.dumps({"task": args.task, "clips": len(clips), "world": world, "batch": args.batch, "steps": args.steps,
                           "sampler": args.sampler, "strength": args.strength, "edit_region": args.edit_region, "La": A.config.audio_tokens(cfg), "seconds_rank0": round(dt, 2), "clips_per_s": round(len(clips) / dt, 4),
                           "graph_captures": pipe.graph_captures, "graph_hits": pipe.graph_hits, "finite": finite,
-                          "wavs_written_rank0": n_wavs, **({"audio_guidance": args.audio_guidance} if dual else {}),
+                          "wavs_written_rank0": n_wavs, **({"audio_guidance": args.audio_guidance} if dual else {}), **shaping,
                           **({"inversion": args.inversion, "source_prompt": args.source_prompt, "source_guidance": args.source_guidance}
                              if args.inversion else {}),
                           **({"rank_by": args.rank_by, "chroma_similarity_mean_rank0": round(sum(r["chroma_similarity"] for r in scored) / max(len(scored), 1), 6)}
