@@ -13,8 +13,9 @@ from .text_encoders import (PromptEncoder, ClapTextModelWithProjection, T5Encode
 from .clap_audio import ClapAudioConfig, ClapAudioModelWithProjection  # noqa: F401
 from .clap_features import ClapFeatureExtractor  # noqa: F401
 from .chroma import chroma_stft, chroma_similarity  # noqa: F401
+from .loudness import integrated_loudness, normalize_loudness  # noqa: F401
 from .wiring import install_ap_adapter, build_processors, ip_layer_names, adapter_state_dict, save_adapter, load_adapter  # noqa: F401
-from . import ops, distributed, autograd, config, sharded, chroma  # noqa: F401
+from . import ops, distributed, autograd, config, sharded, chroma, loudness  # noqa: F401
 from .config import get_config  # noqa: F401
 from .ops import set_float32_matmul_precision, get_float32_matmul_precision  # noqa: F401
 from .training import AdapterTrainer, add_noise  # noqa: F401

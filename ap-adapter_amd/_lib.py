@@ -190,6 +190,9 @@ SYMBOLS = {
     # chroma features and chroma similarity (score_fidelity)
     "apad_chroma": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "apad_chroma_similarity": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
+    # BS.1770 loudness and the gain towards a target (normalize_loudness)
+    "apad_loudness": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "apad_loudness_gain": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _f32, _vp]),
 }
 
 _lock = threading.Lock()

@@ -1065,6 +1065,72 @@ def chroma_similarity(a, b, ref_index, ref_index_host, frames, frames_host, out=
     return out
 
 
+def _host_table(t, name, dtype, n):
+    if t.is_cuda or t.dtype != dtype or t.numel() != n or not t.is_contiguous():
+        raise RuntimeError(f"{name}: expected {n} contiguous {dtype} values on the host")
+    return t
+
+
+def loudness(x, offsets, offsets_host, coef, powers, stats, hop, hop_energy=None):
+    """apad_loudness on pre-allocated buffers (hipGraph-capturable: no allocation, no read-back): x fp32 [sum n] = the clips packed back
+    to back, offsets int64 [B + 1] on the device and ``offsets_host`` the same on the host, coef [10] and powers [2, 65, 2, 2, 2] fp32
+    (``loudness.tables`` for the clips' rate), ``hop`` samples per 100 ms -> stats fp32 [B, 4] = (LUFS, sample peak, blocks above the
+    absolute gate, blocks above both gates); ``hop_energy`` fp32 [B, target_hops] receives the K-weighted energy of every whole hop (0
+    past a clip's last whole hop)."""
+    for t, name in ((x, "x"), (coef, "coef"), (powers, "powers"), (stats, "stats")) + (((hop_energy, "hop_energy"),) if hop_energy is not None else ()):
+        if not _req(t, "loudness." + name, torch.float32).is_contiguous():
+            raise RuntimeError(f"loudness.{name}: must be contiguous")
+    _req(offsets, "loudness.offsets", torch.int64)
+    B = offsets_host.numel() - 1
+    _host_table(offsets_host, "loudness.offsets_host", torch.int64, B + 1)
+    if B < 1 or offsets.numel() != B + 1 or not offsets.is_contiguous() or tuple(stats.shape) != (B, 4):
+        raise RuntimeError(f"loudness: offsets {tuple(offsets.shape)} / stats {tuple(stats.shape)} do not describe {B} clips as [B + 1] / [B, 4]")
+    if coef.numel() != 10 or tuple(powers.shape) != (2, 65, 2, 2, 2):
+        raise RuntimeError("loudness: expected coef [10] and powers [2, 65, 2, 2, 2]")
+    if hop_energy is not None and (hop_energy.dim() != 2 or hop_energy.shape[0] != B or hop_energy.shape[1] < 1):
+        raise RuntimeError(f"loudness.hop_energy: expected [{B}, target_hops], got {tuple(hop_energy.shape)}")
+    if x.numel() < int(offsets_host[-1]):
+        raise RuntimeError(f"loudness.x: {x.numel()} samples, the offsets end at {int(offsets_host[-1])}")
+    L.check(L.lib().apad_loudness(x.data_ptr(), offsets.data_ptr(), offsets_host.data_ptr(), coef.data_ptr(), powers.data_ptr(), stats.data_ptr(),
+                                  _ptr(hop_energy), B, int(hop), 0 if hop_energy is None else hop_energy.shape[1], _stream()), "apad_loudness")
+    return stats
+
+
+def loudness_gain(x, offsets, offsets_host, stats, out, gains, peak_limit, target=None, ref_stats=None, ref_index=None, ref_index_host=None):
+    """apad_loudness_gain on pre-allocated buffers: x / offsets / offsets_host and stats [B, 4] as for ``loudness`` -> gains fp32 [B] and
+    out = gains[b] * x (packed as x; ``out`` may be ``x``).  The per-clip target in LUFS is ``target`` fp32 [B] on the device, or
+    ``ref_stats[ref_index[b], 0]`` for ref_stats fp32 [m, 4] and ref_index int32 [B] on the device with its host copy (validation only).
+    ``peak_limit`` > 0 (linear) caps gain * peak; 0 = no guard."""
+    by_ref = ref_stats is not None or ref_index is not None or ref_index_host is not None
+    if by_ref == (target is not None) or (by_ref and (ref_stats is None or ref_index is None or ref_index_host is None)):
+        raise RuntimeError("loudness_gain: give either target, or ref_stats with ref_index and ref_index_host")
+    for t, name in ((x, "x"), (stats, "stats"), (out, "out"), (gains, "gains")) + (((ref_stats, "ref_stats"),) if by_ref else ((target, "target"),)):
+        if not _req(t, "loudness_gain." + name, torch.float32).is_contiguous():
+            raise RuntimeError(f"loudness_gain.{name}: must be contiguous")
+    _req(offsets, "loudness_gain.offsets", torch.int64)
+    B = offsets_host.numel() - 1
+    _host_table(offsets_host, "loudness_gain.offsets_host", torch.int64, B + 1)
+    if B < 1 or offsets.numel() != B + 1 or not offsets.is_contiguous() or tuple(stats.shape) != (B, 4) or gains.numel() != B:
+        raise RuntimeError(f"loudness_gain: offsets {tuple(offsets.shape)} / stats {tuple(stats.shape)} / gains {tuple(gains.shape)} do not describe "
+                           f"{B} clips")
+    if x.numel() < int(offsets_host[-1]) or out.numel() < int(offsets_host[-1]):
+        raise RuntimeError(f"loudness_gain: x {x.numel()} / out {out.numel()} samples, the offsets end at {int(offsets_host[-1])}")
+    m = 0
+    if by_ref:
+        if ref_stats.dim() != 2 or ref_stats.shape[1] != 4 or ref_stats.shape[0] < 1:
+            raise RuntimeError(f"loudness_gain.ref_stats: expected [m, 4], got {tuple(ref_stats.shape)}")
+        m = ref_stats.shape[0]
+        if _req(ref_index, "loudness_gain.ref_index", torch.int32).numel() != B or not ref_index.is_contiguous():
+            raise RuntimeError(f"loudness_gain.ref_index: expected {B} contiguous int32 values")
+        _host_table(ref_index_host, "loudness_gain.ref_index_host", torch.int32, B)
+    elif target.numel() != B:
+        raise RuntimeError(f"loudness_gain.target: expected {B} values")
+    L.check(L.lib().apad_loudness_gain(x.data_ptr(), offsets.data_ptr(), offsets_host.data_ptr(), stats.data_ptr(), _ptr(target), _ptr(ref_stats),
+                                       _ptr(ref_index), _ptr(ref_index_host), out.data_ptr(), gains.data_ptr(), B, m, float(peak_limit), _stream()),
+            "apad_loudness_gain")
+    return out
+
+
 def gaussian_sample(moments, noise, scale=1.0):
     """moments [rows, 2L] = (mean | logvar), noise [rows, L] -> (mean + exp(0.5 * clamp(logvar, -30, 20)) * noise) * scale"""
     _req(moments, "gaussian_sample.moments")

@@ -29,6 +29,11 @@ similarity is the AP-adapter paper's fidelity metric; PARITY UNPINNED
 and vocoder as the candidates, both sides become chromagrams (``apad_chroma``) and each prompt's own candidates are ordered by their
 similarity to that source (``apad_chroma_similarity``), all from the vocoder's device output.  A call without ``rank_by=`` takes none of
 this.
+
+Loudness (``target_loudness=``, ``peak_limit_db=``, ``loudness_reference=``; ITU-R BS.1770-4 integrated loudness; PARITY UNPINNED
+against other meters, loudness.py): right after the vocoder and the crop, on the device, every candidate is measured (``apad_loudness``) and
+multiplied by the gain that takes it to a target in LUFS or to its source's loudness (``apad_loudness_gain``), under a sample-peak guard.
+A call without ``target_loudness=`` takes none of this.
 """
 import math
 from dataclasses import dataclass
@@ -93,6 +98,7 @@ class AudioLDM2Pipeline:
         self.logit_scale_t = math.log(1.0 / 0.07)  # ClapModel.logit_scale_t (logit_scale_init_value); set it from a checkpoint's value
         self.last_logits_per_text = None
         self.last_chroma_similarity = None
+        self.last_loudness = None
         self.scheduler = scheduler or DDIMScheduler()
         self.audiomae = audiomae
         self._uncond_cache = {}
@@ -213,6 +219,57 @@ class AudioLDM2Pipeline:
             logits = self.last_logits_per_text
         scores = mixed_scores(weights, sim, logits, math.exp(self.logit_scale_t), num_waveforms_per_prompt)
         return torch.index_select(audio, 0, group_order(scores, num_waveforms_per_prompt))
+
+    def check_loudness_arguments(self, target_loudness, peak_limit_db, loudness_reference, editing, batch):
+        """every argument check of ``target_loudness=`` / ``peak_limit_db=`` / ``loudness_reference=``, on the host, before any device
+        work.  Returns None (today's path) or (per-clip targets in LUFS, or "source"; the linear peak limit, 0 = no guard)."""
+        from . import loudness
+        if target_loudness is None:
+            if loudness_reference is not None:
+                raise ValueError("loudness_reference is the reference of target_loudness='source'; without it it has no use")
+            return None
+        limit = loudness.peak_limit(peak_limit_db)
+        if isinstance(target_loudness, str):
+            if target_loudness != "source":
+                raise ValueError(f"target_loudness={target_loudness!r}: a loudness in LUFS, one per returned clip, or 'source'")
+            if loudness_reference is None and not editing:
+                raise ValueError("target_loudness='source' matches each clip to its source clip and needs one (source_audio=, source_mel= or "
+                                 "source_latents=), or loudness_reference=")
+            if loudness_reference is not None:
+                shp = tuple(loudness_reference.shape)
+                if len(shp) not in (1, 2) or shp[-1] == 0 or (len(shp) == 2 and (shp[0] == 0 or batch % shp[0] != 0)):
+                    raise ValueError(f"loudness_reference {shp}: expected a waveform [samples] or [b, samples] with b dividing the batch of {batch}")
+            return "source", limit
+        if loudness_reference is not None:
+            raise ValueError("loudness_reference is the reference of target_loudness='source'; with a target in LUFS it has no use")
+        vals = loudness.check_target(target_loudness, batch, "target_loudness")
+        return (vals * batch if len(vals) == 1 else vals), limit
+
+    def _apply_loudness(self, wav, plan, reference):
+        """candidates [B, samples] on the device -> the same clips at their target loudness (fp32, on the device); ``last_loudness`` =
+        (stats of the RETURNED clips [B, 4], gains [B]), in generation order"""
+        from . import loudness
+        sr = int(self.vocoder.config.sampling_rate)
+        wav = wav.float().contiguous()
+        target, limit = plan
+        B, dev = wav.shape[0], wav.device
+        offsets_host = torch.arange(B + 1, dtype=torch.int64) * wav.shape[1]
+        offsets = offsets_host.to(dev)
+        stats = loudness.measure(wav.reshape(-1), offsets, offsets_host, sr)
+        out, gains = torch.empty_like(wav), torch.empty(B, dtype=torch.float32, device=dev)
+        if target == "source":
+            ref = torch.as_tensor(reference).to(dev, torch.float32)
+            ref = (ref[None] if ref.dim() == 1 else ref).contiguous()
+            roh = torch.arange(ref.shape[0] + 1, dtype=torch.int64) * ref.shape[1]
+            ref_stats = loudness.measure(ref.reshape(-1), roh.to(dev), roh, sr)
+            idx_host = torch.tensor(loudness.default_ref_index(B, ref.shape[0]), dtype=torch.int32)
+            ops.loudness_gain(wav.reshape(-1), offsets, offsets_host, stats, out.reshape(-1), gains, limit, ref_stats=ref_stats,
+                              ref_index=idx_host.to(dev), ref_index_host=idx_host)
+        else:
+            ops.loudness_gain(wav.reshape(-1), offsets, offsets_host, stats, out.reshape(-1), gains, limit,
+                              target=torch.tensor(target, dtype=torch.float32).to(dev))
+        self.last_loudness = (loudness.measure(out.reshape(-1), offsets, offsets_host, sr), gains)
+        return out
 
     def _encode_text(self, texts, t5_max_length=None):
         """tokenise as encode_prompt does (:381-392 positive, :485-496 negative) and run the HIP prompt encoder on one CFG half"""
@@ -843,8 +900,8 @@ class AudioLDM2Pipeline:
                  attention_mask=None, negative_attention_mask=None, max_new_tokens=None, return_dict=True,
                  callback=None, callback_steps=1, cross_attention_kwargs=None, output_type="np", mel=None,
                  use_graph=True, source_audio=None, source_mel=None, source_latents=None, strength=1.0, edit_mask=None, edit_region=None,
-                 audio_guidance_scale=None, guidance_rescale=0.0, apg_eta=None, apg_norm_threshold=0.0, apg_momentum=0.0, rank_by=None,
-                 fidelity_reference=None, inversion=None, source_prompt=None, source_guidance_scale=3.0, source_prompt_embeds=None,
+                 audio_guidance_scale=None, guidance_rescale=0.0, apg_eta=None, apg_norm_threshold=0.0, apg_momentum=0.0, target_loudness=None,
+                 peak_limit_db=-1.0, loudness_reference=None, rank_by=None, fidelity_reference=None, inversion=None, source_prompt=None, source_guidance_scale=3.0, source_prompt_embeds=None,
                  source_generated_prompt_embeds=None, source_attention_mask=None):
         """Same keyword surface and defaults as the reference (pipeline_audioldm2.py:748-775, ``output_type="np"`` included): a
         pipeline built with ``vae=`` and ``vocoder=`` returns waveforms by default; ``output_type="latent"`` is the exit for a pipeline
@@ -886,7 +943,18 @@ class AudioLDM2Pipeline:
         orders them by w_t cos_clap + w_f chroma (cos_clap = logits_per_text / logit_scale) and needs what both need.  The reference is the
         source latents decoded by the same VAE and vocoder as the candidates (one more decode), or ``fidelity_reference``: a 16 kHz
         waveform [samples] or [b, samples].  ``last_chroma_similarity`` keeps the scores in generation order; ``output_type="latent"``
-        exits before any scoring, as above."""
+        exits before any scoring, as above.
+
+        Beyond the reference -- ``target_loudness`` (ITU-R BS.1770-4 integrated loudness; PARITY UNPINNED): a float in LUFS, a
+        sequence with one value per returned clip, or "source" (needs a source clip: each candidate is matched to the loudness of its source as
+        the same VAE and vocoder render it, one more decode -- like with like -- or of ``loudness_reference``, a waveform [samples] or
+        [b, samples] at the vocoder's rate).  ``peak_limit_db`` (<= 0 dBFS, None = off) cuts a gain that would take the clip's largest sample
+        over the limit: such a clip ends below its target instead of clipped (a sample-peak guard, not true peak, and no limiter).  The
+        stage acts on the device waveform right after the vocoder and the crop, BEFORE any scoring and before the host copy: ranking sees
+        the normalised candidates -- chroma similarity is level-invariant, CLAP sees level-matched clips.  ``last_loudness`` keeps (stats
+        [B, 4] of the returned clips: LUFS, sample peak, blocks above the absolute gate, blocks above both; gains [B]) on the device, in
+        generation order.  A clip shorter than 400 ms, or silent, has no loudness and keeps gain 1.  ``output_type="latent"`` exits before
+        it; with ``target_loudness=None`` the call takes none of it."""
         dual = audio_guidance_scale is not None
         if dual:
             if mel is None and audio_file is None:
@@ -925,6 +993,9 @@ class AudioLDM2Pipeline:
         rank_weights = None
         if rank_by is not None or fidelity_reference is not None:
             rank_weights = self.check_rank_arguments(rank_by, fidelity_reference, editing, prompt, batch_size * num_waveforms_per_prompt)
+        loud = None
+        if target_loudness is not None or loudness_reference is not None:
+            loud = self.check_loudness_arguments(target_loudness, peak_limit_db, loudness_reference, editing, batch_size * num_waveforms_per_prompt)
         if inversion is not None or source_prompt is not None or source_prompt_embeds is not None or source_generated_prompt_embeds is not None \
                 or source_attention_mask is not None:
             self.check_inversion_arguments(inversion, editing, eta, prompt, source_prompt, source_guidance_scale, source_prompt_embeds,
@@ -985,22 +1056,35 @@ class AudioLDM2Pipeline:
             mel = self.vae.decode(out / scaling)
             mel = getattr(mel, "sample", mel)
             from .clap_features import ClapFeatureExtractor
+            samples = int(audio_length_in_s * 16000)
+
+            def n_sources():
+                return source_latents.shape[0] if source_latents is not None else \
+                    (1 if source_mel.dim() == 2 else source_mel.shape[0]) if source_mel is not None else \
+                    1 if isinstance(source_audio, str) else len(source_audio)
+
+            def device_waveform():
+                """vocoder + crop on the device, then (target_loudness=) the loudness stage: whatever scores or returns reads this"""
+                wav = self.vocoder(mel.squeeze(1) if mel.dim() == 4 else mel)[:, :samples]
+                if loud is None:
+                    return wav
+                ref = loudness_reference
+                if loud[0] == "source" and ref is None:
+                    ref = self._fidelity_reference(src, n_sources(), samples)
+                return self._apply_loudness(wav, loud, ref)
+
             if rank_weights is not None:  # each prompt's own candidates by fidelity to its source, scored from the device copy
-                samples = int(audio_length_in_s * 16000)
-                wav = self.vocoder(mel.squeeze(1) if mel.dim() == 4 else mel)[:, :samples].float().contiguous()
+                wav = device_waveform().float().contiguous()
                 if fidelity_reference is None:
-                    n_sources = source_latents.shape[0] if source_latents is not None else \
-                        (1 if source_mel.dim() == 2 else source_mel.shape[0]) if source_mel is not None else \
-                        1 if isinstance(source_audio, str) else len(source_audio)
-                    fidelity_reference = self._fidelity_reference(src, n_sources, samples).float().contiguous()
+                    fidelity_reference = self._fidelity_reference(src, n_sources(), samples).float().contiguous()
                 out = self._rank_by_fidelity(rank_weights, wav, torch.as_tensor(fidelity_reference), prompt, num_waveforms_per_prompt, dev,
                                              pe.dtype)
             elif ranking and isinstance(self.feature_extractor, ClapFeatureExtractor):  # :1047-1054, scored from the device copy
-                wav = self.vocoder(mel.squeeze(1) if mel.dim() == 4 else mel)[:, : int(audio_length_in_s * 16000)]
+                wav = device_waveform()
                 out = self.score_waveforms(text=prompt, audio=wav.cpu().float(), num_waveforms_per_prompt=num_waveforms_per_prompt, device=dev,
                                            dtype=pe.dtype, audio_device=wav)
             else:
-                out = self.mel_spectrogram_to_waveform(mel)[:, : int(audio_length_in_s * 16000)]
+                out = self.mel_spectrogram_to_waveform(mel)[:, :samples] if loud is None else device_waveform().cpu().float()
                 if ranking:  # :1047-1054
                     out = self.score_waveforms(text=prompt, audio=out, num_waveforms_per_prompt=num_waveforms_per_prompt, device=dev,
                                                dtype=pe.dtype)

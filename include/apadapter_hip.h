@@ -777,6 +777,41 @@ int apad_chroma_similarity(const float* a, const float* b, const int32_t* ref_in
                            const int32_t* frames, const int32_t* frames_host, float* out, float* per_frame, int32_t n, int32_t m,
                            int32_t T, void* stream);
 
+/* Loudness (ITU-R BS.1770-4 integrated loudness of a mono signal with the EBU R 128 gates; restated, PARITY UNPINNED against
+   libebur128 / pyloudnorm; pinned to the standard's 48 kHz coefficient table and to fp64 scipy.signal.sosfilt), additive to ABI 12.
+   x / offsets / offsets_host as for apad_chroma: a ragged batch of fp32 clips, every clip non-empty, offsets[0] == 0.
+   coef fp32 [10] = (b0 b1 b2 a1 a2) of the high-shelf, then of the high-pass, designed on the host in fp64 for the clips' rate and
+   rounded to fp32; y = high-pass(high-shelf(x)), zero initial state.  The shelf runs in the transposed direct form II; the
+   high-pass as its numerator on the shelf's output followed by its all-pole recursion.  powers fp32 [2][65][2][2][2] =
+   [section][j][hi, lo][row][column]: M^j, j = 0..64, M = A^8, A the 2x2 zero-input transition of the shelf's two delay
+   registers (section 0) and of the all-pole recursion's (y[n-1], y[n-1] - y[n-2]) (section 1), taken in fp64 from the ROUNDED
+   coefficients and split into hi + lo fp32: the kernel scans each recursion with them (8 samples per lane, a Kogge-Stone scan
+   over the wave, a serial carry over the waves and tiles), it does not
+   truncate it.  hop = samples per 100 ms hop (1 .. 8192); a block is 4 hops (400 ms), block j covers hops j .. j + 3, a clip of
+   n samples has max(0, n / hop - 3) blocks.
+   stats fp32 [batch][4] = (L, peak, n_abs, n_rel): z_j = the block's mean square of y; n_abs counts z_j > 10^((-70 + 0.691) / 10)
+   (the absolute gate), n_rel those that also exceed 0.1 times the mean of the z_j above the absolute gate (the relative gate, -10
+   LU); L = -0.691 + 10 log10(mean of the z_j above both) in LUFS, -inf with both counts 0 when no block survives (never NaN);
+   peak = max |x| over every sample of the clip (the sample peak, not the standard's oversampled true peak).
+   hop_energy fp32 [batch][target_hops] or NULL: entry h = the sum of y^2 over samples [h hop, (h + 1) hop), whole hops only,
+   0 past the clip's last whole hop.  One workgroup per clip; every sum has a fixed order that depends on the clip's length and
+   hop alone (no atomics): a clip's outputs do not depend on the batch around it.  No host synchronisation (hipGraph-capturable).
+   -1 when a clip is empty, offsets[0] != 0, hop is out of range, batch > 65535, a clip has more than 3072 whole hops, or
+   hop_energy is given and target_hops is smaller than some clip's whole-hop count. */
+int apad_loudness(const float* x, const int64_t* offsets, const int64_t* offsets_host, const float* coef, const float* powers,
+                  float* stats, float* hop_energy, int32_t batch, int32_t hop, int32_t target_hops, void* stream);
+/* The gain that takes each clip to a target loudness, and its application.  stats [batch][4] as apad_loudness wrote it for these
+   clips.  The target of clip b: target[b] (fp32 [batch] in device memory), or -- target NULL -- ref_stats[ref_index[b]][0] for
+   ref_stats fp32 [n_ref][4], ref_index int32 [batch] in device memory and ref_index_host the same on the host (validation only):
+   matching another clip's loudness.  g = 10^((target - L) / 20); with peak_limit > 0 (linear, full scale = 1): if g peak >
+   peak_limit then g = peak_limit / peak; g = 1 when L or the target is not finite or the peak is 0.  gains fp32 [batch] = g,
+   out[i] = g x[i] as ONE fp32 multiply (out packed as x; it may be x itself).
+   -1 when a clip is empty, offsets[0] != 0, batch > 65535, both or neither kind of target is given, or a ref_index is outside
+   [0, n_ref). */
+int apad_loudness_gain(const float* x, const int64_t* offsets, const int64_t* offsets_host, const float* stats, const float* target,
+                       const float* ref_stats, const int32_t* ref_index, const int32_t* ref_index_host, float* out, float* gains,
+                       int32_t batch, int32_t n_ref, float peak_limit, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

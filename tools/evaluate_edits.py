@@ -13,6 +13,10 @@ Every wav is read on the host, resampled to 16 kHz on the GPU (apad_resample_fir
 apad_chroma launches and one apad_chroma_similarity launch per batch; the CLAP leg is score_waveforms' (apad_clap_logmel, the HIP
 audio and text towers).  Chroma similarity is librosa's chroma_stft restated with the tuning fixed at 0 (ap_adapter_amd/chroma.py):
 compare its numbers with each other, not with a librosa-based evaluation.
+
+Every pair also gets the source's and the edit's integrated loudness (ITU-R BS.1770-4, mono, measured on the 16 kHz signal:
+ap_adapter_amd/loudness.py, one apad_loudness launch per side and batch) and their difference in LU -- "this edit came out 5 LU hotter
+than its source".  A clip shorter than 400 ms or silent has no loudness: null.  Not compared against libebur128 / pyloudnorm.
 """
 import argparse
 import glob
@@ -54,6 +58,12 @@ def load_16k(path, dev):
     from ap_adapter_amd import frontend
     w, sr = frontend.load_wav(path)
     return frontend.resample(torch.from_numpy(w[:1]).to(dev), sr, 16000)[0]
+
+
+def lufs(values):
+    """fp32 loudness values -> JSON numbers, None where a clip has no loudness (-inf)"""
+    import math
+    return [round(float(v), 3) if math.isfinite(float(v)) else None for v in values]
 
 
 def build_clap(clap_dir, dev):
@@ -108,6 +118,7 @@ def main():
         chunk = pairs[i:i + args.batch]
         src, edit = [load_16k(s, dev) for _, s, _ in chunk], [load_16k(e, dev) for _, _, e in chunk]
         sim = A.chroma_similarity(edit, src, ref_index=range(len(chunk))).cpu().tolist()
+        l_src, l_edit = lufs(A.integrated_loudness(src).cpu()), lufs(A.integrated_loudness(edit).cpu())
         cos = [None] * len(chunk)
         if pipe is not None:  # one clip at a time: the extractor crops at random past 10 s, the towers batch per call anyway
             import math
@@ -115,12 +126,18 @@ def main():
                 pipe.score_waveforms(text=[prompts[name]], audio=edit[j][None].cpu(), num_waveforms_per_prompt=1, device=dev, dtype=torch.float32,
                                      audio_device=edit[j][None])
                 cos[j] = float(pipe.last_logits_per_text[0, 0]) / math.exp(pipe.logit_scale_t)
-        for (name, s, _), c, t in zip(chunk, sim, cos):
-            rows.append({"edit": name, "source": os.path.basename(s), "chroma_similarity": round(c, 6),
+        for (name, s, _), c, t, ls, le in zip(chunk, sim, cos, l_src, l_edit):
+            rows.append({"edit": name, "source": os.path.basename(s), "chroma_similarity": round(c, 6), "source_lufs": ls, "edit_lufs": le,
+                         "loudness_difference_lu": None if ls is None or le is None else round(le - ls, 3),
                          **({} if t is None else {"prompt": prompts[name], "clap_cosine": round(t, 6)})})
     res = {"pairs": rows, "n": len(rows), "chroma_similarity_mean": round(sum(r["chroma_similarity"] for r in rows) / len(rows), 6),
            "chroma": "librosa.feature.chroma_stft restated (n_fft 2048, hop 512, 16 kHz, tuning fixed at 0); mean per-frame cosine over the "
-                     "frames both clips have"}
+                     "frames both clips have",
+           "loudness": "ITU-R BS.1770-4 integrated loudness, mono, at 16 kHz (LUFS; null = no 400 ms block above the gates); difference = edit "
+                       "- source in LU"}
+    diffs = [r["loudness_difference_lu"] for r in rows if r["loudness_difference_lu"] is not None]
+    if diffs:
+        res["loudness_difference_lu_mean"] = round(sum(diffs) / len(diffs), 3)
     if pipe is not None:
         res["clap_cosine_mean"] = round(sum(r["clap_cosine"] for r in rows) / len(rows), 6)
     if args.out:

@@ -22,6 +22,12 @@ Fidelity of the edits (--rank-by chroma, an edit run with --wav-dir): every writ
 against its source as the same VAE and vocoder render it (the mean of the source's posterior, decoded), and each rank lists its clips best
 first in WAV_DIR/fidelity_rank<R>.json.
     python tools/run_sharded.py --clips 64 --steps 50 --strength 0.6 --wav-dir out --rank-by chroma
+
+Loudness of the written clips (--target-loudness L|source, --peak-limit-db P, with --wav-dir): before a clip is written it is brought to L
+LUFS (ITU-R BS.1770-4 integrated loudness, ``normalize_loudness``), or -- "source", an edit run -- to the loudness of its source as the same
+VAE and vocoder render it; a gain that would take its largest sample over P dBFS (default -1) is cut to the one that puts it there, so
+nothing is clipped on disk.  Each rank lists file, LUFS before and after and gain in WAV_DIR/loudness_rank<R>.json.
+    python tools/run_sharded.py --clips 64 --steps 50 --wav-dir out --target-loudness -14
 """
 import argparse
 import glob
@@ -139,6 +145,10 @@ def main():
     ap.add_argument("--source-guidance", type=float, default=3.0, metavar="S", help="--inversion: the text guidance scale of the inversion pass")
     ap.add_argument("--rank-by", choices=["chroma"], default=None, help="edit + --wav-dir: score every written clip by chroma similarity to its "
                     "source and list each rank's clips best first in WAV_DIR/fidelity_rank<R>.json")
+    ap.add_argument("--target-loudness", default=None, metavar="L|source", help="--wav-dir: bring every written clip to L LUFS (BS.1770-4), or "
+                    "'source' (an edit run): to the loudness of its source as the same VAE and vocoder render it")
+    ap.add_argument("--peak-limit-db", type=float, default=-1.0, metavar="P", help="--target-loudness: no gain takes a clip's largest sample over "
+                    "P dBFS (<= 0)")
     ap.add_argument("--gpus", type=int, default=1, help="N > 1 without a launcher: this script starts its N ranks itself (one per GPU)")
     args = ap.parse_args()
     if args.inversion and args.sampler != "ddim":
@@ -147,6 +157,23 @@ def main():
                                                or args.inversion is not None)):
         ap.error("--rank-by chroma scores decoded edits against their sources: it needs an edit run (--strength / --edit-region / --source-dir / "
                  "--inversion) and --wav-dir")
+    is_edit = args.strength is not None or args.edit_region is not None or args.source_dir is not None or args.inversion is not None
+    if args.target_loudness is not None:
+        if not args.wav_dir:
+            ap.error("--target-loudness acts on the written waveforms: it needs --wav-dir")
+        if args.target_loudness == "source":
+            if not is_edit:
+                ap.error("--target-loudness source matches an edit to its source: it needs an edit run (--strength / --edit-region / --source-dir / "
+                         "--inversion)")
+        else:
+            try:
+                args.target_loudness = float(args.target_loudness)
+            except ValueError:
+                args.target_loudness = float("nan")
+            if not math.isfinite(args.target_loudness):
+                ap.error("--target-loudness: a finite loudness in LUFS, or 'source'")
+        if not args.peak_limit_db <= 0.0:
+            ap.error("--peak-limit-db must be <= 0 dB relative to full scale")
 
     from ap_adapter_amd import distributed as D
     if args.gpus > 1 and not D.launched_by_torchrun():
@@ -228,7 +255,7 @@ def main():
         os.makedirs(args.wav_dir, exist_ok=True)
         vae, voc = build_decoder(dev, dtype, small=args.small)
         pipe.vae, pipe.vocoder = vae, voc
-        scored, rendered = [], {}
+        scored, rendered, levels = [], {}, []
 
         def rendered_source(path):
             """the source as this VAE and vocoder render it: the mean of its posterior, decoded"""
@@ -242,11 +269,21 @@ def main():
             wav = pipe.mel_spectrogram_to_waveform(mel)[0, : int(args.seconds * 16000)]
             c = clips[idx]
             name = f"{c['prompt']}_{idx}_ip{cfg['ap_scale']}_t{cfg['time_pooling']}_f{cfg['freq_pooling']}.wav".replace("/", "_")
+            if args.target_loudness is not None:  # on the device, before the write: a hot clip is turned down instead of clipped on disk
+                to = dict(reference=rendered_source(c["audio"])) if args.target_loudness == "source" else dict(target=args.target_loudness)
+                wav, gain, before = A.normalize_loudness(wav.to(dev), peak_limit_db=args.peak_limit_db, return_stats=True, **to)
+                lufs = lambda v: round(float(v), 3) if math.isfinite(float(v)) else None
+                levels.append({"file": name, "lufs_before": lufs(before[0, 0]), "lufs_after": lufs(A.integrated_loudness(wav)[0]),
+                               "gain": round(float(gain[0]), 6)})
             write_wav16(os.path.join(args.wav_dir, name), wav)
             n_wavs += 1
             if args.rank_by:
                 scored.append({"file": name, "source": os.path.basename(c["audio"]),
                                "chroma_similarity": round(float(pipe.score_fidelity(wav[None].to(dev), rendered_source(c["audio"]))[0]), 6)})
+        if args.target_loudness is not None:
+            with open(os.path.join(args.wav_dir, f"loudness_rank{rank}.json"), "w") as f:
+                json.dump(levels, f, indent=1)
+                f.write("\n")
         if args.rank_by:
             scored.sort(key=lambda r: -r["chroma_similarity"])
             with open(os.path.join(args.wav_dir, f"fidelity_rank{rank}.json"), "w") as f:
@@ -262,7 +299,8 @@ def main():
                           **({"inversion": args.inversion, "source_prompt": args.source_prompt, "source_guidance": args.source_guidance}
                              if args.inversion else {}),
                           **({"rank_by": args.rank_by, "chroma_similarity_mean_rank0": round(sum(r["chroma_similarity"] for r in scored) / max(len(scored), 1), 6)}
-                             if args.rank_by else {})}))
+                             if args.rank_by else {}),
+                          **({"target_loudness": args.target_loudness, "peak_limit_db": args.peak_limit_db} if args.target_loudness is not None else {})}))
         if args.out:
             torch.save({"latents": torch.stack([x.cpu() for x in allc]), "clips": clips}, args.out)
     if world > 1:
