@@ -800,6 +800,8 @@ def linear_qkv(x, w_qkv, B, Lk, heads, q, k, vt, bias=None, ln=None, v=None):
     vt [B, heads, d, Lpad] per-head transposed, one launch.  ln = (gamma, beta, eps): LayerNorm(x) folded in (needs rowstat_of(x)).
     v: optional [B*Lk, C] row-major copy of the values (same rounded numbers as vt)."""
     _req(x, "linear_qkv.x", w_qkv.dtype)
+    if v is not None and w_qkv.dtype not in FUSED_DTYPES:
+        raise RuntimeError("linear_qkv(v=...): the fp32 kernels write q, k and v^T only; the row-major v needs a 16-bit storage type")
     fold = None
     if ln is not None:
         rs = rowstat_of(x)

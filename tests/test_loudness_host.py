@@ -106,7 +106,7 @@ def test_loudness_argument_resolution():
 BAD_TARGETS = [float("nan"), float("inf"), -float("inf"), "loud", "", [-23.0, float("nan")], [-23.0], [-23.0] * 5, [], object()]
 
 
-@pytest.mark.parametrize("bad", BAD_TARGETS, ids=[repr(b)[:24] for b in BAD_TARGETS])
+@pytest.mark.parametrize("bad", BAD_TARGETS, ids=["object()" if type(b) is object else repr(b)[:24] for b in BAD_TARGETS])  # (an object's repr holds its address: no stable id)
 def test_target_loudness_refuses_anything_else(bad):
     with pytest.raises(ValueError, match="target_loudness"):
         _pipe().check_loudness_arguments(bad, -1.0, None, True, 4)

@@ -65,6 +65,91 @@ def exact_operand(*shape, seed=0, std=1.0, shift=None):
     return torch.where(t.abs() < 2.0 ** -14, torch.zeros_like(t), t)
 
 
+# ---- integer operands: the linear kernels held to every bit (tests/exact_cases.py, test_gpu_exact_linear.py) ----
+# With small-integer operands every product and partial sum of a linear kernel is an integer below 2^24, so fp32 accumulation is exact
+# in ANY order (tile shape, K groups, ring stages, wave layout) and the result is a known integer: the kernel must store that integer
+# correctly rounded.  Nothing here is measured on a kernel: the amplitudes follow from the formats, the conditions are checked on the
+# fp64 reference.
+DTYPE_MAX = {torch.bfloat16: 3.3895313892515355e38, torch.float16: 65504.0, torch.float32: 3.4028234663852886e38}
+
+
+def int_operand(*shape, amp, seed, density=1.0):
+    """fp32 integers uniform in [-amp, amp], each kept with probability ``density`` (else 0)"""
+    g = torch.Generator().manual_seed(seed)
+    t = torch.randint(-int(amp), int(amp) + 1, shape, generator=g).float()
+    if density < 1.0:
+        t = t * (torch.rand(shape, generator=g) < density).float()
+    return t
+
+
+def exact_case(K, dtype, tier):
+    """(amp_x, amp_w, density_w) of a reduction of length K.
+    Tier "A" (representable): x in [-2, 2], w in {-1, 0, 1} at density min(1, 36^2 / (2K)): the accumulator's sigma is about
+    sqrt(K * 2 * density * 2/3) <= 30, so |acc| stays below 256 = what bf16 holds exactly (checked per case by assert_exact_conditions).
+    Tier "B" (rounded; 16-bit only): x and w dense in [-a, a], a the smallest integer with a (a + 1) / 3 * sqrt(K) >= 600 (bf16) or 5000
+    (f16): sigma of the outputs, far above the exactly-held range (256 / 2048) and far below the format's maximum."""
+    if tier == "A":
+        return 2, 1, min(1.0, 36.0 ** 2 / (2.0 * K))
+    assert tier == "B" and dtype in (torch.bfloat16, torch.float16), (tier, dtype)
+    target = 600.0 if dtype == torch.bfloat16 else 5000.0
+    a = 1
+    while a * (a + 1) / 3.0 * K ** 0.5 < target:
+        a += 1
+    return a, a, 1.0
+
+
+def rne(t64, dtype):
+    """an fp64 tensor of integers below 2^24 -> ``dtype``, round-to-nearest-even: the fp32 step is exact, the second is torch's rounding"""
+    return t64.float().to(dtype)
+
+
+def unrepresentable_and_ties(t64, dtype):
+    """(fraction of elements ``dtype`` does not hold exactly, fraction that lie exactly half way between two neighbours)"""
+    r = rne(t64, dtype).double()
+    off = r != t64
+    mirror = 2.0 * t64 - r  # the neighbour on the other side, if the element is a tie (else a number the format does not hold)
+    tie = off & (rne(mirror, dtype).double() == mirror)
+    n = max(t64.numel(), 1)
+    return float(off.sum()) / n, float(tie.sum()) / n
+
+
+def assert_exact_conditions(ref, intermediates, dtype, tier, K, amp_x, amp_w, side=()):
+    """the conditions under which a linear kernel's output is determined in every bit, asserted on the fp64 reference alone (never on a
+    kernel's output).  ref: the value the final rounding sees (a tensor, or a list of them); intermediates: the accumulator and
+    every value a kernel may round on the way (acc + bias, ...); side: fp32 side outputs (row statistics)."""
+    refs = list(ref) if isinstance(ref, (list, tuple)) else [ref]
+    for t in refs + list(intermediates) + list(side):
+        assert t.dtype == torch.float64 and torch.equal(t, t.round()), "not an integer"
+    assert K * amp_x * amp_w < 2 ** 24, (K, amp_x, amp_w)
+    top = max(float(t.abs().max()) for t in refs + list(intermediates))
+    if tier == "A":
+        assert top <= 256, f"max |value| {top} leaves the range bf16 holds exactly"
+        for t in side:
+            assert float(t.abs().max()) < 2 ** 24
+    else:
+        assert tier == "B" and dtype in (torch.bfloat16, torch.float16)
+        assert not side, "tier B has no exact side outputs"
+        assert top < DTYPE_MAX[dtype] / 2 and top < 2 ** 24, top
+        for t in refs:
+            off, tie = unrepresentable_and_ties(t, dtype)
+            assert off >= 0.25 and tie >= 0.10, f"only {off:.1%} of the outputs are rounded, {tie:.1%} are ties"
+
+
+def assert_bits_equal(out, expected, what=""):
+    """torch.equal on the bit patterns; the message names the first differing (row, column) of the [-1, last dim] view"""
+    assert out.dtype == expected.dtype and tuple(out.shape) == tuple(expected.shape), (what, out.dtype, expected.dtype, tuple(out.shape), tuple(expected.shape))
+    idt = torch.int16 if out.element_size() == 2 else torch.int32
+    a, e = out.detach().cpu().contiguous(), expected.detach().cpu().contiguous()
+    if torch.equal(a.view(idt), e.view(idt)):
+        return
+    cols = a.shape[-1] if a.dim() else 1
+    bad = (a.view(idt) != e.view(idt)).reshape(-1)
+    i = int(bad.to(torch.uint8).argmax())
+    av, ev = float(a.reshape(-1)[i]), float(e.reshape(-1)[i])
+    raise AssertionError(f"{what + ': ' if what else ''}{int(bad.sum())} of {bad.numel()} elements differ; first at (row {i // cols}, column {i % cols}): "
+                         f"expected {ev!r}, got {av!r}, difference {av - ev!r}")
+
+
 def block_rel_err(out, ref, nblocks):
     """(worst, index) of the max-abs error of each of ``nblocks`` equal blocks relative to that block's own max|ref| (the leading
     dims of ``out`` / ``ref`` must enumerate the blocks).  A block whose reference is all zero must be exactly zero: its error is
