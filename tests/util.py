@@ -150,6 +150,52 @@ def assert_bits_equal(out, expected, what=""):
                          f"expected {ev!r}, got {av!r}, difference {av - ev!r}")
 
 
+# ---- attention held to selection / uniform / power-of-two softmaxes (tests/attn_exact_cases.py, test_gpu_exact_attention.py) ----
+_MANT_MINEXP = {torch.bfloat16: (7, -126), torch.float16: (10, -14), torch.float32: (23, -126)}
+
+
+def ulp_of(t64, dtype):
+    """fp64 tensor -> the spacing of ``dtype`` at each value (at zero and in the subnormal range: the subnormal spacing)"""
+    mant, emin = _MANT_MINEXP[dtype]
+    e = torch.frexp(t64.abs().double())[1].double() - 1.0  # |t| in [2^e, 2^(e+1)); frexp(0) gives e = -1, clamped below
+    e = torch.where(t64 == 0, torch.full_like(e, float(emin)), e).clamp_min(float(emin))
+    return torch.exp2(e - mant)
+
+
+def assert_within_half_ulp(out, ref64, absref64, dtype, what=""):
+    """|out - ref64| <= 0.5 ulp_dtype(ref64) + 8 * 2^-24 * absref64: a result whose only inexact steps are a reciprocal, the multiply by
+    it (a few fp32 ulp of the magnitude ``absref64`` = the same attention applied to |V|) and the final rounding to ``dtype``.
+    The message names the first offending (row, column) of the [-1, last dim] view."""
+    assert out.dtype == dtype and tuple(out.shape) == tuple(ref64.shape) == tuple(absref64.shape), \
+        (what, out.dtype, dtype, tuple(out.shape), tuple(ref64.shape), tuple(absref64.shape))
+    a = out.detach().cpu().double()
+    ulp = ulp_of(ref64, dtype)
+    err = (a - ref64).abs()
+    bad = ~(err <= 0.5 * ulp + 8.0 * 2.0 ** -24 * absref64)  # (a NaN is bad)
+    if not bool(bad.any()):
+        return
+    cols = a.shape[-1] if a.dim() else 1
+    i = int(bad.reshape(-1).to(torch.uint8).argmax())
+    av, ev, uv = float(a.reshape(-1)[i]), float(ref64.reshape(-1)[i]), float(ulp.reshape(-1)[i])
+    raise AssertionError(f"{what + ': ' if what else ''}{int(bad.sum())} of {bad.numel()} elements leave the half-ulp bound; first at (row {i // cols}, "
+                         f"column {i % cols}): expected {ev!r}, got {av!r}, error {(av - ev) / uv:.3f} ulp")
+
+
+def nan_padded_vt(v, Lpad, dtype, device, poison=True, zero_to=None):
+    """v [Bk, L, heads, d] (CPU) -> V^T [Bk, heads, d, Lpad] on ``device``; the pad columns [L, Lpad) are NaN (NAN_WORD) with ``poison``,
+    else the zeros the kernels of ops.attention's layout document that they need (csrc/attention.hip: "with zero padding"); zero_to: the
+    columns [L, zero_to) are zeros and only [zero_to, Lpad) NaN"""
+    Bk, L, heads, d = v.shape
+    assert Lpad >= L and Lpad % 32 == 0
+    n = Bk * heads * d * Lpad
+    buf = nan_buffer(n, dtype, device) if poison else torch.zeros(n, dtype=dtype, device=device)
+    buf = buf.view(Bk, heads, d, Lpad)
+    if zero_to is not None:
+        buf[..., L:zero_to] = 0
+    buf[..., :L] = v.permute(0, 2, 3, 1).to(device, dtype)
+    return buf
+
+
 def block_rel_err(out, ref, nblocks):
     """(worst, index) of the max-abs error of each of ``nblocks`` equal blocks relative to that block's own max|ref| (the leading
     dims of ``out`` / ``ref`` must enumerate the blocks).  A block whose reference is all zero must be exactly zero: its error is
