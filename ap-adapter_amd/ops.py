@@ -941,23 +941,30 @@ def softmax_rows(x, scale=1.0, out=None, bias=None):
     return out.view(x.shape)
 
 
-def rms_norm(x, gamma, eps):
-    """T5LayerNorm: x * rsqrt(mean(x^2) + eps) * gamma over the last dim"""
+def _dense_out(out, like, what):
+    """a caller's result buffer: contiguous, on like's device, of like's dtype and shape"""
+    if out.dtype != like.dtype or out.device != like.device or tuple(out.shape) != tuple(like.shape) or not out.is_contiguous():
+        raise ValueError(f"{what}: expected a contiguous {like.dtype} buffer of shape {tuple(like.shape)} on {like.device}")
+    return out
+
+
+def rms_norm(x, gamma, eps, out=None):
+    """T5LayerNorm: x * rsqrt(mean(x^2) + eps) * gamma over the last dim; out: a dense buffer of x's shape and dtype"""
     _req(x, "rms_norm.x", gamma.dtype)
     Cc = x.shape[-1]
     x2 = x.reshape(-1, Cc)
-    out = torch.empty_like(x2)
+    out = torch.empty_like(x2) if out is None else _dense_out(out, x, "rms_norm.out").view(-1, Cc)
     L.check(L.lib().apad_rmsnorm(x2.data_ptr(), gamma.data_ptr(), out.data_ptr(), x2.shape[0], Cc, x2.stride(0), Cc, float(eps), 0, _DT[x.dtype],
                                  _stream()), "apad_rmsnorm")
     return out.view(x.shape)
 
 
-def l2_normalize(x, eps=1e-12):
-    """F.normalize(x, dim=-1)"""
+def l2_normalize(x, eps=1e-12, out=None):
+    """F.normalize(x, dim=-1); out: a dense buffer of x's shape and dtype"""
     _req(x, "l2_normalize.x")
     Cc = x.shape[-1]
     x2 = x.reshape(-1, Cc)
-    out = torch.empty_like(x2)
+    out = torch.empty_like(x2) if out is None else _dense_out(out, x, "l2_normalize.out").view(-1, Cc)
     L.check(L.lib().apad_rmsnorm(x2.data_ptr(), None, out.data_ptr(), x2.shape[0], Cc, x2.stride(0), Cc, float(eps), 1, _DT[x.dtype], _stream()),
             "apad_rmsnorm")
     return out.view(x.shape)
@@ -1227,7 +1234,7 @@ def group_norm(x, gamma, beta, groups, eps, silu=False, out=None):
     return out
 
 
-def group_norm2(xa, xb, gamma, beta, groups, eps, silu=False):
+def group_norm2(xa, xb, gamma, beta, groups, eps, silu=False, out=None):
     """GroupNorm (+ SiLU) of torch.cat([xa, xb], -1) without the concatenation: xa [Ba, HW, Ca], xb [Bb, HW, Cb] -> [B, HW, Ca + Cb]
     with B = max(Ba, Bb), the smaller batch read modulo (see linear2).  16-bit storage types."""
     _req(xa, "group_norm2.xa", gamma.dtype)
@@ -1238,7 +1245,10 @@ def group_norm2(xa, xb, gamma, beta, groups, eps, silu=False):
     if HWb != HW or B % Ba or B % Bb or not (xa.is_contiguous() and xb.is_contiguous()) or xa.dtype not in FUSED_DTYPES:
         raise ValueError(f"group_norm2: xa {tuple(xa.shape)}, xb {tuple(xb.shape)} {xa.dtype}")
     ws = _gn_workspace(xa.device, B, HW, groups)
-    out = torch.empty(B, HW, Ca + Cb, dtype=xa.dtype, device=xa.device)
+    if out is None:
+        out = torch.empty(B, HW, Ca + Cb, dtype=xa.dtype, device=xa.device)
+    elif tuple(out.shape) != (B, HW, Ca + Cb) or out.dtype != xa.dtype or out.device != xa.device or not out.is_contiguous():
+        raise ValueError(f"group_norm2.out: expected a contiguous {xa.dtype} [{B}, {HW}, {Ca + Cb}] buffer on {xa.device}")
     L.check(L.lib().apad_groupnorm2(xa.data_ptr(), xb.data_ptr(), gamma.data_ptr(), beta.data_ptr(), out.data_ptr(), ws.data_ptr(), B, Ba, Bb,
                                     HW, Ca, Cb, groups, eps, 1 if silu else 0, _DT[xa.dtype], _stream()), "apad_groupnorm2")
     return out
@@ -1531,11 +1541,11 @@ def attention_bwd(q, k, v, out, dout, lse, heads, key_bias=None, dout_scale=1.0,
     return dq, dk, dv
 
 
-def layer_norm_bwd(x, gamma, dy, eps, dres=None):
+def layer_norm_bwd(x, gamma, dy, eps, dres=None, out=None):
     """dres: the gradient that reaches x past the LayerNorm (a pre-norm sub-layer's residual connection), added in the same launch"""
     _req(x, "layer_norm_bwd.x", gamma.dtype)
     Cc = x.shape[-1]
-    dx = torch.empty_like(x)
+    dx = torch.empty_like(x) if out is None else _dense_out(out, x, "layer_norm_bwd.out")
     if dres is not None:
         _req(dres, "layer_norm_bwd.dres", x.dtype)
         if not dres.is_contiguous() or dres.shape != x.shape:
@@ -1545,10 +1555,10 @@ def layer_norm_bwd(x, gamma, dy, eps, dres=None):
     return dx
 
 
-def group_norm_bwd(x, gamma, beta, dy, groups, eps, silu):
+def group_norm_bwd(x, gamma, beta, dy, groups, eps, silu, out=None):
     _req(x, "group_norm_bwd.x", gamma.dtype)
     B, HW, Cc = x.shape
-    dx = torch.empty_like(x)
+    dx = torch.empty_like(x) if out is None else _dense_out(out, x, "group_norm_bwd.out")
     L.check(L.lib().apad_groupnorm_bwd(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), dy.data_ptr(), dx.data_ptr(), B, HW,
                                        Cc, groups, eps, 1 if silu else 0, _DT[x.dtype], _stream()), "apad_groupnorm_bwd")
     return dx

@@ -162,16 +162,17 @@ def ulp_of(t64, dtype):
     return torch.exp2(e - mant)
 
 
-def assert_within_half_ulp(out, ref64, absref64, dtype, what=""):
-    """|out - ref64| <= 0.5 ulp_dtype(ref64) + 8 * 2^-24 * absref64: a result whose only inexact steps are a reciprocal, the multiply by
-    it (a few fp32 ulp of the magnitude ``absref64`` = the same attention applied to |V|) and the final rounding to ``dtype``.
+def assert_within_half_ulp(out, ref64, absref64, dtype, what="", coeff=8.0):
+    """|out - ref64| <= 0.5 ulp_dtype(ref64) + coeff * 2^-24 * absref64 (coeff 8: a result whose only inexact steps are a reciprocal, the multiply by
+    it (a few fp32 ulp of the magnitude ``absref64`` = the same attention applied to |V|) and the final rounding to ``dtype``; coeff 16: a normalisation,
+    tests/norm_exact_cases.py).
     The message names the first offending (row, column) of the [-1, last dim] view."""
     assert out.dtype == dtype and tuple(out.shape) == tuple(ref64.shape) == tuple(absref64.shape), \
         (what, out.dtype, dtype, tuple(out.shape), tuple(ref64.shape), tuple(absref64.shape))
     a = out.detach().cpu().double()
     ulp = ulp_of(ref64, dtype)
     err = (a - ref64).abs()
-    bad = ~(err <= 0.5 * ulp + 8.0 * 2.0 ** -24 * absref64)  # (a NaN is bad)
+    bad = ~(err <= 0.5 * ulp + coeff * 2.0 ** -24 * absref64)  # (a NaN is bad)
     if not bool(bad.any()):
         return
     cols = a.shape[-1] if a.dim() else 1
