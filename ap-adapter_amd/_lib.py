@@ -79,6 +79,10 @@ class HsAttnDesc(C.Structure):
                [(n, _f32) for n in ("ln_eps", "softmax_scale", "scale2", "reserved_f")]
 
 
+class Scale2Tab(C.Structure):
+    _fields_ = [("table", _vp), ("step", _vp), ("rows", _i32), ("cols", _i32), ("ld", _i64)]
+
+
 class HsOutDesc(C.Structure):
     _fields_ = [(n, _vp) for n in ("o", "w_packed", "bias", "residual", "out", "rowstat_out")] + [(n, _i32) for n in ("B", "N", "C", "dtype")]
 
@@ -119,6 +123,13 @@ SYMBOLS = {
     "apad_cross_attention_rows": (C.c_int, [C.POINTER(XrowsDesc), _vp]),
     "apad_sizeof_hs_attn_desc": (C.c_int, []),
     "apad_hs_attention": (C.c_int, [C.POINTER(HsAttnDesc), _vp]),
+    # ap_scale from a device table: the four two-segment attention launches with scale2 read at the captured step's counter
+    "apad_sizeof_scale2_tab": (C.c_int, []),
+    "apad_echo_scale2_tab": (C.c_int, [C.POINTER(Scale2Tab), C.POINTER(C.c_double), C.c_int]),
+    "apad_attention_tab": (C.c_int, [C.POINTER(AttnDesc), C.POINTER(Scale2Tab), _vp]),
+    "apad_fused_cross_attention_tab": (C.c_int, [C.POINTER(XattnDesc), C.POINTER(Scale2Tab), _vp]),
+    "apad_cross_attention_rows_tab": (C.c_int, [C.POINTER(XrowsDesc), C.POINTER(Scale2Tab), _vp]),
+    "apad_hs_attention_tab": (C.c_int, [C.POINTER(HsAttnDesc), C.POINTER(Scale2Tab), _vp]),
     "apad_self_attention_fused": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _vp]),
     "apad_hs_geglu": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _vp]),
     "apad_sizeof_hs_out_desc": (C.c_int, []),
@@ -234,7 +245,8 @@ def lib():
                     or h.apad_sizeof_mlp_desc() != C.sizeof(MlpDesc) \
                     or h.apad_sizeof_attn_bwd_desc() != C.sizeof(AttnBwdDesc) \
                     or h.apad_sizeof_xattn_desc() != C.sizeof(XattnDesc) or h.apad_sizeof_xrows_desc() != C.sizeof(XrowsDesc) \
-                    or h.apad_sizeof_hs_attn_desc() != C.sizeof(HsAttnDesc) or h.apad_sizeof_hs_out_desc() != C.sizeof(HsOutDesc):
+                    or h.apad_sizeof_hs_attn_desc() != C.sizeof(HsAttnDesc) or h.apad_sizeof_hs_out_desc() != C.sizeof(HsOutDesc) \
+                    or h.apad_sizeof_scale2_tab() != C.sizeof(Scale2Tab):
                 raise RuntimeError("descriptor layout mismatch between include/apadapter_hip.h and _lib.py")
             _lib = h
     return _lib

@@ -39,6 +39,7 @@ struct AttnP {
     int64_t q_sb, q_sn, k_sb, k_sl, vt_sb, k2_sb, k2_sl, vt2_sb, o_sb, o_sn;
     int32_t B, N, H, L, Lpad, L2, Lpad2, kvdiv, kvdiv2;
     float scale_log2, scale2;
+    Scale2Tab s2;       // apad_attention_tab: scale2 per sample from a device table (table == nullptr: the scalar above)
     int32_t prescaled;  // q already carries softmax_scale * log2(e) (scale_log2 is then exactly 1)
 };
 
@@ -359,6 +360,7 @@ __global__ __launch_bounds__(256) void attn_kernel(AttnP p) {
             f32x2 osum2 = {0.f, 0.f};
             float m2 = NEG_BIG;
             const int bk = b / p.kvdiv2;
+            const float scale2 = scale2_of(p.s2, p.scale2, b);
             const uint8_t* kbase = p.k2 + ((int64_t)bk * p.k2_sb + h * D) * 2;
             const uint8_t* vbase = p.vt2 + ((int64_t)bk * p.vt2_sb + (int64_t)h * D * p.Lpad2) * 2;
             segment<DT, D>(smem, kbase, p.k2_sl, vbase, p.L2, p.Lpad2, nullptr, p.scale_log2, qf, o2, osum2, m2, tid);
@@ -370,7 +372,7 @@ __global__ __launch_bounds__(256) void attn_kernel(AttnP p) {
                 for (int r = 0; r < 16; ++r) {
                     const float t = (float)(typename E::elem)o[dt][r];
                     const float a = (float)(typename E::elem)(o2[dt][r] * inv2);
-                    o[dt][r] = t + (float)(typename E::elem)(p.scale2 * a);
+                    o[dt][r] = t + (float)(typename E::elem)(scale2 * a);
                 }
         }
     }
@@ -1285,6 +1287,7 @@ __global__ __launch_bounds__(256) void attn_short_kernel(AttnP p) {
             for (int r = 0; r < 16; ++r) o2[dt][r] = 0.f;
         float inv2 = 1.f;
         const int bk = b / p.kvdiv2;
+        const float scale2 = scale2_of(p.s2, p.scale2, b);
         const uint8_t* kbase = p.k2 + ((int64_t)bk * p.k2_sb + h * D) * 2;
         const uint8_t* vbase = p.vt2 + ((int64_t)bk * p.vt2_sb + (int64_t)h * D * p.Lpad2) * 2;
         short_segment<DT, D>(kbase, p.k2_sl, vbase, p.L2, p.Lpad2, nullptr, p.scale_log2, qf, o2, inv2, l31, half);
@@ -1295,7 +1298,7 @@ __global__ __launch_bounds__(256) void attn_short_kernel(AttnP p) {
             for (int r = 0; r < 16; ++r) {
                 const float t = (float)(typename E::elem)o[dt][r];
                 const float a = (float)(typename E::elem)(o2[dt][r] * inv2);
-                o[dt][r] = t + (float)(typename E::elem)(p.scale2 * a);
+                o[dt][r] = t + (float)(typename E::elem)(scale2 * a);
             }
     }
     uint8_t* scr = smem + wave * (32 * OROW);
@@ -1418,6 +1421,7 @@ struct XrP {
     uint8_t* out;
     int32_t B, N, L1, Lpad1, L2, Lpad2, tiles_per_sample;
     float eps, scale_log2, scale2;
+    Scale2Tab s2;  // apad_cross_attention_rows_tab (as AttnP::s2)
 };
 
 #include "short_seg.h"
@@ -1520,6 +1524,7 @@ __global__ __launch_bounds__(NW * 64) void xattn_rows_kernel(XrP p) {
     const int b = bid / p.tiles_per_sample, row0 = (bid - b * p.tiles_per_sample) * XR_TM;
     const int nrows = p.N - row0 < XR_TM ? p.N - row0 : XR_TM;
     const uint8_t* const xb = p.x + ((int64_t)b * p.N + row0) * C * 2;
+    const float scale2 = DUAL ? scale2_of(p.s2, p.scale2, b) : 0.f;  // once per workgroup: every row of the tile is sample b's
 
     // ---- 1. LayerNorm -> X ----
     {
@@ -1653,7 +1658,7 @@ __global__ __launch_bounds__(NW * 64) void xattn_rows_kernel(XrP p) {
                     for (int r = 0; r < 16; ++r) {
                         const float t = (float)(typename E::elem)o[dt][r];
                         const float a = (float)(typename E::elem)(o2[dt][r] * inv2);
-                        o[dt][r] = t + (float)(typename E::elem)(p.scale2 * a);
+                        o[dt][r] = t + (float)(typename E::elem)(scale2 * a);
                     }
             }
 #pragma unroll
@@ -1759,9 +1764,13 @@ extern "C" int apad_rows_pack_kv(const void* k, const void* vt, void* out, int32
     return apad_check_launch("apad_rows_pack_kv");
 }
 
-extern "C" int apad_attention(const apad_attn_desc* d, void* stream) {
-    APAD_CHECK(d != nullptr, "apad_attention: null descriptor");
-    if (d->dtype == APAD_F32 || d->dtype == APAD_F32_BF16X3) return apad_f32_attention(d, (hipStream_t)stream);  // fp32 precision modes (f32_ops.hip)
+// apad_attention (t unused) and apad_attention_tab (has_tab) share this launch path
+static int attention_launch(const apad_attn_desc* d, const apad_scale2_tab* t, bool has_tab, void* stream) {
+    const char* const who = has_tab ? "apad_attention_tab" : "apad_attention";
+    APAD_CHECK(d != nullptr, "%s: null descriptor", who);
+    Scale2Tab s2;
+    if (apad_scale2_tab_arg(who, t, has_tab, d->L2, &s2) != 0) return -1;
+    if (d->dtype == APAD_F32 || d->dtype == APAD_F32_BF16X3) return apad_f32_attention(d, s2, (hipStream_t)stream);  // fp32 precision modes (f32_ops.hip)
     APAD_CHECK(d->dtype == APAD_BF16 || d->dtype == APAD_F16, "apad_attention: dtype %d not supported", d->dtype);
     APAD_CHECK(d->q && d->k && d->vt && d->out, "apad_attention: null operand");
     APAD_CHECK(d->B > 0 && d->N > 0 && d->H > 0 && d->L > 0, "apad_attention: empty problem B=%d N=%d H=%d L=%d", d->B, d->N,
@@ -1794,10 +1803,14 @@ extern "C" int apad_attention(const apad_attn_desc* d, void* stream) {
     p.prescaled = d->q_prescaled ? 1 : 0;
     p.scale_log2 = p.prescaled ? 1.0f : d->softmax_scale * 1.4426950408889634f;
     p.scale2 = d->scale2;
+    p.s2 = s2;
     dim3 grid((unsigned)(((d->N + 127) / 128) * (((d->H * d->B) + 7) / 8 * 8)));
     hipStream_t s = (hipStream_t)stream;
     return d->dtype == APAD_BF16 ? launch_dt<APAD_BF16>(p, d->D, dual, grid, s) : launch_dt<APAD_F16>(p, d->D, dual, grid, s);
 }
+
+extern "C" int apad_attention(const apad_attn_desc* d, void* stream) { return attention_launch(d, nullptr, false, stream); }
+extern "C" int apad_attention_tab(const apad_attn_desc* d, const apad_scale2_tab* t, void* stream) { return attention_launch(d, t, true, stream); }
 
 extern "C" int apad_self_attention_fused(const void* x, const void* w_packed, const float* colsum_bias, void* out, int32_t B, int32_t N, int32_t C, int32_t heads,
                                          float ln_eps, int32_t dtype, void* stream) {
@@ -1816,8 +1829,12 @@ extern "C" int apad_self_attention_fused(const void* x, const void* w_packed, co
     return dtype == APAD_BF16 ? sf_go<APAD_BF16, 48, 24, 4, SF_NPP48, SF_NSET48>(p, s) : sf_go<APAD_F16, 48, 24, 4, SF_NPP48, SF_NSET48>(p, s);
 }
 
-extern "C" int apad_cross_attention_rows(const apad_xrows_desc* d, void* stream) {
-    APAD_CHECK(d != nullptr, "apad_cross_attention_rows: null descriptor");
+// apad_cross_attention_rows (t unused) and apad_cross_attention_rows_tab (has_tab) share this launch path
+static int cross_attention_rows_launch(const apad_xrows_desc* d, const apad_scale2_tab* t, bool has_tab, void* stream) {
+    const char* const who = has_tab ? "apad_cross_attention_rows_tab" : "apad_cross_attention_rows";
+    APAD_CHECK(d != nullptr, "%s: null descriptor", who);
+    Scale2Tab s2;
+    if (apad_scale2_tab_arg(who, t, has_tab, d->L2, &s2) != 0) return -1;
     APAD_CHECK(d->dtype == APAD_BF16 || d->dtype == APAD_F16, "apad_cross_attention_rows: dtype %d not supported (16-bit only)", d->dtype);
     if (d->C != 384 || d->heads != 8) {  // (the 64-token level, C = 640: apad_hs_attention + apad_hs_out, hsattn.hip)
         apad_set_error("apad_cross_attention_rows: C=%d heads=%d outside the kernel envelope (384, 8)", d->C, d->heads);
@@ -1846,9 +1863,13 @@ extern "C" int apad_cross_attention_rows(const apad_xrows_desc* d, void* stream)
     p.B = d->B; p.N = d->N; p.L1 = d->L1; p.Lpad1 = d->Lpad1; p.L2 = d->L2; p.Lpad2 = d->Lpad2;
     const int tm = 64;  // tokens per workgroup (xattn_rows_kernel, 8 waves)
     p.tiles_per_sample = (d->N + tm - 1) / tm;
-    p.eps = d->ln_eps; p.scale_log2 = d->softmax_scale * LOG2E; p.scale2 = d->scale2;
+    p.eps = d->ln_eps; p.scale_log2 = d->softmax_scale * LOG2E; p.scale2 = d->scale2; p.s2 = s2;
     hipStream_t s = (hipStream_t)stream;
     // (8 waves: 35.8 us at the bench geometry vs 42.5 with 4 waves x 2 panels; deeper weight prefetch -- 6 / 8 register sets -- within 1 us; round 6: 4 waves x
     //  ONE 32-token panel -- 504 workgroups, three resident per CU -- is step-neutral: 34.54 / 34.52 vs 34.58 / 34.55 ms on the same box)
     return d->dtype == APAD_BF16 ? xattn_rows_launch<APAD_BF16, 384, 8, 3>(p, s) : xattn_rows_launch<APAD_F16, 384, 8, 3>(p, s);
+}
+extern "C" int apad_cross_attention_rows(const apad_xrows_desc* d, void* stream) { return cross_attention_rows_launch(d, nullptr, false, stream); }
+extern "C" int apad_cross_attention_rows_tab(const apad_xrows_desc* d, const apad_scale2_tab* t, void* stream) {
+    return cross_attention_rows_launch(d, t, true, stream);
 }

@@ -78,6 +78,26 @@ extern "C" int apad_echo_attn_desc(const apad_attn_desc* d, double* out, int cap
     return n;
 }
 
+extern "C" int apad_sizeof_scale2_tab(void) { return (int)sizeof(apad_scale2_tab); }
+extern "C" int apad_echo_scale2_tab(const apad_scale2_tab* t, double* out, int cap) {
+    int n = 0;
+    PUTP(t->table); PUTP(t->step); PUT(t->rows); PUT(t->cols); PUT(t->ld);
+    return n;
+}
+
+int apad_scale2_tab_arg(const char* who, const apad_scale2_tab* t, bool has_tab, int L2, Scale2Tab* out) {
+    out->table = nullptr; out->step = nullptr; out->ld = 0; out->rows = 0; out->cols = 1;
+    if (!has_tab) return 0;
+    APAD_CHECK(t != nullptr && t->table != nullptr, "%s: null scale2 table", who);
+    APAD_CHECK(t->rows > 0 && t->cols > 0, "%s: scale2 table needs rows > 0 and cols > 0 (rows=%d cols=%d)", who, t->rows, t->cols);
+    APAD_CHECK(t->ld >= t->cols, "%s: scale2 table row stride %lld < cols %d", who, (long long)t->ld, t->cols);
+    APAD_CHECK((reinterpret_cast<uintptr_t>(t->table) & 3) == 0 && (reinterpret_cast<uintptr_t>(t->step) & 3) == 0,
+               "%s: scale2 table and step pointers must be 4-byte aligned", who);
+    APAD_CHECK(L2 > 0, "%s: a scale2 table needs a second segment (L2 == 0)", who);
+    out->table = t->table; out->step = t->step; out->ld = t->ld; out->rows = t->rows; out->cols = t->cols;
+    return 0;
+}
+
 extern "C" int apad_sizeof_rp_desc(void) { return (int)sizeof(apad_rp_desc); }
 extern "C" int apad_echo_rp_desc(const apad_rp_desc* d, double* out, int cap) {
     int n = 0;

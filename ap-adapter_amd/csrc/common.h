@@ -126,6 +126,40 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// apad_scale2_tab as the two-segment attention kernels carry it in their parameter block: table == nullptr selects the descriptor's scalar.
+struct Scale2Tab {
+    const float* table;
+    const int32_t* step;
+    int64_t ld;
+    int32_t rows, cols;
+};
+// The weight of segment 2 for sample b: table[min(*step, rows - 1) * ld + b % cols], or `scalar` without a table.  Read once per workgroup (per
+// panel group where a tile spans samples), before the key loop: the address is formed from kernel arguments, *step and the workgroup's sample
+// index only -- readfirstlane states that to the compiler -- so it is one scalar load on the uniform path and the value lives in an SGPR.
+__device__ __forceinline__ float scale2_of(const Scale2Tab& t, float scalar, int b) {
+    if (t.table == nullptr) return scalar;
+    int r = t.step ? *t.step : 0;
+    r = r < t.rows - 1 ? r : t.rows - 1;
+    r = r > 0 ? r : 0;
+    const int c = __builtin_amdgcn_readfirstlane(b) % t.cols;
+    return t.table[(int64_t)r * t.ld + c];
+}
+// The same for a persistent kernel that reads the table after it has stored a tile: there the compiler cannot show the table unwritten and
+// would fetch the uniform value through the vector port into a VGPR, one register too many for the 256-register kernels.  Both reads are
+// scalar loads by hand (the scalar cache is clean: nothing in the launch writes the table or the counter).
+__device__ __forceinline__ float scale2_of_sload(const Scale2Tab& t, float scalar, int b) {
+    if (t.table == nullptr) return scalar;
+    int r = 0;
+    if (t.step) asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(r) : "s"(t.step) : "memory");
+    r = r < t.rows - 1 ? r : t.rows - 1;
+    r = r > 0 ? r : 0;
+    const int c = __builtin_amdgcn_readfirstlane(b) % t.cols;
+    const float* src = t.table + ((int64_t)r * t.ld + c);
+    float v;
+    asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) : "s"(src) : "memory");
+    return v;
+}
+
 // host-side error plumbing (capi.cpp)
 void apad_set_error(const char* fmt, ...);
 #define APAD_CHECK(cond, ...)            \
@@ -136,6 +170,9 @@ void apad_set_error(const char* fmt, ...);
         }                                \
     } while (0)
 int apad_check_launch(const char* what);
+// The table of an apad_*_tab entry point `who`, checked (null table, rows / cols <= 0, ld < cols, a pointer off 4 bytes, or a single-segment call
+// L2 == 0: an error naming `who`, -1) and copied into the kernels' form.  t == nullptr (the scalar entry points): *out = no table, 0.
+int apad_scale2_tab_arg(const char* who, const apad_scale2_tab* t, bool has_tab, int L2, Scale2Tab* out);
 // The dtype ladder of the 256-thread element-wise launches, for the `dtype` (APAD_BF16 / APAD_F16 / APAD_F32, checked by the caller) and the
 // stream `s` of the calling scope: kern<DT> (LAUNCH_DT), kern<DT, F> (LAUNCH_DT_F), kern<DT, vec ? 8 : 1> (LAUNCH_DT_V)
 #define LAUNCH_DT(kern, grid, ...)                                                                                \

@@ -323,6 +323,7 @@ struct A32P {
     int64_t q_sb, q_sn, k_sb, k_sl, vt_sb, k2_sb, k2_sl, vt2_sb, o_sb, o_sn;
     int32_t B, N, H, L, Lpad, L2, Lpad2, kvdiv, kvdiv2;
     float scale_log2, scale2;
+    Scale2Tab s2;  // apad_attention_tab: scale2 per sample from a device table (table == nullptr: the scalar above)
 };
 
 constexpr float LOG2E_F = 1.4426950408889634f;
@@ -485,13 +486,14 @@ template <int D, bool X3> __device__ __forceinline__ void attn_f32_body(const A3
         f32x16 o2[DT_TILES];
         float den2, m2;
         const int bk = b / p.kvdiv2;
+        const float scale2 = scale2_of(p.s2, p.scale2, b);
         segment32<D, X3>(p.k2 + (int64_t)bk * p.k2_sb + h * D, p.k2_sl, p.vt2 + (int64_t)bk * p.vt2_sb + (int64_t)h * D * p.Lpad2, p.L2,
                      p.Lpad2, nullptr, p.scale_log2, qf, o2, den2, m2, l31, half);
         const float inv2 = 1.0f / den2;
 #pragma unroll
         for (int dt = 0; dt < DT_TILES; ++dt)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) o[dt][r] += p.scale2 * (o2[dt][r] * inv2);  // attention_processor.py:454
+            for (int r = 0; r < 16; ++r) o[dt][r] += scale2 * (o2[dt][r] * inv2);  // attention_processor.py:454
     }
     if (!qvalid) return;
     float* ob = p.out + (int64_t)b * p.o_sb + (int64_t)qi * p.o_sn + h * D;
@@ -840,7 +842,7 @@ int apad_f32_gemm(const apad_gemm_desc* d, hipStream_t s) {
     return apad_check_launch("apad_gemm(f32)");
 }
 
-int apad_f32_attention(const apad_attn_desc* d, hipStream_t s) {
+int apad_f32_attention(const apad_attn_desc* d, const Scale2Tab& s2, hipStream_t s) {
     APAD_CHECK(d->q && d->k && d->vt && d->out, "apad_attention(f32): null operand");
     APAD_CHECK(d->B > 0 && d->N > 0 && d->H > 0 && d->L > 0, "apad_attention(f32): empty problem B=%d N=%d H=%d L=%d", d->B, d->N, d->H,
                d->L);
@@ -870,6 +872,7 @@ int apad_f32_attention(const apad_attn_desc* d, hipStream_t s) {
     p.kvdiv = d->kv_batch_div; p.kvdiv2 = dual ? d->kv2_batch_div : 1;
     p.scale_log2 = d->q_prescaled ? 1.0f : d->softmax_scale * LOG2E_F;
     p.scale2 = d->scale2;
+    p.s2 = s2;
     const bool x3 = d->dtype == APAD_F32_BF16X3;
     switch (d->D) {
         case 16: return attn_launch<16>(p, x3, s);

@@ -57,6 +57,7 @@ struct HsP {
     uint8_t* out;
     int32_t B, N, L1, Lpad1, L2, Lpad2, normalize, xm;
     float eps, scale_log2, scale2;
+    Scale2Tab s2;  // apad_hs_attention_tab: scale2 per sample from a device table (table == nullptr: the scalar above)
 };
 
 // One sample's rows into the X tile: 8 lanes per row, 64 rows per pass of 512 threads, in two steps so that the caller can put its weight
@@ -223,6 +224,7 @@ __global__ __launch_bounds__(512) void hs_attn_kernel(HsP p) {
     hs_decode(blockIdx.x, p.xm, b, pr);
     if (b >= p.B) return;  // (the grid is padded to whole XCD rounds)
     const int N = p.N;
+    const float scale2 = DUAL ? scale2_of(p.s2, p.scale2, b) : 0.f;  // once per workgroup = (sample, head pair)
 
     // ---- 0. the sample's rows are requested first, the weight stream right behind them: wave w owns row tiles w (and w + 8) of the pair's block ----
     uint4 xr[HS_CH];
@@ -381,7 +383,7 @@ __global__ __launch_bounds__(512) void hs_attn_kernel(HsP p) {
                 for (int r = 0; r < 16; ++r) {
                     const float t = (float)(typename E::elem)o[dt][r];
                     const float a = (float)(typename E::elem)(o2[dt][r] * inv2);
-                    o[dt][r] = t + (float)(typename E::elem)(p.scale2 * a);
+                    o[dt][r] = t + (float)(typename E::elem)(scale2 * a);
                 }
         }
         // O(head, panel) over this wave's own q values in the Q tile (nobody else reads them)
@@ -868,8 +870,12 @@ inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) =
 extern "C" int apad_sizeof_hs_attn_desc(void) { return (int)sizeof(apad_hs_attn_desc); }
 extern "C" int apad_sizeof_hs_out_desc(void) { return (int)sizeof(apad_hs_out_desc); }
 
-extern "C" int apad_hs_attention(const apad_hs_attn_desc* d, void* stream) {
-    APAD_CHECK(d != nullptr, "apad_hs_attention: null descriptor");
+// apad_hs_attention (t unused) and apad_hs_attention_tab (has_tab) share this launch path
+static int hs_attention_launch(const apad_hs_attn_desc* d, const apad_scale2_tab* t, bool has_tab, void* stream) {
+    const char* const who = has_tab ? "apad_hs_attention_tab" : "apad_hs_attention";
+    APAD_CHECK(d != nullptr, "%s: null descriptor", who);
+    Scale2Tab s2;
+    if (apad_scale2_tab_arg(who, t, has_tab, d->L2, &s2) != 0) return -1;
     APAD_CHECK(d->dtype == APAD_BF16 || d->dtype == APAD_F16, "apad_hs_attention: dtype %d not supported (16-bit only)", d->dtype);
     if (d->C != HS_C || d->heads != HS_H || d->N < 1 || d->N > HS_TM) {
         apad_set_error("apad_hs_attention: C=%d heads=%d N=%d outside the kernel envelope (640, 8, 1..64)", d->C, d->heads, d->N);
@@ -897,11 +903,14 @@ extern "C" int apad_hs_attention(const apad_hs_attn_desc* d, void* stream) {
     p.k1 = (const uint8_t*)d->k1; p.vt1 = (const uint8_t*)d->vt1; p.bias1 = d->key_bias; p.k2 = (const uint8_t*)d->k2; p.vt2 = (const uint8_t*)d->vt2;
     p.out = (uint8_t*)d->out;
     p.B = d->B; p.N = d->N; p.L1 = d->L1; p.Lpad1 = d->Lpad1; p.L2 = d->L2; p.Lpad2 = d->Lpad2;
-    p.eps = d->ln_eps; p.scale_log2 = d->q_prescaled ? 1.0f : d->softmax_scale * LOG2E; p.scale2 = d->scale2;
+    p.eps = d->ln_eps; p.scale_log2 = d->q_prescaled ? 1.0f : d->softmax_scale * LOG2E; p.scale2 = d->scale2; p.s2 = s2;
     p.xm = 8;
     hipStream_t s = (hipStream_t)stream;
     return d->dtype == APAD_BF16 ? hs_attn_launch<APAD_BF16>(p, self, s) : hs_attn_launch<APAD_F16>(p, self, s);
 }
+
+extern "C" int apad_hs_attention(const apad_hs_attn_desc* d, void* stream) { return hs_attention_launch(d, nullptr, false, stream); }
+extern "C" int apad_hs_attention_tab(const apad_hs_attn_desc* d, const apad_scale2_tab* t, void* stream) { return hs_attention_launch(d, t, true, stream); }
 
 extern "C" int apad_hs_geglu(const void* x, const void* w_packed, const float* w_bias, void* out, int32_t B, int32_t N, int32_t C, int32_t normalize, float ln_eps,
                              int32_t dtype, void* stream) {

@@ -51,7 +51,20 @@ struct XaP {
     uint8_t* out;
     int32_t B, N, L1, L2, ppn, npanels, ntiles;
     float eps, scale_log2, scale2;
+    Scale2Tab s2;  // apad_fused_cross_attention_tab: scale2 per sample from a device table (table == nullptr: the scalar above)
 };
+
+// scale2 of sample b (common.h, scale2_of_sload) with the table's fields read from the kernel-argument segment HERE, where a panel group needs
+// them, not held from the kernel's entry through the persistent loop: the general forms have no scalar register left for eight more
+// (the empty asm keeps the compiler from merging these reads with the entry block's reads of the other arguments)
+__device__ __forceinline__ float xa_scale2(float scalar, int b) {
+    uint64_t ka = (uint64_t)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ka));
+    const auto* kp = (const __attribute__((address_space(4))) Scale2Tab*)(ka + offsetof(XaP, s2));
+    Scale2Tab t;
+    t.table = kp->table; t.step = kp->step; t.ld = kp->ld; t.rows = kp->rows; t.cols = kp->cols;
+    return scale2_of_sload(t, scalar, b);
+}
 
 // bytes of one (sample, head) block of a packed K/V set: [K fragments: nsub x 2][V^T fragments: nsub x 2], 1 KB each
 __host__ __device__ inline int64_t xa_kv_block(int L) { return (int64_t)((L + 31) / 32) * 4 * 1024; }
@@ -527,6 +540,7 @@ __global__ __launch_bounds__(512) void xattn_kernel(XaP p) {
                 }
             }
             const float* bias1 = p.bias1 ? p.bias1 + (int64_t)b * p.L1 : nullptr;
+            const float scale2 = DUAL ? xa_scale2(p.scale2, b) : 0.f;  // of THIS panel group's sample: a tile can span two
             f32x16 o[NP];
 #pragma unroll
             for (int u = 0; u < NP; ++u) {
@@ -537,8 +551,8 @@ __global__ __launch_bounds__(512) void xattn_kernel(XaP p) {
                 if constexpr (EXACT) xa_segment_exact<DT, G1, BIAS1>(f1, bias1, p.scale_log2, 1.0f, qb[u], o[u], true, half);
                 else xa_segment<DT, NS1>(f1, p.L1, bias1, p.scale_log2, 1.0f, qb[u], o[u], true, half);
                 if (DUAL) {
-                    if constexpr (EXACT && DUAL) xa_segment_exact<DT, (G2 > 0 ? G2 : 1), false>(f2, nullptr, p.scale_log2, p.scale2, qb[u], o[u], false, half);
-                    else xa_segment<DT, DUAL ? NS2 : 1>(f2, p.L2, nullptr, p.scale_log2, p.scale2, qb[u], o[u], false, half);
+                    if constexpr (EXACT && DUAL) xa_segment_exact<DT, (G2 > 0 ? G2 : 1), false>(f2, nullptr, p.scale_log2, scale2, qb[u], o[u], false, half);
+                    else xa_segment<DT, DUAL ? NS2 : 1>(f2, p.L2, nullptr, p.scale_log2, scale2, qb[u], o[u], false, half);
                 }
             }
             // O_h^T (lane = token, registers = head dims 8g + 4 half + j) -> O tile [token][h*32 + dim] (over the parked q)
@@ -552,6 +566,7 @@ __global__ __launch_bounds__(512) void xattn_kernel(XaP p) {
             constexpr int CNT = decltype(cnt_tag)::value;
             xa_fetch<DT, NS1>(f1, p.kv1 + ((int64_t)b * XH + h) * xa_kv_block(p.L1), p.L1, lane);
             const int nsub2 = p.L2 >> 5;
+            const float scale2 = xa_scale2(p.scale2, b);
             const gptr kb = sgpr_ptr(p.kv2 + ((int64_t)b * XH + h) * xa_kv_block(p.L2));
             const gptr vb = kb + nsub2 * 2048;
             f32x16 o2[CNT];
@@ -603,7 +618,7 @@ __global__ __launch_bounds__(512) void xattn_kernel(XaP p) {
             for (int u = 0; u < CNT; ++u) {
                 typename E::v8 qb[2];
                 load_q(u, qb);
-                const float w2 = p.scale2 * __builtin_amdgcn_rcpf(half_sum(l0[u] + l1[u]));  // ap_scale / row sum (attention_processor.py:454)
+                const float w2 = scale2 * __builtin_amdgcn_rcpf(half_sum(l0[u] + l1[u]));  // ap_scale / row sum (attention_processor.py:454)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) o2[u][r] *= w2;
                 // the text segment on top (its probabilities normalised before they are rounded, as in the resident-fragment forms)
@@ -818,8 +833,12 @@ extern "C" int apad_xattn_pack_kv(const void* k, const void* vt, void* packed, i
     return apad_check_launch("apad_xattn_pack_kv");
 }
 
-extern "C" int apad_fused_cross_attention(const apad_xattn_desc* d, void* stream) {
-    APAD_CHECK(d != nullptr, "apad_fused_cross_attention: null descriptor");
+// apad_fused_cross_attention (t unused) and apad_fused_cross_attention_tab (has_tab) share this launch path
+static int fused_cross_attention_launch(const apad_xattn_desc* d, const apad_scale2_tab* t, bool has_tab, void* stream) {
+    const char* const who = has_tab ? "apad_fused_cross_attention_tab" : "apad_fused_cross_attention";
+    APAD_CHECK(d != nullptr, "%s: null descriptor", who);
+    Scale2Tab s2;
+    if (apad_scale2_tab_arg(who, t, has_tab, d->L2, &s2) != 0) return -1;
     APAD_CHECK(d->dtype == APAD_BF16 || d->dtype == APAD_F16, "apad_fused_cross_attention: dtype %d not supported", d->dtype);
     const bool long2 = d->L2 > 32 * XMAXSUB;  // the chunked form: 8 text keys + 64 n <= 512 audio keys, no key bias
     if (d->C != XC || d->heads != XH || d->L1 > 64 || d->L2 > 32 * XMAXSUB2 || (long2 && (d->L1 != 8 || d->L2 % 64 != 0 || d->key_bias != nullptr))) {
@@ -845,7 +864,7 @@ extern "C" int apad_fused_cross_attention(const apad_xattn_desc* d, void* stream
     p.ppn = (d->N + 31) / 32;
     p.npanels = d->B * p.ppn;
     p.ntiles = (p.npanels + 3) / 4;
-    p.eps = d->ln_eps; p.scale_log2 = d->softmax_scale * XA_LOG2E; p.scale2 = d->scale2;
+    p.eps = d->ln_eps; p.scale_log2 = d->softmax_scale * XA_LOG2E; p.scale2 = d->scale2; p.s2 = s2;
     hipStream_t s = (hipStream_t)stream;
     const int ns1 = (d->L1 + 31) / 32, ns2 = (d->L2 + 31) / 32;
     if (long2) return d->dtype == APAD_BF16 ? xa_launch<APAD_BF16, 1, 2, 1, 8, false, true>(p, s) : xa_launch<APAD_F16, 1, 2, 1, 8, false, true>(p, s);
@@ -862,4 +881,8 @@ extern "C" int apad_fused_cross_attention(const apad_xattn_desc* d, void* stream
 #undef XA_CASE
     apad_set_error("apad_fused_cross_attention: no kernel for L1=%d L2=%d", d->L1, d->L2);
     return -1;
+}
+extern "C" int apad_fused_cross_attention(const apad_xattn_desc* d, void* stream) { return fused_cross_attention_launch(d, nullptr, false, stream); }
+extern "C" int apad_fused_cross_attention_tab(const apad_xattn_desc* d, const apad_scale2_tab* t, void* stream) {
+    return fused_cross_attention_launch(d, t, true, stream);
 }

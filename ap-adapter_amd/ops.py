@@ -4,6 +4,7 @@ PyTorch is used only as plumbing here: device memory (torch.empty), the current 
 arithmetic happens in libapadapter_hip.so.  Nothing in this module falls back to torch ops: a missing library
 or a CPU tensor raises.
 """
+import collections
 import ctypes as C
 import math
 
@@ -33,6 +34,39 @@ def _req(t, name, dtype=None):
     if t.stride(-1) != 1:
         raise RuntimeError(f"{name}: last dim must be contiguous")
     return t
+
+
+Scale2Binding = collections.namedtuple("Scale2Binding", "table step_ptr cols")
+Scale2Binding.__doc__ = """``scale2=`` of the two-segment attention ops as a device table instead of a float: sample b of the launch uses
+table[min(*step_ptr, rows - 1)][b % cols] (include/apadapter_hip.h, apad_scale2_tab).  table: contiguous fp32 [rows, >= cols] on the
+operands' device; step_ptr: a device int32 (the captured step's counter) or None = row 0; cols: 1 or the number of clips."""
+
+
+def _launch_scale2(name, d, scale2, dev):
+    """the launch of a two-segment attention descriptor: a float ``scale2`` through apad_<name>, a Scale2Binding (or a plain (table, step_ptr,
+    cols) tuple) through apad_<name>_tab.  Device, dtype, contiguity and shape are checked here; what the values decide (rows, cols, the row
+    stride, a missing table, a single-segment call) is the entry point's check."""
+    lib = L.lib()
+    if not isinstance(scale2, tuple):
+        d.scale2 = float(scale2)
+        L.check(getattr(lib, "apad_" + name)(C.byref(d), _stream()), "apad_" + name)
+        return
+    table, step_ptr, cols = scale2
+    fn = name + ".scale2"
+    t = L.Scale2Tab()
+    if table is not None:
+        _req(table, fn + " table", torch.float32)
+        if table.dim() != 2 or not table.is_contiguous() or table.device != dev:
+            raise RuntimeError(f"{fn}: expected a contiguous fp32 [rows, cols] table on {dev}, got {tuple(table.shape)} on {table.device}")
+        t.table, t.rows, t.ld = table.data_ptr(), table.shape[0], table.shape[1]
+    if step_ptr is not None:
+        _req(step_ptr, fn + " step_ptr", torch.int32)
+        if step_ptr.numel() != 1 or step_ptr.device != dev:
+            raise RuntimeError(f"{fn}: step_ptr must be ONE int32 on {dev}, got {tuple(step_ptr.shape)} on {step_ptr.device}")
+        t.step = step_ptr.data_ptr()
+    t.cols = int(cols)
+    d.scale2 = 0.0
+    L.check(getattr(lib, "apad_" + name + "_tab")(C.byref(d), C.byref(t), _stream()), "apad_" + name + "_tab")
 
 
 def round_up(x, m):
@@ -347,7 +381,8 @@ def fused_cross_attention(x, wq_packed, wo_packed, bo, kv1_packed, L1, heads, ln
                           scale2=0.0, out=None, q_fold=None):
     """out = x + to_out(A(q, k1, v1, bias) [+ scale2 * A(q, k2, v2)]) + bo with q = to_q(LayerNorm(x)): the whole
     cross-attention sub-layer in one launch.  x [B, N, C]; weights from xattn_pack_weight, K/V from xattn_pack_kv.  With ln: wq_packed and
-    q_fold = xattn_pack_weight(to_q.weight, ln) (the LayerNorm is folded into the projection)."""
+    q_fold = xattn_pack_weight(to_q.weight, ln) (the LayerNorm is folded into the projection).  scale2: a float, or a Scale2Binding (the weight per
+    sample from a device table, apad_fused_cross_attention_tab)."""
     _req(x, "fused_cross_attention.x", wq_packed.dtype)
     B, N, Cc = x.shape
     if Cc != XATTN_C or heads != XATTN_HEADS or not xattn_lengths_ok(L1, L2, key_bias is not None) or x.dtype not in FUSED_DTYPES:
@@ -367,8 +402,8 @@ def fused_cross_attention(x, wq_packed, wo_packed, bo, kv1_packed, L1, heads, ln
     d.B, d.N, d.C, d.heads, d.L1 = B, N, Cc, heads, L1
     if L2 > 0:
         d.kv2_packed, d.L2 = kv2_packed.data_ptr(), L2
-    d.dtype, d.softmax_scale, d.scale2 = _DT[x.dtype], 1.0 / math.sqrt(Cc // heads), float(scale2)
-    L.check(L.lib().apad_fused_cross_attention(C.byref(d), _stream()), "apad_fused_cross_attention")
+    d.dtype, d.softmax_scale = _DT[x.dtype], 1.0 / math.sqrt(Cc // heads)
+    _launch_scale2("fused_cross_attention", d, scale2, x.device)
     return out
 
 
@@ -442,7 +477,8 @@ def _rows_kv_args(k, vt, B, heads, hd, dtype, what):
 def cross_attention_rows(x, wq_packed, wo_packed, bo, k1, vt1, heads, ln=None, key_bias=None, k2=None, vt2=None, scale2=0.0, out=None):
     """The fused cross-attention sub-layer at the 384-wide level: out = x + to_out(A(q, k1, v1, bias) [+ scale2 * A(q, k2, v2)]) + bo,
     q = to_q(LayerNorm(x)), one launch (csrc/attention.hip, xattn_rows_kernel).  x [B, N, C]; k* [B, L, C] row-major, vt* [B, heads, d,
-    Lpad] as ops.attention takes them, or k* = a RowsKV (rows_pack_kv) and vt* = None; weights from xrows_pack_weight."""
+    Lpad] as ops.attention takes them, or k* = a RowsKV (rows_pack_kv) and vt* = None; weights from xrows_pack_weight.  scale2: a float, or a
+    Scale2Binding (apad_cross_attention_rows_tab)."""
     _req(x, "cross_attention_rows.x", wq_packed.dtype)
     B, N, Cc = x.shape
     L1, L2 = k1.shape[1], (0 if k2 is None else k2.shape[1])
@@ -461,8 +497,8 @@ def cross_attention_rows(x, wq_packed, wo_packed, bo, k1, vt1, heads, ln=None, k
     d.B, d.N, d.C, d.heads = B, N, Cc, heads
     if L2 > 0:
         d.k2, d.vt2, d.L2, d.Lpad2 = _rows_kv_args(k2, vt2, B, heads, Cc // heads, x.dtype, "cross_attention_rows.k2 / vt2")
-    d.dtype, d.softmax_scale, d.scale2 = _DT[x.dtype], 1.0 / math.sqrt(Cc // heads), float(scale2)
-    L.check(L.lib().apad_cross_attention_rows(C.byref(d), _stream()), "apad_cross_attention_rows")
+    d.dtype, d.softmax_scale = _DT[x.dtype], 1.0 / math.sqrt(Cc // heads)
+    _launch_scale2("cross_attention_rows", d, scale2, x.device)
     return out
 
 
@@ -638,7 +674,8 @@ def hs_attention(x, w_packed, w_bias, *, self_attention, normalize=True, ln_eps=
                  scale2=0.0, q_prescaled=False, out=None):
     """O = heads' softmax attention of the 64-token level in ONE launch (apad_hs_attention): rows of x normalised (the LayerNorm's affine
     part lives in w_packed / w_bias: hs_pack_qkv / hs_pack_rows), q|k|v (self) or q (cross: k*, vt* = the hoisted sets in ops.attention's
-    layout, or k* = a RowsKV and vt* = None) projected per head pair, both heads attended, O [B, N, 640] written.  to_out + residual: ``hs_out``."""
+    layout, or k* = a RowsKV and vt* = None) projected per head pair, both heads attended, O [B, N, 640] written.  to_out + residual: ``hs_out``.
+    scale2: a float, or a Scale2Binding (apad_hs_attention_tab)."""
     _req(x, "hs_attention.x", w_packed.dtype)
     B, N, Cc = x.shape
     if Cc != HS_C or N > HS_MAXN or x.dtype not in FUSED_DTYPES or not x.is_contiguous():
@@ -660,8 +697,8 @@ def hs_attention(x, w_packed, w_bias, *, self_attention, normalize=True, ln_eps=
     d.out = out.data_ptr()
     d.B, d.N, d.C, d.heads = B, N, Cc, HS_HEADS
     d.self_attention, d.q_prescaled, d.dtype, d.normalize = int(bool(self_attention)), int(bool(q_prescaled)), _DT[x.dtype], int(bool(normalize))
-    d.ln_eps, d.softmax_scale, d.scale2 = float(ln_eps), 1.0 / math.sqrt(80.0), float(scale2)
-    L.check(L.lib().apad_hs_attention(C.byref(d), _stream()), "apad_hs_attention")
+    d.ln_eps, d.softmax_scale = float(ln_eps), 1.0 / math.sqrt(80.0)
+    _launch_scale2("hs_attention", d, scale2, x.device)
     return out
 
 
@@ -1171,7 +1208,8 @@ def attention(q, k, vt, Lk, heads, key_bias=None, k2=None, vt2=None, L2=0, scale
               kv2_batch_div=1, out=None, q_prescaled=False):
     """q [B,N,C]; k [Bk,Lk,C]; vt [Bk,heads,d,Lpad]; optional second (audio) segment k2/vt2 with its own softmax,
     blended as seg1 + scale2*seg2.  key_bias: fp32 [B,Lk] additive.  q_prescaled: q was projected with to_q rows already
-    multiplied by log2(e) / sqrt(d) (processors._qkv_weight), i.e. it is the base-2 exponent operand."""
+    multiplied by log2(e) / sqrt(d) (processors._qkv_weight), i.e. it is the base-2 exponent operand.  scale2: a float, or a Scale2Binding
+    (table, step_ptr, cols): sample b uses table[min(*step_ptr, rows - 1)][b % cols] (apad_attention_tab)."""
     _req(q, "attention.q")
     _req(k, "attention.k", q.dtype)
     _req(vt, "attention.vt", q.dtype)
@@ -1189,13 +1227,12 @@ def attention(q, k, vt, Lk, heads, key_bias=None, k2=None, vt2=None, L2=0, scale
     d.kv_batch_div, d.kv2_batch_div = kv_batch_div, kv2_batch_div
     d.dtype = _f32_dtype(q.dtype)
     d.softmax_scale = 1.0 / math.sqrt(d_head)
-    d.scale2 = float(scale2)
     d.q_prescaled = 1 if q_prescaled else 0
     if L2 > 0:
         d.k2, d.vt2 = k2.data_ptr(), vt2.data_ptr()
         d.k2_stride_b, d.k2_stride_l, d.vt2_stride_b = k2.stride(0), k2.stride(1), vt2.stride(0)
         d.L2, d.Lpad2 = L2, vt2.shape[-1]
-    L.check(L.lib().apad_attention(C.byref(d), _stream()), "apad_attention")
+    _launch_scale2("attention", d, scale2, q.device)
     return out
 
 

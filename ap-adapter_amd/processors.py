@@ -374,6 +374,8 @@ class _Processor(nn.Module):
         kv = self._hoisted(_loose_key(attn, ehs) + (r,), lambda: self._kv_signature(attn, ehs), make)
         bias = self._bias(attention_mask, B, L1)
         scale2 = self._scale2()
+        if L2 == 0 and isinstance(scale2, tuple):
+            raise ValueError("ap_scale: the table weighs the audio branch, and encoder_hidden_states holds no audio tokens")
         if r == "fused":
             wq_p, q_fold, wo_p = _xattn_weights(attn, ln)
             return ops.fused_cross_attention(x, wq_p, wo_p, bo, kv.pk1, L1, heads, ln=ln, key_bias=bias, kv2_packed=kv.pk2, L2=L2, scale2=scale2,
@@ -458,6 +460,7 @@ class IPAttnProcessor2_0(_Processor):
         self.cross_attention_dim = cross_attention_dim
         self.num_tokens = num_tokens
         self.scale = scale
+        self.scale_table = None  # set_ap_scale_table: an ops.Scale2Binding read in place of ``scale``
         self.name = name
         self.to_k_ip = nn.Linear(cross_attention_dim or hidden_size, hidden_size, bias=False)
         self.to_v_ip = nn.Linear(cross_attention_dim or hidden_size, hidden_size, bias=False)
@@ -496,12 +499,22 @@ class IPAttnProcessor2_0(_Processor):
             return None
         return attention_mask.reshape(B, -1)[:, :1].float().expand(B, Lt).contiguous()
 
+    def set_ap_scale_table(self, table, step_ptr, cols=None):
+        """read the weight of the audio branch from a device table -- fp32 [steps, cols], row ``*step_ptr`` (an int32 on the device, None = row 0),
+        column ``sample % cols`` -- instead of ``self.scale``, which is then neither read nor changed.  Inference only."""
+        self.scale_table = ops.Scale2Binding(table, step_ptr, int(table.shape[1] if cols is None else cols))
+
+    def clear_ap_scale_table(self):
+        self.scale_table = None
+
     def _scale2(self):
-        return self.scale
+        return self.scale if self.scale_table is None else self.scale_table
 
     def _call_train(self, attn, hidden_states, ehs, attention_mask, _residual, _ln):
         """Training mode (reference :347-470 under autograd; train_apadapter_v2.py:941-957): gradients w.r.t.
         hidden_states, to_k_ip.weight and to_v_ip.weight (and the condition tokens if they require grad)."""
+        if self.scale_table is not None:
+            raise ValueError("ap_scale: the training path keeps the float `scale`; clear_ap_scale_table() before a forward under autograd")
         B = hidden_states.shape[0]
         nt = self.num_tokens
         txt, aud = ehs[:, :nt, :].contiguous(), ehs[:, nt:, :].contiguous()

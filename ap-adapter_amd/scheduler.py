@@ -122,6 +122,46 @@ def shape_table(guidance_rescale, apg_eta, apg_norm_threshold, apg_momentum, num
     return torch.tensor(cols, dtype=torch.float64).t().float().contiguous()
 
 
+def ap_scale_table(ap_scale, num_inference_steps, start=0, clips=None):
+    """fp32 [N - start, cols], row i = the weight of the audio branch (``scale`` of attention_processor.py:454) at step ``start + i``: the table
+    the decoupled cross-attention launches read at ``*step_ptr`` (apad_scale2_tab).  ``ap_scale``: a float (every step, every clip; cols = 1), a
+    1-D sequence of exactly N floats over the FULL grid (a per-step schedule; a 1-D sequence is always per step; cols = 1), or a 2-D array-like
+    / tensor [N, B] or [1, B] (per step and per clip, a single row broadcast over the steps; cols = B, which must equal ``clips`` = batch x
+    num_waveforms_per_prompt, in generation order, when that is given).  Rows ``start:`` are kept, like ``guidance_table``; every kept value
+    must be finite -- any finite value, negative included: the reference constrains nothing -- and entries before ``start`` are not read and may
+    be NaN.  Errors are ValueErrors whose text starts with ``ap_scale``."""
+    n, start = int(num_inference_steps), int(start)
+    if not 0 <= start < n:
+        raise ValueError(f"ap_scale: start={start!r} must lie in [0, {n})")
+    v = ap_scale
+    if isinstance(v, torch.Tensor):
+        v = v.detach().cpu().tolist()
+    try:
+        two_d = hasattr(v, "__len__") and len(v) > 0 and all(hasattr(r, "__len__") for r in v)
+        if not hasattr(v, "__len__"):
+            rows = [[float(v)]] * n
+        elif two_d:
+            rows = [[float(x) for x in r] for r in v]
+            if len(rows) == 1:
+                rows = rows * n
+        else:
+            rows = [[float(x)] for x in v]
+    except (TypeError, ValueError):
+        raise ValueError(f"ap_scale={ap_scale!r}: expected a float, a sequence of {n} floats or a 2-D [{n} or 1, clips] array") from None
+    if len(rows) != n:
+        raise ValueError(f"ap_scale holds {len(rows)} rows; a per-step schedule needs exactly num_inference_steps = {n} (or ONE row of per-clip "
+                         "values)")
+    cols = len(rows[0])
+    if cols < 1 or any(len(r) != cols for r in rows):
+        raise ValueError("ap_scale: every row of a 2-D value must hold the same number (>= 1) of per-clip values")
+    if two_d and clips is not None and cols != int(clips):
+        raise ValueError(f"ap_scale holds {cols} per-clip values; the run generates {int(clips)} clips (batch x num_waveforms_per_prompt)")
+    rows = rows[start:]
+    if not all(math.isfinite(x) for r in rows for x in r):
+        raise ValueError(f"ap_scale: every value from step {start} on must be finite")
+    return torch.tensor(rows, dtype=torch.float64).float().contiguous()
+
+
 class _EditSchedule:
     """what an edit run needs of either scheduler (both share the timestep grid and alphas_cumprod): where it starts, the add_noise
     coefficients of the start and the per-step (kx, kz) of the kept region.  PARITY UNPINNED, like the samplers: diffusers' img2img /

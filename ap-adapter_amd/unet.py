@@ -416,6 +416,7 @@ class AudioLDM2UNet2DConditionModel(nn.Module):
         self.conv_out = nn.Conv2d(boc[0], cfg.out_channels, 3, padding=1)
         self._time_tables = None
         self.low_res_streams = None  # optional (stream, stream): see forward_nhwc
+        self._ap_scale_cols = None   # columns of the table set_ap_scale_table bound (None: no table)
         self.low_res_levels = 1      # how many of the lowest-resolution levels run on the two streams
 
     # ---- processor plumbing (modeling_audioldm2.py:517-574) ----
@@ -458,6 +459,22 @@ class AudioLDM2UNet2DConditionModel(nn.Module):
                 p.kv_cache_enabled = enabled
                 if clear:
                     p.clear_kv_cache()
+
+    def set_ap_scale_table(self, table, step_ptr, cols=None):
+        """Hand every decoupled processor a device table of ap_scale -- fp32 [steps, cols], read at row ``*step_ptr`` (a device int32, None = row
+        0) and column ``sample % cols`` (cols = 1: every sample; else the number of clips, the CFG branches of a clip sharing its column) -- in
+        place of its ``scale`` attribute, which is neither read nor changed while the table is set.  The launches then go through the
+        apad_*_tab entry points; a sweep or a per-step schedule rewrites the table, not the processors.  Inference only."""
+        self._ap_scale_cols = int(table.shape[1] if cols is None else cols)
+        for p in set(self.attn_processors.values()):
+            if hasattr(p, "set_ap_scale_table"):
+                p.set_ap_scale_table(table, step_ptr, cols)
+
+    def clear_ap_scale_table(self):
+        self._ap_scale_cols = None
+        for p in set(self.attn_processors.values()):
+            if hasattr(p, "clear_ap_scale_table"):
+                p.clear_ap_scale_table()
 
     def drop_kv_owner(self, owner):
         """drop the hoisted results created on behalf of ``owner`` (processors.HOIST_OWNER at their creation)"""
@@ -616,8 +633,9 @@ class AudioLDM2UNet2DConditionModel(nn.Module):
         nsp = len(self.low_res_streams) if self.low_res_streams is not None else 0
         # (only while a hipGraph is being captured -- that is what the fork / join is for, and the captured allocations come from the graph's
         #  private pool; an EAGER forward on side streams was measured wrong in the fp32 mode at batch 32, round 5: it stays on one stream)
+        # (a per-clip ap_scale table is indexed by sample % clips: a part of the batch keeps that only when it holds whole sets of clips)
         split = (nsp > 1 and timestep is None and B % nsp == 0 and not AG.on(x) and nb >= 2 and x.is_cuda
-                 and torch.cuda.is_current_stream_capturing())
+                 and torch.cuda.is_current_stream_capturing() and (self._ap_scale_cols in (None, 1) or (B // nsp) % self._ap_scale_cols == 0))
         k0 = max(1, nb - self.low_res_levels) if split else nb  # first down block of the two-stream section
         for i in range(k0):
             x, H, W = down(i, x, H, W, skips, *cond)

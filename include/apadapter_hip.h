@@ -12,6 +12,11 @@
  *                       (APadapter/ap_adapter/attention_processor.py:429-431, :443-445, :454) and the single
  *                       SDPA of AttnProcessor2_0.__call__ (:274-276); also timm Block attention inside
  *                       forward_encoder_no_random_mask_no_average (audio_encoder/models_mae.py:566-568)
+ *   apad_attention_tab / apad_fused_cross_attention_tab / apad_cross_attention_rows_tab / apad_hs_attention_tab
+ *                       the same launches with `scale` of attention_processor.py:454 (ap_scale, the weight of the audio branch) read
+ *                       from a device table at the captured step's counter, one column per clip (apad_scale2_tab below).  A table
+ *                       holding one value is bit-equal to the scalar entry point with that value; a per-step schedule and per-clip
+ *                       values have no counterpart in the reference, which sets ONE scale per processor before the loop
  *   apad_gemm           attn.to_q/to_k/to_v/to_out, to_k_ip/to_v_ip (attention_processor.py:387,:406-407,
  *                       :435-436,:457); diffusers GEGLU/FeedForward, proj_in/proj_out, ResnetBlock2D /
  *                       Downsample2D / Upsample2D 3x3 convolutions and time_emb_proj
@@ -339,6 +344,29 @@ typedef struct apad_hs_attn_desc {
 } apad_hs_attn_desc;
 int apad_sizeof_hs_attn_desc(void);
 int apad_hs_attention(const apad_hs_attn_desc* d, void* stream);
+
+/* The weight of segment 2 (ap_scale) from a device table instead of the descriptor's float, for the four two-segment attention entry
+ * points.  Sample b of the launch uses
+ *     table[min(*step, rows - 1) * ld + (b % cols)]
+ * and the descriptor's scale2 is ignored.  The modulo maps the two or three guidance branches of a clip onto one column for effective
+ * batch rows [branch 0 clips ; branch 1 clips ; ...]; a counter past the table reads the last row, never past it (the convention of the
+ * step kernels' tables).  The value is read once per workgroup, on the scalar path, and enters the expression the descriptor's float
+ * enters: a launch is bit-equal to the scalar launch with the same value.  The unchanged entry points run the same kernels without a
+ * table.  Rejected (negative code, apad_last_error() names the entry point, nothing launched): a NULL table, rows <= 0, cols <= 0,
+ * ld < cols, a table pointer off 4-byte alignment, and a table given to a single-segment call (L2 == 0). */
+typedef struct apad_scale2_tab {
+    const float*   table;   /* fp32 [rows][ld]                                            */
+    const int32_t* step;    /* device int32 (the captured step's counter) or NULL = row 0 */
+    int32_t rows, cols;     /* cols = 1 (every sample) or the number of clips             */
+    int64_t ld;             /* row stride in elements, >= cols                            */
+} apad_scale2_tab;
+int apad_sizeof_scale2_tab(void);
+int apad_echo_scale2_tab(const apad_scale2_tab* t, double* out, int cap);
+int apad_attention_tab(const apad_attn_desc* d, const apad_scale2_tab* t, void* stream);
+int apad_fused_cross_attention_tab(const apad_xattn_desc* d, const apad_scale2_tab* t, void* stream);
+int apad_cross_attention_rows_tab(const apad_xrows_desc* d, const apad_scale2_tab* t, void* stream);
+int apad_hs_attention_tab(const apad_hs_attn_desc* d, const apad_scale2_tab* t, void* stream);
+
 typedef struct apad_hs_out_desc {
     const void* o;         /* [B*N][640] attention output (all heads)                                 */
     const void* w_packed;  /* to_out[0].weight, packed as above                                       */

@@ -28,6 +28,12 @@ LUFS (ITU-R BS.1770-4 integrated loudness, ``normalize_loudness``), or -- "sourc
 VAE and vocoder render it; a gain that would take its largest sample over P dBFS (default -1) is cut to the one that puts it there, so
 nothing is clipped on disk.  Each rank lists file, LUFS before and after and gain in WAV_DIR/loudness_rank<R>.json.
     python tools/run_sharded.py --clips 64 --steps 50 --wav-dir out --target-loudness -14
+
+The weight of the audio prompt (--ap-scale V, or V0,V1,... with one value per step): ``text + ap_scale * audio`` in every decoupled attn2, read by
+the captured step from a device table (``pipeline.denoise(ap_scale=)``) instead of the task preset's value baked into the processors; a
+comma-separated list is a per-step schedule over the full grid.  Both passes of --inversion run under it.  The written wavs carry it in their
+names (a schedule as "sched") and the summary line holds the values.
+    python tools/run_sharded.py --clips 64 --steps 4 --ap-scale 1.0,0.7,0.4,0.1
 """
 import argparse
 import glob
@@ -149,6 +155,8 @@ def main():
                     "'source' (an edit run): to the loudness of its source as the same VAE and vocoder render it")
     ap.add_argument("--peak-limit-db", type=float, default=-1.0, metavar="P", help="--target-loudness: no gain takes a clip's largest sample over "
                     "P dBFS (<= 0)")
+    ap.add_argument("--ap-scale", default=None, metavar="V|V0,V1,...", help="the weight of the audio prompt in the decoupled cross-attention: one "
+                    "float, or one per step (a schedule over the full grid); default: the task preset's value, set on the processors")
     ap.add_argument("--gpus", type=int, default=1, help="N > 1 without a launcher: this script starts its N ranks itself (one per GPU)")
     args = ap.parse_args()
     if args.inversion and args.sampler != "ddim":
@@ -174,6 +182,13 @@ def main():
                 ap.error("--target-loudness: a finite loudness in LUFS, or 'source'")
         if not args.peak_limit_db <= 0.0:
             ap.error("--peak-limit-db must be <= 0 dB relative to full scale")
+
+    if args.ap_scale is not None:
+        try:
+            vals = [float(v) for v in args.ap_scale.split(",")]
+        except ValueError:
+            ap.error("--ap-scale: one float, or a comma-separated list with one float per step")
+        args.ap_scale = vals[0] if len(vals) == 1 else vals
 
     from ap_adapter_amd import distributed as D
     if args.gpus > 1 and not D.launched_by_torchrun():
@@ -225,24 +240,31 @@ def main():
     except ValueError as err:
         ap.error(str(err))
     shaping = shaping if shaped else {}
+    aps = {}
+    if args.ap_scale is not None:  # the values of the steps the job runs, checked once; both passes of an inversion run take the keyword
+        try:
+            A.scheduler.ap_scale_table(args.ap_scale, args.steps, start if editing else 0)
+        except ValueError as err:
+            ap.error(str(err))
+        aps = {"ap_scale": args.ap_scale}
 
     def denoise(lat, gen, t5, mask, gs, clips=None):
         if not editing:
-            return pipe.denoise(lat, gen, t5, mask, args.steps, gs, **dual, **shaping)
+            return pipe.denoise(lat, gen, t5, mask, args.steps, gs, **dual, **shaping, **aps)
         # z0 = the clip's seeded latents (what a generation run would start from); the posterior draw is seeded by the clip index too
         post = torch.stack([torch.randn(8, H, 16, generator=torch.Generator().manual_seed(7919 * c["index"] + 1)) for c in clips])
         src = A.EditSource(z0=lat, moments=torch.cat([source_moments(c["audio"]) for c in clips]), post_noise=post,
                            scale=pipe.vae.config.scaling_factor, mask=region_mask)
         if args.inversion is None:
-            return pipe.denoise(None, gen, t5, mask, args.steps, gs, source=src, start=start, **dual, **shaping)
+            return pipe.denoise(None, gen, t5, mask, args.steps, gs, source=src, start=start, **dual, **shaping, **aps)
         # the source condition: the batch's own, with the positive branch's text (the last b rows; 8 generated tokens) replaced
         b = lat.shape[0]
         sg, st, sm = S.synthetic_text_embeddings(args.source_prompt, t5_len=t5.shape[1])
         sgen, st5, smask = gen.clone(), t5.clone(), mask.clone()
         sgen[-b:, :8], st5[-b:], smask[-b:] = sg.to(gen), st.to(t5), sm.to(mask)
         inv = pipe.invert(src, sgen, st5, smask, args.steps, args.source_guidance, start=start, eta=1.0,
-                          generator=torch.Generator().manual_seed(104729 * clips[0]["index"] + 2), **dual)
-        return pipe.denoise(None, gen, t5, mask, args.steps, gs, source=inv, start=start, eta=1.0, **dual, **shaping)
+                          generator=torch.Generator().manual_seed(104729 * clips[0]["index"] + 2), **dual, **aps)
+        return pipe.denoise(None, gen, t5, mask, args.steps, gs, source=inv, start=start, eta=1.0, **dual, **shaping, **aps)
 
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -268,7 +290,8 @@ def main():
             mel = vae.decode(local_out[idx][None].to(dev, dtype) / vae.config.scaling_factor).sample
             wav = pipe.mel_spectrogram_to_waveform(mel)[0, : int(args.seconds * 16000)]
             c = clips[idx]
-            name = f"{c['prompt']}_{idx}_ip{cfg['ap_scale']}_t{cfg['time_pooling']}_f{cfg['freq_pooling']}.wav".replace("/", "_")
+            ip = cfg["ap_scale"] if args.ap_scale is None else "sched" if isinstance(args.ap_scale, list) else args.ap_scale
+            name = f"{c['prompt']}_{idx}_ip{ip}_t{cfg['time_pooling']}_f{cfg['freq_pooling']}.wav".replace("/", "_")
             if args.target_loudness is not None:  # on the device, before the write: a hot clip is turned down instead of clipped on disk
                 to = dict(reference=rendered_source(c["audio"])) if args.target_loudness == "source" else dict(target=args.target_loudness)
                 wav, gain, before = A.normalize_loudness(wav.to(dev), peak_limit_db=args.peak_limit_db, return_stats=True, **to)
@@ -295,7 +318,7 @@ def main():
         print(json.dumps({"task": args.task, "clips": len(clips), "world": world, "batch": args.batch, "steps": args.steps,
                           "sampler": args.sampler, "strength": args.strength, "edit_region": args.edit_region, "La": A.config.audio_tokens(cfg), "seconds_rank0": round(dt, 2), "clips_per_s": round(len(clips) / dt, 4),
                           "graph_captures": pipe.graph_captures, "graph_hits": pipe.graph_hits, "finite": finite,
-                          "wavs_written_rank0": n_wavs, **({"audio_guidance": args.audio_guidance} if dual else {}), **shaping,
+                          "wavs_written_rank0": n_wavs, **({"audio_guidance": args.audio_guidance} if dual else {}), **shaping, **aps,
                           **({"inversion": args.inversion, "source_prompt": args.source_prompt, "source_guidance": args.source_guidance}
                              if args.inversion else {}),
                           **({"rank_by": args.rank_by, "chroma_similarity_mean_rank0": round(sum(r["chroma_similarity"] for r in scored) / max(len(scored), 1), 6)}
