@@ -83,6 +83,10 @@ class Scale2Tab(C.Structure):
     _fields_ = [("table", _vp), ("step", _vp), ("rows", _i32), ("cols", _i32), ("ld", _i64)]
 
 
+class QueryWeight(C.Structure):
+    _fields_ = [("w", _vp), ("cols", _i32), ("reserved", _i32), ("ld", _i64)]
+
+
 class HsOutDesc(C.Structure):
     _fields_ = [(n, _vp) for n in ("o", "w_packed", "bias", "residual", "out", "rowstat_out")] + [(n, _i32) for n in ("B", "N", "C", "dtype")]
 
@@ -130,6 +134,11 @@ SYMBOLS = {
     "apad_fused_cross_attention_tab": (C.c_int, [C.POINTER(XattnDesc), C.POINTER(Scale2Tab), _vp]),
     "apad_cross_attention_rows_tab": (C.c_int, [C.POINTER(XrowsDesc), C.POINTER(Scale2Tab), _vp]),
     "apad_hs_attention_tab": (C.c_int, [C.POINTER(HsAttnDesc), C.POINTER(Scale2Tab), _vp]),
+    # the audio prompt by region: the three row-per-lane two-segment launches with scale2 multiplied by a per-query map entry
+    "apad_sizeof_query_weight": (C.c_int, []),
+    "apad_attention_qw": (C.c_int, [C.POINTER(AttnDesc), C.POINTER(Scale2Tab), C.POINTER(QueryWeight), _vp]),
+    "apad_cross_attention_rows_qw": (C.c_int, [C.POINTER(XrowsDesc), C.POINTER(Scale2Tab), C.POINTER(QueryWeight), _vp]),
+    "apad_hs_attention_qw": (C.c_int, [C.POINTER(HsAttnDesc), C.POINTER(Scale2Tab), C.POINTER(QueryWeight), _vp]),
     "apad_self_attention_fused": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _vp]),
     "apad_hs_geglu": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _vp]),
     "apad_sizeof_hs_out_desc": (C.c_int, []),
@@ -246,7 +255,7 @@ def lib():
                     or h.apad_sizeof_attn_bwd_desc() != C.sizeof(AttnBwdDesc) \
                     or h.apad_sizeof_xattn_desc() != C.sizeof(XattnDesc) or h.apad_sizeof_xrows_desc() != C.sizeof(XrowsDesc) \
                     or h.apad_sizeof_hs_attn_desc() != C.sizeof(HsAttnDesc) or h.apad_sizeof_hs_out_desc() != C.sizeof(HsOutDesc) \
-                    or h.apad_sizeof_scale2_tab() != C.sizeof(Scale2Tab):
+                    or h.apad_sizeof_scale2_tab() != C.sizeof(Scale2Tab) or h.apad_sizeof_query_weight() != C.sizeof(QueryWeight):
                 raise RuntimeError("descriptor layout mismatch between include/apadapter_hip.h and _lib.py")
             _lib = h
     return _lib

@@ -41,6 +41,7 @@ struct AttnP {
     float scale_log2, scale2;
     Scale2Tab s2;       // apad_attention_tab: scale2 per sample from a device table (table == nullptr: the scalar above)
     int32_t prescaled;  // q already carries softmax_scale * log2(e) (scale_log2 is then exactly 1)
+    QueryW qw;          // apad_attention_qw: the weight map of segment 2, read by the QW instantiations only
 };
 
 constexpr float LOG2E = 1.4426950408889634f;
@@ -288,7 +289,7 @@ __device__ __forceinline__ void segment(uint8_t* smem, const uint8_t* kbase, int
     }
 }
 
-template <int DT, int D, bool DUAL>
+template <int DT, int D, bool DUAL, bool QW = false>
 __global__ __launch_bounds__(256) void attn_kernel(AttnP p) {
     using E = ET<DT>;
     using Y = Lay<D>;
@@ -361,10 +362,12 @@ __global__ __launch_bounds__(256) void attn_kernel(AttnP p) {
             float m2 = NEG_BIG;
             const int bk = b / p.kvdiv2;
             const float scale2 = scale2_of(p.s2, p.scale2, b);
+            const float wq = query_weight<QW>(p.qw, b, qi);  // (requested before the key loop, used after it)
             const uint8_t* kbase = p.k2 + ((int64_t)bk * p.k2_sb + h * D) * 2;
             const uint8_t* vbase = p.vt2 + ((int64_t)bk * p.vt2_sb + (int64_t)h * D * p.Lpad2) * 2;
             segment<DT, D>(smem, kbase, p.k2_sl, vbase, p.L2, p.Lpad2, nullptr, p.scale_log2, qf, o2, osum2, m2, tid);
             const float inv2 = 1.0f / half_sum(osum2[0] + osum2[1]);
+            const float sw = weighted_scale2<QW>(scale2, wq);
             // the un-fused reference rounds each branch, and scale * audio, to the storage type before the add
 #pragma unroll
             for (int dt = 0; dt < Y::DT_TILES; ++dt)
@@ -372,7 +375,7 @@ __global__ __launch_bounds__(256) void attn_kernel(AttnP p) {
                 for (int r = 0; r < 16; ++r) {
                     const float t = (float)(typename E::elem)o[dt][r];
                     const float a = (float)(typename E::elem)(o2[dt][r] * inv2);
-                    o[dt][r] = t + (float)(typename E::elem)(scale2 * a);
+                    o[dt][r] = t + (float)(typename E::elem)(sw * a);
                 }
         }
     }
@@ -1242,7 +1245,7 @@ __device__ __forceinline__ void short_segment(const uint8_t* kbase, int64_t k_sl
     }
 }
 
-template <int DT, int D, bool DUAL>
+template <int DT, int D, bool DUAL, bool QW = false>
 __global__ __launch_bounds__(256) void attn_short_kernel(AttnP p) {
     // (a one-workgroup-per-32-queries-x-all-heads shape, meant to consume whole 2*C-byte rows while their lines are hot,
     //  measured slower: 38 vs 28 us at the 1000-token level -- the heads serialise inside a wave)
@@ -1288,9 +1291,11 @@ __global__ __launch_bounds__(256) void attn_short_kernel(AttnP p) {
         float inv2 = 1.f;
         const int bk = b / p.kvdiv2;
         const float scale2 = scale2_of(p.s2, p.scale2, b);
+        const float wq = query_weight<QW>(p.qw, b, qi);  // (requested before the key loop, used after it)
         const uint8_t* kbase = p.k2 + ((int64_t)bk * p.k2_sb + h * D) * 2;
         const uint8_t* vbase = p.vt2 + ((int64_t)bk * p.vt2_sb + (int64_t)h * D * p.Lpad2) * 2;
         short_segment<DT, D>(kbase, p.k2_sl, vbase, p.L2, p.Lpad2, nullptr, p.scale_log2, qf, o2, inv2, l31, half);
+        const float sw = weighted_scale2<QW>(scale2, wq);
         // the un-fused reference rounds each branch, and scale * audio, to the storage type before the add
 #pragma unroll
         for (int dt = 0; dt < Y::DT_TILES; ++dt)
@@ -1298,7 +1303,7 @@ __global__ __launch_bounds__(256) void attn_short_kernel(AttnP p) {
             for (int r = 0; r < 16; ++r) {
                 const float t = (float)(typename E::elem)o[dt][r];
                 const float a = (float)(typename E::elem)(o2[dt][r] * inv2);
-                o[dt][r] = t + (float)(typename E::elem)(scale2 * a);
+                o[dt][r] = t + (float)(typename E::elem)(sw * a);
             }
     }
     uint8_t* scr = smem + wave * (32 * OROW);
@@ -1332,7 +1337,9 @@ template <int DT, int D> int launch_d(const AttnP& p, bool dual, dim3 grid, hipS
     constexpr bool no_short = false;
     if (!no_short && p.L <= 64 && (!dual || p.L2 <= 64) && p.lse == nullptr) {
         dim3 g2((unsigned)((p.N + 127) / 128), (unsigned)(p.B * p.H));
-        if (dual)
+        if (dual && p.qw.w != nullptr)
+            hipLaunchKernelGGL((attn_short_kernel<DT, D, true, true>), g2, dim3(256), 0, s, p);
+        else if (dual)
             hipLaunchKernelGGL((attn_short_kernel<DT, D, true>), g2, dim3(256), 0, s, p);
         else
             hipLaunchKernelGGL((attn_short_kernel<DT, D, false>), g2, dim3(256), 0, s, p);
@@ -1368,7 +1375,9 @@ template <int DT, int D> int launch_d(const AttnP& p, bool dual, dim3 grid, hipS
             return apad_check_launch("apad_attention");
         }
     }
-    if (dual)
+    if (dual && p.qw.w != nullptr)
+        hipLaunchKernelGGL((attn_kernel<DT, D, true, true>), grid, dim3(256), 0, s, p);
+    else if (dual)
         hipLaunchKernelGGL((attn_kernel<DT, D, true>), grid, dim3(256), 0, s, p);
     else
         hipLaunchKernelGGL((attn_kernel<DT, D, false>), grid, dim3(256), 0, s, p);
@@ -1422,6 +1431,7 @@ struct XrP {
     int32_t B, N, L1, Lpad1, L2, Lpad2, tiles_per_sample;
     float eps, scale_log2, scale2;
     Scale2Tab s2;  // apad_cross_attention_rows_tab (as AttnP::s2)
+    QueryW qw;     // apad_cross_attention_rows_qw (as AttnP::qw)
 };
 
 #include "short_seg.h"
@@ -1498,7 +1508,7 @@ __device__ __forceinline__ void xr_project(const uint8_t* wpk, const uint8_t* sr
     }
 }
 
-template <int DT, int C, int NS1, int NS2, int NW, int NSET>
+template <int DT, int C, int NS1, int NS2, int NW, int NSET, bool QW = false>
 __global__ __launch_bounds__(NW * 64) void xattn_rows_kernel(XrP p) {
     constexpr bool DUAL = NS2 > 0;
     // one 32-token panel per wave quartet: 8 waves = 64 tokens (C = 384), 4 waves = 32 tokens (C = 640: two 64-token tiles would not fit the LDS)
@@ -1573,6 +1583,12 @@ __global__ __launch_bounds__(NW * 64) void xattn_rows_kernel(XrP p) {
             }
 #pragma unroll
             for (int i = 0; i < CH; ++i) *reinterpret_cast<uint4*>(X + row * ROWB + (sub + 8 * i) * 16) = pack8<DT>(v[i]);
+            // the map entry of each token of the tile (a row past the sample: its last token's) is requested here, under the LayerNorm, and parked
+            // in the 16 pad bytes behind its row of the Q tile, which no projection writes: the blend reads it back from LDS.  Held in a register
+            // across the segments, or loaded at the blend, it costs the 256-register forms scratch (profiles/ap_region_resources.txt)
+            if constexpr (QW) {
+                if (sub == 0) *reinterpret_cast<float*>(Q + row * ROWB + C * 2) = query_weight<true>(p.qw, b, ok ? row0 + row : p.N - 1);
+            }
         }
     }
     __syncthreads();
@@ -1652,13 +1668,16 @@ __global__ __launch_bounds__(NW * 64) void xattn_rows_kernel(XrP p) {
                 } else
                     short_compute<DT, D, NSB>(f2, p.L2, nullptr, p.scale_log2, qf, o2, inv2, half);
                 // (as attn_short_kernel: each branch, and scale * audio, rounded to the storage type before the add)
+                float wq = 1.0f;  // the map entry of this lane's token, parked behind its Q row in phase 1
+                if constexpr (QW) wq = *reinterpret_cast<const float*>(Q + (mt * 32 + l31) * ROWB + C * 2);
+                const float sw = weighted_scale2<QW>(scale2, wq);
 #pragma unroll
                 for (int dt = 0; dt < DTT; ++dt)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         const float t = (float)(typename E::elem)o[dt][r];
                         const float a = (float)(typename E::elem)(o2[dt][r] * inv2);
-                        o[dt][r] = t + (float)(typename E::elem)(scale2 * a);
+                        o[dt][r] = t + (float)(typename E::elem)(sw * a);
                     }
             }
 #pragma unroll
@@ -1713,6 +1732,11 @@ template <int DT, int C, int NW, int NSET> int xattn_rows_launch(const XrP& p, h
     const int ns1 = p.L1 > 32 ? 2 : 1, ns2 = (p.L2 + 31) / 32;
     // (ns1 == 1: checked by the caller) 8 text + 65 .. 512 audio keys, in 64-key chunks (round 6; the one-tile form of 65 .. 128 keys -- NS2 = 4, its fragments
     //  requested as they are used -- was slower at 128 keys than the chunked form at 256: 50 vs 54 us)
+    if (p.qw.w != nullptr) {  // apad_cross_attention_rows_qw (ns2 > 0: checked by the caller)
+        if (ns2 > 2) return go(xattn_rows_kernel<DT, C, 1, 16, NW, NSET, true>);
+        if (ns1 == 1 && ns2 == 1) return go(xattn_rows_kernel<DT, C, 1, 1, NW, NSET, true>);
+        return go(xattn_rows_kernel<DT, C, 2, 2, NW, NSET, true>);
+    }
     if (ns2 > 2) return go(xattn_rows_kernel<DT, C, 1, 16, NW, NSET>);
     if (ns1 == 1 && ns2 == 0) return go(xattn_rows_kernel<DT, C, 1, 0, NW, NSET>);
     if (ns1 == 1 && ns2 == 1) return go(xattn_rows_kernel<DT, C, 1, 1, NW, NSET>);
@@ -1764,13 +1788,15 @@ extern "C" int apad_rows_pack_kv(const void* k, const void* vt, void* out, int32
     return apad_check_launch("apad_rows_pack_kv");
 }
 
-// apad_attention (t unused) and apad_attention_tab (has_tab) share this launch path
-static int attention_launch(const apad_attn_desc* d, const apad_scale2_tab* t, bool has_tab, void* stream) {
-    const char* const who = has_tab ? "apad_attention_tab" : "apad_attention";
+// apad_attention (t unused), apad_attention_tab (has_tab) and apad_attention_qw (has_qw; its table is optional) share this launch path
+static int attention_launch(const apad_attn_desc* d, const apad_scale2_tab* t, bool has_tab, const apad_query_weight* w, bool has_qw, void* stream) {
+    const char* const who = has_qw ? "apad_attention_qw" : has_tab ? "apad_attention_tab" : "apad_attention";
     APAD_CHECK(d != nullptr, "%s: null descriptor", who);
     Scale2Tab s2;
     if (apad_scale2_tab_arg(who, t, has_tab, d->L2, &s2) != 0) return -1;
-    if (d->dtype == APAD_F32 || d->dtype == APAD_F32_BF16X3) return apad_f32_attention(d, s2, (hipStream_t)stream);  // fp32 precision modes (f32_ops.hip)
+    QueryW qw;
+    if (apad_query_weight_arg(who, w, has_qw, d->N, d->L2, &qw) != 0) return -1;
+    if (d->dtype == APAD_F32 || d->dtype == APAD_F32_BF16X3) return apad_f32_attention(d, s2, qw, (hipStream_t)stream);  // fp32 precision modes (f32_ops.hip)
     APAD_CHECK(d->dtype == APAD_BF16 || d->dtype == APAD_F16, "apad_attention: dtype %d not supported", d->dtype);
     APAD_CHECK(d->q && d->k && d->vt && d->out, "apad_attention: null operand");
     APAD_CHECK(d->B > 0 && d->N > 0 && d->H > 0 && d->L > 0, "apad_attention: empty problem B=%d N=%d H=%d L=%d", d->B, d->N,
@@ -1804,13 +1830,19 @@ static int attention_launch(const apad_attn_desc* d, const apad_scale2_tab* t, b
     p.scale_log2 = p.prescaled ? 1.0f : d->softmax_scale * 1.4426950408889634f;
     p.scale2 = d->scale2;
     p.s2 = s2;
+    p.qw = qw;
     dim3 grid((unsigned)(((d->N + 127) / 128) * (((d->H * d->B) + 7) / 8 * 8)));
     hipStream_t s = (hipStream_t)stream;
     return d->dtype == APAD_BF16 ? launch_dt<APAD_BF16>(p, d->D, dual, grid, s) : launch_dt<APAD_F16>(p, d->D, dual, grid, s);
 }
 
-extern "C" int apad_attention(const apad_attn_desc* d, void* stream) { return attention_launch(d, nullptr, false, stream); }
-extern "C" int apad_attention_tab(const apad_attn_desc* d, const apad_scale2_tab* t, void* stream) { return attention_launch(d, t, true, stream); }
+extern "C" int apad_attention(const apad_attn_desc* d, void* stream) { return attention_launch(d, nullptr, false, nullptr, false, stream); }
+extern "C" int apad_attention_tab(const apad_attn_desc* d, const apad_scale2_tab* t, void* stream) {
+    return attention_launch(d, t, true, nullptr, false, stream);
+}
+extern "C" int apad_attention_qw(const apad_attn_desc* d, const apad_scale2_tab* t, const apad_query_weight* w, void* stream) {
+    return attention_launch(d, t, t != nullptr, w, true, stream);
+}
 
 extern "C" int apad_self_attention_fused(const void* x, const void* w_packed, const float* colsum_bias, void* out, int32_t B, int32_t N, int32_t C, int32_t heads,
                                          float ln_eps, int32_t dtype, void* stream) {
@@ -1829,12 +1861,15 @@ extern "C" int apad_self_attention_fused(const void* x, const void* w_packed, co
     return dtype == APAD_BF16 ? sf_go<APAD_BF16, 48, 24, 4, SF_NPP48, SF_NSET48>(p, s) : sf_go<APAD_F16, 48, 24, 4, SF_NPP48, SF_NSET48>(p, s);
 }
 
-// apad_cross_attention_rows (t unused) and apad_cross_attention_rows_tab (has_tab) share this launch path
-static int cross_attention_rows_launch(const apad_xrows_desc* d, const apad_scale2_tab* t, bool has_tab, void* stream) {
-    const char* const who = has_tab ? "apad_cross_attention_rows_tab" : "apad_cross_attention_rows";
+// apad_cross_attention_rows (t unused), apad_cross_attention_rows_tab (has_tab) and apad_cross_attention_rows_qw (has_qw) share this launch path
+static int cross_attention_rows_launch(const apad_xrows_desc* d, const apad_scale2_tab* t, bool has_tab, const apad_query_weight* w, bool has_qw,
+                                       void* stream) {
+    const char* const who = has_qw ? "apad_cross_attention_rows_qw" : has_tab ? "apad_cross_attention_rows_tab" : "apad_cross_attention_rows";
     APAD_CHECK(d != nullptr, "%s: null descriptor", who);
     Scale2Tab s2;
     if (apad_scale2_tab_arg(who, t, has_tab, d->L2, &s2) != 0) return -1;
+    QueryW qw;
+    if (apad_query_weight_arg(who, w, has_qw, d->N, d->L2, &qw) != 0) return -1;
     APAD_CHECK(d->dtype == APAD_BF16 || d->dtype == APAD_F16, "apad_cross_attention_rows: dtype %d not supported (16-bit only)", d->dtype);
     if (d->C != 384 || d->heads != 8) {  // (the 64-token level, C = 640: apad_hs_attention + apad_hs_out, hsattn.hip)
         apad_set_error("apad_cross_attention_rows: C=%d heads=%d outside the kernel envelope (384, 8)", d->C, d->heads);
@@ -1863,13 +1898,18 @@ static int cross_attention_rows_launch(const apad_xrows_desc* d, const apad_scal
     p.B = d->B; p.N = d->N; p.L1 = d->L1; p.Lpad1 = d->Lpad1; p.L2 = d->L2; p.Lpad2 = d->Lpad2;
     const int tm = 64;  // tokens per workgroup (xattn_rows_kernel, 8 waves)
     p.tiles_per_sample = (d->N + tm - 1) / tm;
-    p.eps = d->ln_eps; p.scale_log2 = d->softmax_scale * LOG2E; p.scale2 = d->scale2; p.s2 = s2;
+    p.eps = d->ln_eps; p.scale_log2 = d->softmax_scale * LOG2E; p.scale2 = d->scale2; p.s2 = s2; p.qw = qw;
     hipStream_t s = (hipStream_t)stream;
     // (8 waves: 35.8 us at the bench geometry vs 42.5 with 4 waves x 2 panels; deeper weight prefetch -- 6 / 8 register sets -- within 1 us; round 6: 4 waves x
     //  ONE 32-token panel -- 504 workgroups, three resident per CU -- is step-neutral: 34.54 / 34.52 vs 34.58 / 34.55 ms on the same box)
     return d->dtype == APAD_BF16 ? xattn_rows_launch<APAD_BF16, 384, 8, 3>(p, s) : xattn_rows_launch<APAD_F16, 384, 8, 3>(p, s);
 }
-extern "C" int apad_cross_attention_rows(const apad_xrows_desc* d, void* stream) { return cross_attention_rows_launch(d, nullptr, false, stream); }
+extern "C" int apad_cross_attention_rows(const apad_xrows_desc* d, void* stream) {
+    return cross_attention_rows_launch(d, nullptr, false, nullptr, false, stream);
+}
 extern "C" int apad_cross_attention_rows_tab(const apad_xrows_desc* d, const apad_scale2_tab* t, void* stream) {
-    return cross_attention_rows_launch(d, t, true, stream);
+    return cross_attention_rows_launch(d, t, true, nullptr, false, stream);
+}
+extern "C" int apad_cross_attention_rows_qw(const apad_xrows_desc* d, const apad_scale2_tab* t, const apad_query_weight* w, void* stream) {
+    return cross_attention_rows_launch(d, t, t != nullptr, w, true, stream);
 }

@@ -98,6 +98,20 @@ int apad_scale2_tab_arg(const char* who, const apad_scale2_tab* t, bool has_tab,
     return 0;
 }
 
+extern "C" int apad_sizeof_query_weight(void) { return (int)sizeof(apad_query_weight); }
+
+int apad_query_weight_arg(const char* who, const apad_query_weight* w, bool has_qw, int N, int L2, QueryW* out) {
+    out->w = nullptr; out->ld = 0; out->cols = 1; out->pad = 0;
+    if (!has_qw) return 0;
+    APAD_CHECK(w != nullptr && w->w != nullptr, "%s: null query weight map", who);
+    APAD_CHECK(w->cols > 0, "%s: the query weight map needs cols > 0 (cols=%d)", who, w->cols);
+    APAD_CHECK(w->ld >= N, "%s: query weight map row stride %lld < N %d", who, (long long)w->ld, N);
+    APAD_CHECK((reinterpret_cast<uintptr_t>(w->w) & 3) == 0, "%s: the query weight map must be 4-byte aligned", who);
+    APAD_CHECK(L2 > 0, "%s: a query weight map needs a second segment (L2 == 0)", who);
+    out->w = w->w; out->ld = w->ld; out->cols = w->cols;
+    return 0;
+}
+
 extern "C" int apad_sizeof_rp_desc(void) { return (int)sizeof(apad_rp_desc); }
 extern "C" int apad_echo_rp_desc(const apad_rp_desc* d, double* out, int cap) {
     int n = 0;

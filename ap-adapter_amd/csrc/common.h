@@ -160,6 +160,27 @@ __device__ __forceinline__ float scale2_of_sload(const Scale2Tab& t, float scala
     return v;
 }
 
+// apad_query_weight as the kernels' QW instantiations carry it (the other instantiations never read it: w == nullptr).
+struct QueryW {
+    const float* w;
+    int64_t ld;
+    int32_t cols, pad;
+};
+// The weight of segment 2 for query n of sample b (n < N: the caller clamps a tail lane as it clamps its q load): s * w[(b % cols) * ld + n], ONE
+// fp32 multiply of the workgroup's scalar by the lane's own map entry -- one vector load per lane, its row base formed on the scalar path.
+// The product stands where the scalar stands in the blend, so a map entry v is bit-equal to the scalar launch with (float)s * v.
+template <bool QW> __device__ __forceinline__ float query_weight(const QueryW& q, int b, int n) {
+    if constexpr (!QW) return 1.0f;
+    else {
+        const float* const row = q.w + (int64_t)(__builtin_amdgcn_readfirstlane(b) % q.cols) * q.ld;  // uniform: a scalar base
+        return row[(uint32_t)n];                                                                      // + the lane's 32-bit offset
+    }
+}
+template <bool QW> __device__ __forceinline__ float weighted_scale2(float s, float w) {
+    if constexpr (!QW) return s;
+    else return s * w;
+}
+
 // host-side error plumbing (capi.cpp)
 void apad_set_error(const char* fmt, ...);
 #define APAD_CHECK(cond, ...)            \
@@ -173,6 +194,9 @@ int apad_check_launch(const char* what);
 // The table of an apad_*_tab entry point `who`, checked (null table, rows / cols <= 0, ld < cols, a pointer off 4 bytes, or a single-segment call
 // L2 == 0: an error naming `who`, -1) and copied into the kernels' form.  t == nullptr (the scalar entry points): *out = no table, 0.
 int apad_scale2_tab_arg(const char* who, const apad_scale2_tab* t, bool has_tab, int L2, Scale2Tab* out);
+// The map of an apad_*_qw entry point `who`, checked (a null struct or map, cols <= 0, ld < N, a map off 4 bytes, or a single-segment call: an
+// error naming `who`, -1) and copied into the kernels' form.  has_qw false (every other entry point): *out = no map, 0.
+int apad_query_weight_arg(const char* who, const apad_query_weight* w, bool has_qw, int N, int L2, QueryW* out);
 // The dtype ladder of the 256-thread element-wise launches, for the `dtype` (APAD_BF16 / APAD_F16 / APAD_F32, checked by the caller) and the
 // stream `s` of the calling scope: kern<DT> (LAUNCH_DT), kern<DT, F> (LAUNCH_DT_F), kern<DT, vec ? 8 : 1> (LAUNCH_DT_V)
 #define LAUNCH_DT(kern, grid, ...)                                                                                \

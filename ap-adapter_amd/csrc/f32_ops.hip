@@ -324,6 +324,7 @@ struct A32P {
     int32_t B, N, H, L, Lpad, L2, Lpad2, kvdiv, kvdiv2;
     float scale_log2, scale2;
     Scale2Tab s2;  // apad_attention_tab: scale2 per sample from a device table (table == nullptr: the scalar above)
+    QueryW qw;     // apad_attention_qw: the weight map of segment 2, read by the QW instantiations only
 };
 
 constexpr float LOG2E_F = 1.4426950408889634f;
@@ -442,7 +443,7 @@ __device__ __forceinline__ void segment32(const float* kbase, int64_t k_sl, cons
     den = half_sum(sum);
 }
 
-template <int D, bool X3> __device__ __forceinline__ void attn_f32_body(const A32P& p) {
+template <int D, bool X3, bool QW> __device__ __forceinline__ void attn_f32_body(const A32P& p) {
     constexpr int DT_TILES = (D + 31) / 32;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int half = lane >> 5, l31 = lane & 31;
@@ -487,13 +488,15 @@ template <int D, bool X3> __device__ __forceinline__ void attn_f32_body(const A3
         float den2, m2;
         const int bk = b / p.kvdiv2;
         const float scale2 = scale2_of(p.s2, p.scale2, b);
+        const float wq = query_weight<QW>(p.qw, b, qi);  // (requested before the key loop, used after it)
         segment32<D, X3>(p.k2 + (int64_t)bk * p.k2_sb + h * D, p.k2_sl, p.vt2 + (int64_t)bk * p.vt2_sb + (int64_t)h * D * p.Lpad2, p.L2,
                      p.Lpad2, nullptr, p.scale_log2, qf, o2, den2, m2, l31, half);
         const float inv2 = 1.0f / den2;
+        const float sw = weighted_scale2<QW>(scale2, wq);
 #pragma unroll
         for (int dt = 0; dt < DT_TILES; ++dt)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) o[dt][r] += scale2 * (o2[dt][r] * inv2);  // attention_processor.py:454
+            for (int r = 0; r < 16; ++r) o[dt][r] += sw * (o2[dt][r] * inv2);  // attention_processor.py:454
     }
     if (!qvalid) return;
     float* ob = p.out + (int64_t)b * p.o_sb + (int64_t)qi * p.o_sn + h * D;
@@ -509,12 +512,22 @@ template <int D, bool X3> __device__ __forceinline__ void attn_f32_body(const A3
         }
 }
 
-template <int D> __global__ __launch_bounds__(256) void attn_f32_kernel(A32P p) { attn_f32_body<D, false>(p); }
-template <int D> __global__ __launch_bounds__(256) void attn_f32x3_kernel(A32P p) { attn_f32_body<D, true>(p); }
+template <int D> __global__ __launch_bounds__(256) void attn_f32_kernel(A32P p) { attn_f32_body<D, false, false>(p); }
+template <int D> __global__ __launch_bounds__(256) void attn_f32x3_kernel(A32P p) { attn_f32_body<D, true, false>(p); }
+// apad_attention_qw: the weight of segment 2 multiplied by the lane's own entry of a per-query map
+template <int D> __global__ __launch_bounds__(256) void attn_f32_qw_kernel(A32P p) { attn_f32_body<D, false, true>(p); }
+template <int D> __global__ __launch_bounds__(256) void attn_f32x3_qw_kernel(A32P p) { attn_f32_body<D, true, true>(p); }
 
 template <int D> int attn_launch(const A32P& p, bool x3, hipStream_t s) {
     dim3 grid((unsigned)((p.N + 127) / 128), (unsigned)(p.B * p.H));
-    if (x3) {
+    if (p.qw.w != nullptr) {  // apad_attention_qw (a second segment: checked by the caller)
+        if (x3) {
+            hipLaunchKernelGGL((attn_f32x3_qw_kernel<D>), grid, dim3(256), 0, s, p);
+            ++g_f32x3_launches;
+        } else {
+            hipLaunchKernelGGL((attn_f32_qw_kernel<D>), grid, dim3(256), 0, s, p);
+        }
+    } else if (x3) {
         hipLaunchKernelGGL((attn_f32x3_kernel<D>), grid, dim3(256), 0, s, p);
         ++g_f32x3_launches;
     } else {
@@ -842,7 +855,7 @@ int apad_f32_gemm(const apad_gemm_desc* d, hipStream_t s) {
     return apad_check_launch("apad_gemm(f32)");
 }
 
-int apad_f32_attention(const apad_attn_desc* d, const Scale2Tab& s2, hipStream_t s) {
+int apad_f32_attention(const apad_attn_desc* d, const Scale2Tab& s2, const QueryW& qw, hipStream_t s) {
     APAD_CHECK(d->q && d->k && d->vt && d->out, "apad_attention(f32): null operand");
     APAD_CHECK(d->B > 0 && d->N > 0 && d->H > 0 && d->L > 0, "apad_attention(f32): empty problem B=%d N=%d H=%d L=%d", d->B, d->N, d->H,
                d->L);
@@ -873,6 +886,7 @@ int apad_f32_attention(const apad_attn_desc* d, const Scale2Tab& s2, hipStream_t
     p.scale_log2 = d->q_prescaled ? 1.0f : d->softmax_scale * LOG2E_F;
     p.scale2 = d->scale2;
     p.s2 = s2;
+    p.qw = qw;
     const bool x3 = d->dtype == APAD_F32_BF16X3;
     switch (d->D) {
         case 16: return attn_launch<16>(p, x3, s);

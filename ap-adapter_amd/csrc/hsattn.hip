@@ -58,6 +58,7 @@ struct HsP {
     int32_t B, N, L1, Lpad1, L2, Lpad2, normalize, xm;
     float eps, scale_log2, scale2;
     Scale2Tab s2;  // apad_hs_attention_tab: scale2 per sample from a device table (table == nullptr: the scalar above)
+    QueryW qw;     // apad_hs_attention_qw: the weight map of segment 2, read by the QW instantiations only
 };
 
 // One sample's rows into the X tile: 8 lanes per row, 64 rows per pass of 512 threads, in two steps so that the caller can put its weight
@@ -206,7 +207,7 @@ __device__ __forceinline__ void hs_tile_to_rows(const uint8_t* T, uint8_t* dst_r
     }
 }
 
-template <int DT, bool SELF, bool NORM, int NS1, int NS2, int NSET>
+template <int DT, bool SELF, bool NORM, int NS1, int NS2, int NSET, bool QW = false>
 __global__ __launch_bounds__(512) void hs_attn_kernel(HsP p) {
     using E = ET<DT>;
     constexpr int D = HS_D, KC = D / 16, DTT = (D + 31) / 32;
@@ -253,6 +254,12 @@ __global__ __launch_bounds__(512) void hs_attn_kernel(HsP p) {
 
     // ---- 1. LayerNorm -> X ----
     hs_rows_store<DT, NORM>(xr, p.eps, N, X, tid);
+    // the map entry of each token (a row past the sample: its last token's) is parked in the 16 pad bytes behind its X row, which nothing else
+    // reads or writes: the blend reads it back from LDS (as xattn_rows_kernel; at the blend, or held across the segments, it costs scratch)
+    if constexpr (QW) {
+        const int row = tid >> 3;
+        if ((tid & 7) == 0) *reinterpret_cast<float*>(X + row * XROWB + HS_C * 2) = query_weight<true>(p.qw, b, row < N ? row : N - 1);
+    }
     if (proj) {
 #pragma unroll
         for (int i = PRE; i < NSET; ++i)
@@ -377,13 +384,16 @@ __global__ __launch_bounds__(512) void hs_attn_kernel(HsP p) {
             else
                 short_compute<DT, D, NSB>(f2, p.L2, nullptr, p.scale_log2, qf, o2, inv2, half);
             // (as attn_short_kernel: each branch, and scale * audio, rounded to the storage type before the add)
+            float wq = 1.0f;  // the map entry of this lane's token, parked behind its X row in phase 1
+            if constexpr (QW) wq = *reinterpret_cast<const float*>(X + (mt * 32 + l31) * XROWB + HS_C * 2);
+            const float sw = weighted_scale2<QW>(scale2, wq);
 #pragma unroll
             for (int dt = 0; dt < DTT; ++dt)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const float t = (float)(typename E::elem)o[dt][r];
                     const float a = (float)(typename E::elem)(o2[dt][r] * inv2);
-                    o[dt][r] = t + (float)(typename E::elem)(scale2 * a);
+                    o[dt][r] = t + (float)(typename E::elem)(sw * a);
                 }
         }
         // O(head, panel) over this wave's own q values in the Q tile (nobody else reads them)
@@ -813,23 +823,28 @@ __global__ __launch_bounds__(512) void hs_ff2_kernel(HfP p) {
         hf_body<DT, 2>(p, smem, b, cq, tid, lane, wave);
 }
 
-template <int DT, bool SELF, bool NORM, int NS1, int NS2> int hs_attn_go2(const HsP& p, hipStream_t s) {
+template <int DT, bool SELF, bool NORM, int NS1, int NS2, bool QW = false> int hs_attn_go2(const HsP& p, hipStream_t s) {
     constexpr int NSET = HS_NSET;
     constexpr int LDS = SELF ? X_BYTES + 2 * Q_BYTES + V_BYTES + HS_BIAS_BYTES : X_BYTES + Q_BYTES + HS_BIAS_BYTES;
     static unsigned devs = 0;
-    auto kern = hs_attn_kernel<DT, SELF, NORM, NS1, NS2, NSET>;
+    auto kern = hs_attn_kernel<DT, SELF, NORM, NS1, NS2, NSET, QW>;
     if (apad_ensure_dyn_lds(reinterpret_cast<const void*>(kern), LDS, &devs) != 0) return -1;
     hipLaunchKernelGGL(kern, dim3((unsigned)hs_grid(p.B, p.xm)), dim3(512), LDS, s, p);
     return apad_check_launch("apad_hs_attention");
 }
-template <int DT, bool SELF, int NS1, int NS2> int hs_attn_go(const HsP& p, hipStream_t s) {
-    return p.normalize ? hs_attn_go2<DT, SELF, true, NS1, NS2>(p, s) : hs_attn_go2<DT, SELF, false, NS1, NS2>(p, s);
+template <int DT, bool SELF, int NS1, int NS2, bool QW = false> int hs_attn_go(const HsP& p, hipStream_t s) {
+    return p.normalize ? hs_attn_go2<DT, SELF, true, NS1, NS2, QW>(p, s) : hs_attn_go2<DT, SELF, false, NS1, NS2, QW>(p, s);
 }
 
 template <int DT> int hs_attn_launch(const HsP& p, bool self, hipStream_t s) {
     if (self) return p.N > 32 ? hs_attn_go<DT, true, 2, 0>(p, s) : hs_attn_go<DT, true, 1, 0>(p, s);
     // sub-tile counts of the two segments are compile-time (the fragment registers of an unused sub-tile would not fit beside the rest)
     const int ns1 = p.L1 > 32 ? 2 : 1, ns2 = (p.L2 + 31) / 32;
+    if (p.qw.w != nullptr) {  // apad_hs_attention_qw (cross-attention with ns2 > 0: checked by the caller)
+        if (ns2 > 2) return hs_attn_go<DT, false, 1, 16, true>(p, s);
+        if (ns1 == 1 && ns2 == 1) return hs_attn_go<DT, false, 1, 1, true>(p, s);
+        return hs_attn_go<DT, false, 2, 2, true>(p, s);
+    }
     if (ns2 > 2) return hs_attn_go<DT, false, 1, 16>(p, s);  // (ns1 == 1: checked by the caller) 8 text + 65 .. 512 audio keys, in 64-key chunks (long_segment)
     if (ns1 == 1 && ns2 == 0) return hs_attn_go<DT, false, 1, 0>(p, s);
     if (ns1 == 1 && ns2 == 1) return hs_attn_go<DT, false, 1, 1>(p, s);
@@ -870,12 +885,14 @@ inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) =
 extern "C" int apad_sizeof_hs_attn_desc(void) { return (int)sizeof(apad_hs_attn_desc); }
 extern "C" int apad_sizeof_hs_out_desc(void) { return (int)sizeof(apad_hs_out_desc); }
 
-// apad_hs_attention (t unused) and apad_hs_attention_tab (has_tab) share this launch path
-static int hs_attention_launch(const apad_hs_attn_desc* d, const apad_scale2_tab* t, bool has_tab, void* stream) {
-    const char* const who = has_tab ? "apad_hs_attention_tab" : "apad_hs_attention";
+// apad_hs_attention (t unused), apad_hs_attention_tab (has_tab) and apad_hs_attention_qw (has_qw; its table is optional) share this launch path
+static int hs_attention_launch(const apad_hs_attn_desc* d, const apad_scale2_tab* t, bool has_tab, const apad_query_weight* w, bool has_qw, void* stream) {
+    const char* const who = has_qw ? "apad_hs_attention_qw" : has_tab ? "apad_hs_attention_tab" : "apad_hs_attention";
     APAD_CHECK(d != nullptr, "%s: null descriptor", who);
     Scale2Tab s2;
     if (apad_scale2_tab_arg(who, t, has_tab, d->L2, &s2) != 0) return -1;
+    QueryW qw;
+    if (apad_query_weight_arg(who, w, has_qw, d->N, d->L2, &qw) != 0) return -1;
     APAD_CHECK(d->dtype == APAD_BF16 || d->dtype == APAD_F16, "apad_hs_attention: dtype %d not supported (16-bit only)", d->dtype);
     if (d->C != HS_C || d->heads != HS_H || d->N < 1 || d->N > HS_TM) {
         apad_set_error("apad_hs_attention: C=%d heads=%d N=%d outside the kernel envelope (640, 8, 1..64)", d->C, d->heads, d->N);
@@ -903,14 +920,19 @@ static int hs_attention_launch(const apad_hs_attn_desc* d, const apad_scale2_tab
     p.k1 = (const uint8_t*)d->k1; p.vt1 = (const uint8_t*)d->vt1; p.bias1 = d->key_bias; p.k2 = (const uint8_t*)d->k2; p.vt2 = (const uint8_t*)d->vt2;
     p.out = (uint8_t*)d->out;
     p.B = d->B; p.N = d->N; p.L1 = d->L1; p.Lpad1 = d->Lpad1; p.L2 = d->L2; p.Lpad2 = d->Lpad2;
-    p.eps = d->ln_eps; p.scale_log2 = d->q_prescaled ? 1.0f : d->softmax_scale * LOG2E; p.scale2 = d->scale2; p.s2 = s2;
+    p.eps = d->ln_eps; p.scale_log2 = d->q_prescaled ? 1.0f : d->softmax_scale * LOG2E; p.scale2 = d->scale2; p.s2 = s2; p.qw = qw;
     p.xm = 8;
     hipStream_t s = (hipStream_t)stream;
     return d->dtype == APAD_BF16 ? hs_attn_launch<APAD_BF16>(p, self, s) : hs_attn_launch<APAD_F16>(p, self, s);
 }
 
-extern "C" int apad_hs_attention(const apad_hs_attn_desc* d, void* stream) { return hs_attention_launch(d, nullptr, false, stream); }
-extern "C" int apad_hs_attention_tab(const apad_hs_attn_desc* d, const apad_scale2_tab* t, void* stream) { return hs_attention_launch(d, t, true, stream); }
+extern "C" int apad_hs_attention(const apad_hs_attn_desc* d, void* stream) { return hs_attention_launch(d, nullptr, false, nullptr, false, stream); }
+extern "C" int apad_hs_attention_tab(const apad_hs_attn_desc* d, const apad_scale2_tab* t, void* stream) {
+    return hs_attention_launch(d, t, true, nullptr, false, stream);
+}
+extern "C" int apad_hs_attention_qw(const apad_hs_attn_desc* d, const apad_scale2_tab* t, const apad_query_weight* w, void* stream) {
+    return hs_attention_launch(d, t, t != nullptr, w, true, stream);
+}
 
 extern "C" int apad_hs_geglu(const void* x, const void* w_packed, const float* w_bias, void* out, int32_t B, int32_t N, int32_t C, int32_t normalize, float ln_eps,
                              int32_t dtype, void* stream) {

@@ -42,13 +42,34 @@ table[min(*step_ptr, rows - 1)][b % cols] (include/apadapter_hip.h, apad_scale2_
 operands' device; step_ptr: a device int32 (the captured step's counter) or None = row 0; cols: 1 or the number of clips."""
 
 
-def _launch_scale2(name, d, scale2, dev):
+QueryWeight = collections.namedtuple("QueryWeight", "w cols")
+QueryWeight.__doc__ = """``query_weight=`` of the row-per-lane two-segment attention ops (attention, cross_attention_rows, hs_attention): query n of
+sample b blends its audio segment with scale2 * w[b % cols][n] (include/apadapter_hip.h, apad_query_weight).  w: contiguous fp32 [>= cols,
+ld >= N] on the operands' device; entries at or past N of a row are not read; cols: 1 or the number of clips."""
+
+
+def _launch_scale2(name, d, scale2, dev, query_weight=None):
     """the launch of a two-segment attention descriptor: a float ``scale2`` through apad_<name>, a Scale2Binding (or a plain (table, step_ptr,
-    cols) tuple) through apad_<name>_tab.  Device, dtype, contiguity and shape are checked here; what the values decide (rows, cols, the row
-    stride, a missing table, a single-segment call) is the entry point's check."""
+    cols) tuple) through apad_<name>_tab; with a QueryWeight (or a plain (w, cols) tuple) either of them through apad_<name>_qw.  Device,
+    dtype, contiguity and shape are checked here; what the values decide (rows, cols, the row stride, a missing table or map, a
+    single-segment call) is the entry point's check."""
     lib = L.lib()
+    qw = None
+    if query_weight is not None:
+        w, qcols = query_weight
+        fn = name + ".query_weight"
+        qw = L.QueryWeight()
+        if w is not None:
+            _req(w, fn + " w", torch.float32)
+            if w.dim() != 2 or not w.is_contiguous() or w.device != dev or w.shape[0] < int(qcols):
+                raise RuntimeError(f"{fn}: expected a contiguous fp32 [>= cols = {int(qcols)}, >= N] map on {dev}, got {tuple(w.shape)} on {w.device}")
+            qw.w, qw.ld = w.data_ptr(), w.shape[1]
+        qw.cols = int(qcols)
     if not isinstance(scale2, tuple):
         d.scale2 = float(scale2)
+        if qw is not None:
+            L.check(getattr(lib, "apad_" + name + "_qw")(C.byref(d), None, C.byref(qw), _stream()), "apad_" + name + "_qw")
+            return
         L.check(getattr(lib, "apad_" + name)(C.byref(d), _stream()), "apad_" + name)
         return
     table, step_ptr, cols = scale2
@@ -66,6 +87,9 @@ def _launch_scale2(name, d, scale2, dev):
         t.step = step_ptr.data_ptr()
     t.cols = int(cols)
     d.scale2 = 0.0
+    if qw is not None:
+        L.check(getattr(lib, "apad_" + name + "_qw")(C.byref(d), C.byref(t), C.byref(qw), _stream()), "apad_" + name + "_qw")
+        return
     L.check(getattr(lib, "apad_" + name + "_tab")(C.byref(d), C.byref(t), _stream()), "apad_" + name + "_tab")
 
 
@@ -474,11 +498,13 @@ def _rows_kv_args(k, vt, B, heads, hd, dtype, what):
     return k.data_ptr(), vt.data_ptr(), k.shape[1], vt.shape[-1]
 
 
-def cross_attention_rows(x, wq_packed, wo_packed, bo, k1, vt1, heads, ln=None, key_bias=None, k2=None, vt2=None, scale2=0.0, out=None):
+def cross_attention_rows(x, wq_packed, wo_packed, bo, k1, vt1, heads, ln=None, key_bias=None, k2=None, vt2=None, scale2=0.0, out=None,
+                         query_weight=None):
     """The fused cross-attention sub-layer at the 384-wide level: out = x + to_out(A(q, k1, v1, bias) [+ scale2 * A(q, k2, v2)]) + bo,
     q = to_q(LayerNorm(x)), one launch (csrc/attention.hip, xattn_rows_kernel).  x [B, N, C]; k* [B, L, C] row-major, vt* [B, heads, d,
     Lpad] as ops.attention takes them, or k* = a RowsKV (rows_pack_kv) and vt* = None; weights from xrows_pack_weight.  scale2: a float, or a
-    Scale2Binding (apad_cross_attention_rows_tab)."""
+    Scale2Binding (apad_cross_attention_rows_tab).  query_weight: None, or a QueryWeight (scale2 times a per-token map,
+    apad_cross_attention_rows_qw)."""
     _req(x, "cross_attention_rows.x", wq_packed.dtype)
     B, N, Cc = x.shape
     L1, L2 = k1.shape[1], (0 if k2 is None else k2.shape[1])
@@ -498,7 +524,7 @@ def cross_attention_rows(x, wq_packed, wo_packed, bo, k1, vt1, heads, ln=None, k
     if L2 > 0:
         d.k2, d.vt2, d.L2, d.Lpad2 = _rows_kv_args(k2, vt2, B, heads, Cc // heads, x.dtype, "cross_attention_rows.k2 / vt2")
     d.dtype, d.softmax_scale = _DT[x.dtype], 1.0 / math.sqrt(Cc // heads)
-    _launch_scale2("cross_attention_rows", d, scale2, x.device)
+    _launch_scale2("cross_attention_rows", d, scale2, x.device, query_weight)
     return out
 
 
@@ -671,11 +697,11 @@ def hs_ff2(h, w2_packed, bias, residual, rowstat=False, out=None):
 
 
 def hs_attention(x, w_packed, w_bias, *, self_attention, normalize=True, ln_eps=1e-5, k1=None, vt1=None, key_bias=None, k2=None, vt2=None,
-                 scale2=0.0, q_prescaled=False, out=None):
+                 scale2=0.0, q_prescaled=False, out=None, query_weight=None):
     """O = heads' softmax attention of the 64-token level in ONE launch (apad_hs_attention): rows of x normalised (the LayerNorm's affine
     part lives in w_packed / w_bias: hs_pack_qkv / hs_pack_rows), q|k|v (self) or q (cross: k*, vt* = the hoisted sets in ops.attention's
     layout, or k* = a RowsKV and vt* = None) projected per head pair, both heads attended, O [B, N, 640] written.  to_out + residual: ``hs_out``.
-    scale2: a float, or a Scale2Binding (apad_hs_attention_tab)."""
+    scale2: a float, or a Scale2Binding (apad_hs_attention_tab).  query_weight: None, or a QueryWeight (apad_hs_attention_qw)."""
     _req(x, "hs_attention.x", w_packed.dtype)
     B, N, Cc = x.shape
     if Cc != HS_C or N > HS_MAXN or x.dtype not in FUSED_DTYPES or not x.is_contiguous():
@@ -698,7 +724,7 @@ def hs_attention(x, w_packed, w_bias, *, self_attention, normalize=True, ln_eps=
     d.B, d.N, d.C, d.heads = B, N, Cc, HS_HEADS
     d.self_attention, d.q_prescaled, d.dtype, d.normalize = int(bool(self_attention)), int(bool(q_prescaled)), _DT[x.dtype], int(bool(normalize))
     d.ln_eps, d.softmax_scale = float(ln_eps), 1.0 / math.sqrt(80.0)
-    _launch_scale2("hs_attention", d, scale2, x.device)
+    _launch_scale2("hs_attention", d, scale2, x.device, query_weight)
     return out
 
 
@@ -1205,11 +1231,12 @@ LOG2E = 1.4426950408889634
 
 
 def attention(q, k, vt, Lk, heads, key_bias=None, k2=None, vt2=None, L2=0, scale2=0.0, kv_batch_div=1,
-              kv2_batch_div=1, out=None, q_prescaled=False):
+              kv2_batch_div=1, out=None, q_prescaled=False, query_weight=None):
     """q [B,N,C]; k [Bk,Lk,C]; vt [Bk,heads,d,Lpad]; optional second (audio) segment k2/vt2 with its own softmax,
     blended as seg1 + scale2*seg2.  key_bias: fp32 [B,Lk] additive.  q_prescaled: q was projected with to_q rows already
     multiplied by log2(e) / sqrt(d) (processors._qkv_weight), i.e. it is the base-2 exponent operand.  scale2: a float, or a Scale2Binding
-    (table, step_ptr, cols): sample b uses table[min(*step_ptr, rows - 1)][b % cols] (apad_attention_tab)."""
+    (table, step_ptr, cols): sample b uses table[min(*step_ptr, rows - 1)][b % cols] (apad_attention_tab).  query_weight: None, or a
+    QueryWeight (w, cols): query n of sample b uses scale2 * w[b % cols][n] (apad_attention_qw)."""
     _req(q, "attention.q")
     _req(k, "attention.k", q.dtype)
     _req(vt, "attention.vt", q.dtype)
@@ -1232,7 +1259,7 @@ def attention(q, k, vt, Lk, heads, key_bias=None, k2=None, vt2=None, L2=0, scale
         d.k2, d.vt2 = k2.data_ptr(), vt2.data_ptr()
         d.k2_stride_b, d.k2_stride_l, d.vt2_stride_b = k2.stride(0), k2.stride(1), vt2.stride(0)
         d.L2, d.Lpad2 = L2, vt2.shape[-1]
-    _launch_scale2("attention", d, scale2, q.device)
+    _launch_scale2("attention", d, scale2, q.device, query_weight)
     return out
 
 

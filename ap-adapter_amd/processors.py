@@ -30,13 +30,15 @@ USE_FUSED_XATTN = True
 USE_XATTN_ROWS = True  # the 384-wide level's kernel alone (follows USE_FUSED_XATTN)
 
 
-def route(kind, attn, hidden_states, residual=None, ln=None, L1=0, L2=0, masked=False, same_batch=True):
+def route(kind, attn, hidden_states, residual=None, ln=None, L1=0, L2=0, masked=False, same_batch=True, query_weighted=False):
     """Which kernels run this attention sub-layer.  Decided ONCE per call, before the hoist, from shapes, dtypes, strides and module attributes
     only (CPU tensors do; nothing is launched); both the packing of the hoisted key / value sets and the dispatch read the answer.
 
     ``kind``: "self", "cross" (AttnProcessor2_0 over a condition) or "decoupled" (IPAttnProcessor2_0); ``residual`` / ``ln``: what the caller
     fuses (the block entry passes ``residual is hidden_states`` and its LayerNorm); ``L1`` / ``L2``: key counts of the one or two segments;
-    ``masked``: a key bias will be passed; ``same_batch``: the condition has the batch of the hidden states.
+    ``masked``: a key bias will be passed; ``same_batch``: the condition has the batch of the hidden states; ``query_weighted``: the audio segment
+    is weighed per query token (a bound ap_mask map): apad_fused_cross_attention has no such form, so what would be "fused" is "chain" -- every
+    other answer is unchanged.
 
       "fused"  apad_fused_cross_attention: LayerNorm + to_q + attention + to_out + residual in one launch (C = 256)
       "rows"   apad_cross_attention_rows: the same sub-layer in one launch on row tiles (C = 384)
@@ -62,7 +64,7 @@ def route(kind, attn, hidden_states, residual=None, ln=None, L1=0, L2=0, masked=
     # the one-launch kernels take the block entry only: they apply its LayerNorm and add x itself
     entry = USE_FUSED_XATTN and residual is x and ln is not None and square_q and x.is_contiguous() and x.dtype in ops.FUSED_DTYPES
     if entry and C_ == ops.XATTN_C and heads == ops.XATTN_HEADS and ops.xattn_lengths_ok(L1, L2, masked):
-        return "fused"
+        return "chain" if query_weighted else "fused"
     if entry and USE_XATTN_ROWS and same_batch and ops.xrows_ok(C_, heads, L1, L2):
         return "rows"
     if hs and same_batch and ops.hs_cross_lengths_ok(L1, L2):
@@ -235,7 +237,7 @@ class _Processor(nn.Module):
     """What the two processors share: the entry of the reference's processors (guards, the 4-D form), the hoist of timestep-invariant results
     and the dispatch over ``route``.  Adds no parameter, buffer or sub-module.  A subclass describes its condition: ``_lengths`` (key counts of
     the one or two segments), ``_segments`` (source rows and projection weights of each), ``_kv_signature`` (what the hoisted sets were
-    computed from), ``_bias`` (its mask rule) and ``_scale2`` (the weight of the second segment)."""
+    computed from), ``_bias`` (its mask rule), ``_scale2`` (the weight of the second segment) and ``_query_weight`` (its per-token map)."""
 
     fuses_residual = True
     kind = None
@@ -361,7 +363,8 @@ class _Processor(nn.Module):
             o = ops.attention(q, k, vt, N, heads, key_bias=self._bias(attention_mask, B, N), q_prescaled=prescaled)
             return ops.fused_linear(o, wo, bo, residual=residual, rowstat=True)
         L1, L2 = self._lengths(ehs)
-        r = route(self.kind, attn, x, residual, ln, L1, L2, masked, ehs.shape[0] == B)
+        qw = self._query_weight(N) if L2 > 0 else None
+        r = route(self.kind, attn, x, residual, ln, L1, L2, masked, ehs.shape[0] == B, query_weighted=qw is not None)
         persistent = self.kv_cache_enabled
 
         def make():  # the projections, packed with them into what the route's kernel reads
@@ -384,11 +387,12 @@ class _Processor(nn.Module):
             k1 = _rows_kv(kv.pk1, B, L1, attn)
             k2 = _rows_kv(kv.pk2, B, L2, attn) if L2 > 0 else None
             if r == "hs":
-                return _hs_sublayer(attn, x, residual, ln, k1=k1, vt1=None, key_bias=bias, k2=k2, vt2=None, scale2=scale2)
+                return _hs_sublayer(attn, x, residual, ln, k1=k1, vt1=None, key_bias=bias, k2=k2, vt2=None, scale2=scale2, query_weight=qw)
             wq_p, wo_p = _xrows_weights(attn)
-            return ops.cross_attention_rows(x, wq_p, wo_p, bo, k1, None, heads, ln=ln, key_bias=bias, k2=k2, vt2=None, scale2=scale2)
+            return ops.cross_attention_rows(x, wq_p, wo_p, bo, k1, None, heads, ln=ln, key_bias=bias, k2=k2, vt2=None, scale2=scale2,
+                                            query_weight=qw)
         q = ops.fused_linear(x, attn.to_q.weight, ln=ln)
-        o = ops.attention(q, kv.k1, kv.vt1, L1, heads, key_bias=bias, k2=kv.k2, vt2=kv.vt2, L2=L2, scale2=scale2)
+        o = ops.attention(q, kv.k1, kv.vt1, L1, heads, key_bias=bias, k2=kv.k2, vt2=kv.vt2, L2=L2, scale2=scale2, query_weight=qw)
         return ops.fused_linear(o, wo, bo, residual=residual, rowstat=True)
 
 
@@ -424,6 +428,9 @@ class AttnProcessor2_0(_Processor):
 
     def _scale2(self):
         return 0.0
+
+    def _query_weight(self, N):
+        return None
 
     def _call_train(self, attn, hidden_states, ehs, attention_mask, _residual, _ln):
         """Training mode (gradients flow to hidden_states; autograd.py): the un-fused chain LayerNorm ->
@@ -461,6 +468,7 @@ class IPAttnProcessor2_0(_Processor):
         self.num_tokens = num_tokens
         self.scale = scale
         self.scale_table = None  # set_ap_scale_table: an ops.Scale2Binding read in place of ``scale``
+        self.token_weights = None  # set_ap_token_weights: {token count N: ops.QueryWeight}, the map that multiplies the scale per query token
         self.name = name
         self.to_k_ip = nn.Linear(cross_attention_dim or hidden_size, hidden_size, bias=False)
         self.to_v_ip = nn.Linear(cross_attention_dim or hidden_size, hidden_size, bias=False)
@@ -510,11 +518,30 @@ class IPAttnProcessor2_0(_Processor):
     def _scale2(self):
         return self.scale if self.scale_table is None else self.scale_table
 
+    def set_ap_token_weights(self, maps, cols):
+        """weigh the audio branch per query token: ``maps`` = {N: fp32 [cols, N] device tensor}, one map per token count this processor is called
+        with (the levels of ``UNet.attention_grids``, tokens in ``_as_tokens``' row-major order); query n of sample b uses (``scale`` or the
+        bound table's entry) * maps[N][b % cols][n] (the apad_*_qw entry points).  While maps are bound the 256-wide sites run the chain
+        instead of the fused kernel (``route(query_weighted=True)``).  Inference only."""
+        self.token_weights = {int(n): ops.QueryWeight(w, int(cols)) for n, w in maps.items()}
+
+    def clear_ap_token_weights(self):
+        self.token_weights = None
+
+    def _query_weight(self, N):
+        if self.token_weights is None:
+            return None
+        if N not in self.token_weights:
+            raise ValueError(f"ap_mask: no weight map is bound for a call of {N} tokens (bound: {sorted(self.token_weights)})")
+        return self.token_weights[N]
+
     def _call_train(self, attn, hidden_states, ehs, attention_mask, _residual, _ln):
         """Training mode (reference :347-470 under autograd; train_apadapter_v2.py:941-957): gradients w.r.t.
         hidden_states, to_k_ip.weight and to_v_ip.weight (and the condition tokens if they require grad)."""
         if self.scale_table is not None:
             raise ValueError("ap_scale: the training path keeps the float `scale`; clear_ap_scale_table() before a forward under autograd")
+        if self.token_weights is not None:
+            raise ValueError("ap_mask: the training path has no per-token weight; clear_ap_token_weights() before a forward under autograd")
         B = hidden_states.shape[0]
         nt = self.num_tokens
         txt, aud = ehs[:, :nt, :].contiguous(), ehs[:, nt:, :].contiguous()

@@ -162,6 +162,28 @@ def ap_scale_table(ap_scale, num_inference_steps, start=0, clips=None):
     return torch.tensor(rows, dtype=torch.float64).float().contiguous()
 
 
+def ap_mask_pyramid(mask, grids):
+    """The per-token weight maps of the audio prompt for every attention level: ``mask`` fp32 [cols, 1, H, W] over the latent grid (the weight of
+    the audio branch at each latent cell; any finite value), ``grids`` the (h, w) of the levels (``UNet.attention_grids(H, W)``).  Per level,
+    ``adaptive_avg_pool2d`` of the mask to (h, w) -- a token's weight is the mean over the latent cells it covers -- flattened row-major to
+    [cols, h * w], the token order of the processors' 4-D entry; computed on the host, once per call.  Returns {h * w: fp32 [cols, h * w]},
+    what ``set_ap_token_weights`` takes (a processor picks its map by its token count).  The latent-grid mask of an ``ap_region`` is binary and
+    so is a level whose pooling windows do not straddle the region's ends; a coarser level gets FRACTIONAL edge rows there (a window half
+    inside weighs 0.5), and every pooled value of a mask in [0, 1] stays in [0, 1].  Errors are ValueErrors whose text starts with ``ap_mask``."""
+    m = torch.as_tensor(mask).detach().to("cpu", torch.float32)
+    if m.dim() != 4 or m.shape[1] != 1 or m.shape[0] < 1:
+        raise ValueError(f"ap_mask: expected a [cols, 1, H, W] mask, got {tuple(m.shape)}")
+    if not bool(torch.isfinite(m).all()):
+        raise ValueError("ap_mask: every value must be finite")
+    out = {}
+    for h, w in grids:
+        level = torch.nn.functional.adaptive_avg_pool2d(m, (int(h), int(w))).reshape(m.shape[0], int(h) * int(w)).contiguous()
+        if int(h) * int(w) in out:
+            raise ValueError(f"ap_mask: two attention levels hold {int(h) * int(w)} tokens; the maps are picked by the token count")
+        out[int(h) * int(w)] = level
+    return out
+
+
 class _EditSchedule:
     """what an edit run needs of either scheduler (both share the timestep grid and alphas_cumprod): where it starts, the add_noise
     coefficients of the start and the per-step (kx, kz) of the kept region.  PARITY UNPINNED, like the samplers: diffusers' img2img /

@@ -417,6 +417,7 @@ class AudioLDM2UNet2DConditionModel(nn.Module):
         self._time_tables = None
         self.low_res_streams = None  # optional (stream, stream): see forward_nhwc
         self._ap_scale_cols = None   # columns of the table set_ap_scale_table bound (None: no table)
+        self._ap_mask_cols = None    # columns of the maps set_ap_token_weights bound (None: no maps)
         self.low_res_levels = 1      # how many of the lowest-resolution levels run on the two streams
 
     # ---- processor plumbing (modeling_audioldm2.py:517-574) ----
@@ -475,6 +476,41 @@ class AudioLDM2UNet2DConditionModel(nn.Module):
         for p in set(self.attn_processors.values()):
             if hasattr(p, "clear_ap_scale_table"):
                 p.clear_ap_scale_table()
+
+    def set_ap_token_weights(self, maps, cols):
+        """Hand every decoupled processor the per-token weight maps of the audio prompt: ``maps`` = {token count: fp32 [cols, tokens] device
+        tensor}, one per level of ``attention_grids`` (``scheduler.ap_mask_pyramid``), column ``sample % cols``.  Query n of sample b then blends
+        its audio branch with (scale or the bound table's entry) * map[b % cols][n], through the apad_*_qw entry points; the 256-wide sites run
+        the chain instead of the fused kernel while maps are bound.  Inference only."""
+        self._ap_mask_cols = int(cols)
+        for p in set(self.attn_processors.values()):
+            if hasattr(p, "set_ap_token_weights"):
+                p.set_ap_token_weights(maps, cols)
+
+    def clear_ap_token_weights(self):
+        self._ap_mask_cols = None
+        for p in set(self.attn_processors.values()):
+            if hasattr(p, "clear_ap_token_weights"):
+                p.clear_ap_token_weights()
+
+    def attention_grids(self, H, W):
+        """the (h, w) token grid of every resolution level that holds a decoupled ``attn2`` (an IPAttnProcessor2_0), finest first, for an
+        [H, W] latent: h -> (h + 1) // 2 per stride-2 downsampler (3x3, padding 1); the up path returns to the same grids."""
+        def decoupled(block):
+            return any(getattr(m.get_processor(return_deprecated_lora=True), "kind", None) == "decoupled"
+                       for m in block.modules() if hasattr(m, "get_processor"))
+
+        levels, (h, w) = [], (int(H), int(W))
+        for blk in self.down_blocks:
+            levels.append((h, w))
+            if blk.downsamplers is not None:
+                h, w = (h + 1) // 2, (w + 1) // 2
+        n = len(levels)
+        held = {i for i, blk in enumerate(self.down_blocks) if blk.has_cross_attention and decoupled(blk)}
+        held |= {n - 1 - i for i, blk in enumerate(self.up_blocks) if blk.has_cross_attention and decoupled(blk)}
+        if decoupled(self.mid_block):
+            held.add(n - 1)
+        return [levels[i] for i in sorted(held)]
 
     def drop_kv_owner(self, owner):
         """drop the hoisted results created on behalf of ``owner`` (processors.HOIST_OWNER at their creation)"""
@@ -633,9 +669,11 @@ class AudioLDM2UNet2DConditionModel(nn.Module):
         nsp = len(self.low_res_streams) if self.low_res_streams is not None else 0
         # (only while a hipGraph is being captured -- that is what the fork / join is for, and the captured allocations come from the graph's
         #  private pool; an EAGER forward on side streams was measured wrong in the fp32 mode at batch 32, round 5: it stays on one stream)
-        # (a per-clip ap_scale table is indexed by sample % clips: a part of the batch keeps that only when it holds whole sets of clips)
+        # (a per-clip ap_scale table, or per-clip ap_mask maps, are indexed by sample % clips: a part of the batch keeps that only when it holds
+        #  whole sets of clips)
         split = (nsp > 1 and timestep is None and B % nsp == 0 and not AG.on(x) and nb >= 2 and x.is_cuda
-                 and torch.cuda.is_current_stream_capturing() and (self._ap_scale_cols in (None, 1) or (B // nsp) % self._ap_scale_cols == 0))
+                 and torch.cuda.is_current_stream_capturing()
+                 and all(c in (None, 1) or (B // nsp) % c == 0 for c in (self._ap_scale_cols, self._ap_mask_cols)))
         k0 = max(1, nb - self.low_res_levels) if split else nb  # first down block of the two-stream section
         for i in range(k0):
             x, H, W = down(i, x, H, W, skips, *cond)

@@ -17,6 +17,10 @@
  *                       from a device table at the captured step's counter, one column per clip (apad_scale2_tab below).  A table
  *                       holding one value is bit-equal to the scalar entry point with that value; a per-step schedule and per-clip
  *                       values have no counterpart in the reference, which sets ONE scale per processor before the loop
+ *   apad_attention_qw / apad_cross_attention_rows_qw / apad_hs_attention_qw
+ *                       the same launches with that scale multiplied, per query token, by an entry of a device map
+ *                       (apad_query_weight below): the audio prompt by region.  No counterpart in the reference (diffusers knows the
+ *                       control as IP-Adapter attention masks); an entry v is bit-equal to the scalar entry point with scale * v
  *   apad_gemm           attn.to_q/to_k/to_v/to_out, to_k_ip/to_v_ip (attention_processor.py:387,:406-407,
  *                       :435-436,:457); diffusers GEGLU/FeedForward, proj_in/proj_out, ResnetBlock2D /
  *                       Downsample2D / Upsample2D 3x3 convolutions and time_emb_proj
@@ -366,6 +370,25 @@ int apad_attention_tab(const apad_attn_desc* d, const apad_scale2_tab* t, void* 
 int apad_fused_cross_attention_tab(const apad_xattn_desc* d, const apad_scale2_tab* t, void* stream);
 int apad_cross_attention_rows_tab(const apad_xrows_desc* d, const apad_scale2_tab* t, void* stream);
 int apad_hs_attention_tab(const apad_hs_attn_desc* d, const apad_scale2_tab* t, void* stream);
+
+/* The weight of segment 2 per QUERY: sample b, query n of the launch blends with
+ *     sw = s * w[(b % cols) * ld + n]
+ * where s is the table entry above (t != NULL) or the descriptor's scale2 (t == NULL), and sw -- ONE fp32 multiply -- stands where s
+ * stands: text + elem(sw * audio) in the 16-bit kernels, out += sw * audio in the fp32 modes.  A map entry v is therefore bit-equal to
+ * the scalar entry point with (float)s * v on that row, and an all-ones map to the launch without a map.  The modulo is the table's: the
+ * guidance branches of a clip share a column.  A lane reads the entry of its own query (one vector load; s stays one scalar load per
+ * workgroup) and nothing at or past index N of a row.  apad_fused_cross_attention has no such form: its sites run the un-fused chain
+ * under a map.  Rejected (negative code, apad_last_error() names the entry point, nothing launched): a NULL struct or a NULL w,
+ * cols <= 0, ld < N, w off 4-byte alignment, a single-segment call (L2 == 0), and what the _tab entry points reject about a non-NULL t. */
+typedef struct apad_query_weight {
+    const float* w;         /* fp32 [cols][ld]: the weight of query n of sample b is w[(b % cols) * ld + n] */
+    int32_t cols, reserved; /* cols = 1 (every sample) or the number of clips                              */
+    int64_t ld;             /* row stride in elements, >= N                                                */
+} apad_query_weight;
+int apad_sizeof_query_weight(void);
+int apad_attention_qw(const apad_attn_desc* d, const apad_scale2_tab* t /* NULL: d->scale2 */, const apad_query_weight* w, void* stream);
+int apad_cross_attention_rows_qw(const apad_xrows_desc* d, const apad_scale2_tab* t, const apad_query_weight* w, void* stream);
+int apad_hs_attention_qw(const apad_hs_attn_desc* d, const apad_scale2_tab* t, const apad_query_weight* w, void* stream);
 
 typedef struct apad_hs_out_desc {
     const void* o;         /* [B*N][640] attention output (all heads)                                 */

@@ -4,6 +4,8 @@ bytes per lane, LDS bytes and waves per SIMD, from hipcc's -Rpass-analysis=kerne
     python tools/resource_table.py [--csrc DIR] [--label TEXT] xattn.hip attention.hip hsattn.hip f32_ops.hip > table.txt
     python tools/resource_table.py --diff before.txt after.txt     # fails when a kernel gained scratch or lost occupancy
     python tools/resource_table.py --diff both.txt both.txt --sections "parent commit" "this commit"   # two labelled tables in one file
+    python tools/resource_table.py --diff before.txt after.txt --defaulted-false   # a kernel template gained a trailing `bool = false` parameter:
+                                                                                    # its <..., false> instantiation is compared with the old name
 
 Two tables of two commits compare line by line: the kernels are sorted by their mangled name."""
 import argparse
@@ -61,8 +63,21 @@ def parse(path, section=None):
     return out
 
 
-def diff(before, after, sections=(None, None)):
+def under_old_names(a, b):
+    """``b`` with every kernel whose template gained a trailing ``bool = false`` parameter since ``a`` filed under its name in ``a`` (Itanium
+    mangling: the template argument list ends "...ELb0EEEv" where it ended "...EEEv"); its <..., true> instantiations stay new kernels"""
+    b = dict(b)
+    for src, name in [k for k in b if k not in a]:
+        old = (src, name.replace("ELb0EEEv", "EEEv", 1))
+        if old != (src, name) and old in a and old not in b:
+            b[old] = b.pop((src, name))
+    return b
+
+
+def diff(before, after, sections=(None, None), defaulted_false=False):
     a, b = parse(before, sections[0]), parse(after, sections[1])
+    if defaulted_false:
+        b = under_old_names(a, b)
     bad = 0
     for k in sorted(set(a) | set(b)):
         if k not in a or k not in b:
@@ -83,10 +98,11 @@ def main():
     ap.add_argument("--label", default="")
     ap.add_argument("--diff", nargs=2)
     ap.add_argument("--sections", nargs=2, default=(None, None))
+    ap.add_argument("--defaulted-false", action="store_true")
     ap.add_argument("srcs", nargs="*")
     a = ap.parse_args()
     if a.diff:
-        sys.exit(diff(*a.diff, sections=tuple(a.sections)))
+        sys.exit(diff(*a.diff, sections=tuple(a.sections), defaulted_false=a.defaulted_false))
     with ThreadPoolExecutor(4) as ex:
         tabs = list(ex.map(lambda s: remarks(a.csrc, s), a.srcs))
     if a.label:

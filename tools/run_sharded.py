@@ -34,6 +34,11 @@ the captured step from a device table (``pipeline.denoise(ap_scale=)``) instead 
 comma-separated list is a per-step schedule over the full grid.  Both passes of --inversion run under it.  The written wavs carry it in their
 names (a schedule as "sched") and the summary line holds the values.
     python tools/run_sharded.py --clips 64 --steps 4 --ap-scale 1.0,0.7,0.4,0.1
+
+The audio prompt by region (--ap-region A:B, seconds): the weight above is kept between A and B and is zero elsewhere, per query token of every
+decoupled attn2 (``pipeline.denoise(ap_region=)``; the 256-wide sites then run the un-fused chain).  It composes with --ap-scale, and both
+passes of --inversion run under it.
+    python tools/run_sharded.py --clips 64 --steps 50 --ap-region 4:7
 """
 import argparse
 import glob
@@ -157,6 +162,8 @@ def main():
                     "P dBFS (<= 0)")
     ap.add_argument("--ap-scale", default=None, metavar="V|V0,V1,...", help="the weight of the audio prompt in the decoupled cross-attention: one "
                     "float, or one per step (a schedule over the full grid); default: the task preset's value, set on the processors")
+    ap.add_argument("--ap-region", default=None, metavar="A:B", help="seconds: the audio prompt weighs the tokens between A and B only "
+                    "(ap_region=(A, B)); default: the whole clip")
     ap.add_argument("--gpus", type=int, default=1, help="N > 1 without a launcher: this script starts its N ranks itself (one per GPU)")
     args = ap.parse_args()
     if args.inversion and args.sampler != "ddim":
@@ -189,6 +196,13 @@ def main():
         except ValueError:
             ap.error("--ap-scale: one float, or a comma-separated list with one float per step")
         args.ap_scale = vals[0] if len(vals) == 1 else vals
+
+    if args.ap_region is not None:
+        try:
+            a0, a1 = (float(v) for v in args.ap_region.split(":"))
+        except ValueError:
+            ap.error("--ap-region: A:B in seconds")
+        args.ap_region = (a0, a1)
 
     from ap_adapter_amd import distributed as D
     if args.gpus > 1 and not D.launched_by_torchrun():
@@ -247,6 +261,12 @@ def main():
         except ValueError as err:
             ap.error(str(err))
         aps = {"ap_scale": args.ap_scale}
+    if args.ap_region is not None:  # the rows of the region, checked once against the job's latent height
+        try:
+            pipe.check_ap_mask(args.ap_region, None, 1, H, 16, has_audio=True)
+        except ValueError as err:
+            ap.error(str(err))
+        aps["ap_region"] = args.ap_region
 
     def denoise(lat, gen, t5, mask, gs, clips=None):
         if not editing:
