@@ -1628,17 +1628,24 @@ def group_norm_bwd(x, gamma, beta, dy, groups, eps, silu, out=None):
     return dx
 
 
-def geglu(proj):
+def geglu(proj, out=None):
+    """h [..., N] = value * gelu(gate) of the stored projection [..., 2N] = [value | gate]; out: a dense buffer of h's shape and dtype"""
     _req(proj, "geglu.proj")
     N = proj.shape[-1] // 2
-    h = torch.empty(*proj.shape[:-1], N, dtype=proj.dtype, device=proj.device)
+    if out is None:
+        h = torch.empty(*proj.shape[:-1], N, dtype=proj.dtype, device=proj.device)
+    elif out.dtype != proj.dtype or out.device != proj.device or tuple(out.shape) != (*proj.shape[:-1], N) or not out.is_contiguous():
+        raise ValueError(f"geglu.out: expected a contiguous {proj.dtype} buffer of shape {(*proj.shape[:-1], N)} on {proj.device}")
+    else:
+        h = out
     L.check(L.lib().apad_geglu(proj.data_ptr(), h.data_ptr(), proj.numel() // (2 * N), N, _DT[proj.dtype], _stream()), "apad_geglu")
     return h
 
 
-def geglu_bwd(proj, dh):
+def geglu_bwd(proj, dh, out=None):
+    """dproj [..., 2N] = [dh * gelu(gate) | dh * value * gelu'(gate)]; out: a dense buffer of proj's shape and dtype"""
     N = proj.shape[-1] // 2
-    dproj = torch.empty_like(proj)
+    dproj = torch.empty_like(proj) if out is None else _dense_out(out, proj, "geglu_bwd.out")
     L.check(L.lib().apad_geglu_bwd(proj.data_ptr(), dh.data_ptr(), dproj.data_ptr(), proj.numel() // (2 * N), N,
                                    _DT[proj.dtype], _stream()), "apad_geglu_bwd")
     return dproj

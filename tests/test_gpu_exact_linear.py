@@ -26,8 +26,8 @@ test_gemm_ring_form_equals_the_tiled_kernel_bit_for_bit, test_conv3x3_implicit_g
 No mutant survived this file.
 
 Forms not in the table: the big-tile kernel's up-sampled convolution form (>= 16000 output pixels), the 128-tile two-stage convolution, ring
-mode 1; kernels with transcendentals or normalisation in them (GEGLU / SiLU / GELU epilogues, the LayerNorm-folded GEMM, the fused feed-forward)
-stay on their tolerance tests; attention is held to exact softmaxes in tests/test_gpu_exact_attention.py."""
+mode 1.  The GEGLU / SiLU / GELU / tanh epilogues and the fused feed-forward are held to saturated gates in tests/test_gpu_exact_activation.py, the
+LayerNorm inside the linear kernels in tests/test_gpu_exact_norm.py, attention to exact softmaxes in tests/test_gpu_exact_attention.py."""
 import pytest
 import torch
 

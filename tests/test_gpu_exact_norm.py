@@ -57,7 +57,8 @@ Mutants of these kernels, run against the 252 tests of test_gpu_kernels.py with 
   11. attention.hip, xattn_rows_kernel's LayerNorm: gamma read one vector to the left (clamped): old 36; new 4: every xrows_ln case.
   12. attention.hip, sattn_fused_kernel: ``mean = shift[n]`` (the mean's second term dropped): old 44; new 4: every sattn_ln case.
 
-Left out: the GELU / GEGLU consumers (hs_geglu, geglu_mlp*, layernorm_geglu_packed: the activation is not exact); ``dres`` and SiLU in the backward (both round to the storage type mid-way); off-centre sets (deliberate, see
+The GELU / GEGLU consumers (hs_geglu, geglu_mlp*, layernorm_geglu_packed) are held on tier-R rows by tests/test_gpu_exact_activation.py (the activation
+is exact where it saturates).  Left out: ``dres`` and SiLU in the backward (both round to the storage type mid-way); off-centre sets (deliberate, see
 norm_exact_cases.py).  A balanced two-valued row of 256 channels shows a reduction that is one vector short only in f16 (eight elements of 256 missing move
 the mean by at most a / 32 and the output by a few 2^-8 of gamma: around half a bf16 ulp, many f16 ulp); tier K's spikes show it in every mode."""
 import pytest
