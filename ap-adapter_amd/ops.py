@@ -1566,6 +1566,16 @@ def attention_bwd(q, k, v, out, dout, lse, heads, key_bias=None, dout_scale=1.0,
     B, N, Cc = q.shape
     Lk = k.shape[1]
     Npad, Lpad = round_up(N, 32), round_up(Lk, 32)
+    # the kernels take these on trust: a dq they would write past or read at another stride, stats rows of another length
+    if lse.dtype != torch.float32 or tuple(lse.shape) != (B, heads, Npad) or not lse.is_contiguous() or lse.device != q.device:
+        raise RuntimeError(f"attention_bwd.lse: expected a contiguous fp32 [{B}, {heads}, {Npad}] tensor (attention_lse's, padded to round_up(N, 32)), "
+                           f"got {lse.dtype} {tuple(lse.shape)}")
+    if dq is not None:
+        if dq.dtype != q.dtype or dq.device != q.device or tuple(dq.shape) != (B, N, Cc) or not dq.is_contiguous():
+            raise RuntimeError(f"attention_bwd.dq: expected a contiguous {q.dtype} [{B}, {N}, {Cc}] tensor to accumulate into, got {dq.dtype} "
+                               f"{tuple(dq.shape)} with strides {tuple(dq.stride())}")
+        if packed:
+            raise RuntimeError("attention_bwd: packed=True allocates the [B, N, 3C] buffer itself and cannot accumulate into a given dq")
     d = L.AttnBwdDesc()
     f32 = q.dtype == torch.float32  # fp32 training mode: plain-FMA kernels on the row-major operands, no transposed copies
     same = need_dkv and not f32 and N == Lk  # self-attention: q, k and dO transposed by ONE launch

@@ -41,7 +41,8 @@ No mutant survived this file.  The tolerance tests are not blind to mutants 1, 3
 2e-2 of max|ref| too); what they miss is mutant 2 in every test that calls ops.attention directly.
 
 Out of scope: ``apad_self_attention_fused`` (its LayerNorm cannot be switched off, so q, k and v are never exact; its key loop ``tile_compute2`` is
-the one attn2q_kernel runs here), the backward (``attention_bwd``), ``window_attention`` and the text-encoder and CLAP towers."""
+the one attn2q_kernel runs here), ``window_attention`` and the text-encoder and CLAP towers.  The backward (``attention_bwd``) has its own exact suite,
+tests/test_gpu_exact_attention_bwd.py."""
 import pytest
 import torch
 
