@@ -5,7 +5,7 @@ from .processors import AttnProcessor2_0, IPAttnProcessor2_0  # noqa: F401
 from .unet import AudioLDM2UNet2DConditionModel, UNetConfig  # noqa: F401
 from .audiomae import AudioMAEConditionCTPoolRand, Vanilla_AudioMAE, AudioMAEEncoder  # noqa: F401
 from .scheduler import DDIMScheduler, DPMSolverMultistepScheduler, guidance_table, ap_scale_table, ap_mask_pyramid  # noqa: F401
-from .pipeline import AudioLDM2Pipeline, EditSource, InvertedSource  # noqa: F401
+from .pipeline import AudioLDM2Pipeline, AudioPrompt, EditSource, InvertedSource  # noqa: F401
 from .vocoder import SpeechT5HifiGan, HifiGanConfig  # noqa: F401
 from .vae import AutoencoderKL, VaeConfig  # noqa: F401
 from .text_encoders import (PromptEncoder, ClapTextModelWithProjection, T5EncoderModel, GPT2Model,  # noqa: F401

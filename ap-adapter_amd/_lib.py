@@ -87,6 +87,13 @@ class QueryWeight(C.Structure):
     _fields_ = [("w", _vp), ("cols", _i32), ("reserved", _i32), ("ld", _i64)]
 
 
+class AttnExtra(C.Structure):
+    """apad_attn_extra: one more audio segment of apad_attention_multi"""
+    _fields_ = [("k", _vp), ("vt", _vp), ("k_stride_b", _i64), ("k_stride_l", _i64), ("vt_stride_b", _i64)] + \
+               [(n, _i32) for n in ("L", "Lpad", "kv_batch_div", "reserved")] + [("scale", _f32), ("reserved_f", _f32)] + \
+               [("tab", Scale2Tab), ("qw", QueryWeight)]
+
+
 class HsOutDesc(C.Structure):
     _fields_ = [(n, _vp) for n in ("o", "w_packed", "bias", "residual", "out", "rowstat_out")] + [(n, _i32) for n in ("B", "N", "C", "dtype")]
 
@@ -139,6 +146,9 @@ SYMBOLS = {
     "apad_attention_qw": (C.c_int, [C.POINTER(AttnDesc), C.POINTER(Scale2Tab), C.POINTER(QueryWeight), _vp]),
     "apad_cross_attention_rows_qw": (C.c_int, [C.POINTER(XrowsDesc), C.POINTER(Scale2Tab), C.POINTER(QueryWeight), _vp]),
     "apad_hs_attention_qw": (C.c_int, [C.POINTER(HsAttnDesc), C.POINTER(Scale2Tab), C.POINTER(QueryWeight), _vp]),
+    # several audio prompts per clip: apad_attention_qw with up to three more audio segments
+    "apad_sizeof_attn_extra": (C.c_int, []),
+    "apad_attention_multi": (C.c_int, [C.POINTER(AttnDesc), C.POINTER(Scale2Tab), C.POINTER(QueryWeight), C.POINTER(AttnExtra), _i32, _vp]),
     "apad_self_attention_fused": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _vp]),
     "apad_hs_geglu": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _vp]),
     "apad_sizeof_hs_out_desc": (C.c_int, []),
@@ -255,7 +265,8 @@ def lib():
                     or h.apad_sizeof_attn_bwd_desc() != C.sizeof(AttnBwdDesc) \
                     or h.apad_sizeof_xattn_desc() != C.sizeof(XattnDesc) or h.apad_sizeof_xrows_desc() != C.sizeof(XrowsDesc) \
                     or h.apad_sizeof_hs_attn_desc() != C.sizeof(HsAttnDesc) or h.apad_sizeof_hs_out_desc() != C.sizeof(HsOutDesc) \
-                    or h.apad_sizeof_scale2_tab() != C.sizeof(Scale2Tab) or h.apad_sizeof_query_weight() != C.sizeof(QueryWeight):
+                    or h.apad_sizeof_scale2_tab() != C.sizeof(Scale2Tab) or h.apad_sizeof_query_weight() != C.sizeof(QueryWeight) \
+                    or h.apad_sizeof_attn_extra() != C.sizeof(AttnExtra):
                 raise RuntimeError("descriptor layout mismatch between include/apadapter_hip.h and _lib.py")
             _lib = h
     return _lib

@@ -44,6 +44,25 @@ struct AttnP {
     QueryW qw;          // apad_attention_qw: the weight map of segment 2, read by the QW instantiations only
 };
 
+// apad_attention_multi: AttnP (the text segment and audio prompt 0) with the extra audio segments beside it.  Taken by the MULTI instantiations
+// only; every other instantiation takes AttnP as before.
+struct AttnMP {
+    AttnP p;
+    AttnExtras xs;
+};
+template <bool MULTI> struct AttnArg { typedef AttnP type; };
+template <> struct AttnArg<true> { typedef AttnMP type; };
+__device__ __forceinline__ const AttnP& attn_base(const AttnP& a) { return a; }
+__device__ __forceinline__ const AttnP& attn_base(const AttnMP& a) { return a.p; }
+
+// audio segment j of a MULTI launch: j = 0 is AttnP's segment 2 (its k2 / vt2, scale2, s2, qw), j >= 1 is xs.x[j - 1]
+struct MultiSeg {
+    const uint8_t* k;
+    const uint8_t* vt;
+    int64_t k_sb, k_sl, vt_sb;
+    int32_t L, Lpad, kvdiv;
+};
+
 constexpr float LOG2E = 1.4426950408889634f;
 constexpr float NEG_BIG = -1.0e30f;
 constexpr int KT = 64;  // keys per LDS tile
@@ -289,8 +308,11 @@ __device__ __forceinline__ void segment(uint8_t* smem, const uint8_t* kbase, int
     }
 }
 
-template <int DT, int D, bool DUAL, bool QW = false>
-__global__ __launch_bounds__(256) void attn_kernel(AttnP p) {
+// MULTI (apad_attention_multi; DUAL, QW unused): the segment-2 block runs once per audio prompt, a runtime loop over 1 + xs.n prompts on ONE set
+// of o2 registers; MULTI = false is the code as it was.
+template <int DT, int D, bool DUAL, bool QW = false, bool MULTI = false>
+__global__ __launch_bounds__(256) void attn_kernel(typename AttnArg<MULTI>::type pp) {
+    const AttnP& p = attn_base(pp);
     using E = ET<DT>;
     using Y = Lay<D>;
     constexpr int KC = D / 16;
@@ -351,7 +373,58 @@ __global__ __launch_bounds__(256) void attn_kernel(AttnP p) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) o[dt][r] *= inv;
 
-    if (DUAL) {
+    if constexpr (MULTI) {
+        // acc = f32(elem(text)), then acc += f32(elem(sw_j * f32(elem(o_j * inv_j)))) prompt by prompt: for one prompt the expression below.
+        // The product o * inv is pinned in its fp32 register before it is rounded to the storage type: that is what the single-prompt code of this
+        // kernel computes (there o also feeds the store of a launch without segment 2, so the product exists in fp32); left free here, the compiler
+        // folds the multiply into the f16 conversion (v_fma_mixlo_f16: one rounding instead of two), a last-bit difference on a few elements in
+        // ten thousand (tests/test_gpu_audio_prompts.py, the long f16 cases)
+#pragma unroll
+        for (int dt = 0; dt < Y::DT_TILES; ++dt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                float t = o[dt][r];
+                asm volatile("" : "+v"(t));
+                o[dt][r] = (float)(typename E::elem)t;
+            }
+        f32x16 o2[Y::DT_TILES];
+        const int nseg = 1 + pp.xs.n;
+#pragma nounroll
+        for (int j = 0; j < nseg; ++j) {
+#pragma unroll
+            for (int dt = 0; dt < Y::DT_TILES; ++dt)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) o2[dt][r] = 0.f;
+            f32x2 osum2 = {0.f, 0.f};
+            float m2 = NEG_BIG;
+            MultiSeg sg;
+            float scale2, wq;
+            if (j == 0) {
+                sg = MultiSeg{p.k2, p.vt2, p.k2_sb, p.k2_sl, p.vt2_sb, p.L2, p.Lpad2, p.kvdiv2};
+                scale2 = scale2_of(p.s2, p.scale2, b);
+                wq = query_weight_rt(p.qw, b, qi);  // (requested before the key loop, used after it)
+            } else {
+                const AttnSeg& x = pp.xs.x[j - 1];
+                sg = MultiSeg{(const uint8_t*)x.k, (const uint8_t*)x.vt, x.k_sb, x.k_sl, x.vt_sb, x.L, x.Lpad, x.kvdiv};
+                scale2 = scale2_of(x.s2, x.scale, b);
+                wq = query_weight_rt(x.qw, b, qi);
+            }
+            const int bk = b / sg.kvdiv;
+            const uint8_t* kbase = sg.k + ((int64_t)bk * sg.k_sb + h * D) * 2;
+            const uint8_t* vbase = sg.vt + ((int64_t)bk * sg.vt_sb + (int64_t)h * D * sg.Lpad) * 2;
+            segment<DT, D>(smem, kbase, sg.k_sl, vbase, sg.L, sg.Lpad, nullptr, p.scale_log2, qf, o2, osum2, m2, tid);
+            const float inv2 = 1.0f / half_sum(osum2[0] + osum2[1]);
+            const float sw = scale2 * wq;
+#pragma unroll
+            for (int dt = 0; dt < Y::DT_TILES; ++dt)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const float a = (float)(typename E::elem)(o2[dt][r] * inv2);
+                    o[dt][r] += (float)(typename E::elem)(sw * a);
+                }
+        }
+    }
+    if (DUAL && !MULTI) {
         if (p.L2 > 0) {
             f32x16 o2[Y::DT_TILES];
 #pragma unroll
@@ -1245,8 +1318,9 @@ __device__ __forceinline__ void short_segment(const uint8_t* kbase, int64_t k_sl
     }
 }
 
-template <int DT, int D, bool DUAL, bool QW = false>
-__global__ __launch_bounds__(256) void attn_short_kernel(AttnP p) {
+template <int DT, int D, bool DUAL, bool QW = false, bool MULTI = false>  // (MULTI: as attn_kernel)
+__global__ __launch_bounds__(256) void attn_short_kernel(typename AttnArg<MULTI>::type pp) {
+    const AttnP& p = attn_base(pp);
     // (a one-workgroup-per-32-queries-x-all-heads shape, meant to consume whole 2*C-byte rows while their lines are hot,
     //  measured slower: 38 vs 28 us at the 1000-token level -- the heads serialise inside a wave)
     using E = ET<DT>;
@@ -1282,7 +1356,49 @@ __global__ __launch_bounds__(256) void attn_short_kernel(AttnP p) {
     for (int dt = 0; dt < Y::DT_TILES; ++dt)
 #pragma unroll
         for (int r = 0; r < 16; ++r) o[dt][r] *= inv;
-    if (DUAL) {
+    if constexpr (MULTI) {
+        // (no pin on the product here, unlike attn_kernel: in the single-prompt code of THIS kernel o * inv has no other reader than its conversion,
+        //  and the compiler folds the two -- for f16 -- exactly as it does below)
+#pragma unroll
+        for (int dt = 0; dt < Y::DT_TILES; ++dt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) o[dt][r] = (float)(typename E::elem)o[dt][r];
+        f32x16 o2[Y::DT_TILES];
+        const int nseg = 1 + pp.xs.n;
+#pragma nounroll
+        for (int j = 0; j < nseg; ++j) {
+#pragma unroll
+            for (int dt = 0; dt < Y::DT_TILES; ++dt)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) o2[dt][r] = 0.f;
+            float inv2 = 1.f;
+            MultiSeg sg;
+            float scale2, wq;
+            if (j == 0) {
+                sg = MultiSeg{p.k2, p.vt2, p.k2_sb, p.k2_sl, p.vt2_sb, p.L2, p.Lpad2, p.kvdiv2};
+                scale2 = scale2_of(p.s2, p.scale2, b);
+                wq = query_weight_rt(p.qw, b, qi);  // (requested before the key loop, used after it)
+            } else {
+                const AttnSeg& x = pp.xs.x[j - 1];
+                sg = MultiSeg{(const uint8_t*)x.k, (const uint8_t*)x.vt, x.k_sb, x.k_sl, x.vt_sb, x.L, x.Lpad, x.kvdiv};
+                scale2 = scale2_of(x.s2, x.scale, b);
+                wq = query_weight_rt(x.qw, b, qi);
+            }
+            const int bk = b / sg.kvdiv;
+            const uint8_t* kbase = sg.k + ((int64_t)bk * sg.k_sb + h * D) * 2;
+            const uint8_t* vbase = sg.vt + ((int64_t)bk * sg.vt_sb + (int64_t)h * D * sg.Lpad) * 2;
+            short_segment<DT, D>(kbase, sg.k_sl, vbase, sg.L, sg.Lpad, nullptr, p.scale_log2, qf, o2, inv2, l31, half);
+            const float sw = scale2 * wq;
+#pragma unroll
+            for (int dt = 0; dt < Y::DT_TILES; ++dt)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const float a = (float)(typename E::elem)(o2[dt][r] * inv2);
+                    o[dt][r] += (float)(typename E::elem)(sw * a);
+                }
+        }
+    }
+    if (DUAL && !MULTI) {
         f32x16 o2[Y::DT_TILES];
 #pragma unroll
         for (int dt = 0; dt < Y::DT_TILES; ++dt)
@@ -1382,6 +1498,35 @@ template <int DT, int D> int launch_d(const AttnP& p, bool dual, dim3 grid, hipS
     else
         hipLaunchKernelGGL((attn_kernel<DT, D, false>), grid, dim3(256), 0, s, p);
     return apad_check_launch("apad_attention");
+}
+
+// apad_attention_multi: the short form only when the text segment AND every audio segment of the launch has at most 64 keys, else the long form
+// for every segment
+template <int DT, int D> int launch_multi_d(const AttnMP& mp, dim3 grid, hipStream_t s) {
+    const AttnP& p = mp.p;
+    bool all_short = p.L <= 64 && p.L2 <= 64;
+    for (int j = 0; j < mp.xs.n; ++j) all_short = all_short && mp.xs.x[j].L <= 64;
+    if (all_short) {
+        dim3 g2((unsigned)((p.N + 127) / 128), (unsigned)(p.B * p.H));
+        hipLaunchKernelGGL((attn_short_kernel<DT, D, true, false, true>), g2, dim3(256), 0, s, mp);
+    } else {
+        hipLaunchKernelGGL((attn_kernel<DT, D, true, false, true>), grid, dim3(256), 0, s, mp);
+    }
+    return apad_check_launch("apad_attention_multi");
+}
+
+template <int DT> int launch_multi_dt(const AttnMP& mp, int D, dim3 grid, hipStream_t s) {
+    switch (D) {
+        case 16: return launch_multi_d<DT, 16>(mp, grid, s);
+        case 32: return launch_multi_d<DT, 32>(mp, grid, s);
+        case 48: return launch_multi_d<DT, 48>(mp, grid, s);
+        case 64: return launch_multi_d<DT, 64>(mp, grid, s);
+        case 80: return launch_multi_d<DT, 80>(mp, grid, s);
+        case 96: return launch_multi_d<DT, 96>(mp, grid, s);
+        case 128: return launch_multi_d<DT, 128>(mp, grid, s);
+    }
+    apad_set_error("apad_attention_multi: head dim %d not supported (16,32,48,64,80,96,128)", D);
+    return -1;
 }
 
 template <int DT> int launch_dt(const AttnP& p, int D, bool dual, dim3 grid, hipStream_t s) {
@@ -1789,14 +1934,18 @@ extern "C" int apad_rows_pack_kv(const void* k, const void* vt, void* out, int32
 }
 
 // apad_attention (t unused), apad_attention_tab (has_tab) and apad_attention_qw (has_qw; its table is optional) share this launch path
-static int attention_launch(const apad_attn_desc* d, const apad_scale2_tab* t, bool has_tab, const apad_query_weight* w, bool has_qw, void* stream) {
-    const char* const who = has_qw ? "apad_attention_qw" : has_tab ? "apad_attention_tab" : "apad_attention";
+// xs != nullptr with xs->n > 0: apad_attention_multi's launch of the same descriptor (its own checks are done by then)
+static int attention_launch(const apad_attn_desc* d, const apad_scale2_tab* t, bool has_tab, const apad_query_weight* w, bool has_qw, void* stream,
+                            const AttnExtras* xs = nullptr) {
+    const bool multi = xs != nullptr && xs->n > 0;
+    const char* const who = multi ? "apad_attention_multi" : has_qw ? "apad_attention_qw" : has_tab ? "apad_attention_tab" : "apad_attention";
     APAD_CHECK(d != nullptr, "%s: null descriptor", who);
     Scale2Tab s2;
     if (apad_scale2_tab_arg(who, t, has_tab, d->L2, &s2) != 0) return -1;
     QueryW qw;
     if (apad_query_weight_arg(who, w, has_qw, d->N, d->L2, &qw) != 0) return -1;
-    if (d->dtype == APAD_F32 || d->dtype == APAD_F32_BF16X3) return apad_f32_attention(d, s2, qw, (hipStream_t)stream);  // fp32 precision modes (f32_ops.hip)
+    if (d->dtype == APAD_F32 || d->dtype == APAD_F32_BF16X3)  // fp32 precision modes (f32_ops.hip)
+        return multi ? apad_f32_attention_multi(d, s2, qw, *xs, (hipStream_t)stream) : apad_f32_attention(d, s2, qw, (hipStream_t)stream);
     APAD_CHECK(d->dtype == APAD_BF16 || d->dtype == APAD_F16, "apad_attention: dtype %d not supported", d->dtype);
     APAD_CHECK(d->q && d->k && d->vt && d->out, "apad_attention: null operand");
     APAD_CHECK(d->B > 0 && d->N > 0 && d->H > 0 && d->L > 0, "apad_attention: empty problem B=%d N=%d H=%d L=%d", d->B, d->N,
@@ -1833,6 +1982,12 @@ static int attention_launch(const apad_attn_desc* d, const apad_scale2_tab* t, b
     p.qw = qw;
     dim3 grid((unsigned)(((d->N + 127) / 128) * (((d->H * d->B) + 7) / 8 * 8)));
     hipStream_t s = (hipStream_t)stream;
+    if (multi) {
+        AttnMP mp;
+        mp.p = p;
+        mp.xs = *xs;
+        return d->dtype == APAD_BF16 ? launch_multi_dt<APAD_BF16>(mp, d->D, grid, s) : launch_multi_dt<APAD_F16>(mp, d->D, grid, s);
+    }
     return d->dtype == APAD_BF16 ? launch_dt<APAD_BF16>(p, d->D, dual, grid, s) : launch_dt<APAD_F16>(p, d->D, dual, grid, s);
 }
 
@@ -1842,6 +1997,24 @@ extern "C" int apad_attention_tab(const apad_attn_desc* d, const apad_scale2_tab
 }
 extern "C" int apad_attention_qw(const apad_attn_desc* d, const apad_scale2_tab* t, const apad_query_weight* w, void* stream) {
     return attention_launch(d, t, t != nullptr, w, true, stream);
+}
+
+extern "C" int apad_attention_multi(const apad_attn_desc* d, const apad_scale2_tab* t, const apad_query_weight* w, const apad_attn_extra* extra,
+                                    int32_t n_extra, void* stream) {
+    const char* const who = "apad_attention_multi";
+    APAD_CHECK(d != nullptr, "%s: null descriptor", who);
+    APAD_CHECK(d->L2 > 0, "%s: needs audio prompt 0 as the descriptor's second segment (L2 == 0)", who);
+    APAD_CHECK(d->lse == nullptr, "%s: lse is only defined for a single softmax segment", who);
+    const bool f32 = d->dtype == APAD_F32 || d->dtype == APAD_F32_BF16X3;
+    AttnExtras xs;
+    if (apad_attn_extras_arg(who, extra, n_extra, d->N, f32 ? 4 : 2, &xs) != 0) return -1;
+    {   // t and w are checked under this entry point's name whatever the launch below is
+        Scale2Tab s2;
+        QueryW qw;
+        if (apad_scale2_tab_arg(who, t, t != nullptr, d->L2, &s2) != 0 || apad_query_weight_arg(who, w, w != nullptr, d->N, d->L2, &qw) != 0) return -1;
+    }
+    // n_extra == 0: the apad_attention_qw / _tab / plain launch of the same d, t and w
+    return attention_launch(d, t, t != nullptr, w, w != nullptr, stream, &xs);
 }
 
 extern "C" int apad_self_attention_fused(const void* x, const void* w_packed, const float* colsum_bias, void* out, int32_t B, int32_t N, int32_t C, int32_t heads,

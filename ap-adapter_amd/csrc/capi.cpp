@@ -112,6 +112,37 @@ int apad_query_weight_arg(const char* who, const apad_query_weight* w, bool has_
     return 0;
 }
 
+extern "C" int apad_sizeof_attn_extra(void) { return (int)sizeof(apad_attn_extra); }
+
+int apad_attn_extras_arg(const char* who, const apad_attn_extra* extra, int n_extra, int N, int elem_bytes, AttnExtras* out) {
+    out->n = 0; out->pad = 0;
+    APAD_CHECK(n_extra >= 0 && n_extra <= APAD_MAX_EXTRA, "%s: n_extra %d outside [0, %d]", who, n_extra, APAD_MAX_EXTRA);
+    APAD_CHECK(n_extra == 0 || extra != nullptr, "%s: n_extra = %d with a null extra array", who, n_extra);
+    const int64_t per16 = 16 / elem_bytes;  // elements per 16 bytes
+    for (int j = 0; j < APAD_MAX_EXTRA; ++j) {
+        AttnSeg& x = out->x[j];
+        x.k = nullptr; x.vt = nullptr; x.k_sb = x.k_sl = x.vt_sb = 0; x.L = 0; x.Lpad = 0; x.kvdiv = 1; x.pad = 0; x.scale = 0.f; x.padf = 0.f;
+        apad_scale2_tab_arg(who, nullptr, false, 1, &x.s2);
+        apad_query_weight_arg(who, nullptr, false, N, 1, &x.qw);
+        if (j >= n_extra) continue;
+        const apad_attn_extra& e = extra[j];
+        APAD_CHECK(e.k != nullptr && e.vt != nullptr, "%s: extra[%d] needs k and vt", who, j);
+        APAD_CHECK(e.L > 0, "%s: extra[%d] needs L > 0 (L=%d)", who, j, e.L);
+        APAD_CHECK(e.Lpad >= e.L && e.Lpad % 32 == 0, "%s: extra[%d] Lpad must be >= L and a multiple of 32 (L=%d Lpad=%d)", who, j, e.L, e.Lpad);
+        APAD_CHECK(e.kv_batch_div > 0, "%s: extra[%d] kv_batch_div must be >= 1", who, j);
+        APAD_CHECK((reinterpret_cast<uintptr_t>(e.k) & 15) == 0 && (reinterpret_cast<uintptr_t>(e.vt) & 15) == 0,
+                   "%s: extra[%d] pointers must be 16-byte aligned", who, j);
+        APAD_CHECK(e.k_stride_l % per16 == 0 && e.k_stride_b % per16 == 0 && e.vt_stride_b % per16 == 0,
+                   "%s: extra[%d] strides must keep 16-byte alignment", who, j);
+        if (apad_scale2_tab_arg(who, &e.tab, e.tab.table != nullptr, e.L, &x.s2) != 0) return -1;
+        if (apad_query_weight_arg(who, &e.qw, e.qw.w != nullptr, N, e.L, &x.qw) != 0) return -1;
+        x.k = e.k; x.vt = e.vt; x.k_sb = e.k_stride_b; x.k_sl = e.k_stride_l; x.vt_sb = e.vt_stride_b;
+        x.L = e.L; x.Lpad = e.Lpad; x.kvdiv = e.kv_batch_div; x.scale = e.scale;
+    }
+    out->n = n_extra;
+    return 0;
+}
+
 extern "C" int apad_sizeof_rp_desc(void) { return (int)sizeof(apad_rp_desc); }
 extern "C" int apad_echo_rp_desc(const apad_rp_desc* d, double* out, int cap) {
     int n = 0;

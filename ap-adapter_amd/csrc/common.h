@@ -181,6 +181,31 @@ template <bool QW> __device__ __forceinline__ float weighted_scale2(float s, flo
     else return s * w;
 }
 
+// apad_attention_multi: one more audio segment (apad_attn_extra) as the multi-prompt kernels carry it, and the block of up to three of them that
+// travels beside AttnP / A32P.  Strides in elements of the launch's type.  The kernels index x[] with a runtime j: the block lives in the kernel
+// argument segment, so an entry is a handful of scalar loads.
+struct AttnSeg {
+    const void* k;
+    const void* vt;
+    int64_t k_sb, k_sl, vt_sb;
+    int32_t L, Lpad, kvdiv, pad;
+    float scale, padf;  // read when s2.table == nullptr
+    Scale2Tab s2;
+    QueryW qw;          // w == nullptr: no map
+};
+constexpr int APAD_MAX_EXTRA = 3;
+struct AttnExtras {
+    AttnSeg x[APAD_MAX_EXTRA];
+    int32_t n, pad;
+};
+// The map entry of a multi-prompt launch, where a prompt has a map or not at run time: no map reads as 1.0f, and s * 1.0f is s bit for bit, so
+// both sides are the expressions of query_weight<> / weighted_scale2<>.
+__device__ __forceinline__ float query_weight_rt(const QueryW& q, int b, int n) {
+    if (q.w == nullptr) return 1.0f;  // (wave-uniform)
+    const float* const row = q.w + (int64_t)(__builtin_amdgcn_readfirstlane(b) % q.cols) * q.ld;
+    return row[(uint32_t)n];
+}
+
 // host-side error plumbing (capi.cpp)
 void apad_set_error(const char* fmt, ...);
 #define APAD_CHECK(cond, ...)            \
@@ -197,6 +222,9 @@ int apad_scale2_tab_arg(const char* who, const apad_scale2_tab* t, bool has_tab,
 // The map of an apad_*_qw entry point `who`, checked (a null struct or map, cols <= 0, ld < N, a map off 4 bytes, or a single-segment call: an
 // error naming `who`, -1) and copied into the kernels' form.  has_qw false (every other entry point): *out = no map, 0.
 int apad_query_weight_arg(const char* who, const apad_query_weight* w, bool has_qw, int N, int L2, QueryW* out);
+// The extra segments of apad_attention_multi (`who`), checked (what include/apadapter_hip.h lists: an error naming `who`, -1) and copied into
+// the kernels' form; entries at and past n_extra are zeroed.  N: the launch's queries (a map's row stride); elem_bytes: 2 or 4.
+int apad_attn_extras_arg(const char* who, const apad_attn_extra* extra, int n_extra, int N, int elem_bytes, AttnExtras* out);
 // The dtype ladder of the 256-thread element-wise launches, for the `dtype` (APAD_BF16 / APAD_F16 / APAD_F32, checked by the caller) and the
 // stream `s` of the calling scope: kern<DT> (LAUNCH_DT), kern<DT, F> (LAUNCH_DT_F), kern<DT, vec ? 8 : 1> (LAUNCH_DT_V)
 #define LAUNCH_DT(kern, grid, ...)                                                                                \

@@ -327,6 +327,12 @@ struct A32P {
     QueryW qw;     // apad_attention_qw: the weight map of segment 2, read by the QW instantiations only
 };
 
+// apad_attention_multi: A32P with the extra audio segments beside it (the MULTI instantiations' argument)
+struct A32MP {
+    A32P p;
+    AttnExtras xs;
+};
+
 constexpr float LOG2E_F = 1.4426950408889634f;
 constexpr float NEG_BIG_F = -1.0e30f;
 
@@ -443,7 +449,9 @@ __device__ __forceinline__ void segment32(const float* kbase, int64_t k_sl, cons
     den = half_sum(sum);
 }
 
-template <int D, bool X3, bool QW> __device__ __forceinline__ void attn_f32_body(const A32P& p) {
+// xs != nullptr (apad_attention_multi; QW unused): the segment-2 block runs once per audio prompt, a runtime loop over 1 + xs->n prompts on one
+// o2; xs == nullptr is the code as it was
+template <int D, bool X3, bool QW, bool MULTI = false> __device__ __forceinline__ void attn_f32_body(const A32P& p, const AttnExtras* xs = nullptr) {
     constexpr int DT_TILES = (D + 31) / 32;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int half = lane >> 5, l31 = lane & 31;
@@ -483,7 +491,35 @@ template <int D, bool X3, bool QW> __device__ __forceinline__ void attn_f32_body
     for (int dt = 0; dt < DT_TILES; ++dt)
 #pragma unroll
         for (int r = 0; r < 16; ++r) o[dt][r] *= inv;
-    if (p.L2 > 0) {
+    if constexpr (MULTI) {
+        f32x16 o2[DT_TILES];
+        const int nseg = 1 + xs->n;
+        for (int j = 0; j < nseg; ++j) {
+            float den2, m2, scale2, wq;
+            const float *k2, *vt2;
+            int64_t k2_sb, k2_sl, vt2_sb;
+            int L2, Lpad2, kvdiv2;
+            if (j == 0) {
+                k2 = p.k2; vt2 = p.vt2; k2_sb = p.k2_sb; k2_sl = p.k2_sl; vt2_sb = p.vt2_sb; L2 = p.L2; Lpad2 = p.Lpad2; kvdiv2 = p.kvdiv2;
+                scale2 = scale2_of(p.s2, p.scale2, b);
+                wq = query_weight_rt(p.qw, b, qi);  // (requested before the key loop, used after it)
+            } else {
+                const AttnSeg& x = xs->x[j - 1];
+                k2 = (const float*)x.k; vt2 = (const float*)x.vt; k2_sb = x.k_sb; k2_sl = x.k_sl; vt2_sb = x.vt_sb; L2 = x.L; Lpad2 = x.Lpad; kvdiv2 = x.kvdiv;
+                scale2 = scale2_of(x.s2, x.scale, b);
+                wq = query_weight_rt(x.qw, b, qi);
+            }
+            const int bk = b / kvdiv2;
+            segment32<D, X3>(k2 + (int64_t)bk * k2_sb + h * D, k2_sl, vt2 + (int64_t)bk * vt2_sb + (int64_t)h * D * Lpad2, L2, Lpad2, nullptr,
+                         p.scale_log2, qf, o2, den2, m2, l31, half);
+            const float inv2 = 1.0f / den2;
+            const float sw = scale2 * wq;
+#pragma unroll
+            for (int dt = 0; dt < DT_TILES; ++dt)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) o[dt][r] += sw * (o2[dt][r] * inv2);
+        }
+    } else if (p.L2 > 0) {
         f32x16 o2[DT_TILES];
         float den2, m2;
         const int bk = b / p.kvdiv2;
@@ -518,8 +554,24 @@ template <int D> __global__ __launch_bounds__(256) void attn_f32x3_kernel(A32P p
 template <int D> __global__ __launch_bounds__(256) void attn_f32_qw_kernel(A32P p) { attn_f32_body<D, false, true>(p); }
 template <int D> __global__ __launch_bounds__(256) void attn_f32x3_qw_kernel(A32P p) { attn_f32_body<D, true, true>(p); }
 
-template <int D> int attn_launch(const A32P& p, bool x3, hipStream_t s) {
+// apad_attention_multi: up to four audio prompts, each with a scale and an optional map of its own
+template <int D> __global__ __launch_bounds__(256) void attn_f32_multi_kernel(A32MP mp) { attn_f32_body<D, false, false, true>(mp.p, &mp.xs); }
+template <int D> __global__ __launch_bounds__(256) void attn_f32x3_multi_kernel(A32MP mp) { attn_f32_body<D, true, false, true>(mp.p, &mp.xs); }
+
+template <int D> int attn_launch(const A32P& p, bool x3, hipStream_t s, const AttnExtras* xs = nullptr) {
     dim3 grid((unsigned)((p.N + 127) / 128), (unsigned)(p.B * p.H));
+    if (xs != nullptr) {
+        A32MP mp;
+        mp.p = p;
+        mp.xs = *xs;
+        if (x3) {
+            hipLaunchKernelGGL((attn_f32x3_multi_kernel<D>), grid, dim3(256), 0, s, mp);
+            ++g_f32x3_launches;
+        } else {
+            hipLaunchKernelGGL((attn_f32_multi_kernel<D>), grid, dim3(256), 0, s, mp);
+        }
+        return apad_check_launch("apad_attention_multi(f32)");
+    }
     if (p.qw.w != nullptr) {  // apad_attention_qw (a second segment: checked by the caller)
         if (x3) {
             hipLaunchKernelGGL((attn_f32x3_qw_kernel<D>), grid, dim3(256), 0, s, p);
@@ -855,7 +907,12 @@ int apad_f32_gemm(const apad_gemm_desc* d, hipStream_t s) {
     return apad_check_launch("apad_gemm(f32)");
 }
 
-int apad_f32_attention(const apad_attn_desc* d, const Scale2Tab& s2, const QueryW& qw, hipStream_t s) {
+static int f32_attention(const apad_attn_desc* d, const Scale2Tab& s2, const QueryW& qw, const AttnExtras* xs, hipStream_t s);
+int apad_f32_attention(const apad_attn_desc* d, const Scale2Tab& s2, const QueryW& qw, hipStream_t s) { return f32_attention(d, s2, qw, nullptr, s); }
+int apad_f32_attention_multi(const apad_attn_desc* d, const Scale2Tab& s2, const QueryW& qw, const AttnExtras& xs, hipStream_t s) {
+    return f32_attention(d, s2, qw, &xs, s);
+}
+static int f32_attention(const apad_attn_desc* d, const Scale2Tab& s2, const QueryW& qw, const AttnExtras* xs, hipStream_t s) {
     APAD_CHECK(d->q && d->k && d->vt && d->out, "apad_attention(f32): null operand");
     APAD_CHECK(d->B > 0 && d->N > 0 && d->H > 0 && d->L > 0, "apad_attention(f32): empty problem B=%d N=%d H=%d L=%d", d->B, d->N, d->H,
                d->L);
@@ -889,13 +946,13 @@ int apad_f32_attention(const apad_attn_desc* d, const Scale2Tab& s2, const Query
     p.qw = qw;
     const bool x3 = d->dtype == APAD_F32_BF16X3;
     switch (d->D) {
-        case 16: return attn_launch<16>(p, x3, s);
-        case 32: return attn_launch<32>(p, x3, s);
-        case 48: return attn_launch<48>(p, x3, s);
-        case 64: return attn_launch<64>(p, x3, s);
-        case 80: return attn_launch<80>(p, x3, s);
-        case 96: return attn_launch<96>(p, x3, s);
-        case 128: return attn_launch<128>(p, x3, s);
+        case 16: return attn_launch<16>(p, x3, s, xs);
+        case 32: return attn_launch<32>(p, x3, s, xs);
+        case 48: return attn_launch<48>(p, x3, s, xs);
+        case 64: return attn_launch<64>(p, x3, s, xs);
+        case 80: return attn_launch<80>(p, x3, s, xs);
+        case 96: return attn_launch<96>(p, x3, s, xs);
+        case 128: return attn_launch<128>(p, x3, s, xs);
     }
     apad_set_error("apad_attention(f32): head dim %d not supported (16,32,48,64,80,96,128)", d->D);
     return -1;

@@ -48,32 +48,28 @@ sample b blends its audio segment with scale2 * w[b % cols][n] (include/apadapte
 ld >= N] on the operands' device; entries at or past N of a row are not read; cols: 1 or the number of clips."""
 
 
-def _launch_scale2(name, d, scale2, dev, query_weight=None):
-    """the launch of a two-segment attention descriptor: a float ``scale2`` through apad_<name>, a Scale2Binding (or a plain (table, step_ptr,
-    cols) tuple) through apad_<name>_tab; with a QueryWeight (or a plain (w, cols) tuple) either of them through apad_<name>_qw.  Device,
-    dtype, contiguity and shape are checked here; what the values decide (rows, cols, the row stride, a missing table or map, a
-    single-segment call) is the entry point's check."""
-    lib = L.lib()
-    qw = None
-    if query_weight is not None:
-        w, qcols = query_weight
-        fn = name + ".query_weight"
-        qw = L.QueryWeight()
-        if w is not None:
-            _req(w, fn + " w", torch.float32)
-            if w.dim() != 2 or not w.is_contiguous() or w.device != dev or w.shape[0] < int(qcols):
-                raise RuntimeError(f"{fn}: expected a contiguous fp32 [>= cols = {int(qcols)}, >= N] map on {dev}, got {tuple(w.shape)} on {w.device}")
-            qw.w, qw.ld = w.data_ptr(), w.shape[1]
-        qw.cols = int(qcols)
-    if not isinstance(scale2, tuple):
-        d.scale2 = float(scale2)
-        if qw is not None:
-            L.check(getattr(lib, "apad_" + name + "_qw")(C.byref(d), None, C.byref(qw), _stream()), "apad_" + name + "_qw")
-            return
-        L.check(getattr(lib, "apad_" + name)(C.byref(d), _stream()), "apad_" + name)
-        return
+AudioSegment = collections.namedtuple("AudioSegment", "k vt L scale2 query_weight kv_batch_div", defaults=(0.0, None, 1))
+AudioSegment.__doc__ = """One more audio prompt of ``attention(..., extra=[...])`` (include/apadapter_hip.h, apad_attn_extra): k [Bk, L, C] and vt [Bk, heads,
+d, Lpad] as the op's k2 / vt2, L keys, its own weight ``scale2`` (a float or a Scale2Binding) and its own ``query_weight`` (None or a
+QueryWeight); sample b reads K / V of sample b // kv_batch_div."""
+
+
+def _query_weight_struct(fn, query_weight, dev):
+    """a QueryWeight (or a plain (w, cols) tuple) as the C ABI's struct; device, dtype, contiguity and shape are checked here"""
+    w, qcols = query_weight
+    qw = L.QueryWeight()
+    if w is not None:
+        _req(w, fn + " w", torch.float32)
+        if w.dim() != 2 or not w.is_contiguous() or w.device != dev or w.shape[0] < int(qcols):
+            raise RuntimeError(f"{fn}: expected a contiguous fp32 [>= cols = {int(qcols)}, >= N] map on {dev}, got {tuple(w.shape)} on {w.device}")
+        qw.w, qw.ld = w.data_ptr(), w.shape[1]
+    qw.cols = int(qcols)
+    return qw
+
+
+def _scale2_tab_struct(fn, scale2, dev):
+    """a Scale2Binding (or a plain (table, step_ptr, cols) tuple) as the C ABI's struct, checked like the map above"""
     table, step_ptr, cols = scale2
-    fn = name + ".scale2"
     t = L.Scale2Tab()
     if table is not None:
         _req(table, fn + " table", torch.float32)
@@ -86,11 +82,84 @@ def _launch_scale2(name, d, scale2, dev, query_weight=None):
             raise RuntimeError(f"{fn}: step_ptr must be ONE int32 on {dev}, got {tuple(step_ptr.shape)} on {step_ptr.device}")
         t.step = step_ptr.data_ptr()
     t.cols = int(cols)
+    return t
+
+
+def _launch_scale2(name, d, scale2, dev, query_weight=None):
+    """the launch of a two-segment attention descriptor: a float ``scale2`` through apad_<name>, a Scale2Binding (or a plain (table, step_ptr,
+    cols) tuple) through apad_<name>_tab; with a QueryWeight (or a plain (w, cols) tuple) either of them through apad_<name>_qw.  Device,
+    dtype, contiguity and shape are checked here; what the values decide (rows, cols, the row stride, a missing table or map, a
+    single-segment call) is the entry point's check."""
+    lib = L.lib()
+    qw = None
+    if query_weight is not None:
+        qw = _query_weight_struct(name + ".query_weight", query_weight, dev)
+    if not isinstance(scale2, tuple):
+        d.scale2 = float(scale2)
+        if qw is not None:
+            L.check(getattr(lib, "apad_" + name + "_qw")(C.byref(d), None, C.byref(qw), _stream()), "apad_" + name + "_qw")
+            return
+        L.check(getattr(lib, "apad_" + name)(C.byref(d), _stream()), "apad_" + name)
+        return
+    t = _scale2_tab_struct(name + ".scale2", scale2, dev)
     d.scale2 = 0.0
     if qw is not None:
         L.check(getattr(lib, "apad_" + name + "_qw")(C.byref(d), C.byref(t), C.byref(qw), _stream()), "apad_" + name + "_qw")
         return
     L.check(getattr(lib, "apad_" + name + "_tab")(C.byref(d), C.byref(t), _stream()), "apad_" + name + "_tab")
+
+
+def _launch_attention_multi(d, scale2, dev, query_weight, extra, q, heads):
+    """apad_attention_multi: the descriptor's two segments (audio prompt 0 under ``scale2`` / ``query_weight``) and ``extra`` more audio
+    prompts.  Device, dtype, contiguity, shape and the list's length are checked here, the values by the entry point."""
+    extra = list(extra)
+    if len(extra) > 3:
+        raise RuntimeError(f"apad_attention_multi: attention.extra: at most 3 extra audio segments (four prompts), got {len(extra)}")
+    B, N, Cc = q.shape
+    d_head = Cc // heads
+    xs = (L.AttnExtra * max(len(extra), 1))()
+    keep = []
+    for j, seg in enumerate(extra):
+        fn = f"attention.extra[{j}]"
+        if not isinstance(seg, AudioSegment):
+            raise RuntimeError(f"{fn}: expected an ops.AudioSegment, got {type(seg).__name__}")
+        if seg.k is None or seg.vt is None:
+            raise RuntimeError(f"apad_attention_multi: {fn} needs k and vt")
+        _req(seg.k, fn + " k", q.dtype)
+        _req(seg.vt, fn + " vt", q.dtype)
+        if seg.k.device != dev or seg.vt.device != dev:
+            raise RuntimeError(f"{fn}: k and vt must be on {dev}, got {seg.k.device} and {seg.vt.device}")
+        if seg.k.dim() != 3 or seg.k.shape[2] != Cc or seg.k.shape[1] < int(seg.L):
+            raise RuntimeError(f"{fn}: expected k [Bk, >= L = {int(seg.L)}, {Cc}], got {tuple(seg.k.shape)}")
+        if seg.vt.dim() != 4 or not seg.vt.is_contiguous() or tuple(seg.vt.shape[1:3]) != (heads, d_head) or seg.vt.shape[0] != seg.k.shape[0]:
+            raise RuntimeError(f"{fn}: expected a contiguous vt [{seg.k.shape[0]}, {heads}, {d_head}, Lpad], got {tuple(seg.vt.shape)}")
+        if int(seg.kv_batch_div) >= 1 and seg.k.shape[0] * int(seg.kv_batch_div) < B:
+            raise RuntimeError(f"{fn}: {seg.k.shape[0]} K/V samples x kv_batch_div {int(seg.kv_batch_div)} do not cover the batch of {B}")
+        x = xs[j]
+        x.k, x.vt = seg.k.data_ptr(), seg.vt.data_ptr()
+        x.k_stride_b, x.k_stride_l, x.vt_stride_b = seg.k.stride(0), seg.k.stride(1), seg.vt.stride(0)
+        x.L, x.Lpad, x.kv_batch_div = int(seg.L), seg.vt.shape[-1], int(seg.kv_batch_div)
+        if isinstance(seg.scale2, tuple):
+            x.tab = _scale2_tab_struct(fn + ".scale2", seg.scale2, dev)
+            if not x.tab.table:
+                raise RuntimeError(f"apad_attention_multi: {fn}: null scale2 table")
+        else:
+            x.scale = float(seg.scale2)
+        if seg.query_weight is not None:
+            x.qw = _query_weight_struct(fn + ".query_weight", seg.query_weight, dev)
+            if not x.qw.w:
+                raise RuntimeError(f"apad_attention_multi: {fn}: null query weight map")
+        keep.append(seg)
+    t = qw = None
+    if isinstance(scale2, tuple):
+        t = _scale2_tab_struct("attention.scale2", scale2, dev)
+        d.scale2 = 0.0
+    else:
+        d.scale2 = float(scale2)
+    if query_weight is not None:
+        qw = _query_weight_struct("attention.query_weight", query_weight, dev)
+    L.check(L.lib().apad_attention_multi(C.byref(d), None if t is None else C.byref(t), None if qw is None else C.byref(qw), xs, len(extra),
+                                         _stream()), "apad_attention_multi")
 
 
 def round_up(x, m):
@@ -1231,12 +1300,14 @@ LOG2E = 1.4426950408889634
 
 
 def attention(q, k, vt, Lk, heads, key_bias=None, k2=None, vt2=None, L2=0, scale2=0.0, kv_batch_div=1,
-              kv2_batch_div=1, out=None, q_prescaled=False, query_weight=None):
+              kv2_batch_div=1, out=None, q_prescaled=False, query_weight=None, extra=None):
     """q [B,N,C]; k [Bk,Lk,C]; vt [Bk,heads,d,Lpad]; optional second (audio) segment k2/vt2 with its own softmax,
     blended as seg1 + scale2*seg2.  key_bias: fp32 [B,Lk] additive.  q_prescaled: q was projected with to_q rows already
     multiplied by log2(e) / sqrt(d) (processors._qkv_weight), i.e. it is the base-2 exponent operand.  scale2: a float, or a Scale2Binding
     (table, step_ptr, cols): sample b uses table[min(*step_ptr, rows - 1)][b % cols] (apad_attention_tab).  query_weight: None, or a
-    QueryWeight (w, cols): query n of sample b uses scale2 * w[b % cols][n] (apad_attention_qw)."""
+    QueryWeight (w, cols): query n of sample b uses scale2 * w[b % cols][n] (apad_attention_qw).  extra: None, or a list of up to three
+    AudioSegment -- more audio prompts, each its own softmax over its own K / V with its own scale2 and query_weight, added in list order
+    behind k2 / vt2 (apad_attention_multi; an empty list is the launch without it)."""
     _req(q, "attention.q")
     _req(k, "attention.k", q.dtype)
     _req(vt, "attention.vt", q.dtype)
@@ -1259,6 +1330,9 @@ def attention(q, k, vt, Lk, heads, key_bias=None, k2=None, vt2=None, L2=0, scale
         d.k2, d.vt2 = k2.data_ptr(), vt2.data_ptr()
         d.k2_stride_b, d.k2_stride_l, d.vt2_stride_b = k2.stride(0), k2.stride(1), vt2.stride(0)
         d.L2, d.Lpad2 = L2, vt2.shape[-1]
+    if extra is not None:
+        _launch_attention_multi(d, scale2, q.device, query_weight, extra, q, heads)
+        return out
     _launch_scale2("attention", d, scale2, q.device, query_weight)
     return out
 

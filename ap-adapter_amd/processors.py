@@ -30,7 +30,7 @@ USE_FUSED_XATTN = True
 USE_XATTN_ROWS = True  # the 384-wide level's kernel alone (follows USE_FUSED_XATTN)
 
 
-def route(kind, attn, hidden_states, residual=None, ln=None, L1=0, L2=0, masked=False, same_batch=True, query_weighted=False):
+def route(kind, attn, hidden_states, residual=None, ln=None, L1=0, L2=0, masked=False, same_batch=True, query_weighted=False, multi=False):
     """Which kernels run this attention sub-layer.  Decided ONCE per call, before the hoist, from shapes, dtypes, strides and module attributes
     only (CPU tensors do; nothing is launched); both the packing of the hoisted key / value sets and the dispatch read the answer.
 
@@ -38,7 +38,8 @@ def route(kind, attn, hidden_states, residual=None, ln=None, L1=0, L2=0, masked=
     fuses (the block entry passes ``residual is hidden_states`` and its LayerNorm); ``L1`` / ``L2``: key counts of the one or two segments;
     ``masked``: a key bias will be passed; ``same_batch``: the condition has the batch of the hidden states; ``query_weighted``: the audio segment
     is weighed per query token (a bound ap_mask map): apad_fused_cross_attention has no such form, so what would be "fused" is "chain" -- every
-    other answer is unchanged.
+    other answer is unchanged; ``multi``: the audio tokens are those of two or more prompts (bound audio prompts): the fused, rows and hs kernels
+    have no such form, so every "decoupled" answer is "chain" (apad_attention_multi) -- every other answer is unchanged.
 
       "fused"  apad_fused_cross_attention: LayerNorm + to_q + attention + to_out + residual in one launch (C = 256)
       "rows"   apad_cross_attention_rows: the same sub-layer in one launch on row tiles (C = 384)
@@ -60,6 +61,8 @@ def route(kind, attn, hidden_states, residual=None, ln=None, L1=0, L2=0, masked=
             return "hs"
         if ln is not None and ops.sattn_ok(x, heads) and attn.to_q.bias is None and square_q:
             return "sattn"
+        return "chain"
+    if multi and kind == "decoupled":
         return "chain"
     # the one-launch kernels take the block entry only: they apply its LayerNorm and add x itself
     entry = USE_FUSED_XATTN and residual is x and ln is not None and square_q and x.is_contiguous() and x.dtype in ops.FUSED_DTYPES
@@ -216,13 +219,23 @@ def _as_image(out, shape4):
 class _KV(NamedTuple):
     """the hoisted key / value sets of one cross-attention call, per segment: k [B, L, C] row-major, vt [B, heads, d, Lpad] per-head transposed,
     pk = the fragment packing the call's route reads (ops.xattn_pack_kv for "fused", ops.rows_pack_kv for "rows" / "hs", None for "chain");
-    a call without a second segment leaves its three fields None"""
+    a call without a second segment leaves its three fields None.  Segments 3 to 5 are audio prompts 1 to 3 of a call under bound audio
+    prompts (the chain route: their pk stays None)"""
     k1: torch.Tensor
     vt1: torch.Tensor
     pk1: Optional[torch.Tensor] = None
     k2: Optional[torch.Tensor] = None
     vt2: Optional[torch.Tensor] = None
     pk2: Optional[torch.Tensor] = None
+    k3: Optional[torch.Tensor] = None
+    vt3: Optional[torch.Tensor] = None
+    pk3: Optional[torch.Tensor] = None
+    k4: Optional[torch.Tensor] = None
+    vt4: Optional[torch.Tensor] = None
+    pk4: Optional[torch.Tensor] = None
+    k5: Optional[torch.Tensor] = None
+    vt5: Optional[torch.Tensor] = None
+    pk5: Optional[torch.Tensor] = None
 
 
 def _pack_kv(r, k, vt):
@@ -363,20 +376,28 @@ class _Processor(nn.Module):
             o = ops.attention(q, k, vt, N, heads, key_bias=self._bias(attention_mask, B, N), q_prescaled=prescaled)
             return ops.fused_linear(o, wo, bo, residual=residual, rowstat=True)
         L1, L2 = self._lengths(ehs)
-        qw = self._query_weight(N) if L2 > 0 else None
-        r = route(self.kind, attn, x, residual, ln, L1, L2, masked, ehs.shape[0] == B, query_weighted=qw is not None)
+        prompts = self._prompts(ehs, N)  # None, or one (length, scale2, query weight) per bound audio prompt; L2 is then prompt 0's length
+        if prompts is not None:
+            L2 = prompts[0][0]
+        qw = (self._query_weight(N) if prompts is None else prompts[0][2]) if L2 > 0 else None
+        multi = prompts is not None and len(prompts) > 1
+        r = route(self.kind, attn, x, residual, ln, L1, L2, masked, ehs.shape[0] == B, query_weighted=qw is not None, multi=multi)
         persistent = self.kv_cache_enabled
 
+        # (where each bound prompt's tokens end is fixed HERE, for the life of the hoisted set: a later refresh -- of every cached step's sets, under
+        #  whatever is bound by then -- recomputes this one with the split it was made with)
+        lengths = None if prompts is None else tuple(length for length, _, _ in prompts)
+
         def make():  # the projections, packed with them into what the route's kernel reads
-            kv = [self._project_kv(attn, src, wk, wv, None if persistent else slot) for src, wk, wv, slot in self._segments(attn, ehs)]
+            kv = [self._project_kv(attn, src, wk, wv, None if persistent else slot) for src, wk, wv, slot in self._segments(attn, ehs, lengths)]
             return _KV(*(t for k, vt in kv for t in (k, vt, _pack_kv(r, k, vt))))
 
         # hoisted K/V belong to ONE (Attention site, condition buffer) -- a processor instance may be shared by every site
         # (set_attn_processor(proc)) -- and are valid for one condition content and one set of projection weights (re-assigned or
         # stepped weights, an in-place update of the condition -> recomputed, in place); packed for one route
-        kv = self._hoisted(_loose_key(attn, ehs) + (r,), lambda: self._kv_signature(attn, ehs), make)
+        kv = self._hoisted(_loose_key(attn, ehs) + (r, lengths), lambda: self._kv_signature(attn, ehs, lengths), make)
         bias = self._bias(attention_mask, B, L1)
-        scale2 = self._scale2()
+        scale2 = self._scale2() if prompts is None else prompts[0][1]
         if L2 == 0 and isinstance(scale2, tuple):
             raise ValueError("ap_scale: the table weighs the audio branch, and encoder_hidden_states holds no audio tokens")
         if r == "fused":
@@ -392,7 +413,10 @@ class _Processor(nn.Module):
             return ops.cross_attention_rows(x, wq_p, wo_p, bo, k1, None, heads, ln=ln, key_bias=bias, k2=k2, vt2=None, scale2=scale2,
                                             query_weight=qw)
         q = ops.fused_linear(x, attn.to_q.weight, ln=ln)
-        o = ops.attention(q, kv.k1, kv.vt1, L1, heads, key_bias=bias, k2=kv.k2, vt2=kv.vt2, L2=L2, scale2=scale2, query_weight=qw)
+        extra = None
+        if multi:  # prompts 1 to 3: segments 3 to 5 of the hoisted set, each under its own weight and map
+            extra = [ops.AudioSegment(kv[6 + 3 * j], kv[7 + 3 * j], length, s2, w) for j, (length, s2, w) in enumerate(prompts[1:])]
+        o = ops.attention(q, kv.k1, kv.vt1, L1, heads, key_bias=bias, k2=kv.k2, vt2=kv.vt2, L2=L2, scale2=scale2, query_weight=qw, extra=extra)
         return ops.fused_linear(o, wo, bo, residual=residual, rowstat=True)
 
 
@@ -412,10 +436,10 @@ class AttnProcessor2_0(_Processor):
     def _lengths(self, ehs):
         return ehs.shape[1], 0
 
-    def _segments(self, attn, ehs):
+    def _segments(self, attn, ehs, lengths=None):
         return [(ehs, attn.to_k.weight, attn.to_v.weight, "cross")]
 
-    def _kv_signature(self, attn, ehs):
+    def _kv_signature(self, attn, ehs, lengths=None):
         return (ehs._version, signature(attn.to_k.weight, attn.to_v.weight), _precision_of(attn.to_k.weight))
 
     def _bias(self, attention_mask, B, Lk):
@@ -430,6 +454,9 @@ class AttnProcessor2_0(_Processor):
         return 0.0
 
     def _query_weight(self, N):
+        return None
+
+    def _prompts(self, ehs, N):
         return None
 
     def _call_train(self, attn, hidden_states, ehs, attention_mask, _residual, _ln):
@@ -469,6 +496,7 @@ class IPAttnProcessor2_0(_Processor):
         self.scale = scale
         self.scale_table = None  # set_ap_scale_table: an ops.Scale2Binding read in place of ``scale``
         self.token_weights = None  # set_ap_token_weights: {token count N: ops.QueryWeight}, the map that multiplies the scale per query token
+        self.audio_prompts = None  # set_audio_prompts: ((length, scale, token weights), ...) -- the audio tokens are those of several prompts
         self.name = name
         self.to_k_ip = nn.Linear(cross_attention_dim or hidden_size, hidden_size, bias=False)
         self.to_v_ip = nn.Linear(cross_attention_dim or hidden_size, hidden_size, bias=False)
@@ -488,18 +516,28 @@ class IPAttnProcessor2_0(_Processor):
         Lt = min(self.num_tokens, ehs.shape[1])
         return Lt, ehs.shape[1] - Lt
 
-    def _segments(self, attn, ehs):
+    def _segments(self, attn, ehs, lengths=None):
+        # ``lengths``: the token counts of the bound audio prompts (None: one audio segment)
         # ragged views -> dense rows for the GEMM A operand (plumbing copies of <= 520 x 768 tokens)
         nt = self.num_tokens
         segs = [(ehs[:, :nt, :].contiguous(), attn.to_k.weight, attn.to_v.weight, "ip_txt")]
+        if lengths is not None:  # one segment per prompt, all through the same to_k_ip / to_v_ip
+            at = nt
+            for j, length in enumerate(lengths):
+                segs.append((ehs[:, at:at + length, :].contiguous(), self.to_k_ip.weight, self.to_v_ip.weight, "ip_aud" if j == 0 else f"ip_aud{j}"))
+                at += length
+            return segs
         if ehs.shape[1] > nt:
             segs.append((ehs[:, nt:, :].contiguous(), self.to_k_ip.weight, self.to_v_ip.weight, "ip_aud"))
         return segs
 
-    def _kv_signature(self, attn, ehs):
+    def _kv_signature(self, attn, ehs, lengths=None):
         # all four projection weights: a re-assigned to_k_ip / to_v_ip (inference.py:56-57) or an optimizer step is never served stale K/V
-        return (ehs._version, self.num_tokens, signature(attn.to_k.weight, attn.to_v.weight, self.to_k_ip.weight, self.to_v_ip.weight),
-                _precision_of(attn.to_k.weight))
+        sig = (ehs._version, self.num_tokens, signature(attn.to_k.weight, attn.to_v.weight, self.to_k_ip.weight, self.to_v_ip.weight),
+               _precision_of(attn.to_k.weight))
+        if lengths is not None:  # where one prompt's tokens end and the next one's begin
+            sig += (tuple(lengths),)
+        return sig
 
     def _bias(self, attention_mask, B, Lt):
         """reference :424-428 keeps only mask column 0 (split by the singleton query dim) and broadcasts it over the text keys"""
@@ -535,6 +573,51 @@ class IPAttnProcessor2_0(_Processor):
             raise ValueError(f"ap_mask: no weight map is bound for a call of {N} tokens (bound: {sorted(self.token_weights)})")
         return self.token_weights[N]
 
+    def set_audio_prompts(self, lengths, scales=None, token_weights=None):
+        """read the audio tokens of the condition as those of SEVERAL prompts, [text | prompt 0 tokens | prompt 1 tokens | ...]: prompt j owns
+        ``lengths[j]`` tokens (1 to 4 prompts; the lengths must sum to the audio tokens of every call), runs its own softmax over the
+        ``to_k_ip`` / ``to_v_ip`` projections of its tokens and is added as scales[j] * token_weights[j][N][b % cols][n] * A(q, K_j, V_j).
+        ``scales[j]``: None (this processor's ``scale``), a float or an ops.Scale2Binding; ``token_weights[j]``: None or {N: ops.QueryWeight}.
+        While two or more prompts are bound every site runs the chain (``route(multi=True)``, apad_attention_multi); a bound ap_scale table
+        and ap_mask maps are not read.  Inference only."""
+        lengths = [int(n) for n in lengths]
+        n = len(lengths)
+        if not 1 <= n <= 4:
+            raise ValueError(f"audio_prompts: 1 to 4 prompts, got {n}")
+        if any(length <= 0 for length in lengths):
+            raise ValueError(f"audio_prompts: every prompt needs at least one token, got lengths {lengths}")
+        scales = [None] * n if scales is None else list(scales)
+        token_weights = [None] * n if token_weights is None else list(token_weights)
+        if len(scales) != n or len(token_weights) != n:
+            raise ValueError(f"audio_prompts: {n} lengths, {len(scales)} scales and {len(token_weights)} token weights")
+        bound = []
+        for length, s, tw in zip(lengths, scales, token_weights):
+            if s is not None and not isinstance(s, tuple):
+                s = float(s)
+            elif isinstance(s, tuple):
+                s = ops.Scale2Binding(*s)
+            if tw is not None:
+                tw = {int(k): ops.QueryWeight(*w) for k, w in tw.items()}
+            bound.append((length, s, tw))
+        self.audio_prompts = tuple(bound)
+
+    def clear_audio_prompts(self):
+        self.audio_prompts = None
+
+    def _prompts(self, ehs, N):
+        if self.audio_prompts is None:
+            return None
+        have = ehs.shape[1] - min(self.num_tokens, ehs.shape[1])
+        lengths = [length for length, _, _ in self.audio_prompts]
+        if sum(lengths) != have:
+            raise ValueError(f"audio_prompts: the bound prompts hold {lengths} = {sum(lengths)} tokens, encoder_hidden_states holds {have} audio tokens")
+        out = []
+        for j, (length, s, tw) in enumerate(self.audio_prompts):
+            if tw is not None and N not in tw:
+                raise ValueError(f"audio_prompts: prompt {j} has no weight map for a call of {N} tokens (bound: {sorted(tw)})")
+            out.append((length, self.scale if s is None else s, None if tw is None else tw[N]))
+        return out
+
     def _call_train(self, attn, hidden_states, ehs, attention_mask, _residual, _ln):
         """Training mode (reference :347-470 under autograd; train_apadapter_v2.py:941-957): gradients w.r.t.
         hidden_states, to_k_ip.weight and to_v_ip.weight (and the condition tokens if they require grad)."""
@@ -542,6 +625,8 @@ class IPAttnProcessor2_0(_Processor):
             raise ValueError("ap_scale: the training path keeps the float `scale`; clear_ap_scale_table() before a forward under autograd")
         if self.token_weights is not None:
             raise ValueError("ap_mask: the training path has no per-token weight; clear_ap_token_weights() before a forward under autograd")
+        if self.audio_prompts is not None:
+            raise ValueError("audio_prompts: the training path has one audio prompt; clear_audio_prompts() before a forward under autograd")
         B = hidden_states.shape[0]
         nt = self.num_tokens
         txt, aud = ehs[:, :nt, :].contiguous(), ehs[:, nt:, :].contiguous()

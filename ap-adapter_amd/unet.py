@@ -418,6 +418,7 @@ class AudioLDM2UNet2DConditionModel(nn.Module):
         self.low_res_streams = None  # optional (stream, stream): see forward_nhwc
         self._ap_scale_cols = None   # columns of the table set_ap_scale_table bound (None: no table)
         self._ap_mask_cols = None    # columns of the maps set_ap_token_weights bound (None: no maps)
+        self._ap_prompt_cols = ()    # columns of every table and map set_audio_prompts bound
         self.low_res_levels = 1      # how many of the lowest-resolution levels run on the two streams
 
     # ---- processor plumbing (modeling_audioldm2.py:517-574) ----
@@ -492,6 +493,27 @@ class AudioLDM2UNet2DConditionModel(nn.Module):
         for p in set(self.attn_processors.values()):
             if hasattr(p, "clear_ap_token_weights"):
                 p.clear_ap_token_weights()
+
+    def set_audio_prompts(self, lengths, scales=None, token_weights=None):
+        """Hand every decoupled processor SEVERAL audio prompts: the audio tokens of the condition are [prompt 0 tokens | prompt 1 tokens | ...] of
+        ``lengths[j]`` tokens each; prompt j is added as scales[j] * token_weights[j] * A(q, K_j, V_j) (``IPAttnProcessor2_0.set_audio_prompts``:
+        ``scales[j]`` None, a float or an ops.Scale2Binding; ``token_weights[j]`` None or {token count: ops.QueryWeight}, one per level of
+        ``attention_grids``).  With two or more prompts every decoupled site runs the chain (apad_attention_multi).  Inference only."""
+        n = len(lengths)
+        scales = [None] * n if scales is None else list(scales)
+        token_weights = [None] * n if token_weights is None else list(token_weights)
+        cols = [int(s[2]) for s in scales if isinstance(s, tuple)]
+        cols += [int(w[1]) for tw in token_weights if tw is not None for w in tw.values()]
+        for p in set(self.attn_processors.values()):
+            if hasattr(p, "set_audio_prompts"):
+                p.set_audio_prompts(lengths, scales, token_weights)
+        self._ap_prompt_cols = tuple(cols)
+
+    def clear_audio_prompts(self):
+        self._ap_prompt_cols = ()
+        for p in set(self.attn_processors.values()):
+            if hasattr(p, "clear_audio_prompts"):
+                p.clear_audio_prompts()
 
     def attention_grids(self, H, W):
         """the (h, w) token grid of every resolution level that holds a decoupled ``attn2`` (an IPAttnProcessor2_0), finest first, for an
@@ -670,10 +692,10 @@ class AudioLDM2UNet2DConditionModel(nn.Module):
         # (only while a hipGraph is being captured -- that is what the fork / join is for, and the captured allocations come from the graph's
         #  private pool; an EAGER forward on side streams was measured wrong in the fp32 mode at batch 32, round 5: it stays on one stream)
         # (a per-clip ap_scale table, or per-clip ap_mask maps, are indexed by sample % clips: a part of the batch keeps that only when it holds
-        #  whole sets of clips)
+        #  whole sets of clips; the same for every table and map of bound audio prompts)
         split = (nsp > 1 and timestep is None and B % nsp == 0 and not AG.on(x) and nb >= 2 and x.is_cuda
                  and torch.cuda.is_current_stream_capturing()
-                 and all(c in (None, 1) or (B // nsp) % c == 0 for c in (self._ap_scale_cols, self._ap_mask_cols)))
+                 and all(c in (None, 1) or (B // nsp) % c == 0 for c in (self._ap_scale_cols, self._ap_mask_cols) + self._ap_prompt_cols))
         k0 = max(1, nb - self.low_res_levels) if split else nb  # first down block of the two-stream section
         for i in range(k0):
             x, H, W = down(i, x, H, W, skips, *cond)

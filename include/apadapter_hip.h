@@ -21,6 +21,9 @@
  *                       the same launches with that scale multiplied, per query token, by an entry of a device map
  *                       (apad_query_weight below): the audio prompt by region.  No counterpart in the reference (diffusers knows the
  *                       control as IP-Adapter attention masks); an entry v is bit-equal to the scalar entry point with scale * v
+ *   apad_attention_multi  apad_attention_qw with up to three MORE audio segments, each with its own K / V, scale (float or table) and
+ *                       map (apad_attn_extra below): several audio prompts per clip.  No counterpart in the reference; a prompt at
+ *                       weight zero leaves the bits of the launch without it
  *   apad_gemm           attn.to_q/to_k/to_v/to_out, to_k_ip/to_v_ip (attention_processor.py:387,:406-407,
  *                       :435-436,:457); diffusers GEGLU/FeedForward, proj_in/proj_out, ResnetBlock2D /
  *                       Downsample2D / Upsample2D 3x3 convolutions and time_emb_proj
@@ -389,6 +392,39 @@ int apad_sizeof_query_weight(void);
 int apad_attention_qw(const apad_attn_desc* d, const apad_scale2_tab* t /* NULL: d->scale2 */, const apad_query_weight* w, void* stream);
 int apad_cross_attention_rows_qw(const apad_xrows_desc* d, const apad_scale2_tab* t, const apad_query_weight* w, void* stream);
 int apad_hs_attention_qw(const apad_hs_attn_desc* d, const apad_scale2_tab* t, const apad_query_weight* w, void* stream);
+
+/* Several audio prompts in one launch: text + sum_j s_j * w_j[n] * A(q, K_j, V_j) for up to four recordings, each A an independently
+ * normalised softmax segment.  d, t and w describe the text segment and audio prompt 0 with exactly the meaning they have for
+ * apad_attention_qw (t and w may each be NULL: d->scale2, no map); extra[0 .. n_extra) are prompts 1 to 3, 0 <= n_extra <= 3.  No
+ * counterpart in the reference (diffusers knows the control as several IP-Adapters, each with its scale and its ip_adapter_masks entry).
+ *
+ * Arithmetic, in this fixed order.  16-bit types: acc = f32(elem(text)); for j = 0, 1, ...: acc += f32(elem(sw_j * f32(elem(o_j * inv_j))));
+ * one store of elem(acc), where sw_j = s_j without a map and s_j * w_j[(b % cols_j) * ld_j + n] with one (apad_query_weight's single fp32
+ * multiply).  For one prompt that is apad_attention's expression.  fp32 modes: out += sw_j * audio_j, in the same order.  s_j is read once
+ * per workgroup on the scalar path, as apad_scale2_tab states; a lane requests its map entry before that segment's key loop.
+ *
+ * Kernel selection is per LAUNCH: the short form (one masked tile per segment, fragments straight from global memory) runs only when
+ * d->L <= 64 and EVERY audio segment, d->L2 and each extra[j].L, is <= 64 keys; otherwise every segment of the launch goes through the
+ * long form (64-key tiles staged in LDS, online softmax).  A launch is therefore bit-comparable with single-prompt launches of the same
+ * form: a prompt whose weight is zero contributes +-0 and leaves the bits of the launch without it, a row whose only non-zero map entry
+ * is prompt j's equals the scalar launch with prompt j as segment 2.  The fp32 modes have one form.  n_extra == 0 is legal and is the
+ * apad_attention_qw / apad_attention_tab / apad_attention launch of the same d, t and w.
+ *
+ * Rejected (negative code, apad_last_error() names apad_attention_multi, nothing launched): n_extra outside [0, 3]; n_extra > 0 with
+ * extra == NULL; d->L2 == 0 or d->lse != NULL; an extra with L <= 0, Lpad < L, Lpad % 32 != 0, kv_batch_div <= 0, a NULL k or a NULL vt,
+ * or pointers / strides that break the 16-byte alignment apad_attention asks of k2 / vt2; and, for t, w and every extra's tab / qw, what
+ * apad_attention_tab / apad_attention_qw reject about a table or a map. */
+typedef struct apad_attn_extra {      /* one more audio segment */
+    const void* k;  const void* vt;   /* apad_attention's layouts: k [Bk][L][H*D], vt [Bk][H][D][Lpad] zero padded */
+    int64_t k_stride_b, k_stride_l, vt_stride_b;
+    int32_t L, Lpad, kv_batch_div, reserved;
+    float scale;  float reserved_f;   /* read when tab.table == NULL */
+    apad_scale2_tab   tab;            /* table == NULL: the float above */
+    apad_query_weight qw;             /* w == NULL: no map */
+} apad_attn_extra;
+int apad_sizeof_attn_extra(void);
+int apad_attention_multi(const apad_attn_desc* d, const apad_scale2_tab* t, const apad_query_weight* w,
+                         const apad_attn_extra* extra, int32_t n_extra, void* stream);
 
 typedef struct apad_hs_out_desc {
     const void* o;         /* [B*N][640] attention output (all heads)                                 */

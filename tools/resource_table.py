@@ -69,7 +69,17 @@ def under_old_names(a, b):
     b = dict(b)
     for src, name in [k for k in b if k not in a]:
         old = (src, name.replace("ELb0EEEv", "EEEv", 1))
-        if old != (src, name) and old in a and old not in b:
+        if old == (src, name):
+            continue
+        if old not in a:
+            # the flag also selects the kernel's parameter type (attn_kernel's AttnArg<MULTI>::type): the parameter list is then mangled as a
+            # dependent type, so match on the template argument list alone when exactly one old kernel carries it
+            head = old[1].split("EEEv", 1)[0] + "EEEv"
+            same = [k for k in a if k[0] == src and k[1].startswith(head) and k not in b]
+            if len(same) != 1:
+                continue
+            old = same[0]
+        if old not in b:
             b[old] = b.pop((src, name))
     return b
 

@@ -39,6 +39,12 @@ The audio prompt by region (--ap-region A:B, seconds): the weight above is kept 
 decoupled attn2 (``pipeline.denoise(ap_region=)``; the 256-wide sites then run the un-fused chain).  It composes with --ap-scale, and both
 passes of --inversion run under it.
     python tools/run_sharded.py --clips 64 --steps 50 --ap-region 4:7
+
+Several audio prompts per clip (--audio-prompt FILE[:START:END[:SCALE]], up to four times): every clip is conditioned on THESE recordings instead
+of its own -- each with its own softmax in every decoupled attn2, its own region in seconds and its own weight (default: the whole clip, the
+task preset's weight) -- ``pipeline.denoise(audio_prompts=)``.  One --audio-prompt is --ap-region / --ap-scale on that file; with two or more
+every decoupled site runs the un-fused chain.  Not together with --ap-scale / --ap-region:
+    python tools/run_sharded.py --clips 64 --steps 50 --audio-prompt cello.wav:0:5 --audio-prompt flute.wav:5:10:0.8
 """
 import argparse
 import glob
@@ -164,6 +170,8 @@ def main():
                     "float, or one per step (a schedule over the full grid); default: the task preset's value, set on the processors")
     ap.add_argument("--ap-region", default=None, metavar="A:B", help="seconds: the audio prompt weighs the tokens between A and B only "
                     "(ap_region=(A, B)); default: the whole clip")
+    ap.add_argument("--audio-prompt", action="append", default=None, metavar="FILE[:START:END[:SCALE]]", help="repeatable (1 to 4): condition every "
+                    "clip on these recordings, each weighing the tokens between START and END seconds only, by SCALE (audio_prompts=)")
     ap.add_argument("--gpus", type=int, default=1, help="N > 1 without a launcher: this script starts its N ranks itself (one per GPU)")
     args = ap.parse_args()
     if args.inversion and args.sampler != "ddim":
@@ -204,6 +212,22 @@ def main():
             ap.error("--ap-region: A:B in seconds")
         args.ap_region = (a0, a1)
 
+    if args.audio_prompt is not None:
+        if args.ap_scale is not None or args.ap_region is not None:
+            ap.error("--audio-prompt carries its own START:END and SCALE: not together with --ap-scale / --ap-region")
+        if not 1 <= len(args.audio_prompt) <= 4:
+            ap.error("--audio-prompt: 1 to 4 recordings")
+        parsed = []
+        for spec in args.audio_prompt:
+            f = spec.rsplit(":", 3) if spec.count(":") >= 3 else spec.rsplit(":", 2) if spec.count(":") == 2 else [spec]
+            try:
+                if len(f) not in (1, 3, 4):
+                    raise ValueError(spec)
+                parsed.append((f[0], (float(f[1]), float(f[2])) if len(f) >= 3 else None, float(f[3]) if len(f) == 4 else None))
+            except ValueError:
+                ap.error(f"--audio-prompt {spec!r}: FILE, FILE:START:END or FILE:START:END:SCALE (seconds, a float)")
+        args.audio_prompt = parsed
+
     from ap_adapter_amd import distributed as D
     if args.gpus > 1 and not D.launched_by_torchrun():
         sys.exit(D.spawn_ranks(args.gpus, os.path.abspath(__file__), sys.argv[1:]))
@@ -223,7 +247,13 @@ def main():
     pipe = build_job(dev, dtype, cfg, small=args.small, adapter_ckpt=args.adapter_ckpt, sampler=args.sampler)
     H = int(args.seconds / pipe.vocoder_upsample_factor) // pipe.vae_scale_factor  # latent frames: 10 s -> 250 (pipeline_audioldm2.py:872-880)
 
+    prompt_lengths = []
+
     def encode_audio(path, tp, fp):
+        if args.audio_prompt is not None:  # the job's recordings instead of the clip's own: their tokens one after the other
+            enc = [pipe.encode_audio(load_mel(f, device=dev), tp, fp) for f, _, _ in args.audio_prompt]
+            prompt_lengths[:] = [tok.shape[1] for tok, _ in enc]
+            return torch.cat([tok[0] for tok, _ in enc]), torch.cat([unc[0] for _, unc in enc])
         tok, unc = pipe.encode_audio(load_mel(path, device=dev), tp, fp)
         return tok[0], unc[0]
 
@@ -268,23 +298,35 @@ def main():
             ap.error(str(err))
         aps["ap_region"] = args.ap_region
 
+    if args.audio_prompt is not None:  # every prompt's region and weight, checked once against the job's latent height and steps
+        try:
+            pipe._host_audio_prompts([A.AudioPrompt(length=1, ap_scale=sc, ap_region=reg) for _, reg, sc in args.audio_prompt], args.steps,
+                                     start if editing else 0, 1, H, 16)
+        except ValueError as err:
+            ap.error(str(err))
+
+    def aps_now():  # (the prompts' token counts are known once the first batch has been encoded)
+        if args.audio_prompt is None:
+            return aps
+        return {"audio_prompts": [A.AudioPrompt(length=n, ap_scale=sc, ap_region=reg) for n, (_, reg, sc) in zip(prompt_lengths, args.audio_prompt)]}
+
     def denoise(lat, gen, t5, mask, gs, clips=None):
         if not editing:
-            return pipe.denoise(lat, gen, t5, mask, args.steps, gs, **dual, **shaping, **aps)
+            return pipe.denoise(lat, gen, t5, mask, args.steps, gs, **dual, **shaping, **aps_now())
         # z0 = the clip's seeded latents (what a generation run would start from); the posterior draw is seeded by the clip index too
         post = torch.stack([torch.randn(8, H, 16, generator=torch.Generator().manual_seed(7919 * c["index"] + 1)) for c in clips])
         src = A.EditSource(z0=lat, moments=torch.cat([source_moments(c["audio"]) for c in clips]), post_noise=post,
                            scale=pipe.vae.config.scaling_factor, mask=region_mask)
         if args.inversion is None:
-            return pipe.denoise(None, gen, t5, mask, args.steps, gs, source=src, start=start, **dual, **shaping, **aps)
+            return pipe.denoise(None, gen, t5, mask, args.steps, gs, source=src, start=start, **dual, **shaping, **aps_now())
         # the source condition: the batch's own, with the positive branch's text (the last b rows; 8 generated tokens) replaced
         b = lat.shape[0]
         sg, st, sm = S.synthetic_text_embeddings(args.source_prompt, t5_len=t5.shape[1])
         sgen, st5, smask = gen.clone(), t5.clone(), mask.clone()
         sgen[-b:, :8], st5[-b:], smask[-b:] = sg.to(gen), st.to(t5), sm.to(mask)
         inv = pipe.invert(src, sgen, st5, smask, args.steps, args.source_guidance, start=start, eta=1.0,
-                          generator=torch.Generator().manual_seed(104729 * clips[0]["index"] + 2), **dual, **aps)
-        return pipe.denoise(None, gen, t5, mask, args.steps, gs, source=inv, start=start, eta=1.0, **dual, **shaping, **aps)
+                          generator=torch.Generator().manual_seed(104729 * clips[0]["index"] + 2), **dual, **aps_now())
+        return pipe.denoise(None, gen, t5, mask, args.steps, gs, source=inv, start=start, eta=1.0, **dual, **shaping, **aps_now())
 
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -338,7 +380,7 @@ def main():
         print(json.dumps({"task": args.task, "clips": len(clips), "world": world, "batch": args.batch, "steps": args.steps,
                           "sampler": args.sampler, "strength": args.strength, "edit_region": args.edit_region, "La": A.config.audio_tokens(cfg), "seconds_rank0": round(dt, 2), "clips_per_s": round(len(clips) / dt, 4),
                           "graph_captures": pipe.graph_captures, "graph_hits": pipe.graph_hits, "finite": finite,
-                          "wavs_written_rank0": n_wavs, **({"audio_guidance": args.audio_guidance} if dual else {}), **shaping, **aps,
+                          "wavs_written_rank0": n_wavs, **({"audio_guidance": args.audio_guidance} if dual else {}), **shaping, **({"audio_prompts": [list(p) for p in args.audio_prompt]} if args.audio_prompt is not None else aps),
                           **({"inversion": args.inversion, "source_prompt": args.source_prompt, "source_guidance": args.source_guidance}
                              if args.inversion else {}),
                           **({"rank_by": args.rank_by, "chroma_similarity_mean_rank0": round(sum(r["chroma_similarity"] for r in scored) / max(len(scored), 1), 6)}
