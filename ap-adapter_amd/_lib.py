@@ -223,6 +223,8 @@ SYMBOLS = {
     # BS.1770 loudness and the gain towards a target (normalize_loudness)
     "apad_loudness": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "apad_loudness_gain": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _f32, _vp]),
+    # a region edit spliced back into its reference recording (splice_edit)
+    "apad_splice": (C.c_int, [_vp] * 15 + [_i32, _i32, _vp]),
 }
 
 _lock = threading.Lock()

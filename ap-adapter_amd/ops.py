@@ -1272,6 +1272,47 @@ def loudness_gain(x, offsets, offsets_host, stats, out, gains, peak_limit, targe
     return out
 
 
+SPLICE_PLAN_INTS, SPLICE_SEAMS = 32, 8
+
+
+def splice(edit, offsets, offsets_host, ref, ref_offsets, ref_offsets_host, ref_index, ref_index_host, plan, plan_host, out, gains, seam_start,
+           seam_stats, gain_in=None):
+    """apad_splice on pre-allocated buffers (hipGraph-capturable: no allocation, no read-back): edit fp32 [sum n] = the clips packed back to
+    back with offsets int64 [B + 1] on the device and on the host, ref / ref_offsets / ref_offsets_host the m references packed the same
+    way, ref_index int32 [B] (clip -> reference) on the device and on the host, plan int32 [B, 32] on the device and on the host
+    (``splice.plan_row``) -> out fp32 (packed as edit; neither edit nor ref), gains fp32 [B], seam_start int32 [B, 8] (-1 = no seam) and
+    seam_stats fp32 [B, 8, 2] = (cost, correlation).  ``gain_in`` fp32 [B]: the gain of the clips whose plan asks for a given one."""
+    for t, name in ((edit, "edit"), (ref, "ref"), (out, "out"), (gains, "gains"), (seam_stats, "seam_stats")) + \
+            (((gain_in, "gain_in"),) if gain_in is not None else ()):
+        if not _req(t, "splice." + name, torch.float32).is_contiguous():
+            raise RuntimeError(f"splice.{name}: must be contiguous")
+    B = offsets_host.numel() - 1
+    _host_table(offsets_host, "splice.offsets_host", torch.int64, B + 1)
+    m = ref_offsets_host.numel() - 1
+    _host_table(ref_offsets_host, "splice.ref_offsets_host", torch.int64, m + 1)
+    if B < 1 or m < 1:
+        raise RuntimeError(f"splice: {B} clips and {m} references (need at least one of each)")
+    for t, n, name in ((offsets, B + 1, "offsets"), (ref_offsets, m + 1, "ref_offsets")):
+        if _req(t, "splice." + name, torch.int64).numel() != n or not t.is_contiguous():
+            raise RuntimeError(f"splice.{name}: expected {n} contiguous int64 values")
+    for t, n, name in ((ref_index, B, "ref_index"), (plan, B * SPLICE_PLAN_INTS, "plan"), (seam_start, B * SPLICE_SEAMS, "seam_start")):
+        if _req(t, "splice." + name, torch.int32).numel() != n or not t.is_contiguous():
+            raise RuntimeError(f"splice.{name}: expected {n} contiguous int32 values")
+    _host_table(ref_index_host, "splice.ref_index_host", torch.int32, B)
+    _host_table(plan_host, "splice.plan_host", torch.int32, B * SPLICE_PLAN_INTS)
+    if gains.numel() != B or seam_stats.numel() != B * SPLICE_SEAMS * 2 or (gain_in is not None and gain_in.numel() != B):
+        raise RuntimeError(f"splice: gains {tuple(gains.shape)} / seam_stats {tuple(seam_stats.shape)} / gain_in do not describe {B} clips as [B] / "
+                           f"[B, 8, 2] / [B]")
+    if edit.numel() < int(offsets_host[-1]) or out.numel() < int(offsets_host[-1]) or ref.numel() < int(ref_offsets_host[-1]):
+        raise RuntimeError(f"splice: edit {edit.numel()} / out {out.numel()} / ref {ref.numel()} samples, the offsets end at "
+                           f"{int(offsets_host[-1])} / {int(ref_offsets_host[-1])}")
+    L.check(L.lib().apad_splice(edit.data_ptr(), offsets.data_ptr(), offsets_host.data_ptr(), ref.data_ptr(), ref_offsets.data_ptr(),
+                                ref_offsets_host.data_ptr(), ref_index.data_ptr(), ref_index_host.data_ptr(), plan.data_ptr(),
+                                plan_host.data_ptr(), _ptr(gain_in), out.data_ptr(), gains.data_ptr(), seam_start.data_ptr(),
+                                seam_stats.data_ptr(), B, m, _stream()), "apad_splice")
+    return out
+
+
 def gaussian_sample(moments, noise, scale=1.0):
     """moments [rows, 2L] = (mean | logvar), noise [rows, L] -> (mean + exp(0.5 * clamp(logvar, -30, 20)) * noise) * scale"""
     _req(moments, "gaussian_sample.moments")

@@ -34,6 +34,11 @@ Loudness (``target_loudness=``, ``peak_limit_db=``, ``loudness_reference=``; ITU
 against other meters, loudness.py): right after the vocoder and the crop, on the device, every candidate is measured (``apad_loudness``) and
 multiplied by the gain that takes it to a target in LUFS or to its source's loudness (``apad_loudness_gain``), under a sample-peak guard.
 A call without ``target_loudness=`` takes none of this.
+
+Splicing an edit back into its recording (``splice="source"``, ``splice_reference=``, ``crossfade_s=``, ``seam_search_s=``,
+``crossfade_shape=``, ``splice_gain=``; PARITY UNPINNED, splice.py): right after the vocoder and the crop and BEFORE the loudness stage, on the
+device, each candidate of a region edit is joined to the source recording itself (``apad_splice``): outside the edit regions and the crossfade
+windows the returned samples are the recording's, bit for bit.  A call without ``splice=`` takes none of this.
 """
 import math
 from dataclasses import dataclass
@@ -121,6 +126,7 @@ class AudioLDM2Pipeline:
         self.last_logits_per_text = None
         self.last_chroma_similarity = None
         self.last_loudness = None
+        self.last_splice = None
         self.scheduler = scheduler or DDIMScheduler()
         self.audiomae = audiomae
         self._uncond_cache = {}
@@ -295,6 +301,78 @@ class AudioLDM2Pipeline:
                               target=torch.tensor(target, dtype=torch.float32).to(dev))
         self.last_loudness = (loudness.measure(out.reshape(-1), offsets, offsets_host, sr), gains)
         return out
+
+    def check_splice_arguments(self, splice, splice_reference, crossfade_s, seam_search_s, crossfade_shape, splice_gain, source_audio, source_mel,
+                               source_latents, mask, output_type, batch, samples):
+        """every argument check of ``splice=`` and its keywords, on the host, before any device work; ``mask`` is what
+        ``check_edit_arguments`` returned.  Returns None (today's path) or (per-clip sample regions, W, M, shape, gain)."""
+        from . import splice as S
+        if splice is None:
+            if splice_reference is not None:
+                raise ValueError("splice_reference is the recording of splice='source'; without splice= it has no use")
+            return None
+        if splice != "source":
+            raise ValueError(f"splice={splice!r}: None or 'source' (splice each edit back into its source recording)")
+        if source_audio is None and source_mel is None and source_latents is None:
+            raise ValueError("splice='source' needs a source clip (source_audio=, source_mel= or source_latents=)")
+        if mask is None:
+            raise ValueError("splice='source' needs a region (edit_region= or edit_mask=): without one there is nothing to keep")
+        if output_type == "latent":
+            raise ValueError("splice='source' acts on the waveform: it cannot be combined with output_type='latent'")
+        sr = int(self.vocoder.config.sampling_rate) if self.vocoder is not None else 16000
+        W, M = S.check_lengths(sr, crossfade_s, seam_search_s)
+        shape, gain = S.check_shape(crossfade_shape), S.check_gain(splice_gain, "splice_gain")
+        if source_audio is None:
+            if splice_reference is None:
+                raise ValueError("splice='source' with source_mel= / source_latents= needs the recording itself: splice_reference= (a waveform "
+                                 "[samples] or [b, samples] at the vocoder's rate)")
+            shp = tuple(splice_reference.shape)
+            if len(shp) not in (1, 2) or shp[-1] == 0 or (len(shp) == 2 and (shp[0] == 0 or batch % shp[0] != 0)):
+                raise ValueError(f"splice_reference {shp}: expected a waveform [samples] or [b, samples] with b dividing the batch of {batch}")
+        elif splice_reference is not None:
+            raise ValueError("splice_reference and source_audio are both given: with source_audio the recording is the file itself")
+        regions = S.mask_regions(mask, int(round(sr * self.latent_row_seconds)), samples)
+        if len(regions) not in (1, batch):
+            raise ValueError(f"splice: the edit mask holds {len(regions)} clips for a batch of {batch}")
+        regions = regions * batch if len(regions) == 1 else regions
+        for r in regions:  # (no region, more than 4 of them, nothing kept: a ValueError here, not after the denoise loop)
+            S.plan(samples, r, W, M)
+        return regions, W, M, shape, gain
+
+    def _splice_reference(self, source_audio, splice_reference, samples, dev):
+        """the recordings [m, samples] fp32 on the device: each file's channel 0 resampled to the vocoder's rate (the raw samples, not the
+        level-normalised ones the encoder sees), or ``splice_reference``; cropped or zero-padded to ``samples``"""
+        if splice_reference is not None:
+            ref = torch.as_tensor(splice_reference).to(dev, torch.float32)
+            clips = [ref] if ref.dim() == 1 else list(ref)
+        else:
+            from .frontend import load_wav, resample
+            sr = int(self.vocoder.config.sampling_rate)
+            clips = []
+            for path in ([source_audio] if isinstance(source_audio, str) else list(source_audio)):
+                wav, rate = load_wav(path)
+                clips.append(resample(torch.from_numpy(wav[:1]).to(dev), rate, sr)[0])
+        out = torch.zeros(len(clips), samples, dtype=torch.float32, device=dev)
+        for i, c in enumerate(clips):
+            out[i, :min(samples, c.numel())] = c[:samples]
+        return out
+
+    def _apply_splice(self, wav, plan, ref):
+        """candidates [B, samples] on the device -> each spliced into its recording (fp32, on the device); ``last_splice`` = (gains [B],
+        seam starts int32 [B, 8], seam stats (cost, correlation) [B, 8, 2]), in generation order"""
+        from . import loudness, splice as S
+        regions, W, M, shape, gain = plan
+        wav = wav.float().contiguous()
+        B, n = wav.shape
+        if ref.shape[1] != n:  # (a vocoder that renders fewer samples than the call's length)
+            ref = torch.nn.functional.pad(ref, (0, max(0, n - ref.shape[1])))[:, :n].contiguous()
+        plans = [S.plan(n, [(a, min(b, n)) for a, b in r if a < n], W, M) for r in regions]
+        offsets_host = torch.arange(B + 1, dtype=torch.int64) * n
+        roh = torch.arange(ref.shape[0] + 1, dtype=torch.int64) * n
+        out, gains, starts, stats = S.run(wav.reshape(-1), offsets_host, ref.reshape(-1), roh, loudness.default_ref_index(B, ref.shape[0]), plans,
+                                          shape, gain)
+        self.last_splice = (gains, starts, stats)
+        return out.reshape(B, n)
 
     def _encode_text(self, texts, t5_max_length=None):
         """tokenise as encode_prompt does (:381-392 positive, :485-496 negative) and run the HIP prompt encoder on one CFG half"""
@@ -1144,7 +1222,8 @@ class AudioLDM2Pipeline:
                  callback=None, callback_steps=1, cross_attention_kwargs=None, output_type="np", mel=None,
                  use_graph=True, source_audio=None, source_mel=None, source_latents=None, strength=1.0, edit_mask=None, edit_region=None,
                  audio_guidance_scale=None, guidance_rescale=0.0, apg_eta=None, apg_norm_threshold=0.0, apg_momentum=0.0, ap_scale=None,
-                 ap_region=None, ap_mask=None, audio_prompts=None, target_loudness=None,
+                 ap_region=None, ap_mask=None, audio_prompts=None, splice=None, splice_reference=None, crossfade_s=0.03, seam_search_s=0.08,
+                 crossfade_shape="matched", splice_gain="kept", target_loudness=None,
                  peak_limit_db=-1.0, loudness_reference=None, rank_by=None, fidelity_reference=None, inversion=None, source_prompt=None, source_guidance_scale=3.0, source_prompt_embeds=None,
                  source_generated_prompt_embeds=None, source_attention_mask=None):
         """Same keyword surface and defaults as the reference (pipeline_audioldm2.py:748-775, ``output_type="np"`` included): a
@@ -1199,6 +1278,22 @@ class AudioLDM2Pipeline:
         [B, 4] of the returned clips: LUFS, sample peak, blocks above the absolute gate, blocks above both; gains [B]) on the device, in
         generation order.  A clip shorter than 400 ms, or silent, has no loudness and keeps gain 1.  ``output_type="latent"`` exits before
         it; with ``target_loudness=None`` the call takes none of it.
+
+        Beyond the reference -- ``splice="source"`` (PARITY UNPINNED, splice.py): each candidate of a region edit is spliced back into the
+        source RECORDING, so that what was to be kept is the recording itself and not its re-rendering through the VAE and the vocoder.  It
+        needs a source clip, a region (``edit_region`` / ``edit_mask``) and a waveform output.  The recording: with ``source_audio`` the file's
+        channel 0, resampled to the vocoder's rate and cropped or zero-padded to the clip (the raw samples, not the level-normalised ones the
+        encoder sees); with ``source_mel`` / ``source_latents`` it is ``splice_reference``, a waveform [samples] or [b, samples] at the vocoder's
+        rate with b dividing the batch.  Regions: a latent row is inside a region if ANY of its 16 mask entries is > 0 -- a frequency-band
+        mask therefore counts as its rows, the splice is full-band -- and runs of inside rows become sample ranges at 640 samples per row (16
+        kHz); the mask is per clip or shared.  ``splice_gain``: "kept" (the edit is matched to the recording's level where both hold the
+        kept material), None (1) or a number.  Each seam is placed within ``seam_search_s`` outside its region where recording and edit differ
+        least over ``crossfade_s``, and crossfaded there: ``crossfade_shape`` "matched" (power-complementary for the two signals' measured
+        correlation), "linear" or "equal_power".  The stage runs right after the vocoder and the crop and BEFORE the loudness stage: scoring
+        and ranking see what is returned, and ``target_loudness`` scales the spliced clip as a whole -- the kept part is then the recording
+        times one gain; it is the recording bit for bit with ``target_loudness=None``.  ``last_splice`` keeps (gains [B], window starts int32
+        [B, 8] with -1 = no seam, (cost, correlation) [B, 8, 2]) on the device, in generation order.  No global time alignment of the
+        vocoder's output to the recording is attempted.  With ``splice=None`` the call takes none of it.
 
         Beyond the reference -- ``ap_scale`` (needs ``mel=`` / ``audio_file=`` or audio tokens in ``generated_prompt_embeds``): the weight of the
         audio prompt in every decoupled ``attn2``, ``text + ap_scale * audio`` (attention_processor.py:454), for this call: a float, a sequence
@@ -1275,6 +1370,11 @@ class AudioLDM2Pipeline:
         loud = None
         if target_loudness is not None or loudness_reference is not None:
             loud = self.check_loudness_arguments(target_loudness, peak_limit_db, loudness_reference, editing, batch_size * num_waveforms_per_prompt)
+        spl = None
+        if splice is not None or splice_reference is not None:
+            spl = self.check_splice_arguments(splice, splice_reference, crossfade_s, seam_search_s, crossfade_shape, splice_gain, source_audio,
+                                              source_mel, source_latents, edit_mask, output_type, batch_size * num_waveforms_per_prompt,
+                                              int(audio_length_in_s * 16000))
         if inversion is not None or source_prompt is not None or source_prompt_embeds is not None or source_generated_prompt_embeds is not None \
                 or source_attention_mask is not None:
             self.check_inversion_arguments(inversion, editing, eta, prompt, source_prompt, source_guidance_scale, source_prompt_embeds,
@@ -1365,8 +1465,11 @@ class AudioLDM2Pipeline:
                     1 if isinstance(source_audio, str) else len(source_audio)
 
             def device_waveform():
-                """vocoder + crop on the device, then (target_loudness=) the loudness stage: whatever scores or returns reads this"""
+                """vocoder + crop on the device, then (splice=) the splice into the recording, then (target_loudness=) the loudness stage:
+                whatever scores or returns reads this"""
                 wav = self.vocoder(mel.squeeze(1) if mel.dim() == 4 else mel)[:, :samples]
+                if spl is not None:
+                    wav = self._apply_splice(wav, spl, self._splice_reference(source_audio, splice_reference, samples, wav.device))
                 if loud is None:
                     return wav
                 ref = loudness_reference
@@ -1385,7 +1488,7 @@ class AudioLDM2Pipeline:
                 out = self.score_waveforms(text=prompt, audio=wav.cpu().float(), num_waveforms_per_prompt=num_waveforms_per_prompt, device=dev,
                                            dtype=pe.dtype, audio_device=wav)
             else:
-                out = self.mel_spectrogram_to_waveform(mel)[:, :samples] if loud is None else device_waveform().cpu().float()
+                out = self.mel_spectrogram_to_waveform(mel)[:, :samples] if loud is None and spl is None else device_waveform().cpu().float()
                 if ranking:  # :1047-1054
                     out = self.score_waveforms(text=prompt, audio=out, num_waveforms_per_prompt=num_waveforms_per_prompt, device=dev,
                                                dtype=pe.dtype)

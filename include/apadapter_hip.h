@@ -899,6 +899,46 @@ int apad_loudness_gain(const float* x, const int64_t* offsets, const int64_t* of
                        const float* ref_stats, const int32_t* ref_index, const int32_t* ref_index_host, float* out, float* gains,
                        int32_t batch, int32_t n_ref, float peak_limit, void* stream);
 
+/* Splice of a region edit back into its reference recording (restated, PARITY UNPINNED; held to the fp64 restatement in
+   tests/splice_oracle.py), additive to ABI 12.
+   edit / offsets / offsets_host as for apad_loudness: a ragged batch of fp32 clips e, offsets[0] == 0.  ref / ref_offsets /
+   ref_offsets_host: n_ref reference clips r packed the same way; clip b is spliced into reference ref_index[b] (int32 [batch] in
+   device memory, ref_index_host the same on the host), which must have clip b's length n.
+   plan int32 [batch][APAD_SPLICE_PLAN_INTS] in device memory, plan_host the same on the host (validation only).  A clip's row:
+     [0] regions (1 .. 4)   [1] W, the crossfade length in samples (>= 2)   [2] shape: 0 matched, 1 linear, 2 equal power
+     [3] gain: 0 measured, 1 gain_in[b]   [4] M, the longest seam span (W <= M <= 8192)   [5 .. 7] 0
+     [8 + 6 q ..] region q, in increasing order: a, b (the region [a, b)), then the search span [lo, hi) of its left seam and of its
+     right seam; lo = -1: no seam on that side (the first region's left, the last region's right only), the edit runs to the clip's
+     edge there.  A left span lies between the span before it (or 0) and a, a right span between b and n; each holds W .. M samples.
+   Per clip, in fp32:
+     gain    g = sqrt(sum r^2 / sum e^2) over the kept samples -- those before the first span, between a right span's end and the
+             next left span's start, and after the last span; an absent seam's span runs to the clip's edge -- as IEEE division and
+             square root; g = 1 when either sum is 0 or not finite.  With [3] = 1, g = gain_in[b] (fp32 [batch] in device memory; it
+             may be NULL when no clip asks for it).  ge[i] = g e[i], ONE fp32 multiply.
+     seams   for every start s with [s, s + W) inside the span: cost(s) = sum over i in [s, s + W), in index order, of
+             (r[i] - ge[i])^2.  The smallest cost wins; on a tie the start nearest the region (the largest on a left seam, the
+             smallest on a right seam).  rho = clamp(sum r ge / sqrt(sum r^2 sum ge^2), 0, 1) over the chosen window, 0 when either
+             energy is 0.
+     output  out[i] = r[i], the same bits, outside regions and windows; g e[i] between a region's two windows (from the clip's edge
+             where a seam is absent); in a window, with t = (i - s + 0.5) / W, w_e = t on a left seam and 1 - t on a right one,
+             w_r = 1 - w_e: (w_r r[i] + w_e ge[i]) / sqrt(w_r^2 + w_e^2 + 2 c w_r w_e), c = rho (shape 0), 1 (shape 1), 0 (shape 2):
+             power-complementary for signals of correlation c.
+   gains fp32 [batch] = g; seam_start int32 [batch][8]: entry 2 q = the left window's start of region q, 2 q + 1 the right one's,
+   -1 = no seam; seam_stats fp32 [batch][8][2] = (cost, the measured rho) of the chosen window, (0, 0) without a seam.  out is packed
+   as edit and must be neither edit nor ref.  One workgroup per clip, every sum in a fixed order that depends on the clip's plan
+   alone (no atomics): a clip's outputs do not depend on the batch around it.  No host synchronisation (hipGraph-capturable).
+   -1, with nothing launched, on a null pointer, batch outside [1, 65535], an empty clip or one above 2^30 samples, offsets[0] != 0, a
+   ref_index outside [0, n_ref), a reference of another length, W < 2, M < W, M > 8192, more than 4 regions (8 seams), a shape or
+   gain mode out of range, or a region or seam span that breaks the rules above (outside its clip, out of order, shorter than W or
+   longer than M). */
+#define APAD_SPLICE_PLAN_INTS 32
+#define APAD_SPLICE_MAX_REGIONS 4
+#define APAD_SPLICE_MAX_SPAN 8192
+int apad_splice(const float* edit, const int64_t* offsets, const int64_t* offsets_host, const float* ref, const int64_t* ref_offsets,
+                const int64_t* ref_offsets_host, const int32_t* ref_index, const int32_t* ref_index_host, const int32_t* plan,
+                const int32_t* plan_host, const float* gain_in, float* out, float* gains, int32_t* seam_start, float* seam_stats,
+                int32_t batch, int32_t n_ref, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
