@@ -14,9 +14,10 @@ from .clap_audio import ClapAudioConfig, ClapAudioModelWithProjection  # noqa: F
 from .clap_features import ClapFeatureExtractor  # noqa: F401
 from .chroma import chroma_stft, chroma_similarity  # noqa: F401
 from .loudness import integrated_loudness, normalize_loudness  # noqa: F401
-from .splice import splice_edit  # noqa: F401
+from .splice import splice_edit, splice_edit_aligned  # noqa: F401
+from .align import align_edit  # noqa: F401
 from .wiring import install_ap_adapter, build_processors, ip_layer_names, adapter_state_dict, save_adapter, load_adapter  # noqa: F401
-from . import ops, distributed, autograd, config, sharded, chroma, loudness, splice  # noqa: F401
+from . import ops, distributed, autograd, config, sharded, chroma, loudness, splice, align  # noqa: F401
 from .config import get_config  # noqa: F401
 from .ops import set_float32_matmul_precision, get_float32_matmul_precision  # noqa: F401
 from .training import AdapterTrainer, add_noise  # noqa: F401

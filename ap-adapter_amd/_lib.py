@@ -225,6 +225,9 @@ SYMBOLS = {
     "apad_loudness_gain": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _f32, _vp]),
     # a region edit spliced back into its reference recording (splice_edit)
     "apad_splice": (C.c_int, [_vp] * 15 + [_i32, _i32, _vp]),
+    # an edit aligned to its reference by one integer lag per clip, ahead of the splice (align_edit)
+    "apad_align_corr": (C.c_int, [_vp] * 11 + [_i32] * 4 + [_vp]),
+    "apad_align_apply": (C.c_int, [_vp] * 16 + [_i32] * 4 + [C.c_float, _vp]),
 }
 
 _lock = threading.Lock()

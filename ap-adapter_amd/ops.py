@@ -1313,6 +1313,82 @@ def splice(edit, offsets, offsets_host, ref, ref_offsets, ref_offsets_host, ref_
     return out
 
 
+ALIGN_PLAN_INTS, ALIGN_CHUNK = 16, 4096
+
+
+def _align_operands(who, edit, offsets, offsets_host, ref, ref_offsets, ref_offsets_host, ref_index, ref_index_host, plan, plan_host, partial):
+    """the checks ``align_corr`` and ``align_apply`` share -> (B, m, chunks, lags): partial fp32 [B, chunks, lags], or None -> (B, m, 1, 1)"""
+    for t, name in ((edit, "edit"), (ref, "ref")) + (((partial, "partial"),) if partial is not None else ()):
+        if not _req(t, f"{who}.{name}", torch.float32).is_contiguous():
+            raise RuntimeError(f"{who}.{name}: must be contiguous")
+    B = offsets_host.numel() - 1
+    _host_table(offsets_host, f"{who}.offsets_host", torch.int64, B + 1)
+    m = ref_offsets_host.numel() - 1
+    _host_table(ref_offsets_host, f"{who}.ref_offsets_host", torch.int64, m + 1)
+    if B < 1 or m < 1:
+        raise RuntimeError(f"{who}: {B} clips and {m} references (need at least one of each)")
+    for t, n, name in ((offsets, B + 1, "offsets"), (ref_offsets, m + 1, "ref_offsets")):
+        if _req(t, f"{who}.{name}", torch.int64).numel() != n or not t.is_contiguous():
+            raise RuntimeError(f"{who}.{name}: expected {n} contiguous int64 values")
+    for t, n, name in ((ref_index, B, "ref_index"), (plan, B * ALIGN_PLAN_INTS, "plan")):
+        if _req(t, f"{who}.{name}", torch.int32).numel() != n or not t.is_contiguous():
+            raise RuntimeError(f"{who}.{name}: expected {n} contiguous int32 values")
+    _host_table(ref_index_host, f"{who}.ref_index_host", torch.int32, B)
+    _host_table(plan_host, f"{who}.plan_host", torch.int32, B * ALIGN_PLAN_INTS)
+    if edit.numel() < int(offsets_host[-1]) or ref.numel() < int(ref_offsets_host[-1]):
+        raise RuntimeError(f"{who}: edit {edit.numel()} / ref {ref.numel()} samples, the offsets end at {int(offsets_host[-1])} / "
+                           f"{int(ref_offsets_host[-1])}")
+    if partial is None:
+        return B, m, 1, 1
+    if partial.dim() != 3 or partial.shape[0] != B or partial.shape[1] < 1 or partial.shape[2] < 1:
+        raise RuntimeError(f"{who}.partial: expected [{B}, chunks, lags], got {tuple(partial.shape)}")
+    return B, m, partial.shape[1], partial.shape[2]
+
+
+def align_corr(edit, offsets, offsets_host, ref, ref_offsets, ref_offsets_host, ref_index, ref_index_host, plan, plan_host, partial):
+    """apad_align_corr on pre-allocated buffers (hipGraph-capturable: no allocation, no read-back): edit / ref packed fp32 clips with their
+    offsets and ref_index on the device and on the host as for ``splice``, plan int32 [B, 16] on the device and on the host
+    (``align.plan_row``) -> partial fp32 [B, chunks, lags]: each chunk of 4096 samples' share of the correlation table, entry l + L of a
+    row for the lag l; chunks >= ceil(n / 4096) and lags >= 2 L + 1 for every measured clip."""
+    B, m, chunks, lags = _align_operands("align_corr", edit, offsets, offsets_host, ref, ref_offsets, ref_offsets_host, ref_index, ref_index_host,
+                                         plan, plan_host, partial)
+    L.check(L.lib().apad_align_corr(edit.data_ptr(), offsets.data_ptr(), offsets_host.data_ptr(), ref.data_ptr(), ref_offsets.data_ptr(),
+                                    ref_offsets_host.data_ptr(), ref_index.data_ptr(), ref_index_host.data_ptr(), plan.data_ptr(),
+                                    plan_host.data_ptr(), partial.data_ptr(), B, m, chunks, lags, _stream()), "apad_align_corr")
+    return partial
+
+
+def align_apply(edit, offsets, offsets_host, ref, ref_offsets, ref_offsets_host, ref_index, ref_index_host, plan, plan_host, out, lags_out, stats,
+                min_corr, partial=None, lag_in=None, corr_out=None):
+    """apad_align_apply on pre-allocated buffers: the operands of ``align_corr`` and its ``partial`` (None when every clip has a given lag)
+    -> out fp32 (packed as edit; neither edit nor ref) = the edit shifted by the applied lag, lags_out int32 [B, 2] = (found, applied),
+    stats fp32 [B, 4] = (ncc(l*), ncc(0), c(l*), E_r).  ``lag_in`` int32 [B]: the lag of the clips whose plan gives one; ``corr_out`` fp32
+    [B, lags] receives the folded table; ``min_corr``: the gate on ncc(l*)."""
+    B, m, chunks, lags = _align_operands("align_apply", edit, offsets, offsets_host, ref, ref_offsets, ref_offsets_host, ref_index, ref_index_host,
+                                         plan, plan_host, partial)
+    for t, name in ((out, "out"), (stats, "stats")) + (((corr_out, "corr_out"),) if corr_out is not None else ()):
+        if not _req(t, "align_apply." + name, torch.float32).is_contiguous():
+            raise RuntimeError(f"align_apply.{name}: must be contiguous")
+    for t, name in ((lags_out, "lags_out"),) + (((lag_in, "lag_in"),) if lag_in is not None else ()):
+        if not _req(t, "align_apply." + name, torch.int32).is_contiguous():
+            raise RuntimeError(f"align_apply.{name}: must be contiguous")
+    if lags_out.numel() != 2 * B or stats.numel() != 4 * B or (lag_in is not None and lag_in.numel() != B):
+        raise RuntimeError(f"align_apply: lags_out {tuple(lags_out.shape)} / stats {tuple(stats.shape)} / lag_in do not describe {B} clips as "
+                           f"[B, 2] / [B, 4] / [B]")
+    if corr_out is not None:
+        if partial is None:
+            lags = corr_out.shape[-1]
+        if corr_out.numel() != B * lags:
+            raise RuntimeError(f"align_apply.corr_out: expected [{B}, {lags}], got {tuple(corr_out.shape)}")
+    if out.numel() < int(offsets_host[-1]):
+        raise RuntimeError(f"align_apply.out: {out.numel()} samples, the offsets end at {int(offsets_host[-1])}")
+    L.check(L.lib().apad_align_apply(edit.data_ptr(), offsets.data_ptr(), offsets_host.data_ptr(), ref.data_ptr(), ref_offsets.data_ptr(),
+                                     ref_offsets_host.data_ptr(), ref_index.data_ptr(), ref_index_host.data_ptr(), plan.data_ptr(),
+                                     plan_host.data_ptr(), _ptr(partial), _ptr(lag_in), out.data_ptr(), lags_out.data_ptr(), stats.data_ptr(),
+                                     _ptr(corr_out), B, m, chunks, lags, float(min_corr), _stream()), "apad_align_apply")
+    return out
+
+
 def gaussian_sample(moments, noise, scale=1.0):
     """moments [rows, 2L] = (mean | logvar), noise [rows, L] -> (mean + exp(0.5 * clamp(logvar, -30, 20)) * noise) * scale"""
     _req(moments, "gaussian_sample.moments")

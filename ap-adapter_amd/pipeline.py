@@ -127,6 +127,7 @@ class AudioLDM2Pipeline:
         self.last_chroma_similarity = None
         self.last_loudness = None
         self.last_splice = None
+        self.last_align = None
         self.scheduler = scheduler or DDIMScheduler()
         self.audiomae = audiomae
         self._uncond_cache = {}
@@ -339,6 +340,26 @@ class AudioLDM2Pipeline:
             S.plan(samples, r, W, M)
         return regions, W, M, shape, gain
 
+    def check_align_arguments(self, align, align_search_s, align_min_corr, spl, samples):
+        """every argument check of ``align=`` and its keywords, on the host, before any device work; ``spl`` is what
+        ``check_splice_arguments`` returned.  Returns None (today's path) or (L, min_corr, given lag or None)."""
+        from . import align as A, splice as S
+        if align is None:
+            return None
+        if spl is None:
+            raise ValueError("align= shifts the edit ahead of splice='source'; without splice= it has no use")
+        sr = int(self.vocoder.config.sampling_rate) if self.vocoder is not None else 16000
+        al = A.check_arguments(sr, align, align_search_s, align_min_corr)
+        L, _, lag = al
+        if lag is not None:
+            if abs(lag) >= samples:
+                raise ValueError(f"align={lag} shifts a clip of {samples} samples out of itself")
+            return al
+        regions, W, M = spl[:3]
+        for r in regions:  # (no kept sample L away from every span: a ValueError here, not after the denoise loop)
+            A.plan(samples, S.plan(samples, r, W, M).kept, L)
+        return al
+
     def _splice_reference(self, source_audio, splice_reference, samples, dev):
         """the recordings [m, samples] fp32 on the device: each file's channel 0 resampled to the vocoder's rate (the raw samples, not the
         level-normalised ones the encoder sees), or ``splice_reference``; cropped or zero-padded to ``samples``"""
@@ -357,9 +378,10 @@ class AudioLDM2Pipeline:
             out[i, :min(samples, c.numel())] = c[:samples]
         return out
 
-    def _apply_splice(self, wav, plan, ref):
+    def _apply_splice(self, wav, plan, ref, align=None):
         """candidates [B, samples] on the device -> each spliced into its recording (fp32, on the device); ``last_splice`` = (gains [B],
-        seam starts int32 [B, 8], seam stats (cost, correlation) [B, 8, 2]), in generation order"""
+        seam starts int32 [B, 8], seam stats (cost, correlation) [B, 8, 2]), in generation order.  ``align`` (what ``check_align_arguments``
+        returned): each candidate is first shifted by its lag to the recording; ``last_align`` = (lags int32 [B, 2], stats [B, 4])."""
         from . import loudness, splice as S
         regions, W, M, shape, gain = plan
         wav = wav.float().contiguous()
@@ -369,6 +391,14 @@ class AudioLDM2Pipeline:
         plans = [S.plan(n, [(a, min(b, n)) for a, b in r if a < n], W, M) for r in regions]
         offsets_host = torch.arange(B + 1, dtype=torch.int64) * n
         roh = torch.arange(ref.shape[0] + 1, dtype=torch.int64) * n
+        if align is not None:
+            from . import align as A
+            L, min_corr, lag = align
+            aplans = None if lag is not None else [A.plan(n, p.kept, L) for p in plans]
+            aligned, lags, astats = A.run(wav.reshape(-1), offsets_host, ref.reshape(-1), roh, loudness.default_ref_index(B, ref.shape[0]), aplans,
+                                          min_corr, lag)
+            wav = aligned.reshape(B, n)
+            self.last_align = (lags, astats)
         out, gains, starts, stats = S.run(wav.reshape(-1), offsets_host, ref.reshape(-1), roh, loudness.default_ref_index(B, ref.shape[0]), plans,
                                           shape, gain)
         self.last_splice = (gains, starts, stats)
@@ -1223,7 +1253,7 @@ class AudioLDM2Pipeline:
                  use_graph=True, source_audio=None, source_mel=None, source_latents=None, strength=1.0, edit_mask=None, edit_region=None,
                  audio_guidance_scale=None, guidance_rescale=0.0, apg_eta=None, apg_norm_threshold=0.0, apg_momentum=0.0, ap_scale=None,
                  ap_region=None, ap_mask=None, audio_prompts=None, splice=None, splice_reference=None, crossfade_s=0.03, seam_search_s=0.08,
-                 crossfade_shape="matched", splice_gain="kept", target_loudness=None,
+                 crossfade_shape="matched", splice_gain="kept", align=None, align_search_s=0.02, align_min_corr=0.5, target_loudness=None,
                  peak_limit_db=-1.0, loudness_reference=None, rank_by=None, fidelity_reference=None, inversion=None, source_prompt=None, source_guidance_scale=3.0, source_prompt_embeds=None,
                  source_generated_prompt_embeds=None, source_attention_mask=None):
         """Same keyword surface and defaults as the reference (pipeline_audioldm2.py:748-775, ``output_type="np"`` included): a
@@ -1292,8 +1322,14 @@ class AudioLDM2Pipeline:
         correlation), "linear" or "equal_power".  The stage runs right after the vocoder and the crop and BEFORE the loudness stage: scoring
         and ranking see what is returned, and ``target_loudness`` scales the spliced clip as a whole -- the kept part is then the recording
         times one gain; it is the recording bit for bit with ``target_loudness=None``.  ``last_splice`` keeps (gains [B], window starts int32
-        [B, 8] with -1 = no seam, (cost, correlation) [B, 8, 2]) on the device, in generation order.  No global time alignment of the
-        vocoder's output to the recording is attempted.  With ``splice=None`` the call takes none of it.
+        [B, 8] with -1 = no seam, (cost, correlation) [B, 8, 2]) on the device, in generation order.  With ``splice=None`` the call takes
+        none of it.  ``align`` (PARITY UNPINNED, align.py; needs ``splice="source"``): None = the vocoder's output is spliced as it is, sample i
+        against the recording's sample i; "kept" = each candidate is first shifted by the one integer lag within +- ``align_search_s`` seconds
+        (at most 1024 samples) that correlates it best with the recording over the splice's kept set, if the normalised correlation there
+        reaches ``align_min_corr`` (else by 0); an int = a given lag in samples, positive = the edit is late.  ``last_align`` keeps (lags int32
+        [B, 2] = (found, applied), stats [B, 4] = (ncc at the found lag, ncc at lag 0, c at the found lag, the recording's energy over the
+        kept set)) on the device, in generation order; it is None after a call without ``align``.  Neither default is calibrated on a real
+        decoder.  Not attempted: fractional lags, a lag per seam or time-stretching, polarity inversion, alignment in the mel domain.
 
         Beyond the reference -- ``ap_scale`` (needs ``mel=`` / ``audio_file=`` or audio tokens in ``generated_prompt_embeds``): the weight of the
         audio prompt in every decoupled ``attn2``, ``text + ap_scale * audio`` (attention_processor.py:454), for this call: a float, a sequence
@@ -1375,6 +1411,9 @@ class AudioLDM2Pipeline:
             spl = self.check_splice_arguments(splice, splice_reference, crossfade_s, seam_search_s, crossfade_shape, splice_gain, source_audio,
                                               source_mel, source_latents, edit_mask, output_type, batch_size * num_waveforms_per_prompt,
                                               int(audio_length_in_s * 16000))
+        self.last_align = aln = None
+        if align is not None:
+            aln = self.check_align_arguments(align, align_search_s, align_min_corr, spl, int(audio_length_in_s * 16000))
         if inversion is not None or source_prompt is not None or source_prompt_embeds is not None or source_generated_prompt_embeds is not None \
                 or source_attention_mask is not None:
             self.check_inversion_arguments(inversion, editing, eta, prompt, source_prompt, source_guidance_scale, source_prompt_embeds,
@@ -1469,7 +1508,8 @@ class AudioLDM2Pipeline:
                 whatever scores or returns reads this"""
                 wav = self.vocoder(mel.squeeze(1) if mel.dim() == 4 else mel)[:, :samples]
                 if spl is not None:
-                    wav = self._apply_splice(wav, spl, self._splice_reference(source_audio, splice_reference, samples, wav.device))
+                    wav = self._apply_splice(wav, spl, self._splice_reference(source_audio, splice_reference, samples, wav.device),
+                                             *(() if aln is None else (aln,)))
                 if loud is None:
                     return wav
                 ref = loudness_reference

@@ -16,8 +16,9 @@ What every audio editor does when it replaces a region.  The edit ``e`` and the 
 
 ``plan`` is host code; everything else is ONE HIP launch (``apad_splice``) for a ragged batch, with nothing read back.  **PARITY UNPINNED**:
 no other implementation was available; the stage is held to the fp64 restatement in tests/splice_oracle.py and to its identities (the
-reference's bits outside the windows, one multiply inside).  Not here: a time alignment of edit and reference, splices in the mel domain or
-per frequency band, true peak or limiting.
+reference's bits outside the windows, one multiply inside).  A time alignment of edit and reference by one integer lag per clip is the
+stage before this one (align.py; ``splice_edit(align=)``).  Not here: a lag per seam or a fractional one, splices in the mel domain or per
+frequency band, true peak or limiting.
 """
 import collections
 import math
@@ -200,8 +201,29 @@ def splice_edit(edit, reference, regions, sampling_rate=16000, crossfade_s=0.03,
     "equal_power".  ``gain``: "kept" (the edit is brought to the reference's level, measured where both are the kept material), None
     (1), or a number.  Outside the regions and crossfade windows ``out`` holds the reference's samples, bit for bit.
     ``return_plan`` adds the chosen window starts int32 [b, 8] (entry 2 q / 2 q + 1: left / right seam of region q; -1 = no seam), their
-    (cost, correlation) fp32 [b, 8, 2] and the host Plans.  One ``apad_splice`` launch; nothing is read back."""
+    (cost, correlation) fp32 [b, 8, 2] and the host Plans.  One ``apad_splice`` launch; nothing is read back.  The edit is taken as it
+    is, sample i against the reference's sample i: ``splice_edit_aligned`` shifts it first."""
+    return _splice_edit(edit, reference, regions, sampling_rate, crossfade_s, seam_search_s, crossfade_shape, gain, return_plan)
+
+
+def splice_edit_aligned(edit, reference, regions, sampling_rate=16000, crossfade_s=0.03, seam_search_s=0.08, crossfade_shape="matched", gain="kept",
+                        return_plan=False, align="kept", align_search_s=0.02, align_min_corr=0.5):
+    """``splice_edit`` behind a time alignment (align.py), every other argument as there.  ``align``: None = ``splice_edit``; "kept" = each
+    edit is first shifted by the integer lag, within +- ``align_search_s`` seconds, that correlates it best with its reference over the
+    splice plan's own kept set (shrunk by the search width), provided the normalised correlation reaches ``align_min_corr`` (neither default
+    is calibrated on a real decoder); an int = a given lag in samples, positive = the edit is late.  With ``return_plan`` and ``align`` set
+    the tuple ends in (lags int32 [b, 2] = (found, applied), align stats fp32 [b, 4]).  Two more launches (``apad_align_corr``,
+    ``apad_align_apply``); nothing is read back."""
+    return _splice_edit(edit, reference, regions, sampling_rate, crossfade_s, seam_search_s, crossfade_shape, gain, return_plan, align,
+                        align_search_s, align_min_corr)
+
+
+def _splice_edit(edit, reference, regions, sampling_rate, crossfade_s, seam_search_s, crossfade_shape, gain, return_plan, align=None,
+                 align_search_s=0.02, align_min_corr=0.5):
     from . import loudness
+    if align is not None:
+        from . import align as A
+        al = A.check_arguments(sampling_rate, align, align_search_s, align_min_corr)
     W, M = check_lengths(sampling_rate, crossfade_s, seam_search_s)
     shape, g = check_shape(crossfade_shape), check_gain(gain)
     try:  # the waveform forms of normalize_loudness, checked by its own code
@@ -215,11 +237,20 @@ def splice_edit(edit, reference, regions, sampling_rate=16000, crossfade_s=0.03,
             raise ValueError(f"splice: clip {i} has {n} samples, its reference {ridx[i]} has {rlens[ridx[i]]}")
     per_clip = _region_lists(regions, len(lens), float(sampling_rate))
     plans = [plan(n, [(a, min(b, n)) for a, b in regs if a < n], W, M) for n, regs in zip(lens, per_clip)]
+    if align is not None:  # (nothing kept after the search width is taken off: a ValueError before anything is uploaded)
+        L, min_corr, lag = al
+        if lag is not None and any(abs(lag) >= n for n in lens):
+            raise ValueError(f"splice: align={lag} shifts a clip of {min(lens)} samples out of itself")
+        aplans = None if lag is not None else [A.plan(p.n, p.kept, L) for p in plans]
     packed, offsets_host, dev = loudness._pack(edit)
     rp, roh, _ = loudness._pack(reference, dev)
+    if align is not None:
+        packed, lags, astats = A.run(packed, offsets_host, rp, roh, ridx, aplans, min_corr, lag)
     out, gains, starts, stats = run(packed, offsets_host, rp, roh, ridx, plans, shape, g)
     if torch.is_tensor(edit) or isinstance(edit, np.ndarray):
         res = out.reshape(tuple(edit.shape))
     else:
         res = [out[int(offsets_host[i]): int(offsets_host[i + 1])] for i in range(len(lens))]
-    return (res, gains, starts, stats, plans) if return_plan else (res, gains)
+    if return_plan:
+        return (res, gains, starts, stats, plans) + ((lags, astats) if align is not None else ())
+    return res, gains

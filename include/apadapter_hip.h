@@ -939,6 +939,50 @@ int apad_splice(const float* edit, const int64_t* offsets, const int64_t* offset
                 const int32_t* plan_host, const float* gain_in, float* out, float* gains, int32_t* seam_start, float* seam_stats,
                 int32_t batch, int32_t n_ref, void* stream);
 
+/* Time alignment of an edit to its reference recording by one integer lag per clip, the stage before apad_splice (restated, PARITY
+   UNPINNED; held to the fp64 restatement in tests/align_oracle.py), additive to ABI 12.
+   edit / offsets / offsets_host, ref / ref_offsets / ref_offsets_host, ref_index / ref_index_host as for apad_splice: clip b (e, n
+   samples) is aligned to reference ref_index[b] (r), which must have its length.
+   plan int32 [batch][APAD_ALIGN_PLAN_INTS] in device memory, plan_host the same on the host (validation only).  A clip's row:
+     [0] intervals k (1 .. 5; 0 in given-lag mode)   [1] L, the search half-width in samples (1 .. 1024)
+     [2] mode: 0 measured, 1 given (lag_in[b])        [3] 0
+     [4 + 2 j], [5 + 2 j] lo, hi of kept interval j: disjoint, increasing, L <= lo < hi <= n - L.  K = their union.
+   A lag l means e[i + l] ~ r[i]: positive = the edit is late.  Per clip, in fp32:
+     table    c(l) = sum over i in K of r[i] e[i + l] for l in [-L, L], one fused multiply-add per term.  Samples outside K (for r) and
+              outside K's reach K +- L (for e) never enter the arithmetic: a NaN there moves no bit of any result.
+     winner   the lag of the largest c; ties go to the smaller |l|, then to l >= 0 (a total order); the search starts from (c(0), 0).
+     ncc      E_r = sum_K r[i]^2, E_e(l) = sum_K e[i + l]^2, ncc(l) = c(l) / sqrt(E_r E_e(l)) as IEEE product, square root and division,
+              0 when either energy is 0; for the winner l* and for l = 0 only.
+     gate     the applied lag is l* if c(l*) > 0 and ncc(l*) >= min_corr, else 0.
+     output   out[i] = e[i + lag], the same bits, where 0 <= i + lag < n, +0.0 elsewhere.
+   In given-lag mode the lag is lag_in[b] (any int32; nothing outside the clip is read), nothing is measured: stats 0, found = given.
+
+   apad_align_corr: grid (chunk, clip), a chunk = APAD_ALIGN_CHUNK consecutive samples i.  partial fp32 [batch][chunks][lags]: the
+   chunk's share of c(l) at entry l + L_b of its row (entries 0 .. 2 L_b; lags is the row stride); zeros when the chunk holds no sample
+   of K; nothing is written for a given-lag clip or for chunks at or past ceil(n / 4096).
+   apad_align_apply: one workgroup per clip folds the chunks' shares in increasing chunk order, finds the winner, measures the
+   energies, applies the gate and writes out (packed as edit; neither edit nor ref).  lags_out int32 [batch][2] = (found, applied);
+   stats fp32 [batch][4] = (ncc(l*), ncc(0), c(l*), E_r); corr_out fp32 [batch][lags] (may be NULL) receives the folded table at entries
+   0 .. 2 L_b of a measured clip's row, nothing else is written to it.  partial may be NULL when every clip has a given lag, lag_in
+   (int32 [batch] in device memory) when none has.
+   Every sum is taken in a fixed order that depends on the clip's length and plan row alone (csrc/align.hip states it; no atomics): a
+   clip's outputs do not depend on the batch around it.  No host synchronisation (hipGraph-capturable).
+   -1, with nothing launched, on a null required pointer, batch outside [1, 65535], an empty clip or one above 2^24 samples,
+   offsets[0] != 0, a ref_index outside [0, n_ref), a reference of another length, L outside [1, 1024], a mode out of range; for a
+   measured clip: lags < 2 L + 1, chunks < ceil(n / 4096), no interval or more than 5, no partial, an interval that is empty, out of
+   order, overlapping or not inside [L, n - L); for a given-lag clip: no lag_in, or an interval; apply: out == edit or ref. */
+#define APAD_ALIGN_PLAN_INTS 16
+#define APAD_ALIGN_MAX_INTERVALS 5
+#define APAD_ALIGN_MAX_LAG 1024
+#define APAD_ALIGN_CHUNK 4096
+int apad_align_corr(const float* edit, const int64_t* offsets, const int64_t* offsets_host, const float* ref, const int64_t* ref_offsets,
+                    const int64_t* ref_offsets_host, const int32_t* ref_index, const int32_t* ref_index_host, const int32_t* plan,
+                    const int32_t* plan_host, float* partial, int32_t batch, int32_t n_ref, int32_t chunks, int32_t lags, void* stream);
+int apad_align_apply(const float* edit, const int64_t* offsets, const int64_t* offsets_host, const float* ref, const int64_t* ref_offsets,
+                     const int64_t* ref_offsets_host, const int32_t* ref_index, const int32_t* ref_index_host, const int32_t* plan,
+                     const int32_t* plan_host, const float* partial, const int32_t* lag_in, float* out, int32_t* lags_out, float* stats,
+                     float* corr_out, int32_t batch, int32_t n_ref, int32_t chunks, int32_t lags, float min_corr, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,12 @@ compare its numbers with each other, not with a librosa-based evaluation.
 Every pair also gets the source's and the edit's integrated loudness (ITU-R BS.1770-4, mono, measured on the 16 kHz signal:
 ap_adapter_amd/loudness.py, one apad_loudness launch per side and batch) and their difference in LU -- "this edit came out 5 LU hotter
 than its source".  A clip shorter than 400 ms or silent has no loudness: null.  Not compared against libebur128 / pyloudnorm.
+
+Every pair also gets the integer lag, within +- --align-search-s seconds, at which the edit correlates best with its source over the
+length both have (ap_adapter_amd/align.py: apad_align_corr and apad_align_apply; positive = the edit is late), in samples and in ms, with the
+normalised correlation there and at lag 0 -- whether a decoder's output sits on its recording closely enough for a sample-domain splice,
+the measurement ``splice="source", align="kept"`` acts on.  The whole clip counts as kept material here (no region is known); a pair too
+short for the search width has no lag: null.
 """
 import argparse
 import glob
@@ -93,6 +99,8 @@ def main():
     ap.add_argument("--prompts", default=None, help="JSON {edit file name: text}, or lines of name<TAB>text: the edit prompts, for the CLAP cosine")
     ap.add_argument("--clap", default=None, metavar="DIR", help="local transformers ClapModel checkpoint (weights + tokenizer): adds the CLAP cosine")
     ap.add_argument("--batch", type=int, default=32, help="pairs per launch")
+    ap.add_argument("--align-search-s", type=float, default=0.02, metavar="S", help="the lag of each edit to its source is searched within +-S "
+                    "seconds (at most 1024 samples at 16 kHz)")
     ap.add_argument("--out", default=None, help="write the JSON here (default: print only)")
     args = ap.parse_args()
     if (args.prompts is None) != (args.clap is None):
@@ -119,6 +127,15 @@ def main():
         src, edit = [load_16k(s, dev) for _, s, _ in chunk], [load_16k(e, dev) for _, _, e in chunk]
         sim = A.chroma_similarity(edit, src, ref_index=range(len(chunk))).cpu().tolist()
         l_src, l_edit = lufs(A.integrated_loudness(src).cpu()), lufs(A.integrated_loudness(edit).cpu())
+        lagged = []
+        for sw, ew in zip(src, edit):  # pair by pair: each over the length both have
+            m = min(sw.numel(), ew.numel())
+            try:
+                _, lg, st = A.align_edit([ew[:m]], [sw[:m]], search_s=args.align_search_s, min_corr=-1.0)
+                lagged.append({"lag_samples": int(lg[0, 0]), "lag_ms": round(int(lg[0, 0]) / 16.0, 4), "ncc_at_lag": round(float(st[0, 0]), 6),
+                               "ncc_at_0": round(float(st[0, 1]), 6)})
+            except ValueError:
+                lagged.append({"lag_samples": None, "lag_ms": None, "ncc_at_lag": None, "ncc_at_0": None})
         cos = [None] * len(chunk)
         if pipe is not None:  # one clip at a time: the extractor crops at random past 10 s, the towers batch per call anyway
             import math
@@ -126,15 +143,17 @@ def main():
                 pipe.score_waveforms(text=[prompts[name]], audio=edit[j][None].cpu(), num_waveforms_per_prompt=1, device=dev, dtype=torch.float32,
                                      audio_device=edit[j][None])
                 cos[j] = float(pipe.last_logits_per_text[0, 0]) / math.exp(pipe.logit_scale_t)
-        for (name, s, _), c, t, ls, le in zip(chunk, sim, cos, l_src, l_edit):
+        for (name, s, _), c, t, ls, le, lg in zip(chunk, sim, cos, l_src, l_edit, lagged):
             rows.append({"edit": name, "source": os.path.basename(s), "chroma_similarity": round(c, 6), "source_lufs": ls, "edit_lufs": le,
-                         "loudness_difference_lu": None if ls is None or le is None else round(le - ls, 3),
+                         "loudness_difference_lu": None if ls is None or le is None else round(le - ls, 3), **lg,
                          **({} if t is None else {"prompt": prompts[name], "clap_cosine": round(t, 6)})})
     res = {"pairs": rows, "n": len(rows), "chroma_similarity_mean": round(sum(r["chroma_similarity"] for r in rows) / len(rows), 6),
            "chroma": "librosa.feature.chroma_stft restated (n_fft 2048, hop 512, 16 kHz, tuning fixed at 0); mean per-frame cosine over the "
                      "frames both clips have",
            "loudness": "ITU-R BS.1770-4 integrated loudness, mono, at 16 kHz (LUFS; null = no 400 ms block above the gates); difference = edit "
-                       "- source in LU"}
+                       "- source in LU",
+           "lag": f"the integer lag within +-{args.align_search_s} s of the largest cross-correlation of edit and source over their common "
+                  "length at 16 kHz (positive = the edit is late), with the normalised correlation there and at lag 0; null = too short"}
     diffs = [r["loudness_difference_lu"] for r in rows if r["loudness_difference_lu"] is not None]
     if diffs:
         res["loudness_difference_lu_mean"] = round(sum(diffs) / len(diffs), 3)

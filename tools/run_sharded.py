@@ -32,7 +32,10 @@ nothing is clipped on disk.  Each rank lists file, LUFS before and after and gai
 Splicing a region edit back into its recording (--splice, with --edit-region and --wav-dir; --crossfade-s C, --seam-search-s S): before a clip
 is written (and before --target-loudness) the decoded edit is joined to its source wav itself (``splice_edit``: channel 0, resampled to 16
 kHz), so that outside the region and its two crossfades the file holds the recording's samples, not their re-rendering through the VAE and the
-vocoder.  Each rank lists file, gain and window starts in WAV_DIR/splice_rank<R>.json.
+vocoder.  Each rank lists file, gain and window starts in WAV_DIR/splice_rank<R>.json.  With --align (--align-search-s S, --align-min-corr
+C) the decoded edit is first shifted by the integer lag that correlates it best with the recording over the kept part
+(``splice_edit_aligned``); the list then holds each clip's found lag, applied lag and normalised correlation.  Neither default is calibrated
+on a real decoder.
     python tools/run_sharded.py --clips 64 --steps 50 --strength 0.6 --edit-region 4:7 --wav-dir out --splice
 
 The weight of the audio prompt (--ap-scale V, or V0,V1,... with one value per step): ``text + ap_scale * audio`` in every decoupled attn2, read by
@@ -176,6 +179,12 @@ def main():
                     "(outside the region and its crossfades the file holds the recording's own samples)")
     ap.add_argument("--crossfade-s", type=float, default=0.03, metavar="C", help="--splice: the length of each crossfade in seconds")
     ap.add_argument("--seam-search-s", type=float, default=0.08, metavar="S", help="--splice: how far outside the region a seam may move, in seconds")
+    ap.add_argument("--align", action="store_true", help="--splice: shift every decoded edit by the integer lag that aligns it to its recording, "
+                    "measured on the kept part, before it is spliced")
+    ap.add_argument("--align-search-s", type=float, default=0.02, metavar="S", help="--align: lags up to +-S seconds are searched (at most 1024 "
+                    "samples); not calibrated on a real decoder")
+    ap.add_argument("--align-min-corr", type=float, default=0.5, metavar="C", help="--align: the found lag is applied only if its normalised "
+                    "correlation reaches C; not calibrated on a real decoder")
     ap.add_argument("--ap-scale", default=None, metavar="V|V0,V1,...", help="the weight of the audio prompt in the decoupled cross-attention: one "
                     "float, or one per step (a schedule over the full grid); default: the task preset's value, set on the processors")
     ap.add_argument("--ap-region", default=None, metavar="A:B", help="seconds: the audio prompt weighs the tokens between A and B only "
@@ -214,6 +223,14 @@ def main():
         try:
             from ap_adapter_amd.splice import check_lengths
             check_lengths(16000, args.crossfade_s, args.seam_search_s)
+        except ValueError as err:
+            ap.error(str(err))
+    if args.align:
+        if not args.splice:
+            ap.error("--align shifts an edit ahead of its splice: it needs --splice")
+        try:
+            from ap_adapter_amd.align import check_arguments
+            check_arguments(16000, "kept", args.align_search_s, args.align_min_corr)
         except ValueError as err:
             ap.error(str(err))
 
@@ -362,7 +379,9 @@ def main():
         if args.splice:  # the region as the mask's rows give it, and the whole plan, checked before the first clip is decoded
             n16 = int(args.seconds * 16000)
             spliced = [(a / 16000.0, b / 16000.0) for a, b in A.splice.mask_regions(region_mask, 640, n16)[0]]
-            A.splice.plan(n16, A.splice.mask_regions(region_mask, 640, n16)[0], *A.splice.check_lengths(16000, args.crossfade_s, args.seam_search_s))
+            whole = A.splice.plan(n16, A.splice.mask_regions(region_mask, 640, n16)[0], *A.splice.check_lengths(16000, args.crossfade_s, args.seam_search_s))
+            if args.align:
+                A.align.plan(n16, whole.kept, A.align.check_arguments(16000, "kept", args.align_search_s, args.align_min_corr)[0])
 
         def recording(path):
             """the source wav itself at 16 kHz (channel 0), cropped or zero-padded to the clip"""
@@ -385,9 +404,18 @@ def main():
             ip = cfg["ap_scale"] if args.ap_scale is None else "sched" if isinstance(args.ap_scale, list) else args.ap_scale
             name = f"{c['prompt']}_{idx}_ip{ip}_t{cfg['time_pooling']}_f{cfg['freq_pooling']}.wav".replace("/", "_")
             if args.splice:  # on the device, before the loudness stage: the kept part of the file is the recording itself
-                wav, sg, starts, _, _ = A.splice_edit(wav.to(dev).float(), recording(c["audio"]), spliced, crossfade_s=args.crossfade_s,
-                                                      seam_search_s=args.seam_search_s, return_plan=True)
-                seams.append({"file": name, "gain": round(float(sg[0]), 6), "window_starts": [int(v) for v in starts[0] if int(v) >= 0]})
+                aligned = {}
+                if args.align:
+                    wav, sg, starts, _, _, lags, ast = A.splice_edit_aligned(wav.to(dev).float(), recording(c["audio"]), spliced,
+                                                                             crossfade_s=args.crossfade_s, seam_search_s=args.seam_search_s,
+                                                                             return_plan=True, align="kept", align_search_s=args.align_search_s,
+                                                                             align_min_corr=args.align_min_corr)
+                    aligned = {"lag_found": int(lags[0, 0]), "lag_applied": int(lags[0, 1]), "ncc": round(float(ast[0, 0]), 6),
+                               "ncc_lag0": round(float(ast[0, 1]), 6)}
+                else:
+                    wav, sg, starts, _, _ = A.splice_edit(wav.to(dev).float(), recording(c["audio"]), spliced, crossfade_s=args.crossfade_s,
+                                                          seam_search_s=args.seam_search_s, return_plan=True)
+                seams.append({"file": name, "gain": round(float(sg[0]), 6), "window_starts": [int(v) for v in starts[0] if int(v) >= 0], **aligned})
             if args.target_loudness is not None:  # on the device, before the write: a hot clip is turned down instead of clipped on disk
                 to = dict(reference=rendered_source(c["audio"])) if args.target_loudness == "source" else dict(target=args.target_loudness)
                 wav, gain, before = A.normalize_loudness(wav.to(dev), peak_limit_db=args.peak_limit_db, return_stats=True, **to)
@@ -424,7 +452,8 @@ def main():
                           **({"rank_by": args.rank_by, "chroma_similarity_mean_rank0": round(sum(r["chroma_similarity"] for r in scored) / max(len(scored), 1), 6)}
                              if args.rank_by else {}),
                           **({"target_loudness": args.target_loudness, "peak_limit_db": args.peak_limit_db} if args.target_loudness is not None else {}),
-                          **({"splice": True, "crossfade_s": args.crossfade_s, "seam_search_s": args.seam_search_s} if args.splice else {})}))
+                          **({"splice": True, "crossfade_s": args.crossfade_s, "seam_search_s": args.seam_search_s} if args.splice else {}),
+                          **({"align": True, "align_search_s": args.align_search_s, "align_min_corr": args.align_min_corr} if args.align else {})}))
         if args.out:
             torch.save({"latents": torch.stack([x.cpu() for x in allc]), "clips": clips}, args.out)
     if world > 1:
