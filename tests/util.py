@@ -329,3 +329,18 @@ def poisoned_input(t, ld, tail_rows=GUARD_ROWS):
     view = buf[:rows, :cols]
     view.copy_(t)
     return view
+
+
+def nan_surrounded(x, device, guard=1024):
+    """the 1-D fp32 clip ``x`` (CPU tensor or array) as a view into one flat buffer [guard | len(x) | guard] whose other elements are NaN
+    (NAN_WORD): a kernel that reads a sample before the clip's first or after its last gives NaN"""
+    x = torch.as_tensor(x, dtype=torch.float32)
+    buf = nan_buffer(x.numel() + 2 * guard, torch.float32, device)
+    view = buf[guard:guard + x.numel()]
+    view.copy_(x)
+    return view
+
+
+def nan_neighbours(x, device, before=131, after=257):
+    """[all-NaN clip, x, all-NaN clip] as 1-D fp32 GPU tensors: the ragged batch whose packed buffer puts NaN on either side of ``x``"""
+    return [nan_buffer(before, torch.float32, device), torch.as_tensor(x, dtype=torch.float32).to(device), nan_buffer(after, torch.float32, device)]
